@@ -13,6 +13,11 @@ slowest problem, so its time depends on the draw: every rank cycles through the 
 so `value` is a mean over draws and every rank does the same total work whatever N is.
 `--batch 262144 --gpus 8` is BASELINE.json configs[3] (2 097 152 problems over 8 GPUs) and labels itself so.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline needs: set-up, clock ramp, warm-up, the K timed steps.  `--full` adds, on one GPU, the
+extra keys that take runs of their own (B = 1 latencies, closed loops, other seeds and configs, two batches in flight, the CPU baselines
+and the parity sample; `--quick` / `--no-cpu-baseline` trim those).  `--dump-outputs DIR` writes what rank 0's last timed step computed
+(u0, status, cost, viol, iters -- plus the gathered u0 block when a collective ran) as DIR/<name>.npy, float64 or the run's float dtype.
 """
 import argparse
 import json
@@ -420,6 +425,20 @@ def gpu_config1_latency(local, n=300):
             "p99_us": float(np.percentile(w, 99)), "cost": float(o["cost"][0].item()), "iterations": int(o["iters"][0].item()), "status": int(o["status"][0].item())}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as <dirname>/<name>.npy, float arrays in their own dtype, integer ones (status, iters) as float64.
+    Above DUMP_LIMIT_BYTES in all (less 1 MiB for rounding and headers), every array keeps the same fixed rows 0, s, 2s, ...
+    (s the smallest stride that fits)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+    stride = max(1, -(-sum(v.nbytes for v in arrays.values()) // (DUMP_LIMIT_BYTES - (1 << 20))))
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v[::stride]))
+
+
 K_DRAWS = 4   # seeded batches every rank cycles through (draw 0 is the batch rounds 1-2 quoted alone)
 
 
@@ -431,8 +450,11 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="problems per GPU")
     ap.add_argument("--horizon", type=int, default=20)
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--full", action="store_true", help="one GPU: also measure the extra keys beside the headline (latencies, closed loops, "
+                                                         "other seeds and configs, CPU baselines, parity sample)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="skip the multi-seed and other-config extra keys")
+    ap.add_argument("--quick", action="store_true", help="with --full: skip the multi-seed and other-config extra keys")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse the multi-rank control flow on a one-GPU box)")
     ap.add_argument("--clock-ramp", type=int, default=100, help="untimed launches BEFORE the W warm-up steps that bring the GPU's clocks up from idle (0 = none)")
@@ -440,6 +462,8 @@ def main():
                     help="run the asynchronous RCCL all-gather of the N > 1 loop also at --gpus 1 (1-rank nccl group): prices the collective's overhead on one GPU "
                          "and puts the RCCL path under test before multi-GPU hardware shows up (tests/test_bench_cli.py)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     # dmabuf IPC only on this pool (RCCL / cross-process tensors fail with hipIpcGetMemHandle otherwise): already exported on the boxes; set before the
     # first HIP call in case a launcher dropped it
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -544,6 +568,13 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    # the last timed step's outputs, copied before the gather check below reuses the output slots
+    last = None
+    if a.dump_outputs and rank == 0:
+        s = (a.steps - 1) % K
+        last = {k: outs[s][k].cpu().numpy() for k in ("u0", "status", "cost", "viol", "iters")}
+        if world > 1 or forced:
+            last["u0_gathered"] = gather.out[s].cpu().numpy()
     # untimed: K more steps through the same loop, every gathered [B, 2] block compared with the blocks the ranks solved (this rank's own block exactly;
     # with N > 1 also the block every other rank reports for the same draw -- all ranks solve the same K draws, rotated, and the kernels are deterministic)
     gather_checked, gather_ok = 0, True
@@ -638,7 +669,9 @@ def main():
                                   "gather_wait_stream_ms": {"min": float(allr[:, 3].min()), "mean": float(allr[:, 3].mean()), "max": float(allr[:, 3].max())}},
                       "note": "gather_wait_*: time per step the solve stream (device events) / the host stood in SolutionGather.wait before a launch"},
         }
-        if world == 1:
+        if last is not None:
+            dump_outputs(a.dump_outputs, last)
+        if world == 1 and a.full:
             # p50 per-solve latency: B = 1 through the same entry point, host clock around launch + sync
             one = {k: v[:1].contiguous() for k, v in din.items()}
             o1 = None

@@ -1,11 +1,14 @@
-"""bench.py as the driver calls it (GPU box): the one-GPU line carries every key the contract and VERDICT r1 ask for, and
+"""bench.py as the driver calls it (GPU box): the one-GPU `--full` line carries every key the contract and VERDICT r1 ask for, a plain
+line only the headline's (with the last step's outputs under `--dump-outputs`), and
 `--gpus 2` without a launcher starts two ranks itself (gloo rehearsal on the one GPU of the box: two ranks share it)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +24,7 @@ def _run(args, timeout=600):
 
 
 def test_bench_line_single_gpu():
-    d = _run(["--steps", "5", "--warmup", "2"])
+    d = _run(["--full", "--steps", "5", "--warmup", "2"])
     assert d["n_gpus"] == 1 and d["unit"] == "solves/s" and d["dtype"] == "f64" and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert d["config"]["batch_per_gpu"] == 4096 and d["config"]["horizon"] == 20 and d["config"]["optimal_fraction"] == 1.0
     rf = d["roofline"]
@@ -56,6 +59,32 @@ def test_bench_line_single_gpu():
     assert hp["worst_status"] == 0 and hp["p50_step_us"] < 120 and hp["p50_step_us"] <= hp["p99_step_us"]
     assert d["parity_sample"]["unexplained"] == 0 and d["parity_sample"]["within_tol"] >= 4096 - 8
     assert "unavailable" in d["reference_julia_ipopt_baseline"] or "julia found" in d["reference_julia_ipopt_baseline"]
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps and measures nothing beside the headline; --dump-outputs writes what the last timed step
+    computed, which is the same from run to run and equal to a solve of that step's seeded draw."""
+    runs = []
+    for tag in ("a", "b"):
+        d = _run(["--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / tag)])
+        runs.append({k: np.load(str(tmp_path / tag / (k + ".npy"))) for k in ("u0", "status", "cost", "viol", "iters")})
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["unit"] == "solves/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"] and len(d["ranks"]["kernel_ms_mean"]) == 1
+    for key in ("p50_latency_us_B1", "closed_loop_N8", "config1_gpu_B1_cold", "dropin_host_path_N8", "multi_seed", "two_batches_in_flight",
+                "config3_fp32_B262144", "cpu_baseline", "cpu_baseline_config1", "parity_sample", "reference_julia_ipopt_baseline"):
+        assert key not in d, key
+    a, b = runs
+    assert a["u0"].shape == (4096, 2) and all(a[k].shape == (4096,) for k in ("status", "cost", "viol", "iters"))
+    assert all(v.dtype == np.float64 for v in a.values()) and (a["status"] == 0).all() and (a["iters"] > 0).all()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    # the last timed step (index warmup + steps - 1) solved draw (2 + 3 - 1) % K_DRAWS = 0: the same seeded batch solved here
+    from mkz_mpc_path_follower_amd import BatchMPC
+    from mkz_mpc_path_follower_amd.synthetic import make_batch
+    dr = make_batch(4096, 20, cfg_id=2, seed=20180620 + 2)
+    o = BatchMPC(N=20, device=0).solve(*(torch.as_tensor(dr[k], dtype=torch.float64, device="cuda:0") for k in ("z0", "ref", "v_target", "u_prev")))
+    for k in a:
+        assert np.array_equal(a[k], o[k].cpu().numpy().astype(np.float64)), k
 
 
 def test_bench_launches_its_own_ranks():
