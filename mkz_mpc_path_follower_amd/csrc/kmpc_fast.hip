@@ -435,6 +435,27 @@ template <typename T, int N, int MODEL = 0> struct FastSolver {
             const int cs_ = colok ? col : 0;
             const T dgv = dgs[cs_], sbv = sbs[cs_], rhv = -sc * gb[cs_];
             const T *colK = Lc + offc_rt(cs_);
+            // fp64, Cartesian model, three tile rows (N = 16, 20): every LDS word of the tile column is requested before the first one is
+            // used -- one wait per column instead of a round trip per entry, which the lone wave of a batch's tail sits out in full.
+            // Elsewhere the words are read where they are used: fp32 (four waves per SIMD hide the latency) and the Frenet functor (its
+            // accumulator tiles are live here) would spill a column's words to scratch, a fourth tile row (N >= 24) costs 27-40 more SGPR
+            // spills, and at two tile rows (N = 8, 12) the three-waves-per-SIMD build gains two; those instantiations keep their code.
+            constexpr bool AHEAD = ADJ && sizeof(T) == 8 && NTF == 3;
+            [[maybe_unused]] T cbv[AHEAD ? NTF : 1][4], srv[AHEAD ? NTF : 1][4];
+            if constexpr (AHEAD) {
+#pragma unroll
+                for (int ti = tj; ti < NT; ++ti)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = 16 * ti + Real<T>::row_of(lane, r);
+                        bool rd = ADJ || (row & 1);
+                        if (ti == NTF - 1) rd = rd && row < n;
+                        if (ti == tj) rd = rd && col <= row;
+                        if (tj == NTF - 1) rd = rd && colok;
+                        cbv[ti][r] = cb[(ti == NTF - 1 ? (row < n ? row : 0) : row) >> 1];
+                        srv[ti][r] = *(rd ? colK + row : pt);  // pt[0] is finite: the product with the zero mask below is exact
+                    }
+            }
 #pragma unroll
             for (int ti = tj; ti < NTF; ++ti) {
                 acc_t cm = acc_t{0, 0, 0, 0};
@@ -447,15 +468,21 @@ template <typename T, int N, int MODEL = 0> struct FastSolver {
                     T v = (T)0;
                     if (ti < NT) {
                         const T evm = (!oddrow && !(c & 1)) ? dt2 : (T)0;
-                        v = evm * cb[(ti == NTF - 1 ? (row < n ? row : 0) : row) >> 1];
+                        if constexpr (AHEAD) v = evm * cbv[ti][r];
+                        else v = evm * cb[(ti == NTF - 1 ? (row < n ? row : 0) : row) >> 1];
                         if (!ADJ) v = fma(sc, kt[ti * (ti + 1) / 2 + tj][r], v);
                         bool rd = ADJ || oddrow;
                         if (ti == NTF - 1) rd = rd && row < n;
                         if (ti == tj) rd = rd && col <= row;
                         if (tj == NTF - 1) rd = rd && colok;
-                        const T *src = rd ? colK + row : pt;  // pt[0] is finite: the product with the zero mask below is exact
-                        const T odm = rd ? (T)1 : (T)0;
-                        v = fma(odm, *src, v);
+                        if constexpr (AHEAD) {
+                            const T odm = rd ? (T)1 : (T)0;
+                            v = fma(odm, srv[ti][r], v);
+                        } else {
+                            const T *src = rd ? colK + row : pt;  // pt[0] is finite: the product with the zero mask below is exact
+                            const T odm = rd ? (T)1 : (T)0;
+                            v = fma(odm, *src, v);
+                        }
                         if (ADJ && MSPLIT > 0 && ti < TM) v += cm[r];
                         if (ti == tj) v += row == col ? dgv : (T)0;
                         if (ti <= tj + 1) v += row == col + 2 ? sbv : (T)0;
