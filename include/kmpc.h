@@ -87,8 +87,9 @@ typedef struct kmpc_config {
                                Calls on one handle must be stream-ordered (the permutation workspace belongs to the handle). */
     int32_t model;          /* 0 (default) = MKZMPCPathFollower.jl, Cartesian states (x, y, psi, v); 1 = MKZMPCPathFollowerFrenet.jl,
                                Frenet-frame states (s, e_y, e_psi, v) with a cubic curvature polynomial (kmpc_solve_batch_frenet;
-                               horizons N <= 24, and N = 28 with kernel_variant 0: the compile-time-horizon kernels carry the functor
-                               for N = 8, 12, ..., 28).  kmpc_create picks the cost defaults of the chosen module. */
+                               horizons N <= 24, N = 28 with kernel_variant 0 or 2: the compile-time-horizon kernels carry the functor
+                               for N = 8, 12, ..., 28; and N = 32, 36, 40, 44, 48, 50 with kernel_variant 0 or 2 in fp64 only: the
+                               four-wave kernel).  kmpc_create picks the cost defaults of the chosen module. */
     int32_t start;          /* cold-start point of the inputs (a warm start overrides it): 0 (default) = feed-forward guess inside the bounds
                                (accelerations approach the reference speed, steering the curvature feed-forward); 1 = the reference's own
                                start, every primal 0 (MKZMPCPathFollower.jl:65-72, Q9), moved strictly inside the first-step rate interval

@@ -24,6 +24,7 @@ template <typename T> bool kmpc_quad_available(int N);
 template <typename T> hipError_t kmpc_launch_solve_quad(const KP &, const KIO<T> &, hipStream_t);
 template <typename T> hipError_t kmpc_launch_solve_frenet(const KP &, const KIO<T> &, hipStream_t);
 template <typename T> hipError_t kmpc_launch_solve_fast_frenet(const KP &, const KIO<T> &, hipStream_t);
+template <typename T> hipError_t kmpc_launch_solve_wide_frenet(const KP &, const KIO<T> &, hipStream_t);
 template <typename T> hipError_t kmpc_launch_fast_kkt(const KP &, const KDbgK<T> &, hipStream_t);
 template <typename T> hipError_t kmpc_launch_wide_kkt(const KP &, const KDbgK<T> &, hipStream_t);
 hipError_t kmpc_launch_sim(int, double *, const double *, int, hipStream_t);
@@ -126,8 +127,11 @@ extern "C" int32_t kmpc_create(const kmpc_config *cfg, int32_t device, kmpc_hand
         cfg->kernel_variant < 0 || cfg->kernel_variant > 2 || cfg->mu_strategy < 0 || cfg->mu_strategy > 1 ||
         cfg->indef_strategy < 0 || cfg->indef_strategy > 2 || cfg->schedule < 0 || cfg->schedule > 1 || cfg->model < 0 || cfg->model > 1 ||
         cfg->start < 0 || cfg->start > 1 ||
-        (cfg->model == 1 && cfg->N > 24 && !(cfg->kernel_variant != 1 && cfg->N == 28)))  // Frenet: generic kernel up to N = 24, compile-time kernel also at 28
+        (cfg->model == 1 && cfg->N > 24 && !(cfg->kernel_variant != 1 && (cfg->N == 28 || kmpc_wide_available<double>(cfg->N)))))
+        // Frenet: generic kernel up to N = 24, compile-time kernels also at 28 (one wave) and 32 ... 48, 50 (four waves)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: invalid model / solver parameter");
+    if (cfg->model == 1 && cfg->N > 28 && cfg->dtype != KMPC_F64)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: the Frenet model (model = 1) at N = %d runs in fp64 only (no fp32 four-wave Frenet kernel)", cfg->N);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, KMPC_ERR_NODEVICE, "kmpc_create: no HIP device");
     if (device < 0 || device >= ndev) return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: device %d of %d", device, ndev);
@@ -241,6 +245,7 @@ static int solve_dev(kmpc_handle *h, int B, const void *z0, const void *ref, con
     // start order: only matters once a launch no longer fits on the chip at once (2 waves x 4 SIMDs x 256 CUs)
     if (h->cfg.model == 1) {  // Frenet functor: `ref` carries k_poly [B,4]; index order (the start-order key reads reference points)
         if (h->cfg.kernel_variant != 1 && kmpc_fast_available<T>(P.N)) HIPCHK(h, kmpc_launch_solve_fast_frenet<T>(P, io, st));
+        else if (h->cfg.kernel_variant != 1 && P.N > 28) HIPCHK(h, kmpc_launch_solve_wide_frenet<T>(P, io, st));   // four-wave kernel: N = 32 ... 48, 50
         else HIPCHK(h, kmpc_launch_solve_frenet<T>(P, io, st));   // generic kernel: N <= 24
         return KMPC_OK;
     }

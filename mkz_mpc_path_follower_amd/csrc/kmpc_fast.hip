@@ -156,159 +156,16 @@ template <typename T, int N, int MODEL = 0> struct FastSolver {
     // roll-out + objective at U (lane j: U_j)
     DEV T eval1(T U, StageF<T> &S)
     {
-        if constexpr (MODEL == 1) return eval_frenet(U, S);
+        if constexpr (MODEL == 1) return ipm::eval_frenet(*this, U, S);
         else return ipm::eval_cartesian(*this, U, S);
     }
     // costates -> gradient (returned, lane j: g_j, and left in gb); per-stage scalars go to the LDS records
     DEV T linearize1(const StageF<T> &S, bool exact)
     {
-        if constexpr (MODEL == 1) { const T g = linearize_frenet(S, exact); gb[lane] = g; return g; }
+        if constexpr (MODEL == 1) return ipm::linearize_frenet(*this, S, exact);   // (the Frenet functor: kmpc_ipm.h, shared with kmpc_wide.hip)
         else return ipm::linearize_cartesian(*this, S, exact);
     }
 
-
-    // ================= Frenet functor (MODEL 1), MKZMPCPathFollowerFrenet.jl:112-123 ======================================================
-    // Roll-out: a serial recursion over the stages on wave-uniform values (every lane runs it; lane k keeps stage k).
-    DEV T eval_frenet(T U, StageF<T> &S)
-    {
-        const T dt = pt[PT_DT], rr_ = pt[PT_RR], dtL = pt[PT_DTL];
-        if (lane < n) xb[lane] = U;
-        WSYNC();
-        const int k = lane;
-        const bool st = k < N;
-        const T a = st ? xb[2 * k] : (T)0, d = st ? xb[2 * k + 1] : (T)0;
-        const T an = (k + 1 < N) ? xb[2 * k + 2] : a, dn = (k + 1 < N) ? xb[2 * k + 3] : d;
-        S.a = a; S.d = d;
-        T sd, cd;
-        sincos_small(d, &sd, &cd, kc);
-        const T Dn = cd * cd + rr_ * rr_ * sd * sd;
-        const T rs = rsqrt_(Dn);
-        S.sinb = rr_ * sd * rs;  // sin(atan(r tan d))   (:113)
-        S.cosb = cd * rs;
-        const T iD = rs * rs;
-        S.b1 = rr_ * iD;                                                    // d beta / d d_f
-        S.b2 = rr_ * ((T)1 - rr_ * rr_) * ((T)2 * sd * cd) * (iD * iD);     // d2 beta / d d_f2
-        if (st) { T *q = lin + LSTR * k; q[13] = a; q[14] = S.sinb; q[15] = S.cosb; }  // slots 0..12 hold the stage Jacobians
-        WSYNC();
-        T s_ = x0, ey_ = y0, ep_ = psi0, v_ = v0;
-        S.x = S.y = S.psi = S.v = S.c = S.s = S.K = S.Kp = S.iden = S.dsdt = (T)0;
-#pragma nounroll
-        for (int kk = 0; kk <= N; ++kk) {
-            const T K = ((kp0 * s_ + kp1) * s_ + kp2) * s_ + kp3;               // :112
-            const T Kp = ((T)3 * kp0 * s_ + (T)2 * kp1) * s_ + kp2;
-            if (lane == kk) { S.x = s_; S.y = ey_; S.psi = ep_; S.v = v_; S.K = K; S.Kp = Kp; }
-            if (kk == N) break;
-            const T *q = lin + LSTR * kk;
-            const T ak = q[13], sb = q[14], cbt = q[15];
-            T sp, cp;
-            sincos_mid(ep_, &sp, &cp, kc);
-            const T c = cp * cbt - sp * sb, sn = sp * cbt + cp * sb;            // cos / sin(e_psi + beta)
-            const T iden = rcp_((T)1 - ey_ * K), dsdt = v_ * c * iden;          // :114
-            if (lane == kk) { S.c = c; S.s = sn; S.iden = iden; S.dsdt = dsdt; }
-            s_ += dt * dsdt;                                                     // :118
-            ey_ += dt * (v_ * sn);                                               // :119
-            ep_ += dtL * v_ * sb - dt * dsdt * K;                                // :120
-            v_ += dt * ak;                                                       // :121
-        }
-        WSYNC();
-        const bool cs = (k >= 1 && k <= N);
-        S.ex = cs ? S.x : (T)0;      // zero references (the s weight is 0: Frenet.jl:97-98 has no s term)
-        S.ey = cs ? S.y : (T)0;
-        S.ep = cs ? S.psi : (T)0;
-        S.ev = (k >= 1 && k <= N - 1) ? S.v - vt : (T)0;
-        const T Cx2 = cwt[0], Cy2 = cwt[1], Cp2 = cwt[2], Cv2 = cwt[3], Cda2 = cwt[4], Cdd2 = cwt[5], Ca2 = cwt[6], Cd2 = cwt[7];
-        T Jl = Cx2 * S.ex * S.ex + Cy2 * S.ey * S.ey + Cp2 * S.ep * S.ep + Cv2 * S.ev * S.ev;
-        if (st) Jl += Ca2 * a * a + Cd2 * d * d;
-        if (k < N - 1) Jl += Cda2 * (an - a) * (an - a) + Cdd2 * (dn - d) * (dn - d);
-        Jl *= (T)0.5;
-        return dpp_sum(Jl);
-    }
-
-    // stage record of the Frenet functor: A00 A01 A02 A03 A12 A13 A20 A21 A22 A23 Bs Bey Bep  (A11 = A33 = 1, B_v,acc = dt), roll-out
-    // scratch 13..15, costate of the state 16..19, second-order block 20..34 (upper triangle over (s, e_y, e_psi, v, d_f), row-major)
-    DEV T linearize_frenet(const StageF<T> &S, bool exact)
-    {
-        const T dt = pt[PT_DT], Lb = pt[PT_LB], iLb = pt[PT_DTL] * rcp_(dt);
-        const T Cx2 = cwt[0], Cy2 = cwt[1], Cp2 = cwt[2], Cv2 = cwt[3], Cda2 = cwt[4], Cdd2 = cwt[5], Ca2 = cwt[6], Cd2 = cwt[7];
-        (void)Lb;
-        const int k = lane;
-        const bool st = k < N;
-        if (k <= N) {
-            T *q = lin + LSTR * k;
-            const T v = S.v, c = S.c, sn = S.s, K = S.K, Kp = S.Kp, iden = S.iden, dsdt = S.dsdt, ey = S.y, b1 = S.b1;
-            const T ds_s = v * c * ey * Kp * iden * iden, ds_ey = v * c * K * iden * iden, ds_ep = -v * sn * iden, ds_v = c * iden,
-                    ds_d = -v * sn * iden * b1;
-            q[0] = st ? (T)1 + dt * ds_s : (T)0; q[1] = st ? dt * ds_ey : (T)0; q[2] = st ? dt * ds_ep : (T)0; q[3] = st ? dt * ds_v : (T)0;
-            q[4] = st ? dt * v * c : (T)0; q[5] = st ? dt * sn : (T)0;
-            q[6] = st ? dt * (-ds_s * K - dsdt * Kp) : (T)0; q[7] = st ? -dt * ds_ey * K : (T)0;
-            q[8] = st ? (T)1 - dt * ds_ep * K : (T)0; q[9] = st ? dt * (S.sinb * iLb - ds_v * K) : (T)0;
-            q[10] = st ? dt * ds_d : (T)0; q[11] = st ? dt * v * c * b1 : (T)0; q[12] = st ? dt * (v * iLb * S.cosb * b1 - ds_d * K) : (T)0;
-            T *l = wb + 4 * k;  // stage cost gradient (wb is scratch here; stage_form_weights rewrites it later)
-            l[0] = Cx2 * S.ex; l[1] = Cy2 * S.ey; l[2] = Cp2 * S.ep; l[3] = Cv2 * S.ev;
-        }
-        WSYNC();
-        T l0 = wb[4 * N], l1 = wb[4 * N + 1], l2 = wb[4 * N + 2], l3 = wb[4 * N + 3];  // costate of state N
-        if (lane == 0) { T *ql = lin + LSTR * N + 16; ql[0] = l0; ql[1] = l1; ql[2] = l2; ql[3] = l3; }
-#pragma nounroll
-        for (int kk = N - 1; kk >= 0; --kk) {  // costates: a serial recursion on wave-uniform values
-            const T *q = lin + LSTR * kk;
-            if (lane == 0) { xb[2 * kk] = dt * l3; xb[2 * kk + 1] = q[10] * l0 + q[11] * l1 + q[12] * l2; }  // B_k^T lambda_{k+1}
-            const T t0 = q[0] * l0 + q[6] * l2;
-            const T t1 = q[1] * l0 + l1 + q[7] * l2;
-            const T t2 = q[2] * l0 + q[4] * l1 + q[8] * l2;
-            const T t3 = q[3] * l0 + q[5] * l1 + q[9] * l2 + l3;
-            const T *l = wb + 4 * kk;
-            l0 = t0 + l[0]; l1 = t1 + l[1]; l2 = t2 + l[2]; l3 = t3 + l[3];
-            if (lane == 0) { T *ql = lin + LSTR * kk + 16; ql[0] = l0; ql[1] = l1; ql[2] = l2; ql[3] = l3; }
-        }
-        WSYNC();
-        if (k <= N) {
-            T *q = lin + LSTR * k + 20;  // upper triangle, row-major: ss se sp sv sd | ee ep ev ed | pp pv pd | vv vd | dd
-            T m[15];
-#pragma unroll
-            for (int i = 0; i < 15; ++i) m[i] = (T)0;
-            if (exact && st) {
-                // second derivatives of the Euler step wrt (s, e_y, e_psi, v, d_f), contracted with the costate of state k+1
-                const T *ln = lin + LSTR * (k + 1) + 16;
-                const T m0 = ln[0], m1 = ln[1], m2 = ln[2];
-                const T s_ = S.x, ey = S.y, v = S.v, C = S.c, Sn = S.s, K = S.K, K1 = S.Kp, K2 = (T)6 * kp0 * s_ + (T)2 * kp1;
-                const T D = S.iden, b1 = S.b1, b2 = S.b2, gq = S.dsdt;
-                const T Ds = ey * K1 * D * D, De = K * D * D;
-                const T Dss = ey * K2 * D * D + (T)2 * ey * K1 * D * Ds, Dse = K1 * D * D + (T)2 * ey * K1 * D * De, Dee = (T)2 * K * D * De;
-                const T g_s = v * C * Ds, g_e = v * C * De, g_p = -v * Sn * D, g_v = C * D, g_d = -v * Sn * b1 * D;
-                const T w = m0 - m2 * K, a2 = m2 * K1;
-                m[0] = dt * (w * (v * C * Dss) - (T)2 * a2 * g_s - m2 * gq * K2);
-                m[1] = dt * (w * (v * C * Dse) - a2 * g_e);
-                m[2] = dt * (w * (-v * Sn * Ds) - a2 * g_p);
-                m[3] = dt * (w * (C * Ds) - a2 * g_v);
-                m[4] = dt * (w * (-v * Sn * b1 * Ds) - a2 * g_d);
-                m[5] = dt * (w * (v * C * Dee));
-                m[6] = dt * (w * (-v * Sn * De));
-                m[7] = dt * (w * (C * De));
-                m[8] = dt * (w * (-v * Sn * b1 * De));
-                m[9] = dt * (w * (-v * C * D) + m1 * (-v * Sn));
-                m[10] = dt * (w * (-Sn * D) + m1 * C);
-                m[11] = dt * (w * (-v * C * b1 * D) + m1 * (-v * Sn * b1));
-                m[13] = dt * (w * (-Sn * b1 * D) + m1 * (C * b1) + m2 * (S.cosb * b1 * iLb));
-                m[14] = dt * (w * (v * D * (-C * b1 * b1 - Sn * b2)) + m1 * (v * (-Sn * b1 * b1 + C * b2)) + m2 * (v * (-S.sinb * b1 * b1 + S.cosb * b2) * iLb));
-            }
-#pragma unroll
-            for (int i = 0; i < 15; ++i) q[i] = m[i];   // zero when the Gauss-Newton matrix is wanted (and in record N)
-        }
-        // input-cost terms, Frenet.jl:99-102 (same as the Cartesian model)
-        const T aprev = dpp_mov0<0x138, 0xf>(S.a), dprev = dpp_mov0<0x138, 0xf>(S.d);  // wave_shr:1 -> lane-1
-        const T anext = dpp_mov0<0x130, 0xf>(S.a), dnext = dpp_mov0<0x130, 0xf>(S.d);
-        if (st) {
-            T ga = xb[2 * k] + Ca2 * S.a, gd = xb[2 * k + 1] + Cd2 * S.d;
-            if (k >= 1) { ga += Cda2 * (S.a - aprev); gd += Cdd2 * (S.d - dprev); }
-            if (k < N - 1) { ga -= Cda2 * (anext - S.a); gd -= Cdd2 * (dnext - S.d); }
-            xb[2 * k] = ga; xb[2 * k + 1] = gd;
-        }
-        WSYNC();
-        const T g = lane < n ? xb[lane] : (T)0;
-        WSYNC();
-        return g;
-    }
 
     // Condensing with dense stage Jacobians, on the matrix cores: H = sum_s G_s^T (2 Q_s + M_s^{zz}) G_s accumulates in `acc` (lower 16x16
     // tiles, MFMA C layout, unscaled).  Lane j keeps all four components of column j of G (16 FMAs per stage); each stage's MFMA fragments
@@ -386,12 +243,8 @@ template <typename T, int N, int MODEL = 0> struct FastSolver {
     // when the exact Hessian is wanted, and a fallback inside an iteration clears them.
     DEV void drop_second_order()
     {
-        if constexpr (MODEL == 1) {
-            T z = (T)0;
-            pin(z);  // materialised here: hoisted out of the iteration loop this zero would occupy (and spill) a VGPR pair for the whole solve
-            if (lane <= N) { T *q = lin + LSTR * lane + 20; for (int i = 0; i < 15; ++i) q[i] = z; }
-            WSYNC();
-        } else ipm::drop_second_order_cartesian(*this);
+        if constexpr (MODEL == 1) ipm::drop_second_order_frenet(*this);
+        else ipm::drop_second_order_cartesian(*this);
     }
     DEV void condense(T sc, acc_t (&acc)[NTT])
     {

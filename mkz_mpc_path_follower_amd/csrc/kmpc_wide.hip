@@ -25,7 +25,9 @@
 template <typename T> using StageW = StageV<T>;
 constexpr int WLIN = 16;  // stage record stride: A02 A03 A12 A13 A23 Bdx Bdy Bdp mpp mpv mpd mvd mdd
 
-template <typename T, int N> struct WideSolver {
+// MODEL 0: Cartesian kinematic bicycle; MODEL 1: the Frenet-frame functor (kmpc_ipm.h, eval_frenet / linearize_frenet, shared with the one-wave
+// kernel), condensed by the classical O(N^2) recursion of condense_frenet below instead of the adjoint recursion.
+template <typename T, int N, int MODEL = 0> struct WideSolver {
     KMPC_HORIZON_CONSTANTS(N)
     static constexpr int NTF = (n + 1 + 15) / 16;   // tile rows of K with the rhs row n
     static constexpr int NP = 16 * NTF;              // padded dimension
@@ -35,16 +37,20 @@ template <typename T, int N> struct WideSolver {
     typedef typename Real<T>::acc_t acc_t;
     typedef T real;
     // what kmpc_ipm.h reads: horizon, threads per problem, forms per thread (one), stride of the G_N table, record stride, functor
-    static constexpr int N_ = N, NTH = 256, NF = 1, GS = 128, LSTR = WLIN, MODEL_ID = 0;
+    static constexpr int N_ = N, NTH = 256, NF = 1, GS = 128, LSTR = MODEL == 1 ? KMPC_STG : WLIN, MODEL_ID = MODEL;
     // split adjoint recursion (kmpc_ipm.h, condense_adjoint): threads 128 + j (waves 2 and 3, idle in the unsplit recursion) run the stages below
     // M = N / 2 for the columns j < 2M while threads j < n run the stages from M up: N / 2 trips instead of N
-    static constexpr int MSPLIT = N / 2, LOW0 = 128, GMS = 64, TM = (2 * MSPLIT + 15) / 16;
+    // (Frenet: no split, no G_N / G_M tables -- their LDS goes to the wider stage records)
+    static constexpr int MSPLIT = MODEL == 1 ? 0 : N / 2, LOW0 = 128, GMS = 64, TM = (2 * MSPLIT + 15) / 16;
     static_assert(2 * MSPLIT <= GMS && LOW0 + 2 * MSPLIT <= 256 && N % 2 == 0, "one thread per lower column, G_M rows of 64");
     // LDS map (elements of T)
-    static constexpr int O_LC = 0, O_OPB = (LC + 1) & ~1, O_LIN = O_OPB + 2 * 4 * NP + 256 + 3 * 128 + 3 * GMS + 64, O_XB = O_LIN + WLIN * (N + 1), O_WB = O_XB + 128,
+    static constexpr int O_LC = 0, O_OPB = (LC + 1) & ~1, O_LIN = O_OPB + 2 * 4 * NP + 256 + (MODEL == 1 ? 0 : 3 * 128 + 3 * GMS + 64),
+                         O_XB = O_LIN + LSTR * (N + 1), O_WB = O_XB + 128,
                          O_CBW = O_WB + 256, O_RED = O_CBW + 4 * 64, O_SINV = O_RED + 2 * 32, O_X2 = O_SINV + 16 * NB, O_X3 = O_X2 + 128,
-                         O_GB = O_X3 + 128, O_UB = O_GB + 128, O_CS = O_UB + 128, O_PT = O_CS + 4 * 16, O_KC = O_PT + 32, O_END = O_KC + (sizeof(T) == 8 ? KC_COUNT : 0);
+                         O_GB = O_X3 + 128, O_UB = O_GB + 128, O_CS = O_UB + 128, O_PT = O_CS + 4 * 16, O_KC = O_PT + 32, O_FR = O_KC + (sizeof(T) == 8 ? KC_COUNT : 0),
+                         O_END = O_FR + (MODEL == 1 ? 8 : 0);
     static constexpr int lds_elems() { return O_END; }
+    static_assert(MODEL == 0 || 10 * (N + 1) <= 2 * 4 * NP, "Frenet: the P_k table of condense_frenet lives in the (then idle) panel buffer");
 
     STAMP_MEMBERS
     const KP &P;
@@ -55,8 +61,13 @@ template <typename T, int N> struct WideSolver {
     const T *pt, *cwt;
     int rpar;
     T psi0, v0, vt, rx, ry, rp;   // (x0 = y0 = 0 in vehicle-centred coordinates; u_prev and the offsets are re-read where they are used)
+    // Frenet: start (s, e_y) and K(s) = kp0 s^3 + kp1 s^2 + kp2 s + kp3 -- in LDS (fixed addresses, no register across the solve: held in VGPRs, these
+    // six values put the fp64 instantiations from N = 44 on into scratch)
+    T &x0, &y0, &kp0, &kp1, &kp2, &kp3;
     const T *z0p, *upp_;
-    DEV WideSolver(const KP &p, unsigned char *smem) : P(p), tid(threadIdx.x), lane(threadIdx.x & 63), vid(threadIdx.x), rpar(0)
+    DEV WideSolver(const KP &p, unsigned char *smem)
+        : P(p), tid(threadIdx.x), lane(threadIdx.x & 63), vid(threadIdx.x), rpar(0), x0(fr(smem, 0)), y0(fr(smem, 1)), kp0(fr(smem, 2)), kp1(fr(smem, 3)),
+          kp2(fr(smem, 4)), kp3(fr(smem, 5))
     {
         wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
         T *base = reinterpret_cast<T *>(smem);
@@ -77,10 +88,20 @@ template <typename T, int N> struct WideSolver {
         WGSYNC();
     }
 
+    static DEV T &fr(unsigned char *smem, int i) { return reinterpret_cast<T *>(smem)[(MODEL == 1 ? O_FR : 0) + i]; }
     DEV void load_problem(const T *z0, const T *ref, const T *vtp, const T *upp, int b)
     {
-        // vehicle-centred coordinates (the NLP is translation-invariant; see kmpc_fast.hip)
         z0p = z0 + 4 * (size_t)b; upp_ = upp + 2 * (size_t)b;
+        if constexpr (MODEL == 1) {  // `ref` carries k_poly [B,4]; (s, e_y) are not translation-invariant (K depends on s); zero cost references
+            psi0 = z0p[2]; v0 = z0p[3];
+            vt = vtp[b];
+            rx = ry = rp = (T)0;
+            const T *kp = ref + 4 * (size_t)b;
+            if (tid == 0) { x0 = z0p[0]; y0 = z0p[1]; kp0 = kp[0]; kp1 = kp[1]; kp2 = kp[2]; kp3 = kp[3]; }
+            WGSYNC();
+            return;
+        }
+        // vehicle-centred coordinates (the NLP is translation-invariant; see kmpc_fast.hip)
         const T xoff = z0p[0], yoff = z0p[1];
         psi0 = z0p[2]; v0 = z0p[3];
         vt = vtp[b];
@@ -116,8 +137,8 @@ template <typename T, int N> struct WideSolver {
 
     // ---- hooks of the shared interior-point code (kmpc_ipm.h) ------------------------------------------------------------------------
     DEV T up(int j) const { return upp_[j]; }
-    DEV T xoff() const { return z0p[0]; }
-    DEV T yoff() const { return z0p[1]; }
+    DEV T xoff() const { return MODEL == 1 ? (T)0 : z0p[0]; }
+    DEV T yoff() const { return MODEL == 1 ? (T)0 : z0p[1]; }
     DEV bool rec_writer() const { return wv == 0; }   // every wave holds the same stage data; wave 0 publishes the records
     DEV void refresh_ids() { asm volatile("" : "+v"(tid)); lane = tid & 63; vid = tid; }
     DEV T *pm(int c) const { return x2 + 64 * c; }     // component c of p_j(M), j < 2M: the substitution buffers x2 | x3 are dead while K is built
@@ -141,11 +162,101 @@ template <typename T, int N> struct WideSolver {
     DEV T stage_bcast(T x, int k) const { return readlane_(x, k); }
     DEV T max_any(T x) { T dm[1] = {(T)0}, m[1] = {x}; wg_reduce<0, 1>(dm, m); return m[0]; }
     DEV void stage_form_weights(T w) { const T w1[1] = {w}; ipm::stage_form_weights(*this, w1); }   // (scalar form for the diagnostics kernel)
-    DEV T eval1(T U, StageW<T> &S) { return ipm::eval_cartesian(*this, U, S); }
-    DEV T linearize1(const StageW<T> &S, bool exact) { return ipm::linearize_cartesian(*this, S, exact); }
+    DEV T eval1(T U, StageW<T> &S)
+    {
+        if constexpr (MODEL == 1) return ipm::eval_frenet(*this, U, S);
+        else return ipm::eval_cartesian(*this, U, S);
+    }
+    DEV T linearize1(const StageW<T> &S, bool exact)
+    {
+        if constexpr (MODEL == 1) return ipm::linearize_frenet(*this, S, exact);
+        else return ipm::linearize_cartesian(*this, S, exact);
+    }
     KMPC_IPM_ONE_SLOT_HOOKS
-    DEV void drop_second_order() { ipm::drop_second_order_cartesian(*this); }
-    DEV void condense_adjoint(T sc) { ipm::condense_adjoint(*this, sc); }
+    DEV void drop_second_order()
+    {
+        if constexpr (MODEL == 1) ipm::drop_second_order_frenet(*this);
+        else ipm::drop_second_order_cartesian(*this);
+    }
+    DEV void condense_adjoint(T sc)   // the lower triangle of sc * H (second-order terms included, except the Cartesian m_dd) into the packed image
+    {
+        if constexpr (MODEL == 1) condense_frenet(sc);
+        else ipm::condense_adjoint(*this, sc);
+    }
+
+    // ---- Frenet condensing, classical O(N^2) (the adjoint recursion of the Cartesian model walks G backwards through the inverse of a
+    // unit upper-triangular A_s; the Frenet A_s has A00, A20, A21, A22 != 1) ------------------------------------------------------------
+    //   backward: P_N = W_N, P_k = W_k + A_k^T P_{k+1} A_k  (W_k = 2 Q_k + the state block of record k's second-order terms; 4 x 4
+    //             symmetric, 10 words per stage) -- a serial recursion on wave-uniform values, run by wave 0, into the panel buffer
+    //             (idle until the factorisation);
+    //   forward : thread j < n carries G_{t+1}[:, j] = A_t G_t[:, j] (+ B_t e_j at its birth stage t = j / 2) and writes rows 2t, 2t+1 of
+    //             column j:  H[2t][j] = dt (P_{t+1} G_{t+1})_v,  H[2t+1][j] = B_t,d^T P_{t+1} G_{t+1} + M_t,xd . G_t[:, j] (+ m_dd on the
+    //             diagonal).  Every stage index is wave-uniform (one LDS broadcast per word); waves 0 and 1 hold the columns.
+    DEV void condense_frenet(T sc)
+    {
+        T *ptab = pan;
+        const T dtv = pt[PT_DT];
+        WGSYNC();  // (a factorisation that stopped at a non-positive pivot leaves its last panel unsynchronised)
+        if (wv == 0) {
+            const T Cx2 = cwt[0], Cy2 = cwt[1], Cp2 = cwt[2], Cv2 = cwt[3];
+            const T *m = lin + LSTR * N + 20;   // (record N: no second-order terms, no speed weight on the terminal state)
+            T p00 = Cx2 + m[0], p01 = m[1], p02 = m[2], p03 = m[3], p11 = Cy2 + m[5], p12 = m[6], p13 = m[7], p22 = Cp2 + m[9], p23 = m[10], p33 = m[12];
+            if (lane == 0) { T *o = ptab + 10 * N; o[0] = p00; o[1] = p01; o[2] = p02; o[3] = p03; o[4] = p11; o[5] = p12; o[6] = p13; o[7] = p22; o[8] = p23; o[9] = p33; }
+#pragma nounroll
+            for (int k = N - 1; k >= 1; --k) {
+                const T *q = lin + LSTR * k;
+                const T a00 = q[0], a01 = q[1], a02 = q[2], a03 = q[3], a12 = q[4], a13 = q[5], a20 = q[6], a21 = q[7], a22 = q[8], a23 = q[9];
+                const T *w = q + 20;
+                // y_j = P_{k+1} c_j for the columns c_j of A_k = [a00 a01 a02 a03; 0 1 a12 a13; a20 a21 a22 a23; 0 0 0 1] (the components c_i . y_j needs, i <= j)
+                const T y00 = fma(p02, a20, p00 * a00), y02 = fma(p22, a20, p02 * a00);
+                const T y10 = fma(p02, a21, fma(p00, a01, p01)), y11 = fma(p12, a21, fma(p01, a01, p11)), y12 = fma(p22, a21, fma(p02, a01, p12));
+                const T y20 = fma(p02, a22, fma(p01, a12, p00 * a02)), y21 = fma(p12, a22, fma(p11, a12, p01 * a02)), y22 = fma(p22, a22, fma(p12, a12, p02 * a02));
+                const T y30 = fma(p02, a23, fma(p01, a13, fma(p00, a03, p03))), y31 = fma(p12, a23, fma(p11, a13, fma(p01, a03, p13))),
+                        y32 = fma(p22, a23, fma(p12, a13, fma(p02, a03, p23))), y33 = fma(p23, a23, fma(p13, a13, fma(p03, a03, p33)));
+                // P_k = W_k + c_i . y_j
+                p00 = Cx2 + w[0] + fma(a20, y02, a00 * y00);
+                p01 = w[1] + fma(a20, y12, a00 * y10);
+                p02 = w[2] + fma(a20, y22, a00 * y20);
+                p03 = w[3] + fma(a20, y32, a00 * y30);
+                p11 = Cy2 + w[5] + fma(a21, y12, fma(a01, y10, y11));
+                p12 = w[6] + fma(a21, y22, fma(a01, y20, y21));
+                p13 = w[7] + fma(a21, y32, fma(a01, y30, y31));
+                p22 = Cp2 + w[9] + fma(a22, y22, fma(a12, y21, a02 * y20));
+                p23 = w[10] + fma(a22, y32, fma(a12, y31, a02 * y30));
+                p33 = Cv2 + w[12] + fma(a23, y32, fma(a13, y31, fma(a03, y30, y33)));
+                if (lane == 0) { T *o = ptab + 10 * k; o[0] = p00; o[1] = p01; o[2] = p02; o[3] = p03; o[4] = p11; o[5] = p12; o[6] = p13; o[7] = p22; o[8] = p23; o[9] = p33; }
+            }
+        }
+        WGSYNC();
+        if (tid < n) {
+            const int j = tid;
+            T *colK = Lc + offc_rt(j);
+            T g0 = (T)0, g1 = (T)0, g2 = (T)0, g3 = (T)0;   // sc G_t[:, j] (zero before the column's birth stage; the scaling goes in once, here)
+#pragma nounroll
+            for (int t = 32 * wv; t < N; ++t) {   // (wave 1 holds columns 64 .. n - 1: born at stage 32)
+                const T *q = lin + LSTR * t;
+                const T *pq = ptab + 10 * (t + 1);
+                const T cross = fma(q[33], g3, fma(q[31], g2, fma(q[28], g1, q[24] * g0)));   // M_t,xd . G_t[:, j]
+                T n0 = fma(q[3], g3, fma(q[2], g2, fma(q[1], g1, q[0] * g0)));
+                T n1 = fma(q[5], g3, fma(q[4], g2, g1));
+                T n2 = fma(q[9], g3, fma(q[8], g2, fma(q[7], g1, q[6] * g0)));
+                T n3 = g3;
+                if (j == 2 * t) { n0 = (T)0; n1 = (T)0; n2 = (T)0; n3 = sc * dtv; }
+                if (j == 2 * t + 1) { n0 = sc * q[10]; n1 = sc * q[11]; n2 = sc * q[12]; n3 = (T)0; }
+                g0 = n0; g1 = n1; g2 = n2; g3 = n3;
+                const T y0 = fma(pq[3], g3, fma(pq[2], g2, fma(pq[1], g1, pq[0] * g0)));
+                const T y1 = fma(pq[6], g3, fma(pq[5], g2, fma(pq[4], g1, pq[1] * g0)));
+                const T y2 = fma(pq[8], g3, fma(pq[7], g2, fma(pq[5], g1, pq[2] * g0)));
+                const T y3 = fma(pq[9], g3, fma(pq[8], g2, fma(pq[6], g1, pq[3] * g0)));
+                const T ra = dtv * y3;
+                T rd = fma(q[12], y2, fma(q[11], y1, q[10] * y0)) + cross;
+                if (j == 2 * t + 1) rd += sc * q[34];
+                if (j <= 2 * t) colK[2 * t] = ra;
+                if (j <= 2 * t + 1) colK[2 * t + 1] = rd;
+            }
+        }
+        WGSYNC();
+    }
 
     // Tile rows of wave W (compile-time in everything below: each wave runs its own specialisation, selected once per
     // factorisation by a switch on the wave number; tile indices, liveness tests and register arrays are then all static)
@@ -189,7 +300,7 @@ template <typename T, int N> struct WideSolver {
     template <int W> DEV void build_tiles(T sc, T reg, acc_t (&k0)[Rows<W>::N0], acc_t (&k1)[Rows<W>::N1])
     {
         constexpr int R0 = Rows<W>::R0, R1 = Rows<W>::R1;
-        ipm::kkt_diag_staging(*this, sc, reg, true, dgs, sbs);
+        ipm::kkt_diag_staging(*this, sc, reg, MODEL == 0, dgs, sbs);   // (Frenet: m_dd is in the image already)
         build_row<Rows<W>::N0>(sc, R0, k0);
         if (R1 >= 0) build_row<Rows<W>::N1>(sc, R1, k1);
         WGSYNC();  // dgs / sbs / the odd rows of the image have been consumed: the panel and the factor may overwrite them
@@ -463,6 +574,17 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? (N <= 36 ? 3 : 2) : (N <= 36 
     ipm::run_solver<WideSolver<T, N>>(P, io, smem);
 }
 
+// Frenet-frame functor (kmpc_config.model = 1; io.ref carries k_poly [B,4]), fp64 only.  LDS: the Cartesian map minus the G_N / G_M / hm tables
+// (640 words), plus 20 more words per stage record and 8 for the problem's Frenet scalars -- 46 688 / 52 544 / 59 936 / 66 816 / 75 232 / 79 120 B at
+// N = 32 / 36 / 40 / 44 / 48 / 50.  Two workgroups per CU at every N (245-256 VGPRs, no scratch): at N = 32 / 36 the LDS would allow three, but three
+// cap the registers at 168, which puts the Cartesian kernel into scratch.
+template <typename T, int N>
+__global__ __launch_bounds__(256, 2) void kmpc_solve_wide_frenet_kernel(KP P, KIO<T> io)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[WideSolver<T, N, 1>::lds_elems() * sizeof(T)];
+    ipm::run_solver<WideSolver<T, N, 1>>(P, io, smem);
+}
+
 // diagnostics (tests/test_gpu_kernels.py): the KKT pipeline of this kernel at a given point, form weights, scaling and shift
 template <typename T, int N>
 __global__ __launch_bounds__(256, 2) void kmpc_wide_kkt_kernel(KP P, KDbgK<T> io)
@@ -523,3 +645,21 @@ template bool kmpc_wide_available<double>(int);
 template bool kmpc_wide_available<float>(int);
 template hipError_t kmpc_launch_solve_wide<double>(const KP &, const KIO<double> &, hipStream_t);
 template hipError_t kmpc_launch_solve_wide<float>(const KP &, const KIO<float> &, hipStream_t);
+
+// Frenet functor at the same horizons; fp64 only (kmpc_create refuses fp32 with model = 1 beyond N = 28)
+template <typename T> hipError_t kmpc_launch_solve_wide_frenet(const KP &P, const KIO<T> &io, hipStream_t st)
+{
+    if constexpr (sizeof(T) != 8) return hipErrorInvalidValue;
+    else {
+        if (P.N == 50) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 50>), dim3(P.B), dim3(256), 0, st, P, io);
+        else if (P.N == 48) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 48>), dim3(P.B), dim3(256), 0, st, P, io);
+        else if (P.N == 44) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 44>), dim3(P.B), dim3(256), 0, st, P, io);
+        else if (P.N == 40) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 40>), dim3(P.B), dim3(256), 0, st, P, io);
+        else if (P.N == 36) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 36>), dim3(P.B), dim3(256), 0, st, P, io);
+        else if (P.N == 32) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 32>), dim3(P.B), dim3(256), 0, st, P, io);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
+}
+template hipError_t kmpc_launch_solve_wide_frenet<double>(const KP &, const KIO<double> &, hipStream_t);
+template hipError_t kmpc_launch_solve_wide_frenet<float>(const KP &, const KIO<float> &, hipStream_t);
