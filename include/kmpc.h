@@ -74,7 +74,10 @@ typedef struct kmpc_config {
     int32_t max_ls;      /* back-tracking trial points per iteration */
     int32_t kernel_variant; /* 0 = auto: the compile-time-horizon kernel built for N (see N; at N = 8 batches of 1024 problems or more run the
                                four-problems-per-wave kernel), else the generic one; 1 = always the generic kernel; 2 = as 0 but never the
-                               four-per-wave kernel (one wave / one workgroup per problem at every batch size) */
+                               four-per-wave kernel (one wave / one workgroup per problem at every batch size); 3 = the Frenet model's
+                               four-problems-per-wave kernel at every batch size: accepted only with model = 1 and N = 8 (both dtypes),
+                               KMPC_ERR_ARG otherwise.  Opt-in: with model = 1, N = 8 the values 0 and 2 keep the one-wave kernel.  Measured
+                               in fp64: 1.97 x the one-wave kernel at B = 262 144, 1.17 x at 4096, 0.62 x at 1024 */
     int32_t mu_strategy;    /* barrier update: 0 = Ipopt's default monotone (Fiacco-McCormick), 1 = Mehrotra predictor-corrector
                                (Ipopt's adaptive family; default) */
     int32_t indef_strategy; /* exact Hessian not positive definite: 0 = Gauss-Newton fallback (held for 2 iterations), 1 = Ipopt-style
@@ -89,7 +92,8 @@ typedef struct kmpc_config {
                                Frenet-frame states (s, e_y, e_psi, v) with a cubic curvature polynomial (kmpc_solve_batch_frenet;
                                horizons N <= 24, N = 28 with kernel_variant 0 or 2: the compile-time-horizon kernels carry the functor
                                for N = 8, 12, ..., 28; and N = 32, 36, 40, 44, 48, 50 with kernel_variant 0 or 2 in fp64 only: the
-                               four-wave kernel).  kmpc_create picks the cost defaults of the chosen module. */
+                               four-wave kernel; N = 8 also with kernel_variant 3: four problems per wave, kmpc_quad.hip).  kmpc_create picks
+                               the cost defaults of the chosen module. */
     int32_t start;          /* cold-start point of the inputs (a warm start overrides it): 0 (default) = feed-forward guess inside the bounds
                                (accelerations approach the reference speed, steering the curvature feed-forward); 1 = the reference's own
                                start, every primal 0 (MKZMPCPathFollower.jl:65-72, Q9), moved strictly inside the first-step rate interval

@@ -22,6 +22,7 @@ template <typename T> bool kmpc_wide_available(int N);
 template <typename T> hipError_t kmpc_launch_solve_wide(const KP &, const KIO<T> &, hipStream_t);
 template <typename T> bool kmpc_quad_available(int N);
 template <typename T> hipError_t kmpc_launch_solve_quad(const KP &, const KIO<T> &, hipStream_t);
+template <typename T> hipError_t kmpc_launch_solve_quad_frenet(const KP &, const KIO<T> &, hipStream_t);
 template <typename T> hipError_t kmpc_launch_solve_frenet(const KP &, const KIO<T> &, hipStream_t);
 template <typename T> hipError_t kmpc_launch_solve_fast_frenet(const KP &, const KIO<T> &, hipStream_t);
 template <typename T> hipError_t kmpc_launch_solve_wide_frenet(const KP &, const KIO<T> &, hipStream_t);
@@ -124,12 +125,20 @@ extern "C" int32_t kmpc_create(const kmpc_config *cfg, int32_t device, kmpc_hand
     if (!(cfg->dt > 0) || !(cfg->dt_control > 0) || !(cfg->L_b > 0) || !(cfg->L_a + cfg->L_b > 0) ||
         !(cfg->v_max > cfg->v_min) || !(cfg->a_max > 0) || !(cfg->steer_max > 0) || !(cfg->steer_max < 1.5) ||
         !(cfg->a_dmax > 0) || !(cfg->steer_dmax > 0) || cfg->max_iter < 1 || cfg->max_ls < 1 || !(cfg->tol > 0) ||
-        cfg->kernel_variant < 0 || cfg->kernel_variant > 2 || cfg->mu_strategy < 0 || cfg->mu_strategy > 1 ||
+        cfg->kernel_variant < 0 || cfg->kernel_variant > 3 || cfg->mu_strategy < 0 || cfg->mu_strategy > 1 ||
         cfg->indef_strategy < 0 || cfg->indef_strategy > 2 || cfg->schedule < 0 || cfg->schedule > 1 || cfg->model < 0 || cfg->model > 1 ||
         cfg->start < 0 || cfg->start > 1 ||
         (cfg->model == 1 && cfg->N > 24 && !(cfg->kernel_variant != 1 && (cfg->N == 28 || kmpc_wide_available<double>(cfg->N)))))
         // Frenet: generic kernel up to N = 24, compile-time kernels also at 28 (one wave) and 32 ... 48, 50 (four waves)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: invalid model / solver parameter");
+    if (cfg->kernel_variant == 3) {   // four Frenet problems per wave (kmpc_quad.hip): model 1 at its reference's horizon only
+        if (cfg->model != 1)
+            return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: kernel_variant = 3 is the four-per-wave Frenet kernel (model = 1); for the Cartesian model "
+                        "kernel_variant = 0 picks the four-per-wave kernel by batch size (its padding rows are not gated against the host entry point's completion count)");
+        if (cfg->N != 8)
+            return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: kernel_variant = 3 needs N = 8 (no four-per-wave Frenet kernel at N = %d)", cfg->N);
+        // (both precisions: the fp32 instantiation passed its acceptance run, tests/test_frenet_quad.py::test_frenet_quad_fp32_acceptance)
+    }
     if (cfg->model == 1 && cfg->N > 28 && cfg->dtype != KMPC_F64)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: the Frenet model (model = 1) at N = %d runs in fp64 only (no fp32 four-wave Frenet kernel)", cfg->N);
     int ndev = 0;
@@ -244,7 +253,8 @@ static int solve_dev(kmpc_handle *h, int B, const void *z0, const void *ref, con
     io.done = h->done_flag;   // (set only around the small-batch host entry point's launch)
     // start order: only matters once a launch no longer fits on the chip at once (2 waves x 4 SIMDs x 256 CUs)
     if (h->cfg.model == 1) {  // Frenet functor: `ref` carries k_poly [B,4]; index order (the start-order key reads reference points)
-        if (h->cfg.kernel_variant != 1 && kmpc_fast_available<T>(P.N)) HIPCHK(h, kmpc_launch_solve_fast_frenet<T>(P, io, st));
+        if (h->cfg.kernel_variant == 3) HIPCHK(h, kmpc_launch_solve_quad_frenet<T>(P, io, st));   // four problems per wave: N = 8, every B >= 1
+        else if (h->cfg.kernel_variant != 1 && kmpc_fast_available<T>(P.N)) HIPCHK(h, kmpc_launch_solve_fast_frenet<T>(P, io, st));
         else if (h->cfg.kernel_variant != 1 && P.N > 28) HIPCHK(h, kmpc_launch_solve_wide_frenet<T>(P, io, st));   // four-wave kernel: N = 32 ... 48, 50
         else HIPCHK(h, kmpc_launch_solve_frenet<T>(P, io, st));   // generic kernel: N <= 24
         return KMPC_OK;

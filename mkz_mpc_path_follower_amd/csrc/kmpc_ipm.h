@@ -490,6 +490,62 @@ template <class SV> DEV void drop_second_order_frenet(SV &s)
     xsync<SV::NTH>();
 }
 
+// Classical O(N^2) condensing of the Frenet model, the 4 x 4 block arithmetic both of its back-ends use (kmpc_wide.hip: one thread per column over
+// two waves, the P_k table in the panel buffer; kmpc_quad.hip: one lane per column of a 16-lane row, the table in the row's corrector buffers).
+//   backward: P_N = W_N, P_k = W_k + A_k^T P_{k+1} A_k  (W_k = 2 Q_k + the state block of record k's second-order terms; symmetric, 10 words per
+//             stage: 00 01 02 03 11 12 13 22 23 33), a serial recursion on values that are uniform over the problem's threads;
+//   forward : column j carries sc G_{t+1}[:, j] = A_t G_t[:, j] (+ B_t e_j at its birth stage t = j / 2) and yields rows 2t, 2t+1 of column j:
+//             H[2t][j] = dt (P_{t+1} G_{t+1})_v,  H[2t+1][j] = B_t,d^T P_{t+1} G_{t+1} + M_t,xd . G_t[:, j] (+ m_dd on the diagonal).
+template <typename T> struct FrenetP {
+    T p00, p01, p02, p03, p11, p12, p13, p22, p23, p33;
+    DEV void terminal(const T *m, T Cx2, T Cy2, T Cp2)   // m: second-order block of record N
+    {
+        p00 = Cx2 + m[0]; p01 = m[1]; p02 = m[2]; p03 = m[3]; p11 = Cy2 + m[5]; p12 = m[6]; p13 = m[7]; p22 = Cp2 + m[9]; p23 = m[10]; p33 = m[12];
+    }
+    DEV void store(T *o) const { o[0] = p00; o[1] = p01; o[2] = p02; o[3] = p03; o[4] = p11; o[5] = p12; o[6] = p13; o[7] = p22; o[8] = p23; o[9] = p33; }
+    DEV void step(const T *q, T Cx2, T Cy2, T Cp2, T Cv2)   // q: stage record k; P_{k+1} -> P_k
+    {
+        const T a00 = q[0], a01 = q[1], a02 = q[2], a03 = q[3], a12 = q[4], a13 = q[5], a20 = q[6], a21 = q[7], a22 = q[8], a23 = q[9];
+        const T *w = q + 20;
+        // y_j = P_{k+1} c_j for the columns c_j of A_k = [a00 a01 a02 a03; 0 1 a12 a13; a20 a21 a22 a23; 0 0 0 1] (the components c_i . y_j needs, i <= j)
+        const T y00 = fma(p02, a20, p00 * a00), y02 = fma(p22, a20, p02 * a00);
+        const T y10 = fma(p02, a21, fma(p00, a01, p01)), y11 = fma(p12, a21, fma(p01, a01, p11)), y12 = fma(p22, a21, fma(p02, a01, p12));
+        const T y20 = fma(p02, a22, fma(p01, a12, p00 * a02)), y21 = fma(p12, a22, fma(p11, a12, p01 * a02)), y22 = fma(p22, a22, fma(p12, a12, p02 * a02));
+        const T y30 = fma(p02, a23, fma(p01, a13, fma(p00, a03, p03))), y31 = fma(p12, a23, fma(p11, a13, fma(p01, a03, p13))),
+                y32 = fma(p22, a23, fma(p12, a13, fma(p02, a03, p23))), y33 = fma(p23, a23, fma(p13, a13, fma(p03, a03, p33)));
+        // P_k = W_k + c_i . y_j
+        p00 = Cx2 + w[0] + fma(a20, y02, a00 * y00);
+        p01 = w[1] + fma(a20, y12, a00 * y10);
+        p02 = w[2] + fma(a20, y22, a00 * y20);
+        p03 = w[3] + fma(a20, y32, a00 * y30);
+        p11 = Cy2 + w[5] + fma(a21, y12, fma(a01, y10, y11));
+        p12 = w[6] + fma(a21, y22, fma(a01, y20, y21));
+        p13 = w[7] + fma(a21, y32, fma(a01, y30, y31));
+        p22 = Cp2 + w[9] + fma(a22, y22, fma(a12, y21, a02 * y20));
+        p23 = w[10] + fma(a22, y32, fma(a12, y31, a02 * y30));
+        p33 = Cv2 + w[12] + fma(a23, y32, fma(a13, y31, fma(a03, y30, y33)));
+    }
+};
+// one stage of the forward pass for column j: q = stage record t, pq = P_{t+1}; (g0..g3) = sc G_t[:, j], (n0..n3) = sc G_{t+1}[:, j]
+template <typename T> DEV void frenet_column_step(const T *q, const T *pq, int j, int t, T sc, T dtv, T g0, T g1, T g2, T g3, T &n0, T &n1, T &n2, T &n3, T &ra, T &rd)
+{
+    const T cross = fma(q[33], g3, fma(q[31], g2, fma(q[28], g1, q[24] * g0)));   // M_t,xd . G_t[:, j]
+    n0 = fma(q[3], g3, fma(q[2], g2, fma(q[1], g1, q[0] * g0)));
+    n1 = fma(q[5], g3, fma(q[4], g2, g1));
+    n2 = fma(q[9], g3, fma(q[8], g2, fma(q[7], g1, q[6] * g0)));
+    n3 = g3;
+    if (j == 2 * t) { n0 = (T)0; n1 = (T)0; n2 = (T)0; n3 = sc * dtv; }
+    if (j == 2 * t + 1) { n0 = sc * q[10]; n1 = sc * q[11]; n2 = sc * q[12]; n3 = (T)0; }
+    g0 = n0; g1 = n1; g2 = n2; g3 = n3;
+    const T y0 = fma(pq[3], g3, fma(pq[2], g2, fma(pq[1], g1, pq[0] * g0)));
+    const T y1 = fma(pq[6], g3, fma(pq[5], g2, fma(pq[4], g1, pq[1] * g0)));
+    const T y2 = fma(pq[8], g3, fma(pq[7], g2, fma(pq[5], g1, pq[2] * g0)));
+    const T y3 = fma(pq[9], g3, fma(pq[8], g2, fma(pq[6], g1, pq[3] * g0)));
+    ra = dtv * y3;
+    rd = fma(q[12], y2, fma(q[11], y1, q[10] * y0)) + cross;
+    if (j == 2 * t + 1) rd += sc * q[34];
+}
+
 // stage record as the condensing recursion reads it (uniform address: one LDS broadcast per field)
 template <typename T> struct Rec { T a02, a03, a12, a13, a23, bx, by, bp, mpp, mpv, mpd, mvd, mdd; };
 template <class SV> DEV void load_rec(const SV &s, Rec<typename SV::real> &r, int st)

@@ -16,6 +16,12 @@
 //     FMAs with entries of the lane's row / column read from the packed image; at this size the matrix cores have nothing to offer -- a
 //     trailing update is n^3/3 = 1.4 k flops per problem.
 // Results agree with the one-wave kernel to rounding (different summation trees), not bit for bit: tests/test_quad.py.
+//
+// MODEL 1 (kmpc_solve_quad_frenet_kernel, kernel_variant = 3): the Frenet-frame functor of kmpc_ipm.h at its reference's horizon
+// (MKZMPCPathFollowerFrenet.jl:33).  Its roll-out, costates and the backward P_k recursion of the classical condensing are serial recursions on
+// values that are uniform over a problem's lanes: here they are ROW-uniform, every record address carries the row's base, and one instruction
+// stream serves four problems.  Stage records are KMPC_STG words, there is no G_N table, and condense_frenet replaces the adjoint recursion; KKT
+// assembly, Cholesky, the substitutions and the state machine are the Cartesian ones.  tests/test_frenet_quad.py.
 #include "kmpc_ipm.h"
 
 template <typename T> DEV T row_sum(T x) {   // sum over the 16 lanes of a DPP row, identical bits in every lane
@@ -39,19 +45,21 @@ template <int J> DEV double row_bcast(double x)
 
 template <int R, typename T> DEV T quad_bcast(T x) { return dpp_mov0<R | (R << 2) | (R << 4) | (R << 6), 0xf>(x); }   // value of lane R of the own quad
 
-template <typename T> struct QuadSolver {
+template <typename T, int MODEL = 0> struct QuadSolver {
     static constexpr int N = 8;
     KMPC_HORIZON_CONSTANTS(8)
     typedef T real;
     // what kmpc_ipm.h reads: horizon, threads per problem, forms per thread, stride of the G_N table, record stride, functor
-    static constexpr int N_ = 8, NTH = 16, NF = 3, GS = 16, LSTR = 16, MODEL_ID = 0, MSPLIT = 0 /* every lane of a row carries a column: no spare lanes to split the recursion over */;
+    static constexpr int N_ = 8, NTH = 16, NF = 3, GS = 16, LSTR = MODEL == 1 ? KMPC_STG : 16, MODEL_ID = MODEL, MSPLIT = 0 /* every lane of a row carries a column: no spare lanes to split the recursion over */;
     static_assert(n == 16 && nf <= 48, "one DPP row per problem");
-    // per-row LDS map (elements of T)
+    // per-row LDS map (elements of T); Frenet: wider stage records, no G_N table
     static constexpr int O_LC = 0, O_XB = (LC + 1) & ~1, O_WB = O_XB + 16, O_CB = O_WB + 48, O_LIN = O_CB + 16, O_GNB = O_LIN + LSTR * (N + 1),
-                         O_GB = O_GNB + 3 * GS, O_CS = O_GB + 16, O_UB = O_CS + 16, O_CU = O_UB + 16, O_CL = O_CU + 48, O_EX = O_CL + 48,
-                         ROW = O_EX + 32;
+                         O_GB = O_GNB + (MODEL == 1 ? 0 : 3 * GS), O_CS = O_GB + 16, O_UB = O_CS + 16, O_CU = O_UB + 16, O_CL = O_CU + 48, O_EX = O_CL + 48,
+                         O_FR = O_EX + 32, ROW = O_FR + (MODEL == 1 ? 8 : 0);
     static constexpr int O_PT = 4 * ROW, O_KC = O_PT + 32;
     static constexpr int lds_elems() { return O_KC + (sizeof(T) == 8 ? KC_COUNT : 0); }
+    static_assert(O_CL == O_CU + 48 && 10 * (N + 1) <= 96, "Frenet: the P_k table of condense_frenet lives in the row's corrector buffers cub | clb");
+    static_assert(MODEL == 0 || 4 * (N + 1) <= 48, "linearize_frenet parks the stage cost gradients in wb");
 
     STAMP_MEMBERS
     const KP &P;
@@ -60,11 +68,15 @@ template <typename T> struct QuadSolver {
     const T *pt, *cwt;
     Coef<T> kc;
     T psi0, v0, vt, up0, up1, rx, ry, rp, xoff_, yoff_;
+    // Frenet: start (s, e_y) and K(s) = kp0 s^3 + kp1 s^2 + kp2 s + kp3 of this row's problem -- in the row's LDS (fixed addresses, no register across the solve)
+    T &x0, &y0, &kp0, &kp1, &kp2, &kp3;
     T dinv[4]; // row (lane & 3) of D_q^-1, D_q = the 4x4 diagonal block of L this lane's row runs through (q = lane >> 2)
     T dcol[4]; // column (lane & 3) of D_q^-1
     T yv;      // (L^-1 (-sc g))[lane]
 
-    DEV QuadSolver(const KP &p, unsigned char *smem) : P(p), lane(threadIdx.x & 15), vid(threadIdx.x & 15), row(threadIdx.x >> 4)
+    DEV QuadSolver(const KP &p, unsigned char *smem)
+        : P(p), lane(threadIdx.x & 15), vid(threadIdx.x & 15), row(threadIdx.x >> 4), x0(fr(smem, 0)), y0(fr(smem, 1)), kp0(fr(smem, 2)), kp1(fr(smem, 3)),
+          kp2(fr(smem, 4)), kp3(fr(smem, 5))
     {
         T *base = reinterpret_cast<T *>(smem);
         T *rb = base + ROW * row;
@@ -77,8 +89,20 @@ template <typename T> struct QuadSolver {
         WSYNC();
     }
 
+    static DEV T &fr(unsigned char *smem, int i) { return reinterpret_cast<T *>(smem)[ROW * (int)(threadIdx.x >> 4) + (MODEL == 1 ? O_FR : O_EX) + i]; }
     DEV void load_problem(const T *z0, const T *ref, const T *vtp, const T *upp, int b)   // b: this row's problem
     {
+        if constexpr (MODEL == 1) {  // `ref` carries k_poly [B,4]; (s, e_y) are not translation-invariant (K depends on s); zero cost references
+            const T zx = z0[4 * (size_t)b], zy = z0[4 * (size_t)b + 1];
+            psi0 = z0[4 * (size_t)b + 2]; v0 = z0[4 * (size_t)b + 3];
+            vt = vtp[b];
+            up0 = upp[2 * (size_t)b]; up1 = upp[2 * (size_t)b + 1];
+            const T *kp = ref + 4 * (size_t)b;
+            if (lane == 0) { x0 = zx; y0 = zy; kp0 = kp[0]; kp1 = kp[1]; kp2 = kp[2]; kp3 = kp[3]; }
+            WFENCE();
+            rx = ry = rp = xoff_ = yoff_ = (T)0;
+            return;
+        }
         // vehicle-centred coordinates (the NLP is translation-invariant; see kmpc_fast.hip)
         xoff_ = z0[4 * (size_t)b]; yoff_ = z0[4 * (size_t)b + 1];
         psi0 = z0[4 * (size_t)b + 2]; v0 = z0[4 * (size_t)b + 3];
@@ -124,19 +148,68 @@ template <typename T> struct QuadSolver {
         WFENCE();
         return v;
     }
-    DEV T eval1(T U, StageV<T> &S) { return ipm::eval_cartesian(*this, U, S); }
-    DEV T linearize1(const StageV<T> &S, bool exact) { return ipm::linearize_cartesian(*this, S, exact); }
-    DEV void drop_second_order() { ipm::drop_second_order_cartesian(*this); }
+    DEV T eval1(T U, StageV<T> &S)
+    {
+        if constexpr (MODEL == 1) return ipm::eval_frenet(*this, U, S);
+        else return ipm::eval_cartesian(*this, U, S);
+    }
+    DEV T linearize1(const StageV<T> &S, bool exact)
+    {
+        // (Frenet: the wave_shr:1 / wave_shl:1 moves of the neighbour inputs cross row boundaries only into lanes whose use of them is guarded:
+        //  lane 0 of a row takes no previous input, k >= 1, and lanes >= N - 1 no next one, k < N - 1 = 7)
+        if constexpr (MODEL == 1) return ipm::linearize_frenet(*this, S, exact);
+        else return ipm::linearize_cartesian(*this, S, exact);
+    }
+    DEV void drop_second_order()
+    {
+        if constexpr (MODEL == 1) ipm::drop_second_order_frenet(*this);
+        else ipm::drop_second_order_cartesian(*this);
+    }
+
+    // ---- Frenet condensing, classical O(N^2) (kmpc_ipm.h, FrenetP / frenet_column_step; kmpc_wide.hip, condense_frenet) --------------------------
+    // The backward P_k recursion is row-uniform: every lane of the row runs it in registers (the same instructions serve the wave's four rows) and
+    // lane 0 of the row stores the 10 words of P_N .. P_1 into the row's corrector buffers, dead between the accepted step and the end of the
+    // factorisation.  Forward pass: lane j = column j, all 16 lanes of the row busy, every stage index row-uniform.
+    DEV void condense_frenet(T sc)
+    {
+        T *ptab = cub;
+        const T dtv = pt[PT_DT];
+        {
+            const T Cx2 = cwt[0], Cy2 = cwt[1], Cp2 = cwt[2], Cv2 = cwt[3];
+            ipm::FrenetP<T> p;
+            p.terminal(lin + LSTR * N + 20, Cx2, Cy2, Cp2);   // (record N: no second-order terms, no speed weight on the terminal state)
+            if (lane == 0) p.store(ptab + 10 * N);
+#pragma nounroll
+            for (int k = N - 1; k >= 1; --k) {
+                p.step(lin + LSTR * k, Cx2, Cy2, Cp2, Cv2);
+                if (lane == 0) p.store(ptab + 10 * k);
+            }
+        }
+        WFENCE();
+        const int j = lane;
+        T *colK = Lc + offc_rt(j);
+        T g0 = (T)0, g1 = (T)0, g2 = (T)0, g3 = (T)0;   // sc G_t[:, j] (zero before the column's birth stage)
+#pragma nounroll
+        for (int t = 0; t < N; ++t) {
+            T n0, n1, n2, n3, ra, rd;
+            ipm::frenet_column_step(lin + LSTR * t, ptab + 10 * (t + 1), j, t, sc, dtv, g0, g1, g2, g3, n0, n1, n2, n3, ra, rd);
+            g0 = n0; g1 = n1; g2 = n2; g3 = n3;
+            if (j <= 2 * t) colK[2 * t] = ra;
+            if (j <= 2 * t + 1) colK[2 * t + 1] = rd;
+        }
+        WFENCE();   // the table is consumed: kkt_diag_staging may overwrite cub / clb
+    }
 
     // ---- KKT: K = sc*(H + input Hessian) + A^T W A + reg*I, one row per lane, Cholesky + the affine right-hand side in one sweep ------------
     // (needs stage_form_weights(w) done: wb = form weights, cb = suffix sums of the speed weights)
     DEV bool kkt_factor(T sc, T reg, bool want_hmax)
     {
-        ipm::condense_adjoint(*this, sc);   // column j (rows >= j) of sc*H into the row's packed image
+        if constexpr (MODEL == 1) condense_frenet(sc);
+        else ipm::condense_adjoint(*this, sc);   // column j (rows >= j) of sc*H into the row's packed image
         STAMP(3);
         if (want_hmax) cs[C_HMAX] = row_max(fabs(Lc[offc_rt(lane) + lane]));   // max |sc * H_jj|: scale of the delta_w shift
         T *dgs = cub, *sbs = clb;   // the corrector buffers are dead between the accepted step and the end of the factorisation
-        ipm::kkt_diag_staging(*this, sc, reg, true, dgs, sbs);
+        ipm::kkt_diag_staging(*this, sc, reg, MODEL == 0, dgs, sbs);   // (Frenet: m_dd is in the image already)
         const int i = lane;
         T a[16];   // row i of the KKT matrix, then of its Cholesky factor L (registers only while the factorisation runs)
         const T dt2 = pt[PT_DT2];
@@ -267,6 +340,24 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_ke
     sv.solve(io, b);
 }
 
+// the Frenet functor, same launch shape; start order is index order (io.perm = nullptr), as for every Frenet solve
+template <typename T>
+__global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_frenet_kernel(KP P, KIO<T> io)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[QuadSolver<T, 1>::lds_elems() * sizeof(T)];
+    const int slot = 4 * (int)blockIdx.x + ((int)threadIdx.x >> 4);
+    if (4 * (int)blockIdx.x >= P.B) return;
+    const int sl = slot < P.B ? slot : P.B - 1;   // rows past the end repeat the last problem (same inputs, same stores)
+    const int b = io.perm ? io.perm[sl] : sl;
+#ifdef KMPC_POISON
+    for (int e = threadIdx.x; e < QuadSolver<T, 1>::lds_elems(); e += 64) reinterpret_cast<T *>(smem)[e] = (T)NAN;
+    __syncthreads();
+#endif
+    QuadSolver<T, 1> sv(P, smem);
+    ipm::load_problem_io(sv, io, b);
+    sv.solve(io, b);
+}
+
 template <typename T> bool kmpc_quad_available(int N) { return N == 8; }
 template <typename T> hipError_t kmpc_launch_solve_quad(const KP &P, const KIO<T> &io, hipStream_t st)
 {
@@ -278,3 +369,11 @@ template bool kmpc_quad_available<double>(int);
 template bool kmpc_quad_available<float>(int);
 template hipError_t kmpc_launch_solve_quad<double>(const KP &, const KIO<double> &, hipStream_t);
 template hipError_t kmpc_launch_solve_quad<float>(const KP &, const KIO<float> &, hipStream_t);
+template <typename T> hipError_t kmpc_launch_solve_quad_frenet(const KP &P, const KIO<T> &io, hipStream_t st)
+{
+    if (P.N != 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((kmpc_solve_quad_frenet_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
+    return hipGetLastError();
+}
+template hipError_t kmpc_launch_solve_quad_frenet<double>(const KP &, const KIO<double> &, hipStream_t);
+template hipError_t kmpc_launch_solve_quad_frenet<float>(const KP &, const KIO<float> &, hipStream_t);

@@ -192,6 +192,7 @@ template <typename T, int N, int MODEL = 0> struct WideSolver {
     //   forward : thread j < n carries G_{t+1}[:, j] = A_t G_t[:, j] (+ B_t e_j at its birth stage t = j / 2) and writes rows 2t, 2t+1 of
     //             column j:  H[2t][j] = dt (P_{t+1} G_{t+1})_v,  H[2t+1][j] = B_t,d^T P_{t+1} G_{t+1} + M_t,xd . G_t[:, j] (+ m_dd on the
     //             diagonal).  Every stage index is wave-uniform (one LDS broadcast per word); waves 0 and 1 hold the columns.
+    // (the 4 x 4 block arithmetic of both passes: ipm::FrenetP, ipm::frenet_column_step, shared with kmpc_quad.hip)
     DEV void condense_frenet(T sc)
     {
         T *ptab = pan;
@@ -199,32 +200,13 @@ template <typename T, int N, int MODEL = 0> struct WideSolver {
         WGSYNC();  // (a factorisation that stopped at a non-positive pivot leaves its last panel unsynchronised)
         if (wv == 0) {
             const T Cx2 = cwt[0], Cy2 = cwt[1], Cp2 = cwt[2], Cv2 = cwt[3];
-            const T *m = lin + LSTR * N + 20;   // (record N: no second-order terms, no speed weight on the terminal state)
-            T p00 = Cx2 + m[0], p01 = m[1], p02 = m[2], p03 = m[3], p11 = Cy2 + m[5], p12 = m[6], p13 = m[7], p22 = Cp2 + m[9], p23 = m[10], p33 = m[12];
-            if (lane == 0) { T *o = ptab + 10 * N; o[0] = p00; o[1] = p01; o[2] = p02; o[3] = p03; o[4] = p11; o[5] = p12; o[6] = p13; o[7] = p22; o[8] = p23; o[9] = p33; }
+            ipm::FrenetP<T> p;
+            p.terminal(lin + LSTR * N + 20, Cx2, Cy2, Cp2);   // (record N: no second-order terms, no speed weight on the terminal state)
+            if (lane == 0) p.store(ptab + 10 * N);
 #pragma nounroll
             for (int k = N - 1; k >= 1; --k) {
-                const T *q = lin + LSTR * k;
-                const T a00 = q[0], a01 = q[1], a02 = q[2], a03 = q[3], a12 = q[4], a13 = q[5], a20 = q[6], a21 = q[7], a22 = q[8], a23 = q[9];
-                const T *w = q + 20;
-                // y_j = P_{k+1} c_j for the columns c_j of A_k = [a00 a01 a02 a03; 0 1 a12 a13; a20 a21 a22 a23; 0 0 0 1] (the components c_i . y_j needs, i <= j)
-                const T y00 = fma(p02, a20, p00 * a00), y02 = fma(p22, a20, p02 * a00);
-                const T y10 = fma(p02, a21, fma(p00, a01, p01)), y11 = fma(p12, a21, fma(p01, a01, p11)), y12 = fma(p22, a21, fma(p02, a01, p12));
-                const T y20 = fma(p02, a22, fma(p01, a12, p00 * a02)), y21 = fma(p12, a22, fma(p11, a12, p01 * a02)), y22 = fma(p22, a22, fma(p12, a12, p02 * a02));
-                const T y30 = fma(p02, a23, fma(p01, a13, fma(p00, a03, p03))), y31 = fma(p12, a23, fma(p11, a13, fma(p01, a03, p13))),
-                        y32 = fma(p22, a23, fma(p12, a13, fma(p02, a03, p23))), y33 = fma(p23, a23, fma(p13, a13, fma(p03, a03, p33)));
-                // P_k = W_k + c_i . y_j
-                p00 = Cx2 + w[0] + fma(a20, y02, a00 * y00);
-                p01 = w[1] + fma(a20, y12, a00 * y10);
-                p02 = w[2] + fma(a20, y22, a00 * y20);
-                p03 = w[3] + fma(a20, y32, a00 * y30);
-                p11 = Cy2 + w[5] + fma(a21, y12, fma(a01, y10, y11));
-                p12 = w[6] + fma(a21, y22, fma(a01, y20, y21));
-                p13 = w[7] + fma(a21, y32, fma(a01, y30, y31));
-                p22 = Cp2 + w[9] + fma(a22, y22, fma(a12, y21, a02 * y20));
-                p23 = w[10] + fma(a22, y32, fma(a12, y31, a02 * y30));
-                p33 = Cv2 + w[12] + fma(a23, y32, fma(a13, y31, fma(a03, y30, y33)));
-                if (lane == 0) { T *o = ptab + 10 * k; o[0] = p00; o[1] = p01; o[2] = p02; o[3] = p03; o[4] = p11; o[5] = p12; o[6] = p13; o[7] = p22; o[8] = p23; o[9] = p33; }
+                p.step(lin + LSTR * k, Cx2, Cy2, Cp2, Cv2);
+                if (lane == 0) p.store(ptab + 10 * k);
             }
         }
         WGSYNC();
@@ -234,23 +216,9 @@ template <typename T, int N, int MODEL = 0> struct WideSolver {
             T g0 = (T)0, g1 = (T)0, g2 = (T)0, g3 = (T)0;   // sc G_t[:, j] (zero before the column's birth stage; the scaling goes in once, here)
 #pragma nounroll
             for (int t = 32 * wv; t < N; ++t) {   // (wave 1 holds columns 64 .. n - 1: born at stage 32)
-                const T *q = lin + LSTR * t;
-                const T *pq = ptab + 10 * (t + 1);
-                const T cross = fma(q[33], g3, fma(q[31], g2, fma(q[28], g1, q[24] * g0)));   // M_t,xd . G_t[:, j]
-                T n0 = fma(q[3], g3, fma(q[2], g2, fma(q[1], g1, q[0] * g0)));
-                T n1 = fma(q[5], g3, fma(q[4], g2, g1));
-                T n2 = fma(q[9], g3, fma(q[8], g2, fma(q[7], g1, q[6] * g0)));
-                T n3 = g3;
-                if (j == 2 * t) { n0 = (T)0; n1 = (T)0; n2 = (T)0; n3 = sc * dtv; }
-                if (j == 2 * t + 1) { n0 = sc * q[10]; n1 = sc * q[11]; n2 = sc * q[12]; n3 = (T)0; }
+                T n0, n1, n2, n3, ra, rd;
+                ipm::frenet_column_step(lin + LSTR * t, ptab + 10 * (t + 1), j, t, sc, dtv, g0, g1, g2, g3, n0, n1, n2, n3, ra, rd);
                 g0 = n0; g1 = n1; g2 = n2; g3 = n3;
-                const T y0 = fma(pq[3], g3, fma(pq[2], g2, fma(pq[1], g1, pq[0] * g0)));
-                const T y1 = fma(pq[6], g3, fma(pq[5], g2, fma(pq[4], g1, pq[1] * g0)));
-                const T y2 = fma(pq[8], g3, fma(pq[7], g2, fma(pq[5], g1, pq[2] * g0)));
-                const T y3 = fma(pq[9], g3, fma(pq[8], g2, fma(pq[6], g1, pq[3] * g0)));
-                const T ra = dtv * y3;
-                T rd = fma(q[12], y2, fma(q[11], y1, q[10] * y0)) + cross;
-                if (j == 2 * t + 1) rd += sc * q[34];
                 if (j <= 2 * t) colK[2 * t] = ra;
                 if (j <= 2 * t + 1) colK[2 * t + 1] = rd;
             }

@@ -22,6 +22,11 @@ for dt in (torch.float64, torch.float32):
         o = BatchMPC(N=N, dtype=dt, model=1).solve_frenet(z0, kp, vt, up); torch.cuda.synchronize()
         nb = int((o["status"] != 0).sum()); bad += nb
         print("Frenet    %s N=%2d: not Optimal %d" % (str(dt)[6:], N, nb))
+    z0, kp, vt, up = _cases(512, 8, seed=5)   # four Frenet problems per wave (kernel_variant 3), incl. a batch whose last wave has spare rows
+    for B in (512, 5):
+        o = BatchMPC(N=8, dtype=dt, model=1, kernel_variant=3).solve_frenet(z0[:B], kp[:B], vt[:B], up[:B]); torch.cuda.synchronize()
+        nb = int((o["status"] != 0).sum()); bad += nb
+        print("Frenet quad %s N= 8 B=%d: not Optimal %d" % (str(dt)[6:], B, nb))
 for N, dt in ((13, torch.float64), (20, torch.float64), (50, torch.float64), (20, torch.float32), (33, torch.float32)):   # generic kernel (kernel_variant 1)
     d = make_batch(256, N, cfg_id=2)
     o = BatchMPC(N=N, dtype=dt, kernel_variant=1).solve(d["z0"], d["ref"], d["v_target"], d["u_prev"]); torch.cuda.synchronize()
