@@ -150,6 +150,36 @@ int32_t kmpc_solve_batch_frenet(kmpc_handle *h, int32_t B, const void *z0, const
                                 const void *u_prev, void *warm_U, int32_t warm, void *out_u0, int32_t *out_status,
                                 void *out_cost, void *out_viol, int32_t *out_iters, void *out_U, void *out_X, void *stream);
 
+/* ---- per-problem cost weights and limits ----------------------------------------------------------------------------------------------
+ * Replaces, PER PROBLEM of a batch, update_cost(...) (MKZMPCPathFollower.jl:158-169) and the model constants steer_max, steer_dmax, a_max,
+ * a_dmax, v_min, v_max (:41-48), which kmpc_set_cost / kmpc_config set once for a whole handle: weight sweeps, fleets with different speed or
+ * actuator limits and per-vehicle gain scheduling in ONE launch.  params [B,16], DEVICE, scalars of the handle's dtype (128 B per problem in
+ * fp64, 64 B in fp32: whole lines), record of problem b:
+ *   [0..7]   C_x, C_y, C_psi, C_v, C_dacc, C_ddf, C_acc, C_df   (update_cost order; Frenet handles: slot 0 is the unused x slot, as in
+ *                                                                kmpc_set_cost -- checked for validity, otherwise ignored)
+ *   [8] steer_max  [9] steer_dmax  [10] a_max  [11] a_dmax  [12] v_min  [13] v_max        [14], [15] reserved, must be 0
+ * Everything else (dt, dt_control, L_a, L_b, tolerances, strategies, the horizon) stays with the handle.  A record is valid under the checks
+ * kmpc_create and kmpc_set_cost apply to the same fields: all finite, weights >= 0, a_max, a_dmax, steer_dmax > 0, 0 < steer_max < 1.5,
+ * v_max > v_min, reserved slots 0.  A problem with an invalid record ends with status KMPC_NUMERICAL_ERROR, iters 0, u0 = (0, 0), cost = viol = 0,
+ * out_U / out_X rows 0 (its warm_U row is left as it was) and does not disturb any other problem of the batch; a valid record under which the
+ * problem is infeasible (v0 outside [v_min, v_max], say) reports KMPC_INFEASIBLE exactly as the handle's limits would.
+ * NOT checked, here as in kmpc_create: 0.6 a_max < a_dmax, which the proof that the feed-forward start point is strictly feasible needs
+ * (first finding); a record that breaks it may cost iterations or end Infeasible.
+ * Same dispatch as the plain calls (kernel_variant, batch-size thresholds, start-order pre-pass, whose key reads neither weights nor limits),
+ * every back-end (kernel_variant = 3 included), through kernel instantiations of their own: the plain entry points run the code they ran
+ * before.  A record holding the handle's own values gives the plain call's results bit for bit.  params == NULL IS the plain call.
+ * Out of scope: the packed-record and host-pointer entry points take no per-problem parameters. */
+/* the handle's current weights and limits in record order (HOST, doubles): the record of a problem that changes nothing */
+int32_t kmpc_get_problem_params(kmpc_handle *h, double rec[16]);
+int32_t kmpc_solve_batch_params(kmpc_handle *h, int32_t B, const void *z0, const void *ref, const void *v_target,
+                                const void *u_prev, const void *params, void *warm_U, int32_t warm,
+                                void *out_u0, int32_t *out_status, void *out_cost, void *out_viol,
+                                int32_t *out_iters, void *out_U, void *out_X, void *stream);
+int32_t kmpc_solve_batch_frenet_params(kmpc_handle *h, int32_t B, const void *z0, const void *k_poly, const void *v_target,
+                                       const void *u_prev, const void *params, void *warm_U, int32_t warm,
+                                       void *out_u0, int32_t *out_status, void *out_cost, void *out_viol,
+                                       int32_t *out_iters, void *out_U, void *out_X, void *stream);
+
 /* ---- packed records (ABI v8) -----------------------------------------------------------------------------------------
  * The same hot path on ONE 64-byte-aligned input record and ONE 64-byte output record per problem instead of four input and five output
  * arrays: with the start-order permutation adjacent workgroups read non-adjacent problems, and 8 ... 32-byte entries of separate arrays are

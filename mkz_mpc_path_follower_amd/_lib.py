@@ -31,7 +31,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_debug_condense", "kmpc_debug_mfma_probe",
            "kmpc_path_create", "kmpc_path_destroy", "kmpc_waypoints_batch", "kmpc_path_last_error",
            "kmpc_sim_advance_batch", "kmpc_solve_batch_frenet", "kmpc_debug_kkt", "kmpc_command_batch",
-           "kmpc_record_bytes", "kmpc_pack_records", "kmpc_solve_batch_packed"]
+           "kmpc_record_bytes", "kmpc_pack_records", "kmpc_solve_batch_packed",
+           "kmpc_get_problem_params", "kmpc_solve_batch_params", "kmpc_solve_batch_frenet_params"]
 
 _lib = None
 
@@ -56,6 +57,10 @@ def load():
     L.kmpc_solve_batch.argtypes = sig + [vp]
     L.kmpc_solve_batch_host.argtypes = sig
     L.kmpc_solve_batch_frenet.argtypes = sig + [vp]
+    sig_par = sig[:6] + [vp] + sig[6:] + [vp]   # params [B,16] behind u_prev
+    L.kmpc_solve_batch_params.argtypes = sig_par
+    L.kmpc_solve_batch_frenet_params.argtypes = sig_par
+    L.kmpc_get_problem_params.argtypes = [vp, C.POINTER(C.c_double)]
     L.kmpc_last_error.argtypes = [vp]
     L.kmpc_last_error.restype = C.c_char_p
     L.kmpc_debug_condense.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]

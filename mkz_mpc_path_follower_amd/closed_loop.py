@@ -18,7 +18,7 @@ from .solver import BatchMPC
 
 class ClosedLoop:
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
-                 mpc=None, **options):
+                 mpc=None, params=None, **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -38,6 +38,9 @@ class ClosedLoop:
         self.warm_U = torch.zeros((self.B, self.N, 2), dtype=torch.float64, device=dev)
         self.command_stop = torch.zeros((self.B,), dtype=torch.bool, device=dev)   # the stop latch (one byte per vehicle: kmpc_command_batch's uint8)
         self._lib = _lib.load()
+        # per-vehicle weights and limits [B,16] (BatchMPC.problem_params), owned by the caller: it may be edited between steps (gain scheduling,
+        # a new speed limit); None = the solver handle's values for every vehicle
+        self.params = params
         self.have_warm = False
         self.out = None
         self.k = 0
@@ -52,7 +55,7 @@ class ClosedLoop:
         if time_solve:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-        self.out = self.mpc.solve(z0, ref, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out)
+        self.out = self.mpc.solve(z0, ref, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out, params=self.params)
         solve_s = None
         if time_solve:
             torch.cuda.synchronize()

@@ -233,9 +233,10 @@ static inline int record_scalars(int N, int dtype)
 template <typename T>
 static int solve_dev(kmpc_handle *h, int B, const void *z0, const void *ref, const void *vt, const void *up,
                      void *warmU, int warm, void *u0, int32_t *status, void *cost, void *viol, int32_t *iters,
-                     void *outU, void *outX, hipStream_t st, const void *rec = nullptr, void *orec = nullptr)
+                     void *outU, void *outX, hipStream_t st, const void *rec = nullptr, void *orec = nullptr, const void *par = nullptr)
 {
     KIO<T> io;
+    io.par = (const T *)par;   // per-problem weights and limits [B,16] (kmpc_solve_batch_params), NULL = the handle's
     const int rstride = record_scalars(h->cfg.N, h->cfg.dtype), per = (int)(64 / sizeof(T));
     io.zs = 4; io.rs = h->cfg.model == 1 ? 4 : 3 * (h->cfg.N + 1); io.vs = 1; io.us = 2; io.u0s = 2; io.ss = 1; io.is = 1;
     if (rec) {   // packed records: the same pointers aim into the records, every stride is the record's
@@ -305,6 +306,59 @@ extern "C" int32_t kmpc_solve_batch(kmpc_handle *h, int32_t B, const void *z0, c
                                  out_iters, out_U, out_X, st);
     return solve_dev<float>(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
                             out_iters, out_U, out_X, st);
+}
+
+// MKZMPCPathFollower.jl:158-169 (update_cost) and :41-48 (the limits), as one record per problem
+extern "C" int32_t kmpc_get_problem_params(kmpc_handle *h, double rec[16])
+{
+    if (!h || !rec) return KMPC_ERR_ARG;
+    const kmpc_config &c = h->cfg;
+    memcpy(rec, h->cost, 8 * sizeof(double));
+    rec[8] = c.steer_max; rec[9] = c.steer_dmax; rec[10] = c.a_max; rec[11] = c.a_dmax; rec[12] = c.v_min; rec[13] = c.v_max;
+    rec[14] = rec[15] = 0.0;
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_solve_batch_params(kmpc_handle *h, int32_t B, const void *z0, const void *ref, const void *v_target,
+                                           const void *u_prev, const void *params, void *warm_U, int32_t warm, void *out_u0,
+                                           int32_t *out_status, void *out_cost, void *out_viol, int32_t *out_iters, void *out_U,
+                                           void *out_X, void *stream)
+{
+    if (!params) return kmpc_solve_batch(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, stream);
+    if (!h) return KMPC_ERR_ARG;
+    if (B < 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_params: B=%d", B);
+    if (B == 0) return KMPC_OK;
+    if (!z0 || !ref || !v_target || !u_prev || !out_u0 || !out_status)
+        return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_params: null required buffer");
+    if (h->cfg.model != 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_params: handle was created for the Frenet model; use kmpc_solve_batch_frenet_params");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->cfg.dtype == KMPC_F64)
+        return solve_dev<double>(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
+                                 out_iters, out_U, out_X, st, nullptr, nullptr, params);
+    return solve_dev<float>(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
+                            out_iters, out_U, out_X, st, nullptr, nullptr, params);
+}
+
+extern "C" int32_t kmpc_solve_batch_frenet_params(kmpc_handle *h, int32_t B, const void *z0, const void *k_poly, const void *v_target,
+                                                  const void *u_prev, const void *params, void *warm_U, int32_t warm, void *out_u0,
+                                                  int32_t *out_status, void *out_cost, void *out_viol, int32_t *out_iters, void *out_U,
+                                                  void *out_X, void *stream)
+{
+    if (!params) return kmpc_solve_batch_frenet(h, B, z0, k_poly, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, stream);
+    if (!h) return KMPC_ERR_ARG;
+    if (B < 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet_params: B=%d", B);
+    if (B == 0) return KMPC_OK;
+    if (!z0 || !k_poly || !v_target || !u_prev || !out_u0 || !out_status)
+        return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet_params: null required buffer");
+    if (h->cfg.model != 1) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet_params: handle was created with cfg.model = 0");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->cfg.dtype == KMPC_F64)
+        return solve_dev<double>(h, B, z0, k_poly, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
+                                 out_iters, out_U, out_X, st, nullptr, nullptr, params);
+    return solve_dev<float>(h, B, z0, k_poly, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
+                            out_iters, out_U, out_X, st, nullptr, nullptr, params);
 }
 
 extern "C" int64_t kmpc_record_bytes(int32_t N, int32_t dtype)

@@ -35,7 +35,12 @@ struct KIO {
     int zs, rs, vs, us;      // inputs: z0, ref, v_target, u_prev
     int u0s, ss, is;         // outputs: u0, cost / viol, status / iters
     unsigned int *done;          // host-visible completion counter (pinned memory) of the small-batch host entry point, else NULL: every problem adds 1 after its outputs
+    // per-problem cost weights and limits (kmpc_solve_batch_params): params [B,16], record b = (C[0..7], steer_max, steer_dmax, a_max, a_dmax, v_min, v_max,
+    // 0, 0), indexed by the problem number like every other input; NULL = the handle's values (KP).  Read only by the *_par_kernel instantiations, which
+    // the launchers pick when it is set -- the plain kernels never look at it, so their code is what it was before the member existed.
+    const T *par;
 };
+constexpr int KMPC_PAR_STRIDE = 16;  // scalars per parameter record
 
 template <typename T>
 struct KDbg {

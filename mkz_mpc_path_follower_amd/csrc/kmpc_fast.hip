@@ -525,10 +525,10 @@ template <typename T, int N, int MODEL = 0> struct FastSolver {
 // fp32 at N <= 12 likewise takes a fifth wave (96 VGPRs, 0 / 8 B of scratch): +7 % / +6 % at B = 262 144.
 // The spills cost single-wave latency (N = 8 closed loop, B = 1: 80 -> 86 us p50), so the denser build (kmpc_solve_fast_dense_kernel) is
 // launched only for batches that fill the chip (B > 2048); small batches and the B = 1 latency path keep the spill-free build.
-template <typename T, int N> DEV void kmpc_solve_fast_body(const KP &P, const KIO<T> &io)
+template <typename T, int N, bool PAR = false> DEV void kmpc_solve_fast_body(const KP &P, const KIO<T> &io)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[FastSolver<T, N>::lds_elems() * sizeof(T)];
-    ipm::run_solver<FastSolver<T, N>>(P, io, smem);
+    ipm::run_solver<FastSolver<T, N>, PAR>(P, io, smem);
 }
 template <typename T, int N>
 __global__ __launch_bounds__(64, sizeof(T) == 8 ? (N >= 28 ? 1 : 2) : (N <= 20 ? 4 : 3)) void kmpc_solve_fast_kernel(KP P, KIO<T> io)
@@ -540,6 +540,19 @@ template <typename T, int N>
 __global__ __launch_bounds__(64, sizeof(T) == 8 ? 3 : 5) void kmpc_solve_fast_dense_kernel(KP P, KIO<T> io)
 {
     kmpc_solve_fast_body<T, N>(P, io);
+}
+
+// the same two builds with per-problem weights and limits (io.par, kmpc_solve_batch_params): instantiations of their own, so that the kernels above
+// stay instruction for instruction what they were (tests/test_codegen_budget.py pins their spill and instruction counts)
+template <typename T, int N>
+__global__ __launch_bounds__(64, sizeof(T) == 8 ? (N >= 28 ? 1 : 2) : (N <= 20 ? 4 : 3)) void kmpc_solve_fast_par_kernel(KP P, KIO<T> io)
+{
+    kmpc_solve_fast_body<T, N, true>(P, io);
+}
+template <typename T, int N>
+__global__ __launch_bounds__(64, sizeof(T) == 8 ? 3 : 5) void kmpc_solve_fast_dense_par_kernel(KP P, KIO<T> io)
+{
+    kmpc_solve_fast_body<T, N, true>(P, io);
 }
 
 // diagnostics (tests/test_gpu_kernels.py): the KKT pipeline of THIS kernel -- roll-out, costates, condensing, in-register KKT
@@ -607,11 +620,13 @@ static hipError_t launch_fast_n(const KP &P, const KIO<T> &io, hipStream_t st)
 {
     if constexpr (N <= 12) {
         if (P.B > 2048) {
-            hipLaunchKernelGGL((kmpc_solve_fast_dense_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
+            if (io.par) hipLaunchKernelGGL((kmpc_solve_fast_dense_par_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
+            else hipLaunchKernelGGL((kmpc_solve_fast_dense_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((kmpc_solve_fast_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
+    if (io.par) hipLaunchKernelGGL((kmpc_solve_fast_par_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
+    else hipLaunchKernelGGL((kmpc_solve_fast_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
     return hipGetLastError();
 }
 
@@ -624,10 +639,17 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? (N >= 28 ? 1 : 2) : (N <= 20 ?
     __shared__ __attribute__((aligned(16))) unsigned char smem[FastSolver<T, N, 1>::lds_elems() * sizeof(T)];
     ipm::run_solver<FastSolver<T, N, 1>>(P, io, smem);
 }
+template <typename T, int N>   // per-problem weights and limits (io.par)
+__global__ __launch_bounds__(64, sizeof(T) == 8 ? (N >= 28 ? 1 : 2) : (N <= 20 ? 4 : (N >= 28 ? 2 : 3))) void kmpc_solve_fast_frenet_par_kernel(KP P, KIO<T> io)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[FastSolver<T, N, 1>::lds_elems() * sizeof(T)];
+    ipm::run_solver<FastSolver<T, N, 1>, true>(P, io, smem);
+}
 template <typename T, int N>
 static hipError_t launch_fast_frenet_n(const KP &P, const KIO<T> &io, hipStream_t st)
 {
-    hipLaunchKernelGGL((kmpc_solve_fast_frenet_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
+    if (io.par) hipLaunchKernelGGL((kmpc_solve_fast_frenet_par_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
+    else hipLaunchKernelGGL((kmpc_solve_fast_frenet_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
     return hipGetLastError();
 }
 template <typename T> hipError_t kmpc_launch_solve_fast_frenet(const KP &P, const KIO<T> &io, hipStream_t st)

@@ -800,8 +800,55 @@ template <class SV> DEV void load_problem_io(SV &sv, const KIO<typename SV::real
     sv.load_problem(io.z0 + (size_t)b * io.zs, io.ref + (size_t)b * io.rs, io.vt + (size_t)b * io.vs, io.up + (size_t)b * io.us, 0);
 }
 
-// body of a solve kernel: one problem per workgroup, start order through io.perm
-template <class SV> DEV void run_solver(const KP &P, const KIO<typename SV::real> &io, unsigned char *smem)
+// ---- per-problem cost weights and limits (kmpc_solve_batch_params; record layout: kmpc_device.h, include/kmpc.h) ---------------------------
+// A record is valid under the checks kmpc_create / kmpc_set_cost apply to the same fields of a handle: everything finite, weights >= 0,
+// 0 < steer_max < 1.5, steer_dmax, a_max, a_dmax > 0, v_max > v_min, reserved slots 0.  (i: index in the record, r: its value, vmin: entry 12)
+template <typename T> DEV bool param_entry_valid(int i, T r, T vmin)
+{
+    const bool fin = fabs(r) < (T)INFINITY;   // false for NaN
+    if (i < 8) return fin && r >= (T)0;
+    if (i == 8) return r > (T)0 && r < (T)1.5;
+    if (i < 12) return fin && r > (T)0;
+    if (i == 12) return fin;
+    if (i == 13) return fin && r > vmin;
+    return r == (T)0;
+}
+// where entry i < 14 of a record lives in the parameter table (weights: doubled, as fill_param_table stores them -- doubling is exact, so the
+// table holds bit for bit what the host's 2 * C_i gives for the same number)
+DEV int param_table_slot(int i)
+{
+    return i < 8 ? PT_W + i : i == 8 ? PT_STEER_MAX : i == 9 ? PT_STEER_DMAX : i == 10 ? PT_A_MAX : i == 11 ? PT_A_DMAX : i == 12 ? PT_V_MIN : PT_V_MAX;
+}
+// Thread `t` (0 .. 15 of the problem's wave or row; others idle) checks entry t of the record and, where `writer`, replaces the handle's value in the
+// LDS table `pt` (already filled from KP).  Returns this thread's verdict; the caller reduces it over the problem's threads and orders the table reads.
+template <typename T> DEV bool apply_param_record(T *pt, const T *rec, int t, bool writer)
+{
+    if (t >= KMPC_PAR_STRIDE) return true;
+    const T r = rec[t], vmin = rec[12];
+    if (writer && t < 14) pt[param_table_slot(t)] = t < 8 ? (T)2 * r : r;
+    return param_entry_valid(t, r, vmin);
+}
+// outputs of a problem whose record is invalid: KMPC_NUMERICAL_ERROR, no iteration, zero command / plan / prediction / cost / violation (finite, as
+// include/kmpc.h promises for every call); the warm-start buffer keeps what the caller put there.  t: thread of the problem, nth: threads per problem
+template <typename T> DEV void refuse_problem(const KIO<T> &io, int b, int N, int t, int nth)
+{
+    const int n = 2 * N;
+    for (int j = t; j < n; j += nth) {
+        if (io.outU) io.outU[(size_t)b * n + j] = (T)0;
+        if (j < 2) io.u0[(size_t)b * io.u0s + j] = (T)0;
+    }
+    if (io.outX) for (int j = t; j < 4 * (N + 1); j += nth) io.outX[(size_t)b * (N + 1) * 4 + j] = (T)0;
+    if (t == 0) {
+        io.status[(size_t)b * io.is] = 3;   // KMPC_NUMERICAL_ERROR
+        if (io.cost) io.cost[(size_t)b * io.ss] = (T)0;
+        if (io.viol) io.viol[(size_t)b * io.ss] = (T)0;
+        if (io.iters) io.iters[(size_t)b * io.is] = 0;
+    }
+}
+
+// body of a solve kernel: one problem per workgroup, start order through io.perm.  PAR: the instantiation behind kmpc_solve_batch_params -- the
+// problem's own weights and limits replace the handle's in the table before anything reads them; the solve itself is the same code
+template <class SV, bool PAR = false> DEV void run_solver(const KP &P, const KIO<typename SV::real> &io, unsigned char *smem)
 {
     if ((int)blockIdx.x >= P.B) return;
     const int b = io.perm ? io.perm[blockIdx.x] : (int)blockIdx.x;
@@ -811,6 +858,13 @@ template <class SV> DEV void run_solver(const KP &P, const KIO<typename SV::real
     __syncthreads();
 #endif
     SV sv(P, smem);
+    if constexpr (PAR) {
+        // every wave checks the whole record (so the verdict is in all of them without an exchange), the first 14 threads write the table
+        typedef typename SV::real TR;
+        const bool ok = __all(apply_param_record(const_cast<TR *>(sv.pt), io.par + (size_t)b * KMPC_PAR_STRIDE, (int)threadIdx.x & 63, (int)threadIdx.x < 14));
+        xsync<SV::NTH>();
+        if (!ok) { refuse_problem(io, b, SV::N_, (int)threadIdx.x, SV::NTH); return; }
+    }
     load_problem_io(sv, io, b);
     sv.solve(io, b);
 }

@@ -991,6 +991,38 @@ __global__ __launch_bounds__(64) void kmpc_solve_frenet_kernel(KP P, KIO<T> io)
     sv.solve(io, b);
 }
 
+// per-problem weights and limits (io.par, kmpc_solve_batch_params), both models.  This kernel reads its parameters straight from the argument block (the
+// table of ipm::solve is a register array filled from it, and the model code reads P.v_max and friends in place), so the instantiation works on a copy of
+// the block with the problem's record written over the handle's values: the solver code is the plain kernel's, line for line.
+template <typename T, int NT, int MODEL>
+__global__ __launch_bounds__(64) void kmpc_solve_par_kernel(KP P, KIO<T> io)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if ((int)blockIdx.x >= P.B) return;
+    const int b = io.perm ? io.perm[blockIdx.x] : (int)blockIdx.x;
+#ifdef KMPC_POISON  // diagnostic build (make poison): every LDS word starts as NaN
+    { T *w_ = reinterpret_cast<T *>(smem); const int ne_ = (int)(kmpc_lds_bytes<T>(P.N, NT) / sizeof(T));
+      for (int e = threadIdx.x; e < ne_; e += 64) w_[e] = (T)NAN;
+      __syncthreads(); }
+#endif
+    const T *rec = io.par + (size_t)b * KMPC_PAR_STRIDE;
+    T r[KMPC_PAR_STRIDE];
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < KMPC_PAR_STRIDE; ++i) r[i] = rec[i];
+#pragma unroll
+    for (int i = 0; i < KMPC_PAR_STRIDE; ++i) ok = ok && ipm::param_entry_valid(i, r[i], r[12]);
+    if (!ok) { ipm::refuse_problem(io, b, P.N, (int)threadIdx.x, 64); return; }
+    KP Q = P;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { Q.C[i] = (double)r[i]; Q.C2[i] = (double)((T)2 * r[i]); }
+    Q.steer_max = (double)r[8]; Q.steer_dmax = (double)r[9]; Q.a_max = (double)r[10]; Q.a_dmax = (double)r[11]; Q.v_min = (double)r[12]; Q.v_max = (double)r[13];
+    T scalars[16], params[32];
+    Solver<T, NT, MODEL> sv(Q, smem, scalars, params);
+    ipm::load_problem_io(sv, io, b);   // (plain strides on this path: the same loads as the Frenet kernel's load_problem)
+    sv.solve(io, b);
+}
+
 // diagnostics: condensed Hessian / gradient / cost at a given U (used by the parity tests)
 template <typename T, int NT>
 __global__ __launch_bounds__(64) void kmpc_condense_kernel(KP P, KDbg<T> io)
@@ -1060,6 +1092,13 @@ static hipError_t launch_solve_nt(const KP &P, const KIO<T> &io, hipStream_t st)
 {
     const size_t lds = kmpc_lds_bytes<T>(P.N, NT);
     static size_t lds_set[64] = {0};
+    if (io.par) {
+        static size_t lds_set_par[64] = {0};
+        hipError_t e = ensure_dynamic_lds(&kmpc_solve_par_kernel<T, NT, 0>, lds, lds_set_par);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((kmpc_solve_par_kernel<T, NT, 0>), dim3(P.B), dim3(64), lds, st, P, io);
+        return hipGetLastError();
+    }
     hipError_t e = ensure_dynamic_lds(&kmpc_solve_kernel<T, NT>, lds, lds_set);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((kmpc_solve_kernel<T, NT>), dim3(P.B), dim3(64), lds, st, P, io);
@@ -1070,6 +1109,13 @@ static hipError_t launch_solve_frenet_nt(const KP &P, const KIO<T> &io, hipStrea
 {
     const size_t lds = kmpc_lds_bytes<T>(P.N, NT);
     static size_t lds_set[64] = {0};
+    if (io.par) {
+        static size_t lds_set_par[64] = {0};
+        hipError_t e = ensure_dynamic_lds(&kmpc_solve_par_kernel<T, NT, 1>, lds, lds_set_par);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((kmpc_solve_par_kernel<T, NT, 1>), dim3(P.B), dim3(64), lds, st, P, io);
+        return hipGetLastError();
+    }
     hipError_t e = ensure_dynamic_lds(&kmpc_solve_frenet_kernel<T, NT>, lds, lds_set);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((kmpc_solve_frenet_kernel<T, NT>), dim3(P.B), dim3(64), lds, st, P, io);

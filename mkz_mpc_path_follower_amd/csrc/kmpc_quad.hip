@@ -45,7 +45,9 @@ template <int J> DEV double row_bcast(double x)
 
 template <int R, typename T> DEV T quad_bcast(T x) { return dpp_mov0<R | (R << 2) | (R << 4) | (R << 6), 0xf>(x); }   // value of lane R of the own quad
 
-template <typename T, int MODEL = 0> struct QuadSolver {
+// ROWPT: one parameter table per row instead of one per wave -- the instantiation behind kmpc_solve_batch_params, whose four problems may each carry
+// weights and limits of their own (+ 96 words of LDS: 20 480 B for the Cartesian fp64 kernel, still eight workgroups per CU)
+template <typename T, int MODEL = 0, bool ROWPT = false> struct QuadSolver {
     static constexpr int N = 8;
     KMPC_HORIZON_CONSTANTS(8)
     typedef T real;
@@ -56,7 +58,7 @@ template <typename T, int MODEL = 0> struct QuadSolver {
     static constexpr int O_LC = 0, O_XB = (LC + 1) & ~1, O_WB = O_XB + 16, O_CB = O_WB + 48, O_LIN = O_CB + 16, O_GNB = O_LIN + LSTR * (N + 1),
                          O_GB = O_GNB + (MODEL == 1 ? 0 : 3 * GS), O_CS = O_GB + 16, O_UB = O_CS + 16, O_CU = O_UB + 16, O_CL = O_CU + 48, O_EX = O_CL + 48,
                          O_FR = O_EX + 32, ROW = O_FR + (MODEL == 1 ? 8 : 0);
-    static constexpr int O_PT = 4 * ROW, O_KC = O_PT + 32;
+    static constexpr int O_PT = 4 * ROW, O_KC = O_PT + (ROWPT ? 4 * 32 : 32);
     static constexpr int lds_elems() { return O_KC + (sizeof(T) == 8 ? KC_COUNT : 0); }
     static_assert(O_CL == O_CU + 48 && 10 * (N + 1) <= 96, "Frenet: the P_k table of condense_frenet lives in the row's corrector buffers cub | clb");
     static_assert(MODEL == 0 || 4 * (N + 1) <= 48, "linearize_frenet parks the stage cost gradients in wb");
@@ -84,8 +86,13 @@ template <typename T, int MODEL = 0> struct QuadSolver {
         ubest = rb + O_UB; cub = rb + O_CU; clb = rb + O_CL; ex = rb + O_EX;
         kc.tab = base + O_KC;
         if (sizeof(T) == 8 && threadIdx.x < KC_COUNT) const_cast<T *>(kc.tab)[threadIdx.x] = (T)kmpc_coef[threadIdx.x];
-        pt = base + O_PT; cwt = pt + PT_W;
-        if (threadIdx.x == 0) ipm::fill_param_table(base + O_PT, p, nf);
+        if constexpr (ROWPT) {
+            pt = base + O_PT + 32 * row; cwt = pt + PT_W;
+            if (lane == 0) ipm::fill_param_table(base + O_PT + 32 * row, p, nf);
+        } else {
+            pt = base + O_PT; cwt = pt + PT_W;
+            if (threadIdx.x == 0) ipm::fill_param_table(base + O_PT, p, nf);
+        }
         WSYNC();
     }
 
@@ -358,11 +365,45 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_fr
     sv.solve(io, b);
 }
 
+// per-problem weights and limits (io.par, kmpc_solve_batch_params): row r of a wave replaces the handle's values in ITS table by its problem's record;
+// a row whose record is invalid writes the refusal and leaves, the other rows of the wave solve on (rows branch independently: kmpc_ipm.h, xsync)
+template <typename T, int MODEL> DEV void kmpc_solve_quad_par_body(const KP &P, const KIO<T> &io, unsigned char *smem)
+{
+    typedef QuadSolver<T, MODEL, true> SV;
+    const int slot = 4 * (int)blockIdx.x + ((int)threadIdx.x >> 4);
+    if (4 * (int)blockIdx.x >= P.B) return;
+    const int sl = slot < P.B ? slot : P.B - 1;   // rows past the end repeat the last problem (same inputs, same stores)
+    const int b = io.perm ? io.perm[sl] : sl;
+#ifdef KMPC_POISON
+    for (int e = threadIdx.x; e < SV::lds_elems(); e += 64) reinterpret_cast<T *>(smem)[e] = (T)NAN;
+    __syncthreads();
+#endif
+    SV sv(P, smem);
+    const bool mine = ipm::apply_param_record(const_cast<T *>(sv.pt), io.par + (size_t)b * KMPC_PAR_STRIDE, sv.lane, true);
+    WFENCE();
+    if (row_max(mine ? (T)0 : (T)1) != (T)0) { ipm::refuse_problem(io, b, 8, sv.lane, 16); return; }
+    ipm::load_problem_io(sv, io, b);
+    sv.solve(io, b);
+}
+template <typename T>
+__global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_par_kernel(KP P, KIO<T> io)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[QuadSolver<T, 0, true>::lds_elems() * sizeof(T)];
+    kmpc_solve_quad_par_body<T, 0>(P, io, smem);
+}
+template <typename T>
+__global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_frenet_par_kernel(KP P, KIO<T> io)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[QuadSolver<T, 1, true>::lds_elems() * sizeof(T)];
+    kmpc_solve_quad_par_body<T, 1>(P, io, smem);
+}
+
 template <typename T> bool kmpc_quad_available(int N) { return N == 8; }
 template <typename T> hipError_t kmpc_launch_solve_quad(const KP &P, const KIO<T> &io, hipStream_t st)
 {
     if (P.N != 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((kmpc_solve_quad_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
+    if (io.par) hipLaunchKernelGGL((kmpc_solve_quad_par_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
+    else hipLaunchKernelGGL((kmpc_solve_quad_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
     return hipGetLastError();
 }
 template bool kmpc_quad_available<double>(int);
@@ -372,7 +413,8 @@ template hipError_t kmpc_launch_solve_quad<float>(const KP &, const KIO<float> &
 template <typename T> hipError_t kmpc_launch_solve_quad_frenet(const KP &P, const KIO<T> &io, hipStream_t st)
 {
     if (P.N != 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((kmpc_solve_quad_frenet_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
+    if (io.par) hipLaunchKernelGGL((kmpc_solve_quad_frenet_par_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
+    else hipLaunchKernelGGL((kmpc_solve_quad_frenet_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
     return hipGetLastError();
 }
 template hipError_t kmpc_launch_solve_quad_frenet<double>(const KP &, const KIO<double> &, hipStream_t);

@@ -541,6 +541,13 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? (N <= 36 ? 3 : 2) : (N <= 36 
     __shared__ __attribute__((aligned(16))) unsigned char smem[WideSolver<T, N>::lds_elems() * sizeof(T)];
     ipm::run_solver<WideSolver<T, N>>(P, io, smem);
 }
+// per-problem weights and limits (io.par, kmpc_solve_batch_params): an instantiation of its own, the kernel above stays what it was
+template <typename T, int N>
+__global__ __launch_bounds__(256, sizeof(T) == 8 ? (N <= 36 ? 3 : 2) : (N <= 36 ? 5 : 4)) void kmpc_solve_wide_par_kernel(KP P, KIO<T> io)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[WideSolver<T, N>::lds_elems() * sizeof(T)];
+    ipm::run_solver<WideSolver<T, N>, true>(P, io, smem);
+}
 
 // Frenet-frame functor (kmpc_config.model = 1; io.ref carries k_poly [B,4]), fp64 only.  LDS: the Cartesian map minus the G_N / G_M / hm tables
 // (640 words), plus 20 more words per stage record and 8 for the problem's Frenet scalars -- 46 688 / 52 544 / 59 936 / 66 816 / 75 232 / 79 120 B at
@@ -551,6 +558,12 @@ __global__ __launch_bounds__(256, 2) void kmpc_solve_wide_frenet_kernel(KP P, KI
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[WideSolver<T, N, 1>::lds_elems() * sizeof(T)];
     ipm::run_solver<WideSolver<T, N, 1>>(P, io, smem);
+}
+template <typename T, int N>   // per-problem weights and limits (io.par)
+__global__ __launch_bounds__(256, 2) void kmpc_solve_wide_frenet_par_kernel(KP P, KIO<T> io)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[WideSolver<T, N, 1>::lds_elems() * sizeof(T)];
+    ipm::run_solver<WideSolver<T, N, 1>, true>(P, io, smem);
 }
 
 // diagnostics (tests/test_gpu_kernels.py): the KKT pipeline of this kernel at a given point, form weights, scaling and shift
@@ -598,14 +611,19 @@ template hipError_t kmpc_launch_wide_kkt<float>(const KP &, const KDbgK<float> &
 
 // horizons whose n + 1 rows make 7 (N = 48, the BASELINE's 50), 6 (N = 40, 44) or 5 (N = 32, 36) tile rows, with one thread per form (5N - 2 <= 256)
 template <typename T> bool kmpc_wide_available(int N) { return N == 50 || N == 48 || N == 44 || N == 40 || N == 36 || N == 32; }
+template <typename T, int N> static void launch_wide_n(const KP &P, const KIO<T> &io, hipStream_t st)
+{
+    if (io.par) hipLaunchKernelGGL((kmpc_solve_wide_par_kernel<T, N>), dim3(P.B), dim3(256), 0, st, P, io);
+    else hipLaunchKernelGGL((kmpc_solve_wide_kernel<T, N>), dim3(P.B), dim3(256), 0, st, P, io);
+}
 template <typename T> hipError_t kmpc_launch_solve_wide(const KP &P, const KIO<T> &io, hipStream_t st)
 {
-    if (P.N == 50) hipLaunchKernelGGL((kmpc_solve_wide_kernel<T, 50>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 48) hipLaunchKernelGGL((kmpc_solve_wide_kernel<T, 48>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 44) hipLaunchKernelGGL((kmpc_solve_wide_kernel<T, 44>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 40) hipLaunchKernelGGL((kmpc_solve_wide_kernel<T, 40>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 36) hipLaunchKernelGGL((kmpc_solve_wide_kernel<T, 36>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 32) hipLaunchKernelGGL((kmpc_solve_wide_kernel<T, 32>), dim3(P.B), dim3(256), 0, st, P, io);
+    if (P.N == 50) launch_wide_n<T, 50>(P, io, st);
+    else if (P.N == 48) launch_wide_n<T, 48>(P, io, st);
+    else if (P.N == 44) launch_wide_n<T, 44>(P, io, st);
+    else if (P.N == 40) launch_wide_n<T, 40>(P, io, st);
+    else if (P.N == 36) launch_wide_n<T, 36>(P, io, st);
+    else if (P.N == 32) launch_wide_n<T, 32>(P, io, st);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -615,16 +633,21 @@ template hipError_t kmpc_launch_solve_wide<double>(const KP &, const KIO<double>
 template hipError_t kmpc_launch_solve_wide<float>(const KP &, const KIO<float> &, hipStream_t);
 
 // Frenet functor at the same horizons; fp64 only (kmpc_create refuses fp32 with model = 1 beyond N = 28)
+template <typename T, int N> static void launch_wide_frenet_n(const KP &P, const KIO<T> &io, hipStream_t st)
+{
+    if (io.par) hipLaunchKernelGGL((kmpc_solve_wide_frenet_par_kernel<T, N>), dim3(P.B), dim3(256), 0, st, P, io);
+    else hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, N>), dim3(P.B), dim3(256), 0, st, P, io);
+}
 template <typename T> hipError_t kmpc_launch_solve_wide_frenet(const KP &P, const KIO<T> &io, hipStream_t st)
 {
     if constexpr (sizeof(T) != 8) return hipErrorInvalidValue;
     else {
-        if (P.N == 50) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 50>), dim3(P.B), dim3(256), 0, st, P, io);
-        else if (P.N == 48) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 48>), dim3(P.B), dim3(256), 0, st, P, io);
-        else if (P.N == 44) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 44>), dim3(P.B), dim3(256), 0, st, P, io);
-        else if (P.N == 40) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 40>), dim3(P.B), dim3(256), 0, st, P, io);
-        else if (P.N == 36) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 36>), dim3(P.B), dim3(256), 0, st, P, io);
-        else if (P.N == 32) hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, 32>), dim3(P.B), dim3(256), 0, st, P, io);
+        if (P.N == 50) launch_wide_frenet_n<T, 50>(P, io, st);
+        else if (P.N == 48) launch_wide_frenet_n<T, 48>(P, io, st);
+        else if (P.N == 44) launch_wide_frenet_n<T, 44>(P, io, st);
+        else if (P.N == 40) launch_wide_frenet_n<T, 40>(P, io, st);
+        else if (P.N == 36) launch_wide_frenet_n<T, 36>(P, io, st);
+        else if (P.N == 32) launch_wide_frenet_n<T, 32>(P, io, st);
         else return hipErrorInvalidValue;
         return hipGetLastError();
     }

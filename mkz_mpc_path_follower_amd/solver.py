@@ -64,6 +64,20 @@ class BatchMPC:
         w = (C.c_double * 8)(cx, cy, cp, cv, cda, cdd, ca, cd)
         _lib.check(self.lib.kmpc_set_cost(self.h, w), self.h)
 
+    # ---- per-problem weights and limits (kmpc_solve_batch_params; record layout of include/kmpc.h) ----------
+    P_RECORD = 16                 # scalars per record
+    P_WEIGHTS = slice(0, 8)       # update_cost order: C_x, C_y, C_psi, C_v, C_dacc, C_ddf, C_acc, C_df
+    P_STEER_MAX, P_STEER_DMAX, P_A_MAX, P_A_DMAX, P_V_MIN, P_V_MAX = 8, 9, 10, 11, 12, 13
+    P_RESERVED = slice(14, 16)    # must stay 0
+
+    def problem_params(self, B):
+        """[B,16] device tensor of the handle's dtype, every row the handle's current weights and limits (kmpc_get_problem_params): edit
+        columns (P_WEIGHTS, P_V_MAX, ...) per problem and pass it as `params=` to solve() / solve_frenet()."""
+        rec = (C.c_double * 16)()
+        _lib.check(self.lib.kmpc_get_problem_params(self.h, rec), self.h)
+        row = torch.tensor(list(rec), dtype=torch.float64).to(self.dtype)
+        return row.to(self.device).repeat(int(B), 1).contiguous()
+
     def _dev(self, a, shape):
         # (a device tensor of the right type passes straight through: the B = 1 latency path spends its time here otherwise)
         if type(a) is torch.Tensor and a.dtype == self.dtype and a.device == self.device and a.is_contiguous():
@@ -97,7 +111,7 @@ class BatchMPC:
         o.ptrs = tuple(_ptr(o.get(k)) for k in ("u0", "status", "cost", "viol", "iters", "U", "X"))  # valid while `refs` match
         return o
 
-    def _solve(self, entry, z0, second, second_shape, v_target, u_prev, warm_U, warm, want_U, want_X, out):
+    def _solve(self, entry, z0, second, second_shape, v_target, u_prev, warm_U, warm, want_U, want_X, out, params=None, entry_params=None):
         N = self.N
         z0 = self._dev(z0, (len(z0), 4))
         B = z0.shape[0]
@@ -109,26 +123,36 @@ class BatchMPC:
         o = self._outputs(out, B, want_U, want_X)
         stream = C.c_void_p(_raw_stream(self.device.index))
         pu0, pst, pco, pvi, pit, pU, pX = o.ptrs
-        rc = entry(self.h, B, _ptr(z0), _ptr(second), _ptr(v_target), _ptr(u_prev),
-                   _ptr(warm_U), 1 if (warm and warm_U is not None) else 0,
-                   pu0, pst, pco, pvi, pit, pU if want_U else None, pX if want_X else None, stream)
+        if params is not None:
+            params = self._dev(params, (B, self.P_RECORD))
+            rc = entry_params(self.h, B, _ptr(z0), _ptr(second), _ptr(v_target), _ptr(u_prev), _ptr(params),
+                              _ptr(warm_U), 1 if (warm and warm_U is not None) else 0,
+                              pu0, pst, pco, pvi, pit, pU if want_U else None, pX if want_X else None, stream)
+        else:
+            rc = entry(self.h, B, _ptr(z0), _ptr(second), _ptr(v_target), _ptr(u_prev),
+                       _ptr(warm_U), 1 if (warm and warm_U is not None) else 0,
+                       pu0, pst, pco, pvi, pit, pU if want_U else None, pX if want_X else None, stream)
         _lib.check(rc, self.h)
         if warm_U is not None:
             o["warm_U"] = warm_U
         return o
 
-    def solve(self, z0, ref, v_target, u_prev, warm_U=None, warm=False, want_U=False, want_X=False, out=None):
+    def solve(self, z0, ref, v_target, u_prev, warm_U=None, warm=False, want_U=False, want_X=False, out=None, params=None):
         """z0[B,4], ref[B,N+1,3], v_target[B], u_prev[B,2] (acc, steer) -> dict of device tensors.
 
         Asynchronous on torch's current stream.  `out` may carry the output dict of a previous call: its tensors are
         reused when batch size, dtype and device match (no allocation in the timed path), otherwise replaced.
+        `params` [B,16] (problem_params()): weights and limits per problem; a problem with an invalid record ends with
+        status 3, iters 0 and zero outputs.  None = the handle's values through the plain entry point.
         """
-        return self._solve(self.lib.kmpc_solve_batch, z0, ref, (self.N + 1, 3), v_target, u_prev, warm_U, warm, want_U, want_X, out)
+        return self._solve(self.lib.kmpc_solve_batch, z0, ref, (self.N + 1, 3), v_target, u_prev, warm_U, warm, want_U, want_X, out,
+                           params, self.lib.kmpc_solve_batch_params)
 
-    def solve_frenet(self, z0, k_poly, v_target, u_prev, warm_U=None, warm=False, want_U=False, want_X=False, out=None):
+    def solve_frenet(self, z0, k_poly, v_target, u_prev, warm_U=None, warm=False, want_U=False, want_X=False, out=None, params=None):
         """Frenet-frame variant (handle created with model=1): z0[B,4] = (s, e_y, e_psi, v), k_poly[B,4] curvature polynomial,
-        highest degree first; X[B,N+1,4] = (s, e_y, e_psi, v).  Otherwise as solve()."""
-        return self._solve(self.lib.kmpc_solve_batch_frenet, z0, k_poly, (4,), v_target, u_prev, warm_U, warm, want_U, want_X, out)
+        highest degree first; X[B,N+1,4] = (s, e_y, e_psi, v).  Otherwise as solve() (`params`: slot 0 of the weights is the unused x slot)."""
+        return self._solve(self.lib.kmpc_solve_batch_frenet, z0, k_poly, (4,), v_target, u_prev, warm_U, warm, want_U, want_X, out,
+                           params, self.lib.kmpc_solve_batch_frenet_params)
 
     # ---- packed records (ABI v8, kmpc_solve_batch_packed; include/kmpc.h) -------------------------
     def record_scalars(self):

@@ -118,3 +118,45 @@ def make_ood_batch(B, N, seed, paths=None, dt=0.2, dtype=np.float64):
     z0 = np.stack([x0 - e_y * np.sin(h0), y0 + e_y * np.cos(h0), psi0, v0], axis=-1)
     u_prev = np.stack([acc_prev, df_prev], axis=-1)
     return dict(z0=z0.astype(dtype), ref=ref.astype(dtype), v_target=v_t.astype(dtype), u_prev=u_prev.astype(dtype), hard=np.zeros(B, dtype=bool), family=fam)
+
+
+# ---- per-problem weights and limits (BatchMPC.solve(..., params=), kmpc_solve_batch_params) -----------------------------------------
+PARAM_BASE = np.array([9.0, 9.0, 10.0, 1.0, 100.0, 1000.0, 1.0, 1.0])
+LIMIT_NAMES = ("steer_max", "steer_dmax", "a_max", "a_dmax", "v_min", "v_max")   # record slots 8 ... 13, in this order
+
+
+def make_param_sets(G, seed, model=0):
+    """G seeded (weights[8], limits dict) pairs: weights within a decade either side of PARAM_BASE (C_v, C_acc, C_df zero a quarter of the time; pose and
+    rate weights never), limits inside ranges that keep make_batch's feasibility argument (|acc_prev| <= 0.5 < a_max, first-step margin 0.10 < a_dmax *
+    dt_control) and the start point's 0.6 a_max < a_dmax."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for g in range(G):
+        w = PARAM_BASE * 10.0 ** rng.uniform(-1, 1, 8)
+        z = rng.uniform(size=8) < 0.25
+        z[[0, 1, 2, 4, 5]] = False          # pose and rate weights are never zero
+        w[z] = 0.0
+        if model == 1:
+            w[0] = 0.0                      # the Frenet module has no x slot
+        lim = dict(steer_max=rng.uniform(0.35, 0.5), steer_dmax=rng.uniform(0.3, 0.5), a_max=rng.uniform(0.8, 1.0),
+                   a_dmax=rng.uniform(1.2, 1.5), v_min=0.0, v_max=rng.uniform(9.0, 20.0))
+        out.append((w, lim))
+    return out
+
+
+def param_records(sets, B, dtype=np.float64):
+    """records [B,16] in the layout of include/kmpc.h: problem i carries set i % len(sets)"""
+    rec = np.zeros((B, 16))
+    for i in range(B):
+        w, lim = sets[i % len(sets)]
+        rec[i, 0:8] = w
+        rec[i, 8:14] = [lim[k] for k in LIMIT_NAMES]
+    return rec.astype(dtype)
+
+
+def apply_param_sets(batch, sets, v_col=3):
+    """problem i of `batch` (make_batch dict, or any dict with z0) gets set i % G: its v0 is lowered to min(v0, v_max_i - 0.5) in place; returns records [B,16]"""
+    B = len(batch["z0"])
+    rec = param_records(sets, B, batch["z0"].dtype)
+    batch["z0"][:, v_col] = np.minimum(batch["z0"][:, v_col], rec[:, 13] - 0.5)
+    return rec

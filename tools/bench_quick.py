@@ -1,6 +1,7 @@
 """Diagnostic: B=4096 N=20 fp64 launch time only (HIP events), for quick A/B of kernel changes.
 QMODEL=1: the Frenet functor (cfg.model = 1) on the short-horizon case generator of tests/test_frenet.py at N <= 28 and on the long-horizon one of
-tests/test_frenet_wide.py above.  QVARIANT=v: kmpc_config.kernel_variant (default 0; 3 = four Frenet problems per wave, QMODEL=1 QN=8)."""
+tests/test_frenet_wide.py above.  QVARIANT=v: kmpc_config.kernel_variant (default 0; 3 = four Frenet problems per wave, QMODEL=1 QN=8).
+QPARAMS=1: every solve goes through `params` with the handle's own values for every problem (same work, the per-problem-parameter kernels)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mkz_mpc_path_follower_amd import _lib
@@ -23,6 +24,9 @@ if FRENET:
 else:
     d = make_batch(B, N, cfg_id=2, seed=int(os.environ["QSEED"]) if "QSEED" in os.environ else None, dtype=np.float32 if F32 else np.float64)
 dev = {k: torch.as_tensor(d[k], device="cuda") for k in ("z0", "ref", "v_target", "u_prev")}
+if os.environ.get("QPARAMS") == "1":
+    _plain, _par = s.solve, s.problem_params(B)
+    s.solve = lambda *a, **k: _plain(*a, params=_par, **k)
 WARM = os.environ.get("QWARM") == "1"
 if WARM:
     wu0 = s.solve(dev["z0"], dev["ref"], dev["v_target"], dev["u_prev"], want_U=True)["U"].clone()
@@ -39,4 +43,4 @@ for rep in range(5):
     e1.record(); torch.cuda.synchronize()
     best = min(best, e0.elapsed_time(e1) / 20)
 it = o["iters"].float()
-print("%s%s B=%d N=%d: %.4f ms/launch  %.3f Msolves/s  iters mean %.2f max %d  status!=0: %d" % (" ".join("%s=%s" % (k, v) for k, v in os.environ.items() if k.startswith("X_")), ("frenet" if FRENET else "cartesian") + (" variant=%d" % VARIANT if "QVARIANT" in os.environ else "") + (" warm" if WARM else ""), B, N, best, B / best / 1e3, it.mean().item(), int(it.max().item()), int((o["status"] != 0).sum().item())))
+print("%s%s B=%d N=%d: %.4f ms/launch  %.3f Msolves/s  iters mean %.2f max %d  status!=0: %d" % (" ".join("%s=%s" % (k, v) for k, v in os.environ.items() if k.startswith("X_")), ("frenet" if FRENET else "cartesian") + (" variant=%d" % VARIANT if "QVARIANT" in os.environ else "") + (" warm" if WARM else "") + (" params" if os.environ.get("QPARAMS") == "1" else ""), B, N, best, B / best / 1e3, it.mean().item(), int(it.max().item()), int((o["status"] != 0).sum().item())))
