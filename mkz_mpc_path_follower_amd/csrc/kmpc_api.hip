@@ -11,52 +11,31 @@
 #include <vector>
 
 #include "../../include/kmpc.h"
-#include "kmpc_device.h"
+#include "kmpc_dispatch.h"
 
-template <typename T> hipError_t kmpc_launch_solve(const KP &, const KIO<T> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_condense(const KP &, const KDbg<T> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_probe(const T *, const T *, T *, hipStream_t);
-template <typename T> bool kmpc_fast_available(int N);
-template <typename T> hipError_t kmpc_launch_solve_fast(const KP &, const KIO<T> &, hipStream_t);
-template <typename T> bool kmpc_wide_available(int N);
-template <typename T> hipError_t kmpc_launch_solve_wide(const KP &, const KIO<T> &, hipStream_t);
-template <typename T> bool kmpc_quad_available(int N);
-template <typename T> hipError_t kmpc_launch_solve_quad(const KP &, const KIO<T> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_solve_quad_frenet(const KP &, const KIO<T> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_solve_frenet(const KP &, const KIO<T> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_solve_fast_frenet(const KP &, const KIO<T> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_solve_wide_frenet(const KP &, const KIO<T> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_fast_kkt(const KP &, const KDbgK<T> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_wide_kkt(const KP &, const KDbgK<T> &, hipStream_t);
-hipError_t kmpc_launch_sim(int, double *, const double *, int, hipStream_t);
-hipError_t kmpc_launch_command(int, const double *, const int32_t *, uint8_t *, double *, double *, hipStream_t);
-template <typename T> hipError_t kmpc_launch_schedule(int, int, double, const T *, size_t, const T *, size_t, uint32_t *, uint32_t *, uint32_t *, int32_t *, hipStream_t);
-template <typename T> hipError_t kmpc_launch_pack(int, int, int, const T *, const T *, const T *, const T *, T *, hipStream_t);
-
-#ifndef KMPC_QUAD_MIN_BATCH
+#ifndef KMPC_HOST_ZERO_COPY_MAX
 #define KMPC_HOST_ZERO_COPY_MAX 16   // kmpc_solve_batch_host: batches up to this size run on pinned host memory (no copies); above, staged through device memory
-#define KMPC_QUAD_MIN_BATCH 1024   // below this the one-wave-per-problem kernel's shorter single-solve latency wins (measured: tools/quad_probe.py)
 #endif
 
 struct kmpc_handle {
-    kmpc_config cfg;
-    int device;
-    hipStream_t stream;
-    double cost[8];
+    kmpc_config cfg = {};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    double cost[8] = {};
     std::string err;
     // staging for the host-pointer entry point
-    void *dbuf;
-    size_t dbuf_bytes;
+    void *dbuf = nullptr;
+    size_t dbuf_bytes = 0;
     // ... and for SMALL batches (B <= KMPC_HOST_ZERO_COPY_MAX: the reference's own B = 1 loop) one pinned, device-mapped host buffer the kernel reads its
     // inputs from and writes its outputs to directly: no copy launches at all (round 4: 13 small pageable copies cost 120 us of a 174 us control step)
-    void *hbuf, *hbuf_dev;
-    size_t hbuf_bytes;
-    unsigned int *done_flag;   // device view of the completion counter inside hbuf while such a launch is being issued, else NULL
+    void *hbuf = nullptr, *hbuf_dev = nullptr;
+    size_t hbuf_bytes = 0;
+    unsigned int *done_flag = nullptr;   // device view of the completion counter inside hbuf while such a launch is being issued, else NULL
     // start-order workspace (kmpc_schedule.hip): perm[cap], tag[cap], hist[2][256]
-    int32_t *perm;
-    uint32_t *tag, *hist;
-    size_t sched_cap;
-    unsigned sched_parity;
+    int32_t *perm = nullptr;
+    uint32_t *tag = nullptr, *hist = nullptr;
+    size_t sched_cap = 0;
+    unsigned sched_parity = 0;
 };
 
 static std::string g_create_err;
@@ -127,20 +106,20 @@ extern "C" int32_t kmpc_create(const kmpc_config *cfg, int32_t device, kmpc_hand
         !(cfg->a_dmax > 0) || !(cfg->steer_dmax > 0) || cfg->max_iter < 1 || cfg->max_ls < 1 || !(cfg->tol > 0) ||
         cfg->kernel_variant < 0 || cfg->kernel_variant > 3 || cfg->mu_strategy < 0 || cfg->mu_strategy > 1 ||
         cfg->indef_strategy < 0 || cfg->indef_strategy > 2 || cfg->schedule < 0 || cfg->schedule > 1 || cfg->model < 0 || cfg->model > 1 ||
-        cfg->start < 0 || cfg->start > 1 ||
-        (cfg->model == 1 && cfg->N > 24 && !(cfg->kernel_variant != 1 && (cfg->N == 28 || kmpc_wide_available<double>(cfg->N)))))
-        // Frenet: generic kernel up to N = 24, compile-time kernels also at 28 (one wave) and 32 ... 48, 50 (four waves)
+        cfg->start < 0 || cfg->start > 1)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: invalid model / solver parameter");
-    if (cfg->kernel_variant == 3) {   // four Frenet problems per wave (kmpc_quad.hip): model 1 at its reference's horizon only
-        if (cfg->model != 1)
+    // a configuration is accepted exactly when kmpc_select (kmpc_dispatch.h) has a kernel for it; what follows only words the refusal
+    if (!kmpc_selectable(cfg->model, cfg->kernel_variant, cfg->N, cfg->dtype == KMPC_F64)) {
+        const bool compiled = kmpc_in(kmpc_fast_horizons(), cfg->N) || kmpc_in(kmpc_wide_horizons(), cfg->N);
+        if (cfg->model == 1 && cfg->N > KMPC_GENERIC_FRENET_MAX_N && (cfg->kernel_variant == 1 || !compiled))   // Frenet beyond the generic kernel's horizons
+            return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: invalid model / solver parameter");
+        if (cfg->kernel_variant == 3 && cfg->model != 1)   // four Frenet problems per wave (kmpc_quad.hip): model 1 at its reference's horizon only
             return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: kernel_variant = 3 is the four-per-wave Frenet kernel (model = 1); for the Cartesian model "
                         "kernel_variant = 0 picks the four-per-wave kernel by batch size (its padding rows are not gated against the host entry point's completion count)");
-        if (cfg->N != 8)
+        if (cfg->kernel_variant == 3)   // (both precisions: the fp32 instantiation passed its acceptance run, tests/test_frenet_quad.py::test_frenet_quad_fp32_acceptance)
             return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: kernel_variant = 3 needs N = 8 (no four-per-wave Frenet kernel at N = %d)", cfg->N);
-        // (both precisions: the fp32 instantiation passed its acceptance run, tests/test_frenet_quad.py::test_frenet_quad_fp32_acceptance)
-    }
-    if (cfg->model == 1 && cfg->N > 28 && cfg->dtype != KMPC_F64)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: the Frenet model (model = 1) at N = %d runs in fp64 only (no fp32 four-wave Frenet kernel)", cfg->N);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, KMPC_ERR_NODEVICE, "kmpc_create: no HIP device");
     if (device < 0 || device >= ndev) return fail(nullptr, KMPC_ERR_ARG, "kmpc_create: device %d of %d", device, ndev);
@@ -151,12 +130,6 @@ extern "C" int32_t kmpc_create(const kmpc_config *cfg, int32_t device, kmpc_hand
     kmpc_handle *h = new kmpc_handle();
     h->cfg = *cfg;
     h->device = device;
-    h->dbuf = nullptr;
-    h->dbuf_bytes = 0;
-    h->hbuf = h->hbuf_dev = nullptr;
-    h->hbuf_bytes = 0;
-    h->done_flag = nullptr;
-    h->perm = nullptr; h->tag = nullptr; h->hist = nullptr; h->sched_cap = 0; h->sched_parity = 0;
     const double w0[8] = {9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0};  // MKZMPCPathFollower.jl:51-59
     const double w1[8] = {0.0, 9.0, 10.0, 0.5, 100.0, 1000.0, 0.0, 0.0};  // MKZMPCPathFollowerFrenet.jl:51-59 (no x slot)
     memcpy(h->cost, cfg->model == 1 ? w1 : w0, sizeof w0);
@@ -230,37 +203,47 @@ static inline int record_scalars(int N, int dtype)
     return (8 + 3 * (N + 1) + per_line - 1) / per_line * per_line;
 }
 
+// the buffers of one solve call as the C entry points receive them (element type: the handle's); rec / orec set = packed records, the arrays unused
+struct SolveBuffers {
+    const void *z0, *ref, *vt, *up, *par;
+    void *warmU;
+    int warm;
+    void *u0;
+    int32_t *status;
+    void *cost, *viol;
+    int32_t *iters;
+    void *outU, *outX;
+    const void *rec;
+    void *orec;
+};
+
 template <typename T>
-static int solve_dev(kmpc_handle *h, int B, const void *z0, const void *ref, const void *vt, const void *up,
-                     void *warmU, int warm, void *u0, int32_t *status, void *cost, void *viol, int32_t *iters,
-                     void *outU, void *outX, hipStream_t st, const void *rec = nullptr, void *orec = nullptr, const void *par = nullptr)
+static int solve_dev(kmpc_handle *h, int B, const SolveBuffers &a, hipStream_t st)
 {
+    const kmpc_config &c = h->cfg;
     KIO<T> io;
-    io.par = (const T *)par;   // per-problem weights and limits [B,16] (kmpc_solve_batch_params), NULL = the handle's
-    const int rstride = record_scalars(h->cfg.N, h->cfg.dtype), per = (int)(64 / sizeof(T));
-    io.zs = 4; io.rs = h->cfg.model == 1 ? 4 : 3 * (h->cfg.N + 1); io.vs = 1; io.us = 2; io.u0s = 2; io.ss = 1; io.is = 1;
-    if (rec) {   // packed records: the same pointers aim into the records, every stride is the record's
-        z0 = rec; ref = (const T *)rec + 8; vt = (const T *)rec + 4; up = (const T *)rec + 5;
-        io.zs = io.rs = io.vs = io.us = rstride;
-        u0 = orec; cost = (T *)orec + 2; viol = (T *)orec + 3; status = (int32_t *)((T *)orec + 4); iters = status + 1;
-        io.u0s = io.ss = per; io.is = 16;
+    io.par = (const T *)a.par;   // per-problem weights and limits [B,16] (kmpc_solve_batch_params), NULL = the handle's
+    if (a.rec) {   // packed records: the same pointers aim into the records, every stride is the record's
+        const T *rec = (const T *)a.rec;
+        T *orec = (T *)a.orec;
+        io.z0 = rec; io.ref = rec + 8; io.vt = rec + 4; io.up = rec + 5;
+        io.zs = io.rs = io.vs = io.us = record_scalars(c.N, c.dtype);
+        io.u0 = orec; io.cost = orec + 2; io.viol = orec + 3; io.status = (int32_t *)(orec + 4); io.iters = io.status + 1;
+        io.u0s = io.ss = (int)(64 / sizeof(T)); io.is = 16;
+    } else {
+        io.z0 = (const T *)a.z0; io.ref = (const T *)a.ref; io.vt = (const T *)a.vt; io.up = (const T *)a.up;
+        io.zs = 4; io.rs = c.model == 1 ? 4 : 3 * (c.N + 1); io.vs = 1; io.us = 2;
+        io.u0 = (T *)a.u0; io.cost = (T *)a.cost; io.viol = (T *)a.viol; io.status = a.status; io.iters = a.iters;
+        io.u0s = 2; io.ss = 1; io.is = 1;
     }
-    io.z0 = (const T *)z0; io.ref = (const T *)ref; io.vt = (const T *)vt; io.up = (const T *)up;
-    io.warmU = (T *)warmU; io.u0 = (T *)u0; io.status = status; io.cost = (T *)cost; io.viol = (T *)viol;
-    io.iters = iters; io.outU = (T *)outU; io.outX = (T *)outX;
+    io.warmU = (T *)a.warmU; io.outU = (T *)a.outU; io.outX = (T *)a.outX;
     io.stamps = g_stamps;
-    const KP P = make_kp(h, B, warm && warmU ? 1 : 0, -1);
+    const KP P = make_kp(h, B, a.warm && a.warmU ? 1 : 0, -1);
     io.perm = nullptr;
     io.done = h->done_flag;   // (set only around the small-batch host entry point's launch)
-    // start order: only matters once a launch no longer fits on the chip at once (2 waves x 4 SIMDs x 256 CUs)
-    if (h->cfg.model == 1) {  // Frenet functor: `ref` carries k_poly [B,4]; index order (the start-order key reads reference points)
-        if (h->cfg.kernel_variant == 3) HIPCHK(h, kmpc_launch_solve_quad_frenet<T>(P, io, st));   // four problems per wave: N = 8, every B >= 1
-        else if (h->cfg.kernel_variant != 1 && kmpc_fast_available<T>(P.N)) HIPCHK(h, kmpc_launch_solve_fast_frenet<T>(P, io, st));
-        else if (h->cfg.kernel_variant != 1 && P.N > 28) HIPCHK(h, kmpc_launch_solve_wide_frenet<T>(P, io, st));   // four-wave kernel: N = 32 ... 48, 50
-        else HIPCHK(h, kmpc_launch_solve_frenet<T>(P, io, st));   // generic kernel: N <= 24
-        return KMPC_OK;
-    }
-    if (h->cfg.schedule == 1 && B > 2048) {
+    // start order: only matters once a launch no longer fits on the chip at once.  Cartesian model only: the Frenet functor's `ref` carries k_poly [B,4],
+    // and the start-order key reads reference points
+    if (c.model == 0 && c.schedule == 1 && B > KMPC_CHIP_FILL_BATCH) {
         if ((size_t)B > h->sched_cap) {
             if (h->perm) (void)hipFree(h->perm);
             if (h->tag) (void)hipFree(h->tag);
@@ -280,12 +263,41 @@ static int solve_dev(kmpc_handle *h, int B, const void *z0, const void *ref, con
         h->sched_parity ^= 1;
         io.perm = h->perm;
     }
-    // N = 8 (the reference's own horizon): four problems per wave once a batch has enough problems to fill the chip that way
-    if (h->cfg.kernel_variant == 0 && kmpc_quad_available<T>(P.N) && B >= KMPC_QUAD_MIN_BATCH) HIPCHK(h, kmpc_launch_solve_quad<T>(P, io, st));
-    else if (h->cfg.kernel_variant != 1 && kmpc_fast_available<T>(P.N)) HIPCHK(h, kmpc_launch_solve_fast<T>(P, io, st));   // one wave per problem
-    else if (h->cfg.kernel_variant != 1 && kmpc_wide_available<T>(P.N)) HIPCHK(h, kmpc_launch_solve_wide<T>(P, io, st));  // four waves per problem
-    else HIPCHK(h, kmpc_launch_solve<T>(P, io, st));
+    const kmpc_selection sel = kmpc_select(c.model, c.kernel_variant, P.N, sizeof(T) == 8, B);
+    switch (sel.backend) {
+        case KMPC_BACKEND_QUAD: HIPCHK(h, kmpc_launch_solve_quad<T>(P, io, c.model, st)); break;
+        case KMPC_BACKEND_FAST: HIPCHK(h, kmpc_launch_solve_fast<T>(P, io, c.model, sel.dense, st)); break;
+        case KMPC_BACKEND_WIDE: HIPCHK(h, kmpc_launch_solve_wide<T>(P, io, c.model, st)); break;
+        case KMPC_BACKEND_GENERIC: HIPCHK(h, kmpc_launch_solve<T>(P, io, c.model, st)); break;
+        case KMPC_BACKEND_NONE: return fail(h, KMPC_ERR_ARG, "no kernel for this configuration");   // (kmpc_create refuses such a handle)
+    }
     return KMPC_OK;
+}
+
+// what the kmpc_solve_batch* entry points share; `fn` is the entry point's name, `wrong_model` what it says to a handle of the other model
+static int solve_entry(kmpc_handle *h, const char *fn, int model, const char *wrong_model, int B, const SolveBuffers &a, void *stream)
+{
+    if (!h) return KMPC_ERR_ARG;
+    if (B < 0) return fail(h, KMPC_ERR_ARG, "%s: B=%d", fn, B);
+    if (B == 0) return KMPC_OK;
+    const bool packed = a.rec || a.orec;   // (a packed call without either has no arrays either)
+    if (packed ? !a.rec || !a.orec : !a.z0 || !a.ref || !a.vt || !a.up || !a.u0 || !a.status)
+        return fail(h, KMPC_ERR_ARG, "%s: null required buffer", fn);
+    if (((uintptr_t)a.rec | (uintptr_t)a.orec) & 63) return fail(h, KMPC_ERR_ARG, "%s: records must be 64-byte aligned", fn);
+    if (h->cfg.model != model) return fail(h, KMPC_ERR_ARG, "%s: %s", fn, wrong_model);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;  // NULL = the device's default stream, as in HIP
+    return h->cfg.dtype == KMPC_F64 ? solve_dev<double>(h, B, a, st) : solve_dev<float>(h, B, a, st);
+}
+
+extern "C" int32_t kmpc_solve_batch_params(kmpc_handle *h, int32_t B, const void *z0, const void *ref, const void *v_target,
+                                           const void *u_prev, const void *params, void *warm_U, int32_t warm, void *out_u0,
+                                           int32_t *out_status, void *out_cost, void *out_viol, int32_t *out_iters, void *out_U,
+                                           void *out_X, void *stream)
+{
+    const SolveBuffers a = {z0, ref, v_target, u_prev, params, warm_U, warm, out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, nullptr, nullptr};
+    if (!params) return solve_entry(h, "kmpc_solve_batch", 0, "handle was created for the Frenet model; use kmpc_solve_batch_frenet", B, a, stream);
+    return solve_entry(h, "kmpc_solve_batch_params", 0, "handle was created for the Frenet model; use kmpc_solve_batch_frenet_params", B, a, stream);
 }
 
 extern "C" int32_t kmpc_solve_batch(kmpc_handle *h, int32_t B, const void *z0, const void *ref, const void *v_target,
@@ -293,19 +305,24 @@ extern "C" int32_t kmpc_solve_batch(kmpc_handle *h, int32_t B, const void *z0, c
                                     void *out_cost, void *out_viol, int32_t *out_iters, void *out_U, void *out_X,
                                     void *stream)
 {
-    if (!h) return KMPC_ERR_ARG;
-    if (B < 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch: B=%d", B);
-    if (B == 0) return KMPC_OK;
-    if (!z0 || !ref || !v_target || !u_prev || !out_u0 || !out_status)
-        return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch: null required buffer");
-    if (h->cfg.model != 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch: handle was created for the Frenet model; use kmpc_solve_batch_frenet");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;  // NULL = the device's default stream, as in HIP
-    if (h->cfg.dtype == KMPC_F64)
-        return solve_dev<double>(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
-                                 out_iters, out_U, out_X, st);
-    return solve_dev<float>(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
-                            out_iters, out_U, out_X, st);
+    return kmpc_solve_batch_params(h, B, z0, ref, v_target, u_prev, nullptr, warm_U, warm, out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, stream);
+}
+
+extern "C" int32_t kmpc_solve_batch_frenet_params(kmpc_handle *h, int32_t B, const void *z0, const void *k_poly, const void *v_target,
+                                                  const void *u_prev, const void *params, void *warm_U, int32_t warm, void *out_u0,
+                                                  int32_t *out_status, void *out_cost, void *out_viol, int32_t *out_iters, void *out_U,
+                                                  void *out_X, void *stream)
+{
+    const SolveBuffers a = {z0, k_poly, v_target, u_prev, params, warm_U, warm, out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, nullptr, nullptr};
+    return solve_entry(h, params ? "kmpc_solve_batch_frenet_params" : "kmpc_solve_batch_frenet", 1, "handle was created with cfg.model = 0", B, a, stream);
+}
+
+extern "C" int32_t kmpc_solve_batch_frenet(kmpc_handle *h, int32_t B, const void *z0, const void *k_poly, const void *v_target,
+                                           const void *u_prev, void *warm_U, int32_t warm, void *out_u0, int32_t *out_status,
+                                           void *out_cost, void *out_viol, int32_t *out_iters, void *out_U, void *out_X,
+                                           void *stream)
+{
+    return kmpc_solve_batch_frenet_params(h, B, z0, k_poly, v_target, u_prev, nullptr, warm_U, warm, out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, stream);
 }
 
 // MKZMPCPathFollower.jl:158-169 (update_cost) and :41-48 (the limits), as one record per problem
@@ -317,48 +334,6 @@ extern "C" int32_t kmpc_get_problem_params(kmpc_handle *h, double rec[16])
     rec[8] = c.steer_max; rec[9] = c.steer_dmax; rec[10] = c.a_max; rec[11] = c.a_dmax; rec[12] = c.v_min; rec[13] = c.v_max;
     rec[14] = rec[15] = 0.0;
     return KMPC_OK;
-}
-
-extern "C" int32_t kmpc_solve_batch_params(kmpc_handle *h, int32_t B, const void *z0, const void *ref, const void *v_target,
-                                           const void *u_prev, const void *params, void *warm_U, int32_t warm, void *out_u0,
-                                           int32_t *out_status, void *out_cost, void *out_viol, int32_t *out_iters, void *out_U,
-                                           void *out_X, void *stream)
-{
-    if (!params) return kmpc_solve_batch(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, stream);
-    if (!h) return KMPC_ERR_ARG;
-    if (B < 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_params: B=%d", B);
-    if (B == 0) return KMPC_OK;
-    if (!z0 || !ref || !v_target || !u_prev || !out_u0 || !out_status)
-        return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_params: null required buffer");
-    if (h->cfg.model != 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_params: handle was created for the Frenet model; use kmpc_solve_batch_frenet_params");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (h->cfg.dtype == KMPC_F64)
-        return solve_dev<double>(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
-                                 out_iters, out_U, out_X, st, nullptr, nullptr, params);
-    return solve_dev<float>(h, B, z0, ref, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
-                            out_iters, out_U, out_X, st, nullptr, nullptr, params);
-}
-
-extern "C" int32_t kmpc_solve_batch_frenet_params(kmpc_handle *h, int32_t B, const void *z0, const void *k_poly, const void *v_target,
-                                                  const void *u_prev, const void *params, void *warm_U, int32_t warm, void *out_u0,
-                                                  int32_t *out_status, void *out_cost, void *out_viol, int32_t *out_iters, void *out_U,
-                                                  void *out_X, void *stream)
-{
-    if (!params) return kmpc_solve_batch_frenet(h, B, z0, k_poly, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, stream);
-    if (!h) return KMPC_ERR_ARG;
-    if (B < 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet_params: B=%d", B);
-    if (B == 0) return KMPC_OK;
-    if (!z0 || !k_poly || !v_target || !u_prev || !out_u0 || !out_status)
-        return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet_params: null required buffer");
-    if (h->cfg.model != 1) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet_params: handle was created with cfg.model = 0");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (h->cfg.dtype == KMPC_F64)
-        return solve_dev<double>(h, B, z0, k_poly, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
-                                 out_iters, out_U, out_X, st, nullptr, nullptr, params);
-    return solve_dev<float>(h, B, z0, k_poly, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
-                            out_iters, out_U, out_X, st, nullptr, nullptr, params);
 }
 
 extern "C" int64_t kmpc_record_bytes(int32_t N, int32_t dtype)
@@ -387,37 +362,22 @@ extern "C" int32_t kmpc_pack_records(kmpc_handle *h, int32_t B, const void *z0, 
 extern "C" int32_t kmpc_solve_batch_packed(kmpc_handle *h, int32_t B, const void *records, void *warm_U, int32_t warm, void *out_records,
                                            void *out_U, void *out_X, void *stream)
 {
-    if (!h) return KMPC_ERR_ARG;
-    if (B < 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_packed: B=%d", B);
-    if (B == 0) return KMPC_OK;
-    if (!records || !out_records) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_packed: null required buffer");
-    if (((uintptr_t)records | (uintptr_t)out_records) & 63) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_packed: records must be 64-byte aligned");
-    if (h->cfg.model != 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_packed: Cartesian model only");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (h->cfg.dtype == KMPC_F64)
-        return solve_dev<double>(h, B, nullptr, nullptr, nullptr, nullptr, warm_U, warm, nullptr, nullptr, nullptr, nullptr, nullptr, out_U, out_X, st, records, out_records);
-    return solve_dev<float>(h, B, nullptr, nullptr, nullptr, nullptr, warm_U, warm, nullptr, nullptr, nullptr, nullptr, nullptr, out_U, out_X, st, records, out_records);
+    SolveBuffers a = {};
+    a.warmU = warm_U; a.warm = warm; a.outU = out_U; a.outX = out_X; a.rec = records; a.orec = out_records;
+    return solve_entry(h, "kmpc_solve_batch_packed", 0, "Cartesian model only", B, a, stream);
 }
 
-extern "C" int32_t kmpc_solve_batch_frenet(kmpc_handle *h, int32_t B, const void *z0, const void *k_poly, const void *v_target,
-                                           const void *u_prev, void *warm_U, int32_t warm, void *out_u0, int32_t *out_status,
-                                           void *out_cost, void *out_viol, int32_t *out_iters, void *out_U, void *out_X,
-                                           void *stream)
+// kmpc_solve_batch_host: the 12 arrays of one batch in one allocation, inputs then outputs, each 256-B aligned
+enum { HB_Z0, HB_REF, HB_VT, HB_UP, HB_WARM, HB_U0, HB_STATUS, HB_COST, HB_VIOL, HB_ITERS, HB_OUTU, HB_OUTX, HB_ARRAYS };
+struct HostLayout {
+    size_t sz[HB_ARRAYS], off[HB_ARRAYS], total;
+};
+static HostLayout host_layout(size_t b, size_t N, size_t es)
 {
-    if (!h) return KMPC_ERR_ARG;
-    if (B < 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet: B=%d", B);
-    if (B == 0) return KMPC_OK;
-    if (!z0 || !k_poly || !v_target || !u_prev || !out_u0 || !out_status)
-        return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet: null required buffer");
-    if (h->cfg.model != 1) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_frenet: handle was created with cfg.model = 0");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (h->cfg.dtype == KMPC_F64)
-        return solve_dev<double>(h, B, z0, k_poly, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
-                                 out_iters, out_U, out_X, st);
-    return solve_dev<float>(h, B, z0, k_poly, v_target, u_prev, warm_U, warm, out_u0, out_status, out_cost, out_viol,
-                            out_iters, out_U, out_X, st);
+    HostLayout L = {{b * 4 * es, b * (N + 1) * 3 * es, b * es, b * 2 * es, b * N * 2 * es,
+                     b * 2 * es, b * 4, b * es, b * es, b * 4, b * N * 2 * es, b * (N + 1) * 4 * es}, {}, 0};
+    for (int i = 0; i < HB_ARRAYS; ++i) { L.off[i] = L.total; L.total += (L.sz[i] + 255) & ~(size_t)255; }
+    return L;
 }
 
 extern "C" int32_t kmpc_solve_batch_host(kmpc_handle *h, int32_t B, const void *z0, const void *ref,
@@ -433,38 +393,37 @@ extern "C" int32_t kmpc_solve_batch_host(kmpc_handle *h, int32_t B, const void *
     if (h->cfg.model != 0) return fail(h, KMPC_ERR_ARG, "kmpc_solve_batch_host: Cartesian model only (use kmpc_solve_batch_frenet with device buffers)");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t es = h->cfg.dtype == KMPC_F64 ? 8 : 4;
-    const size_t N = h->cfg.N, b = (size_t)B;
-    // carve one device allocation: inputs then outputs, each 256-B aligned
-    const size_t sz[13] = {b * 4 * es, b * (N + 1) * 3 * es, b * es, b * 2 * es, b * N * 2 * es,  // z0 ref vt up warmU
-                           b * 2 * es, b * 4, b * es, b * es, b * 4, b * N * 2 * es, b * (N + 1) * 4 * es, 0};
-    size_t off[13], total = 0;
-    for (int i = 0; i < 13; ++i) { off[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
+    const HostLayout L = host_layout((size_t)B, (size_t)h->cfg.N, es);
+    // copy-in: the four inputs, and the warm start when it is used; copy-out, in this order: the outputs the caller asked for, then the warm start
+    const void *in[5] = {z0, ref, v_target, u_prev, warm_U && warm ? warm_U : nullptr};
+    const int out_slot[8] = {HB_U0, HB_STATUS, HB_COST, HB_VIOL, HB_ITERS, HB_OUTU, HB_OUTX, HB_WARM};
+    void *out[8] = {out_u0, out_status, out_cost, out_viol, out_iters, out_U, out_X, warm_U};
     hipStream_t st = h->stream;
+    auto solve_at = [&](char *d) {   // d: the allocation as the device sees it
+        return kmpc_solve_batch(h, B, d + L.off[HB_Z0], d + L.off[HB_REF], d + L.off[HB_VT], d + L.off[HB_UP], warm_U ? d + L.off[HB_WARM] : nullptr, warm,
+                                d + L.off[HB_U0], (int32_t *)(d + L.off[HB_STATUS]), d + L.off[HB_COST], d + L.off[HB_VIOL], (int32_t *)(d + L.off[HB_ITERS]),
+                                out_U ? d + L.off[HB_OUTU] : nullptr, out_X ? d + L.off[HB_OUTX] : nullptr, st);
+    };
     if (B <= KMPC_HOST_ZERO_COPY_MAX) {
         // small batch: the kernel works on pinned host memory (inputs: one burst of loads per problem when it starts; outputs: posted writes when it ends)
-        if (total > h->hbuf_bytes) {
+        if (L.total > h->hbuf_bytes) {
             if (h->hbuf) HIPCHK(h, hipHostFree(h->hbuf));
             h->hbuf = h->hbuf_dev = nullptr; h->hbuf_bytes = 0;
-            size_t cap = 0;   // sized once for the largest zero-copy batch of this handle's horizon
-            { const size_t bb = KMPC_HOST_ZERO_COPY_MAX;
-              const size_t szm[12] = {bb * 4 * es, bb * (N + 1) * 3 * es, bb * es, bb * 2 * es, bb * N * 2 * es, bb * 2 * es, bb * 4, bb * es, bb * es, bb * 4, bb * N * 2 * es, bb * (N + 1) * 4 * es};
-              for (int i = 0; i < 12; ++i) cap += (szm[i] + 255) & ~(size_t)255; }
-            cap += 256;   // + the completion counter
+            // sized once for the largest zero-copy batch of this handle's horizon, + the completion counter
+            const size_t cap = host_layout(KMPC_HOST_ZERO_COPY_MAX, (size_t)h->cfg.N, es).total + 256;
             HIPCHK(h, hipHostMalloc(&h->hbuf, cap, hipHostMallocMapped));
             HIPCHK(h, hipHostGetDevicePointer(&h->hbuf_dev, h->hbuf, 0));
             h->hbuf_bytes = cap;
         }
         char *hp = (char *)h->hbuf, *dp = (char *)h->hbuf_dev;
-        memcpy(hp + off[0], z0, sz[0]); memcpy(hp + off[1], ref, sz[1]); memcpy(hp + off[2], v_target, sz[2]); memcpy(hp + off[3], u_prev, sz[3]);
-        if (warm_U && warm) memcpy(hp + off[4], warm_U, sz[4]);
+        for (int i = 0; i < 5; ++i)
+            if (in[i]) memcpy(hp + L.off[i], in[i], L.sz[i]);
         // completion: every problem adds 1 to a counter in the pinned buffer after its outputs (release, system scope); the host spins on it -- the runtime's
         // own completion path (interrupt / signal wait) is several microseconds slower -- and falls back to the stream after 2 ms (long solves, stalled device)
         volatile unsigned int *flag_h = (volatile unsigned int *)(hp + h->hbuf_bytes - 256);
         *flag_h = 0u;
         h->done_flag = (unsigned int *)(dp + h->hbuf_bytes - 256);
-        int rc = kmpc_solve_batch(h, B, dp + off[0], dp + off[1], dp + off[2], dp + off[3], warm_U ? dp + off[4] : nullptr, warm,
-                                  dp + off[5], (int32_t *)(dp + off[6]), dp + off[7], dp + off[8], (int32_t *)(dp + off[9]),
-                                  out_U ? dp + off[10] : nullptr, out_X ? dp + off[11] : nullptr, st);
+        int rc = solve_at(dp);
         h->done_flag = nullptr;
         if (rc != KMPC_OK) return rc;
         {
@@ -477,39 +436,23 @@ extern "C" int32_t kmpc_solve_batch_host(kmpc_handle *h, int32_t B, const void *
             }
             if (!seen) HIPCHK(h, hipStreamSynchronize(st));
         }
-        memcpy(out_u0, hp + off[5], sz[5]); memcpy(out_status, hp + off[6], sz[6]);
-        if (out_cost) memcpy(out_cost, hp + off[7], sz[7]);
-        if (out_viol) memcpy(out_viol, hp + off[8], sz[8]);
-        if (out_iters) memcpy(out_iters, hp + off[9], sz[9]);
-        if (out_U) memcpy(out_U, hp + off[10], sz[10]);
-        if (out_X) memcpy(out_X, hp + off[11], sz[11]);
-        if (warm_U) memcpy(warm_U, hp + off[4], sz[4]);
+        for (int i = 0; i < 8; ++i)
+            if (out[i]) memcpy(out[i], hp + L.off[out_slot[i]], L.sz[out_slot[i]]);
         return KMPC_OK;
     }
-    if (total > h->dbuf_bytes) {
+    if (L.total > h->dbuf_bytes) {
         if (h->dbuf) HIPCHK(h, hipFree(h->dbuf));
         h->dbuf = nullptr; h->dbuf_bytes = 0;
-        HIPCHK(h, hipMalloc(&h->dbuf, total));
-        h->dbuf_bytes = total;
+        HIPCHK(h, hipMalloc(&h->dbuf, L.total));
+        h->dbuf_bytes = L.total;
     }
     char *d = (char *)h->dbuf;
-    HIPCHK(h, hipMemcpyAsync(d + off[0], z0, sz[0], hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d + off[1], ref, sz[1], hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d + off[2], v_target, sz[2], hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d + off[3], u_prev, sz[3], hipMemcpyHostToDevice, st));
-    if (warm_U && warm) HIPCHK(h, hipMemcpyAsync(d + off[4], warm_U, sz[4], hipMemcpyHostToDevice, st));
-    int rc = kmpc_solve_batch(h, B, d + off[0], d + off[1], d + off[2], d + off[3], warm_U ? d + off[4] : nullptr, warm,
-                              d + off[5], (int32_t *)(d + off[6]), d + off[7], d + off[8], (int32_t *)(d + off[9]),
-                              out_U ? d + off[10] : nullptr, out_X ? d + off[11] : nullptr, st);
+    for (int i = 0; i < 5; ++i)
+        if (in[i]) HIPCHK(h, hipMemcpyAsync(d + L.off[i], in[i], L.sz[i], hipMemcpyHostToDevice, st));
+    int rc = solve_at(d);
     if (rc != KMPC_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(out_u0, d + off[5], sz[5], hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out_status, d + off[6], sz[6], hipMemcpyDeviceToHost, st));
-    if (out_cost) HIPCHK(h, hipMemcpyAsync(out_cost, d + off[7], sz[7], hipMemcpyDeviceToHost, st));
-    if (out_viol) HIPCHK(h, hipMemcpyAsync(out_viol, d + off[8], sz[8], hipMemcpyDeviceToHost, st));
-    if (out_iters) HIPCHK(h, hipMemcpyAsync(out_iters, d + off[9], sz[9], hipMemcpyDeviceToHost, st));
-    if (out_U) HIPCHK(h, hipMemcpyAsync(out_U, d + off[10], sz[10], hipMemcpyDeviceToHost, st));
-    if (out_X) HIPCHK(h, hipMemcpyAsync(out_X, d + off[11], sz[11], hipMemcpyDeviceToHost, st));
-    if (warm_U) HIPCHK(h, hipMemcpyAsync(warm_U, d + off[4], sz[4], hipMemcpyDeviceToHost, st));
+    for (int i = 0; i < 8; ++i)
+        if (out[i]) HIPCHK(h, hipMemcpyAsync(out[i], d + L.off[out_slot[i]], L.sz[out_slot[i]], hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     return KMPC_OK;
 }
@@ -540,8 +483,10 @@ static int debug_kkt(kmpc_handle *h, int B, const void *z0, const void *ref, con
     const KP P = make_kp(h, B, 0, hessian);
     KDbgK<T> io = {(const T *)z0, (const T *)ref, (const T *)vt, (const T *)up, (const T *)U, (const T *)w, (const T *)b, sc, reg,
                    (T *)K, (T *)g, (T *)x, ok};
-    if (kmpc_fast_available<T>(P.N)) HIPCHK(h, kmpc_launch_fast_kkt<T>(P, io, st));
-    else if (kmpc_wide_available<T>(P.N)) HIPCHK(h, kmpc_launch_wide_kkt<T>(P, io, st));
+    // the compile-time-horizon kernel of this N, whatever the handle's kernel_variant (= 2: neither the generic nor the four-per-wave kernel)
+    const kmpc_backend backend = kmpc_select(0, 2, P.N, sizeof(T) == 8, B).backend;
+    if (backend == KMPC_BACKEND_FAST) HIPCHK(h, kmpc_launch_fast_kkt<T>(P, io, st));
+    else if (backend == KMPC_BACKEND_WIDE) HIPCHK(h, kmpc_launch_wide_kkt<T>(P, io, st));
     else return fail(h, KMPC_ERR_ARG, "kmpc_debug_kkt: no compile-time-horizon kernel for N=%d in this element type", P.N);
     return KMPC_OK;
 }
@@ -570,19 +515,6 @@ extern "C" int32_t kmpc_debug_mfma_probe(kmpc_handle *h, const void *a, const vo
 }
 
 // ---- batched waypoint generation (scripts/gps_utils/ref_gps_traj.py) -------------------------------
-struct WP {
-    int M, B, H;
-    int use_vtarget;
-    double traj_dt;
-    const double *t, *X, *Y, *psi, *s;
-    const double *pose;
-    const double *vt;
-    double *ref;
-    int32_t *stop;
-    int32_t *closest;
-};
-hipError_t kmpc_launch_waypoints(const WP &w, hipStream_t st);
-
 struct kmpc_path {
     int device, M;
     double *d;  // t | X | Y | psi | s, each M doubles

@@ -1,0 +1,110 @@
+// kmpc_dispatch.h -- what crosses translation units on the host side: which kernel runs for a configuration (the contract of kmpc_config in
+// include/kmpc.h, as ONE function), the lists of compiled horizons it rests on, and the launchers kmpc_api.hip calls.
+// The first part is plain C++17 with no HIP types (tests/test_dispatch.py compiles it with the host compiler); the second needs hipcc.
+#pragma once
+#include <utility>
+
+#include "kmpc_device.h"
+
+// ---- compiled horizons: each list is written here and nowhere else ---------------------------------------------------------------------------------
+typedef std::integer_sequence<int, 8, 12, 16, 20, 24, 28> kmpc_fast_horizons;    // one wave per problem: N % 4 == 0 and 2N + 1 <= 64
+typedef std::integer_sequence<int, 32, 36, 40, 44, 48, 50> kmpc_wide_horizons;   // four waves: 5 (N = 32, 36), 6 (40, 44) or 7 (48, 50) tile rows, 5N - 2 <= 256
+typedef std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7> kmpc_generic_tiles;      // generic kernel: column tiles NT = ceil(2N / 16), N <= 56
+typedef std::integer_sequence<int, 1, 2, 3> kmpc_generic_frenet_tiles;           // ... with the Frenet functor: N <= 24
+constexpr int KMPC_QUAD_HORIZON = 8;          // four problems per wave: the reference's own horizon only
+constexpr int KMPC_FAST_DENSE_MAX_N = 12;     // the one-wave kernel has a build at one more wave per SIMD up to here (kmpc_fast.hip)
+constexpr int KMPC_GENERIC_FRENET_MAX_N = 24;
+#ifndef KMPC_QUAD_MIN_BATCH
+#define KMPC_QUAD_MIN_BATCH 1024   // below this the one-wave-per-problem kernel's shorter single-solve latency wins (measured: tools/quad_probe.py)
+#endif
+// a launch of more problems than this no longer fits on the chip at once (2 waves x 4 SIMDs x 256 CUs): the start order matters (kmpc_schedule.hip),
+// and the denser one-wave build pays for its spills
+constexpr int KMPC_CHIP_FILL_BATCH = 2048;
+
+template <int... Ns> constexpr bool kmpc_in(std::integer_sequence<int, Ns...>, int v) { return ((v == Ns) || ...); }
+// run-time value -> compile-time value: f(std::integral_constant<int, V>()) for the list's V equal to v, `none` when there is no such entry
+template <typename R, int... Ns, typename F> inline R kmpc_dispatch(std::integer_sequence<int, Ns...>, int v, R none, F &&f)
+{
+    R r = none;
+    (void)((v == Ns ? (r = f(std::integral_constant<int, Ns>()), true) : false) || ...);
+    return r;
+}
+
+// ---- the selection rule ------------------------------------------------------------------------------------------------------------------------------
+enum kmpc_backend {
+    KMPC_BACKEND_NONE = 0,   // no kernel: kmpc_create refuses the configuration
+    KMPC_BACKEND_GENERIC,    // run-time horizon, one wave (kmpc_kernels.hip)
+    KMPC_BACKEND_FAST,       // compile-time horizon, one wave (kmpc_fast.hip)
+    KMPC_BACKEND_WIDE,       // compile-time horizon, four waves (kmpc_wide.hip)
+    KMPC_BACKEND_QUAD        // four problems per wave (kmpc_quad.hip)
+};
+struct kmpc_selection {
+    kmpc_backend backend;
+    bool dense;   // KMPC_BACKEND_FAST only: the build at one more wave per SIMD
+};
+// The kernel for (model, kernel_variant, N, element type, B); per-problem parameters pick the _par_kernel twin of the same answer.  B enters through the
+// two thresholds only, so a configuration is acceptable when it has a kernel at B = 1 and at a B above both (kmpc_selectable).
+inline kmpc_selection kmpc_select(int model, int kernel_variant, int N, bool fp64, int B)
+{
+    const bool fast = kmpc_in(kmpc_fast_horizons(), N), wide = kmpc_in(kmpc_wide_horizons(), N);
+    if (model == 1) {   // Frenet functor
+        if (kernel_variant == 3) return {N == KMPC_QUAD_HORIZON ? KMPC_BACKEND_QUAD : KMPC_BACKEND_NONE, false};   // every B >= 1
+        if (kernel_variant != 1 && fast) return {KMPC_BACKEND_FAST, false};
+        if (kernel_variant != 1 && wide) return {fp64 ? KMPC_BACKEND_WIDE : KMPC_BACKEND_NONE, false};   // no fp32 four-wave Frenet kernel
+        return {N <= KMPC_GENERIC_FRENET_MAX_N ? KMPC_BACKEND_GENERIC : KMPC_BACKEND_NONE, false};
+    }
+    if (kernel_variant == 3) return {KMPC_BACKEND_NONE, false};   // the Cartesian four-per-wave kernel is picked by batch size, never forced
+    if (kernel_variant == 0 && N == KMPC_QUAD_HORIZON && B >= KMPC_QUAD_MIN_BATCH) return {KMPC_BACKEND_QUAD, false};
+    if (kernel_variant != 1 && fast) return {KMPC_BACKEND_FAST, N <= KMPC_FAST_DENSE_MAX_N && B > KMPC_CHIP_FILL_BATCH};
+    if (kernel_variant != 1 && wide) return {KMPC_BACKEND_WIDE, false};
+    return {KMPC_BACKEND_GENERIC, false};
+}
+inline bool kmpc_selectable(int model, int kernel_variant, int N, bool fp64)
+{
+    return kmpc_select(model, kernel_variant, N, fp64, 1).backend != KMPC_BACKEND_NONE &&
+           kmpc_select(model, kernel_variant, N, fp64, 1 << 30).backend != KMPC_BACKEND_NONE;
+}
+
+// ---- launchers (hipcc only) --------------------------------------------------------------------------------------------------------------------------
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+template <typename... P, typename... A>
+inline hipError_t kmpc_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &... args)
+{
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+
+// solves: one per back-end; `model` and `dense` are what kmpc_select answered, io.par picks the twin.  hipErrorInvalidValue = no such instantiation.
+template <typename T> hipError_t kmpc_launch_solve(const KP &, const KIO<T> &, int model, hipStream_t);
+template <typename T> hipError_t kmpc_launch_solve_fast(const KP &, const KIO<T> &, int model, bool dense, hipStream_t);
+template <typename T> hipError_t kmpc_launch_solve_wide(const KP &, const KIO<T> &, int model, hipStream_t);
+template <typename T> hipError_t kmpc_launch_solve_quad(const KP &, const KIO<T> &, int model, hipStream_t);
+// diagnostics
+template <typename T> hipError_t kmpc_launch_condense(const KP &, const KDbg<T> &, hipStream_t);
+template <typename T> hipError_t kmpc_launch_probe(const T *, const T *, T *, hipStream_t);
+template <typename T> hipError_t kmpc_launch_fast_kkt(const KP &, const KDbgK<T> &, hipStream_t);
+template <typename T> hipError_t kmpc_launch_wide_kkt(const KP &, const KDbgK<T> &, hipStream_t);
+// start order and packed records (kmpc_schedule.hip)
+template <typename T> hipError_t kmpc_launch_schedule(int B, int N, double dt, const T *z0, size_t zs, const T *ref, size_t rs, uint32_t *hist, uint32_t *hist_next,
+                                                      uint32_t *tag, int32_t *perm, hipStream_t st);
+template <typename T> hipError_t kmpc_launch_pack(int B, int N, int stride, const T *z0, const T *ref, const T *vt, const T *up, T *rec, hipStream_t st);
+// closed-loop simulator (kmpc_sim.hip)
+hipError_t kmpc_launch_sim(int B, double *state, const double *cmd, int n_updates, hipStream_t st);
+hipError_t kmpc_launch_command(int B, const double *u0, const int32_t *stop, uint8_t *latch, double *u_prev, double *cmd, hipStream_t st);
+
+// batched waypoint generation (kmpc_waypoints.hip; scripts/gps_utils/ref_gps_traj.py)
+struct WP {
+    int M, B, H;         // path samples, vehicles, horizon (H+1 waypoints)
+    int use_vtarget;     // 1: arclength grid with per-vehicle v_target, 0: time grid
+    double traj_dt;
+    const double *t, *X, *Y, *psi, *s;
+    const double *pose;  // [B,3] x, y, yaw
+    const double *vt;    // [B] or null
+    double *ref;         // [B,H+1,3] x, y, psi
+    int32_t *stop;       // [B]
+    int32_t *closest;    // [B] or null (diagnostic)
+};
+hipError_t kmpc_launch_waypoints(const WP &w, hipStream_t st);
+#endif

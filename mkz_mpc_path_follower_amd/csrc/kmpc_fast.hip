@@ -29,6 +29,7 @@
 //     gradient and the corrector terms live in LDS, not in VGPRs (2 waves per SIMD = 256 VGPRs,
 //     20 KB of LDS per wave = exactly 8 waves per CU at N = 20).
 #include "kmpc_ipm.h"
+#include "kmpc_dispatch.h"
 
 
 template <typename T> using StageF = StageV<T>;
@@ -594,42 +595,6 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : (N <= 20 ? 4 : 3)) void km
     if (lane < n) { io.g[(size_t)b * n + lane] = g; io.x[(size_t)b * n + lane] = x; }
     if (lane == 0) io.ok[b] = okf ? 1 : 0;
 }
-template <typename T, int N>
-static hipError_t launch_fast_kkt_n(const KP &P, const KDbgK<T> &io, hipStream_t st)
-{
-    hipLaunchKernelGGL((kmpc_fast_kkt_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
-    return hipGetLastError();
-}
-template <typename T> hipError_t kmpc_launch_fast_kkt(const KP &P, const KDbgK<T> &io, hipStream_t st)
-{
-    switch (P.N) {
-        case 8: return launch_fast_kkt_n<T, 8>(P, io, st);
-        case 12: return launch_fast_kkt_n<T, 12>(P, io, st);
-        case 16: return launch_fast_kkt_n<T, 16>(P, io, st);
-        case 20: return launch_fast_kkt_n<T, 20>(P, io, st);
-        case 24: return launch_fast_kkt_n<T, 24>(P, io, st);
-        case 28: return launch_fast_kkt_n<T, 28>(P, io, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-template hipError_t kmpc_launch_fast_kkt<double>(const KP &, const KDbgK<double> &, hipStream_t);
-template hipError_t kmpc_launch_fast_kkt<float>(const KP &, const KDbgK<float> &, hipStream_t);
-
-template <typename T, int N>
-static hipError_t launch_fast_n(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    if constexpr (N <= 12) {
-        if (P.B > 2048) {
-            if (io.par) hipLaunchKernelGGL((kmpc_solve_fast_dense_par_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
-            else hipLaunchKernelGGL((kmpc_solve_fast_dense_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
-            return hipGetLastError();
-        }
-    }
-    if (io.par) hipLaunchKernelGGL((kmpc_solve_fast_par_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
-    else hipLaunchKernelGGL((kmpc_solve_fast_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
-    return hipGetLastError();
-}
-
 // Frenet-frame functor (kmpc_config.model = 1): io.ref carries k_poly [B,4]  (fp64 at N = 28: 34.5 KB of LDS per wave leave one wave per
 // SIMD anyway, so the bound says so and the allocator may use all 512 registers; fp64 at N = 8 ran at three waves per SIMD with 42 spilled registers
 // until the degenerate-pair rule moved one of the spill stores into a divergent region -- tools/spill_exec_check.py -- two waves, no scratch)
@@ -645,44 +610,28 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? (N >= 28 ? 1 : 2) : (N <= 20 ?
     __shared__ __attribute__((aligned(16))) unsigned char smem[FastSolver<T, N, 1>::lds_elems() * sizeof(T)];
     ipm::run_solver<FastSolver<T, N, 1>, true>(P, io, smem);
 }
-template <typename T, int N>
-static hipError_t launch_fast_frenet_n(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    if (io.par) hipLaunchKernelGGL((kmpc_solve_fast_frenet_par_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
-    else hipLaunchKernelGGL((kmpc_solve_fast_frenet_kernel<T, N>), dim3(P.B), dim3(64), 0, st, P, io);
-    return hipGetLastError();
-}
-template <typename T> hipError_t kmpc_launch_solve_fast_frenet(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    switch (P.N) {
-        case 8: return launch_fast_frenet_n<T, 8>(P, io, st);
-        case 12: return launch_fast_frenet_n<T, 12>(P, io, st);
-        case 16: return launch_fast_frenet_n<T, 16>(P, io, st);
-        case 20: return launch_fast_frenet_n<T, 20>(P, io, st);
-        case 24: return launch_fast_frenet_n<T, 24>(P, io, st);
-        case 28: return launch_fast_frenet_n<T, 28>(P, io, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-template hipError_t kmpc_launch_solve_fast_frenet<double>(const KP &, const KIO<double> &, hipStream_t);
-template hipError_t kmpc_launch_solve_fast_frenet<float>(const KP &, const KIO<float> &, hipStream_t);
 
-// horizons with a compiled fast kernel; everything else runs the generic kernel
-// compile-time horizons: N % 4 == 0 and 2N + 1 <= 64
-template <typename T> bool kmpc_fast_available(int N) { return N == 8 || N == 12 || N == 16 || N == 20 || N == 24 || N == 28; }
-template <typename T> hipError_t kmpc_launch_solve_fast(const KP &P, const KIO<T> &io, hipStream_t st)
+// ---- launchers (called from kmpc_api.hip): everything else than kmpc_fast_horizons runs another kernel ----------------------------------------------
+template <typename T> hipError_t kmpc_launch_fast_kkt(const KP &P, const KDbgK<T> &io, hipStream_t st)
 {
-    switch (P.N) {
-        case 8: return launch_fast_n<T, 8>(P, io, st);
-        case 12: return launch_fast_n<T, 12>(P, io, st);
-        case 16: return launch_fast_n<T, 16>(P, io, st);
-        case 20: return launch_fast_n<T, 20>(P, io, st);
-        case 24: return launch_fast_n<T, 24>(P, io, st);
-        case 28: return launch_fast_n<T, 28>(P, io, st);
-        default: return hipErrorInvalidValue;
-    }
+    return kmpc_dispatch(kmpc_fast_horizons(), P.N, hipErrorInvalidValue, [&](auto n) {
+        return kmpc_launch(&kmpc_fast_kkt_kernel<T, decltype(n)::value>, dim3(P.B), dim3(64), 0, st, P, io);
+    });
 }
-template bool kmpc_fast_available<double>(int);
-template bool kmpc_fast_available<float>(int);
-template hipError_t kmpc_launch_solve_fast<double>(const KP &, const KIO<double> &, hipStream_t);
-template hipError_t kmpc_launch_solve_fast<float>(const KP &, const KIO<float> &, hipStream_t);
+template hipError_t kmpc_launch_fast_kkt<double>(const KP &, const KDbgK<double> &, hipStream_t);
+template hipError_t kmpc_launch_fast_kkt<float>(const KP &, const KDbgK<float> &, hipStream_t);
+
+template <typename T> hipError_t kmpc_launch_solve_fast(const KP &P, const KIO<T> &io, int model, bool dense, hipStream_t st)
+{
+    return kmpc_dispatch(kmpc_fast_horizons(), P.N, hipErrorInvalidValue, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        void (*kernel)(KP, KIO<T>) = io.par ? &kmpc_solve_fast_par_kernel<T, N> : &kmpc_solve_fast_kernel<T, N>;
+        if (model == 1) kernel = io.par ? &kmpc_solve_fast_frenet_par_kernel<T, N> : &kmpc_solve_fast_frenet_kernel<T, N>;
+        else if constexpr (N <= KMPC_FAST_DENSE_MAX_N) {
+            if (dense) kernel = io.par ? &kmpc_solve_fast_dense_par_kernel<T, N> : &kmpc_solve_fast_dense_kernel<T, N>;
+        }
+        return kmpc_launch(kernel, dim3(P.B), dim3(64), 0, st, P, io);
+    });
+}
+template hipError_t kmpc_launch_solve_fast<double>(const KP &, const KIO<double> &, int, bool, hipStream_t);
+template hipError_t kmpc_launch_solve_fast<float>(const KP &, const KIO<float> &, int, bool, hipStream_t);

@@ -846,17 +846,22 @@ template <typename T> DEV void refuse_problem(const KIO<T> &io, int b, int N, in
     }
 }
 
+// diagnostic build (make poison): every LDS word of the workgroup starts as NaN, so a read of a word nobody wrote shows up in the results; nothing otherwise
+template <typename T> DEV void poison_lds(unsigned char *smem, int elems, int nth)
+{
+#ifdef KMPC_POISON
+    for (int e = threadIdx.x; e < elems; e += nth) reinterpret_cast<T *>(smem)[e] = (T)NAN;
+    __syncthreads();
+#endif
+}
+
 // body of a solve kernel: one problem per workgroup, start order through io.perm.  PAR: the instantiation behind kmpc_solve_batch_params -- the
 // problem's own weights and limits replace the handle's in the table before anything reads them; the solve itself is the same code
 template <class SV, bool PAR = false> DEV void run_solver(const KP &P, const KIO<typename SV::real> &io, unsigned char *smem)
 {
     if ((int)blockIdx.x >= P.B) return;
     const int b = io.perm ? io.perm[blockIdx.x] : (int)blockIdx.x;
-#ifdef KMPC_POISON  // diagnostic build (make poison): every LDS word starts as NaN, so a read of a word nobody wrote shows up in the results
-    typedef typename SV::real T;
-    for (int e = threadIdx.x; e < SV::lds_elems(); e += SV::NTH) reinterpret_cast<T *>(smem)[e] = (T)NAN;
-    __syncthreads();
-#endif
+    poison_lds<typename SV::real>(smem, SV::lds_elems(), SV::NTH);
     SV sv(P, smem);
     if constexpr (PAR) {
         // every wave checks the whole record (so the verdict is in all of them without an exchange), the first 14 threads write the table

@@ -29,6 +29,7 @@
 //   stage data: lane k <-> stage / state k (k = 0..N)
 //   H tiles: lower-triangular 16x16 tiles in MFMA C/D layout (col = lane&15, row from Real<T>)
 #include "kmpc_ipm.h"
+#include "kmpc_dispatch.h"
 
 // per-lane stage record: lane k holds state k (k = 0..N) and input k (k < N)
 template <typename T> struct Stage {
@@ -957,17 +958,21 @@ template <typename T, int NT, int MODEL = 0> struct Solver {
     DEV void solve(const KIO<T> &io, int b) { ipm::solve(*this, io, b); }
 };
 
+// diagnostic build (make poison): the dynamic LDS of this launch starts as NaN; nothing otherwise (the size is not even computed)
+template <typename T, int NT> DEV void poison_dynamic_lds(const KP &P, unsigned char *smem)
+{
+#ifdef KMPC_POISON
+    ipm::poison_lds<T>(smem, (int)(kmpc_lds_bytes<T>(P.N, NT) / sizeof(T)), 64);
+#endif
+}
+
 template <typename T, int NT>
 __global__ __launch_bounds__(64) void kmpc_solve_kernel(KP P, KIO<T> io)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if ((int)blockIdx.x >= P.B) return;
     const int b = io.perm ? io.perm[blockIdx.x] : (int)blockIdx.x;
-#ifdef KMPC_POISON  // diagnostic build (make poison): every LDS word starts as NaN
-    { T *w_ = reinterpret_cast<T *>(smem); const int ne_ = (int)(kmpc_lds_bytes<T>(P.N, NT) / sizeof(T));
-      for (int e = threadIdx.x; e < ne_; e += 64) w_[e] = (T)NAN;
-      __syncthreads(); }
-#endif
+    poison_dynamic_lds<T, NT>(P, smem);
     T scalars[16], params[32];
     Solver<T, NT> sv(P, smem, scalars, params);
     ipm::load_problem_io(sv, io, b);
@@ -980,11 +985,7 @@ __global__ __launch_bounds__(64) void kmpc_solve_frenet_kernel(KP P, KIO<T> io)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if ((int)blockIdx.x >= P.B) return;
     const int b = (int)blockIdx.x;
-#ifdef KMPC_POISON  // diagnostic build (make poison): every LDS word starts as NaN
-    { T *w_ = reinterpret_cast<T *>(smem); const int ne_ = (int)(kmpc_lds_bytes<T>(P.N, NT) / sizeof(T));
-      for (int e = threadIdx.x; e < ne_; e += 64) w_[e] = (T)NAN;
-      __syncthreads(); }
-#endif
+    poison_dynamic_lds<T, NT>(P, smem);
     T scalars[16], params[32];
     Solver<T, NT, 1> sv(P, smem, scalars, params);
     sv.load_problem(io.z0, io.ref, io.vt, io.up, b);  // io.ref = k_poly [B,4]
@@ -1000,11 +1001,7 @@ __global__ __launch_bounds__(64) void kmpc_solve_par_kernel(KP P, KIO<T> io)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if ((int)blockIdx.x >= P.B) return;
     const int b = io.perm ? io.perm[blockIdx.x] : (int)blockIdx.x;
-#ifdef KMPC_POISON  // diagnostic build (make poison): every LDS word starts as NaN
-    { T *w_ = reinterpret_cast<T *>(smem); const int ne_ = (int)(kmpc_lds_bytes<T>(P.N, NT) / sizeof(T));
-      for (int e = threadIdx.x; e < ne_; e += 64) w_[e] = (T)NAN;
-      __syncthreads(); }
-#endif
+    poison_dynamic_lds<T, NT>(P, smem);
     const T *rec = io.par + (size_t)b * KMPC_PAR_STRIDE;
     T r[KMPC_PAR_STRIDE];
     bool ok = true;
@@ -1076,104 +1073,50 @@ __global__ __launch_bounds__(64) void kmpc_mfma_probe_kernel(const T *a, const T
 // ---- launchers (called from kmpc_api.hip) ------------------------------------------------------
 // The dynamic-LDS limit of a kernel is a property of the (function, device) pair: it is raised once, the first time a launch
 // needs more than what was set before (horizons differ in their LDS need), not on every launch.
-template <typename K> static hipError_t ensure_dynamic_lds(K kernel, size_t lds, size_t (&set_for_device)[64])
+template <auto KERNEL, typename T, typename IO> static hipError_t launch_dynamic_lds(const KP &P, int NT, const IO &io, hipStream_t st)
 {
+    static size_t set_for_device[64] = {0};   // one per kernel function
+    const size_t lds = kmpc_lds_bytes<T>(P.N, NT);
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (lds <= set_for_device[dev]) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) set_for_device[dev] = lds;
-    return e;
-}
-template <typename T, int NT>
-static hipError_t launch_solve_nt(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    const size_t lds = kmpc_lds_bytes<T>(P.N, NT);
-    static size_t lds_set[64] = {0};
-    if (io.par) {
-        static size_t lds_set_par[64] = {0};
-        hipError_t e = ensure_dynamic_lds(&kmpc_solve_par_kernel<T, NT, 0>, lds, lds_set_par);
+    if (lds > set_for_device[dev]) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((kmpc_solve_par_kernel<T, NT, 0>), dim3(P.B), dim3(64), lds, st, P, io);
-        return hipGetLastError();
+        set_for_device[dev] = lds;
     }
-    hipError_t e = ensure_dynamic_lds(&kmpc_solve_kernel<T, NT>, lds, lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((kmpc_solve_kernel<T, NT>), dim3(P.B), dim3(64), lds, st, P, io);
-    return hipGetLastError();
-}
-template <typename T, int NT>
-static hipError_t launch_solve_frenet_nt(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    const size_t lds = kmpc_lds_bytes<T>(P.N, NT);
-    static size_t lds_set[64] = {0};
-    if (io.par) {
-        static size_t lds_set_par[64] = {0};
-        hipError_t e = ensure_dynamic_lds(&kmpc_solve_par_kernel<T, NT, 1>, lds, lds_set_par);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((kmpc_solve_par_kernel<T, NT, 1>), dim3(P.B), dim3(64), lds, st, P, io);
-        return hipGetLastError();
-    }
-    hipError_t e = ensure_dynamic_lds(&kmpc_solve_frenet_kernel<T, NT>, lds, lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((kmpc_solve_frenet_kernel<T, NT>), dim3(P.B), dim3(64), lds, st, P, io);
-    return hipGetLastError();
-}
-template <typename T, int NT>
-static hipError_t launch_condense_nt(const KP &P, const KDbg<T> &io, hipStream_t st)
-{
-    const size_t lds = kmpc_lds_bytes<T>(P.N, NT);
-    static size_t lds_set[64] = {0};
-    hipError_t e = ensure_dynamic_lds(&kmpc_condense_kernel<T, NT>, lds, lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((kmpc_condense_kernel<T, NT>), dim3(P.B), dim3(64), lds, st, P, io);
-    return hipGetLastError();
+    return kmpc_launch(KERNEL, dim3(P.B), dim3(64), lds, st, P, io);
 }
 
-#define KMPC_DISPATCH_NT(FN, ...)                                   \
-    switch (NT) {                                                   \
-        case 1: return FN<T, 1>(__VA_ARGS__);                       \
-        case 2: return FN<T, 2>(__VA_ARGS__);                       \
-        case 3: return FN<T, 3>(__VA_ARGS__);                       \
-        case 4: return FN<T, 4>(__VA_ARGS__);                       \
-        case 5: return FN<T, 5>(__VA_ARGS__);                       \
-        case 6: return FN<T, 6>(__VA_ARGS__);                       \
-        case 7: return FN<T, 7>(__VA_ARGS__);                       \
-        default: return hipErrorInvalidValue;                       \
-    }
-
-template <typename T> hipError_t kmpc_launch_solve(const KP &P, const KIO<T> &io, hipStream_t st)
+// the Frenet functor is built for horizons up to N = 24 (kmpc_generic_frenet_tiles; the reference's is N = 8)
+template <typename T> hipError_t kmpc_launch_solve(const KP &P, const KIO<T> &io, int model, hipStream_t st)
 {
-    const int NT = (2 * P.N + 15) / 16;
-    KMPC_DISPATCH_NT(launch_solve_nt, P, io, st)
-}
-// Frenet functor: built for horizons up to N = 24 (the reference's is N = 8)
-template <typename T> hipError_t kmpc_launch_solve_frenet(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    switch ((2 * P.N + 15) / 16) {
-        case 1: return launch_solve_frenet_nt<T, 1>(P, io, st);
-        case 2: return launch_solve_frenet_nt<T, 2>(P, io, st);
-        case 3: return launch_solve_frenet_nt<T, 3>(P, io, st);
-        default: return hipErrorInvalidValue;
-    }
+    const int nt = (2 * P.N + 15) / 16;
+    if (model == 1)
+        return kmpc_dispatch(kmpc_generic_frenet_tiles(), nt, hipErrorInvalidValue, [&](auto t) {
+            constexpr int NT = decltype(t)::value;
+            return io.par ? launch_dynamic_lds<&kmpc_solve_par_kernel<T, NT, 1>, T>(P, NT, io, st) : launch_dynamic_lds<&kmpc_solve_frenet_kernel<T, NT>, T>(P, NT, io, st);
+        });
+    return kmpc_dispatch(kmpc_generic_tiles(), nt, hipErrorInvalidValue, [&](auto t) {
+        constexpr int NT = decltype(t)::value;
+        return io.par ? launch_dynamic_lds<&kmpc_solve_par_kernel<T, NT, 0>, T>(P, NT, io, st) : launch_dynamic_lds<&kmpc_solve_kernel<T, NT>, T>(P, NT, io, st);
+    });
 }
 template <typename T> hipError_t kmpc_launch_condense(const KP &P, const KDbg<T> &io, hipStream_t st)
 {
-    const int NT = (2 * P.N + 15) / 16;
-    KMPC_DISPATCH_NT(launch_condense_nt, P, io, st)
+    return kmpc_dispatch(kmpc_generic_tiles(), (2 * P.N + 15) / 16, hipErrorInvalidValue, [&](auto t) {
+        constexpr int NT = decltype(t)::value;
+        return launch_dynamic_lds<&kmpc_condense_kernel<T, NT>, T>(P, NT, io, st);
+    });
 }
 template <typename T> hipError_t kmpc_launch_probe(const T *a, const T *b, T *d, hipStream_t st)
 {
-    hipLaunchKernelGGL((kmpc_mfma_probe_kernel<T>), dim3(1), dim3(64), 0, st, a, b, d);
-    return hipGetLastError();
+    return kmpc_launch(&kmpc_mfma_probe_kernel<T>, dim3(1), dim3(64), 0, st, a, b, d);
 }
 
-template hipError_t kmpc_launch_solve<double>(const KP &, const KIO<double> &, hipStream_t);
-template hipError_t kmpc_launch_solve<float>(const KP &, const KIO<float> &, hipStream_t);
-template hipError_t kmpc_launch_solve_frenet<double>(const KP &, const KIO<double> &, hipStream_t);
-template hipError_t kmpc_launch_solve_frenet<float>(const KP &, const KIO<float> &, hipStream_t);
+template hipError_t kmpc_launch_solve<double>(const KP &, const KIO<double> &, int, hipStream_t);
+template hipError_t kmpc_launch_solve<float>(const KP &, const KIO<float> &, int, hipStream_t);
 template hipError_t kmpc_launch_condense<double>(const KP &, const KDbg<double> &, hipStream_t);
 template hipError_t kmpc_launch_condense<float>(const KP &, const KDbg<float> &, hipStream_t);
 template hipError_t kmpc_launch_probe<double>(const double *, const double *, double *, hipStream_t);

@@ -23,6 +23,7 @@
 // stream serves four problems.  Stage records are KMPC_STG words, there is no G_N table, and condense_frenet replaces the adjoint recursion; KKT
 // assembly, Cholesky, the substitutions and the state machine are the Cartesian ones.  tests/test_frenet_quad.py.
 #include "kmpc_ipm.h"
+#include "kmpc_dispatch.h"
 
 template <typename T> DEV T row_sum(T x) {   // sum over the 16 lanes of a DPP row, identical bits in every lane
     x += dpp_mov0<0x128, 0xf>(x); x += dpp_mov0<0x124, 0xf>(x); x += dpp_mov0<0x122, 0xf>(x); x += dpp_mov0<0x121, 0xf>(x);
@@ -338,10 +339,7 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_ke
     // whose size is not a multiple of four repeat its last problem (same inputs, same stores)
     const int sl = slot < P.B ? slot : P.B - 1;
     const int b = io.perm ? io.perm[sl] : sl;
-#ifdef KMPC_POISON
-    for (int e = threadIdx.x; e < QuadSolver<T>::lds_elems(); e += 64) reinterpret_cast<T *>(smem)[e] = (T)NAN;
-    __syncthreads();
-#endif
+    ipm::poison_lds<T>(smem, QuadSolver<T>::lds_elems(), 64);
     QuadSolver<T> sv(P, smem);
     ipm::load_problem_io(sv, io, b);
     sv.solve(io, b);
@@ -356,10 +354,7 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_fr
     if (4 * (int)blockIdx.x >= P.B) return;
     const int sl = slot < P.B ? slot : P.B - 1;   // rows past the end repeat the last problem (same inputs, same stores)
     const int b = io.perm ? io.perm[sl] : sl;
-#ifdef KMPC_POISON
-    for (int e = threadIdx.x; e < QuadSolver<T, 1>::lds_elems(); e += 64) reinterpret_cast<T *>(smem)[e] = (T)NAN;
-    __syncthreads();
-#endif
+    ipm::poison_lds<T>(smem, QuadSolver<T, 1>::lds_elems(), 64);
     QuadSolver<T, 1> sv(P, smem);
     ipm::load_problem_io(sv, io, b);
     sv.solve(io, b);
@@ -374,10 +369,7 @@ template <typename T, int MODEL> DEV void kmpc_solve_quad_par_body(const KP &P, 
     if (4 * (int)blockIdx.x >= P.B) return;
     const int sl = slot < P.B ? slot : P.B - 1;   // rows past the end repeat the last problem (same inputs, same stores)
     const int b = io.perm ? io.perm[sl] : sl;
-#ifdef KMPC_POISON
-    for (int e = threadIdx.x; e < SV::lds_elems(); e += 64) reinterpret_cast<T *>(smem)[e] = (T)NAN;
-    __syncthreads();
-#endif
+    ipm::poison_lds<T>(smem, SV::lds_elems(), 64);
     SV sv(P, smem);
     const bool mine = ipm::apply_param_record(const_cast<T *>(sv.pt), io.par + (size_t)b * KMPC_PAR_STRIDE, sv.lane, true);
     WFENCE();
@@ -398,24 +390,13 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_fr
     kmpc_solve_quad_par_body<T, 1>(P, io, smem);
 }
 
-template <typename T> bool kmpc_quad_available(int N) { return N == 8; }
-template <typename T> hipError_t kmpc_launch_solve_quad(const KP &P, const KIO<T> &io, hipStream_t st)
+// launcher (called from kmpc_api.hip): P.B problems in ceil(P.B / 4) waves
+template <typename T> hipError_t kmpc_launch_solve_quad(const KP &P, const KIO<T> &io, int model, hipStream_t st)
 {
-    if (P.N != 8) return hipErrorInvalidValue;
-    if (io.par) hipLaunchKernelGGL((kmpc_solve_quad_par_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
-    else hipLaunchKernelGGL((kmpc_solve_quad_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
-    return hipGetLastError();
+    if (P.N != KMPC_QUAD_HORIZON) return hipErrorInvalidValue;
+    void (*kernel)(KP, KIO<T>) = io.par ? &kmpc_solve_quad_par_kernel<T> : &kmpc_solve_quad_kernel<T>;
+    if (model == 1) kernel = io.par ? &kmpc_solve_quad_frenet_par_kernel<T> : &kmpc_solve_quad_frenet_kernel<T>;
+    return kmpc_launch(kernel, dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
 }
-template bool kmpc_quad_available<double>(int);
-template bool kmpc_quad_available<float>(int);
-template hipError_t kmpc_launch_solve_quad<double>(const KP &, const KIO<double> &, hipStream_t);
-template hipError_t kmpc_launch_solve_quad<float>(const KP &, const KIO<float> &, hipStream_t);
-template <typename T> hipError_t kmpc_launch_solve_quad_frenet(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    if (P.N != 8) return hipErrorInvalidValue;
-    if (io.par) hipLaunchKernelGGL((kmpc_solve_quad_frenet_par_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
-    else hipLaunchKernelGGL((kmpc_solve_quad_frenet_kernel<T>), dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
-    return hipGetLastError();
-}
-template hipError_t kmpc_launch_solve_quad_frenet<double>(const KP &, const KIO<double> &, hipStream_t);
-template hipError_t kmpc_launch_solve_quad_frenet<float>(const KP &, const KIO<float> &, hipStream_t);
+template hipError_t kmpc_launch_solve_quad<double>(const KP &, const KIO<double> &, int, hipStream_t);
+template hipError_t kmpc_launch_solve_quad<float>(const KP &, const KIO<float> &, int, hipStream_t);

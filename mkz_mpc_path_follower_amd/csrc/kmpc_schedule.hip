@@ -15,7 +15,7 @@
 // Implementation: a 256-bucket counting sort on the quantised key in two small kernels -- keys + histogram ranks
 // (atomics), then prefix + scatter -- into a permutation the solve kernels index through (KIO::perm).
 #include <hip/hip_runtime.h>
-#include "kmpc_device.h"
+#include "kmpc_dispatch.h"
 
 template <typename T>
 __device__ __forceinline__ uint32_t sched_bucket(int i, int N, double dt, const T *z0, size_t zs, const T *ref, size_t rs)

@@ -13,18 +13,7 @@
 // Arithmetic mirrors numpy exactly (no FMA contraction in the distance and in np.interp's
 // slope*(x - xp[j]) + fp[j]) so that indices match bit for bit and values to the last ulp.
 #include "kmpc_common.h"
-
-struct WP {
-    int M, B, H;         // path samples, vehicles, horizon (H+1 waypoints)
-    int use_vtarget;     // 1: arclength grid with per-vehicle v_target, 0: time grid
-    double traj_dt;
-    const double *t, *X, *Y, *psi, *s;
-    const double *pose;  // [B,3] x, y, yaw
-    const double *vt;    // [B] or null
-    double *ref;         // [B,H+1,3] x, y, psi
-    int32_t *stop;       // [B]
-    int32_t *closest;    // [B] or null (diagnostic)
-};
+#include "kmpc_dispatch.h"
 
 // np.interp (numpy/core/src/multiarray/compiled_base.c arr_interp) for one query point
 DEV double np_interp(double xq, const double *xp, const double *fp, int M)

@@ -19,6 +19,7 @@
 //   * workgroup barriers only where data crosses waves: one per block-step of the factorisation, one per reduction; the three triangular
 //     substitutions run in wave 0 with two slots per lane (v_readlane broadcasts, no barrier inside).
 #include "kmpc_ipm.h"
+#include "kmpc_dispatch.h"
 
 #define WGSYNC() __syncthreads()
 
@@ -595,62 +596,28 @@ __global__ __launch_bounds__(256, 2) void kmpc_wide_kkt_kernel(KP P, KDbgK<T> io
     if (tid < n) { io.g[(size_t)b * n + tid] = g; io.x[(size_t)b * n + tid] = x; }
     if (tid == 0) io.ok[b] = okf ? 1 : 0;
 }
+// ---- launchers (called from kmpc_api.hip) --------------------------------------------------------------------------------------------------------------
 template <typename T> hipError_t kmpc_launch_wide_kkt(const KP &P, const KDbgK<T> &io, hipStream_t st)
 {
-    if (P.N == 50) hipLaunchKernelGGL((kmpc_wide_kkt_kernel<T, 50>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 48) hipLaunchKernelGGL((kmpc_wide_kkt_kernel<T, 48>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 44) hipLaunchKernelGGL((kmpc_wide_kkt_kernel<T, 44>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 40) hipLaunchKernelGGL((kmpc_wide_kkt_kernel<T, 40>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 36) hipLaunchKernelGGL((kmpc_wide_kkt_kernel<T, 36>), dim3(P.B), dim3(256), 0, st, P, io);
-    else if (P.N == 32) hipLaunchKernelGGL((kmpc_wide_kkt_kernel<T, 32>), dim3(P.B), dim3(256), 0, st, P, io);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return kmpc_dispatch(kmpc_wide_horizons(), P.N, hipErrorInvalidValue, [&](auto n) {
+        return kmpc_launch(&kmpc_wide_kkt_kernel<T, decltype(n)::value>, dim3(P.B), dim3(256), 0, st, P, io);
+    });
 }
 template hipError_t kmpc_launch_wide_kkt<double>(const KP &, const KDbgK<double> &, hipStream_t);
 template hipError_t kmpc_launch_wide_kkt<float>(const KP &, const KDbgK<float> &, hipStream_t);
 
-// horizons whose n + 1 rows make 7 (N = 48, the BASELINE's 50), 6 (N = 40, 44) or 5 (N = 32, 36) tile rows, with one thread per form (5N - 2 <= 256)
-template <typename T> bool kmpc_wide_available(int N) { return N == 50 || N == 48 || N == 44 || N == 40 || N == 36 || N == 32; }
-template <typename T, int N> static void launch_wide_n(const KP &P, const KIO<T> &io, hipStream_t st)
+// the Frenet functor is fp64 only (kmpc_select has no fp32 answer for it): no fp32 instantiation
+template <typename T> hipError_t kmpc_launch_solve_wide(const KP &P, const KIO<T> &io, int model, hipStream_t st)
 {
-    if (io.par) hipLaunchKernelGGL((kmpc_solve_wide_par_kernel<T, N>), dim3(P.B), dim3(256), 0, st, P, io);
-    else hipLaunchKernelGGL((kmpc_solve_wide_kernel<T, N>), dim3(P.B), dim3(256), 0, st, P, io);
+    return kmpc_dispatch(kmpc_wide_horizons(), P.N, hipErrorInvalidValue, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        void (*kernel)(KP, KIO<T>) = io.par ? &kmpc_solve_wide_par_kernel<T, N> : &kmpc_solve_wide_kernel<T, N>;
+        if (model == 1) {
+            if constexpr (sizeof(T) != 8) return hipErrorInvalidValue;
+            else kernel = io.par ? &kmpc_solve_wide_frenet_par_kernel<T, N> : &kmpc_solve_wide_frenet_kernel<T, N>;
+        }
+        return kmpc_launch(kernel, dim3(P.B), dim3(256), 0, st, P, io);
+    });
 }
-template <typename T> hipError_t kmpc_launch_solve_wide(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    if (P.N == 50) launch_wide_n<T, 50>(P, io, st);
-    else if (P.N == 48) launch_wide_n<T, 48>(P, io, st);
-    else if (P.N == 44) launch_wide_n<T, 44>(P, io, st);
-    else if (P.N == 40) launch_wide_n<T, 40>(P, io, st);
-    else if (P.N == 36) launch_wide_n<T, 36>(P, io, st);
-    else if (P.N == 32) launch_wide_n<T, 32>(P, io, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-template bool kmpc_wide_available<double>(int);
-template bool kmpc_wide_available<float>(int);
-template hipError_t kmpc_launch_solve_wide<double>(const KP &, const KIO<double> &, hipStream_t);
-template hipError_t kmpc_launch_solve_wide<float>(const KP &, const KIO<float> &, hipStream_t);
-
-// Frenet functor at the same horizons; fp64 only (kmpc_create refuses fp32 with model = 1 beyond N = 28)
-template <typename T, int N> static void launch_wide_frenet_n(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    if (io.par) hipLaunchKernelGGL((kmpc_solve_wide_frenet_par_kernel<T, N>), dim3(P.B), dim3(256), 0, st, P, io);
-    else hipLaunchKernelGGL((kmpc_solve_wide_frenet_kernel<T, N>), dim3(P.B), dim3(256), 0, st, P, io);
-}
-template <typename T> hipError_t kmpc_launch_solve_wide_frenet(const KP &P, const KIO<T> &io, hipStream_t st)
-{
-    if constexpr (sizeof(T) != 8) return hipErrorInvalidValue;
-    else {
-        if (P.N == 50) launch_wide_frenet_n<T, 50>(P, io, st);
-        else if (P.N == 48) launch_wide_frenet_n<T, 48>(P, io, st);
-        else if (P.N == 44) launch_wide_frenet_n<T, 44>(P, io, st);
-        else if (P.N == 40) launch_wide_frenet_n<T, 40>(P, io, st);
-        else if (P.N == 36) launch_wide_frenet_n<T, 36>(P, io, st);
-        else if (P.N == 32) launch_wide_frenet_n<T, 32>(P, io, st);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-}
-template hipError_t kmpc_launch_solve_wide_frenet<double>(const KP &, const KIO<double> &, hipStream_t);
-template hipError_t kmpc_launch_solve_wide_frenet<float>(const KP &, const KIO<float> &, hipStream_t);
+template hipError_t kmpc_launch_solve_wide<double>(const KP &, const KIO<double> &, int, hipStream_t);
+template hipError_t kmpc_launch_solve_wide<float>(const KP &, const KIO<float> &, int, hipStream_t);

@@ -4,6 +4,8 @@ import os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from mkz_mpc_path_follower_amd import _lib
+if os.environ.get("KMPC_LIB"): _lib.LIB_PATH = os.path.abspath(os.environ["KMPC_LIB"])  # A/B of library builds
 from mkz_mpc_path_follower_amd import KinematicMPC
 for N in (8, 20):
     k = KinematicMPC(N=N)
