@@ -911,7 +911,7 @@ template <class SV> DEV void solve(SV &s, const KIO<typename SV::real> &io, int 
     // cancellation once an active slack is ~1e-9
     T sup[NF], slo[NF], isu[NF], isl[NF], lu[NF], ll[NF], aut[NF], w[NF];  // isu/isl = 1/slack, refreshed when the slacks move
     bool fv[NF];
-    // degenerate pairs (slack and multiplier vanish together: Newton halves them per iteration, x0.375 with the corrector; kmpc_common.h): a side of a form
+    // degenerate pairs (slack and multiplier vanish together: Newton halves them per iteration, x0.375 with the corrector; kmpc_tuning.h): a side of a form
     // whose slack and multiplier the last accepted full step shrank by similar shares enters K (and the recovery of its multiplier step, consistently) with
     // its barrier stiffness lambda/s scaled by KMPC_DEGEN_THETA -- the step of a double root.  Candidates are marked where the step is computed (its step-length
     // shares are the signature; two lowest mantissa bits of a_f^T du), a candidate becomes a mark when the step is accepted in full: the lowest mantissa bit of
@@ -1003,7 +1003,7 @@ template <class SV> DEV void solve(SV &s, const KIO<typename SV::real> &io, int 
         // lanes stale slot contents -- lets the method converge, by its own measure, on a KKT point of a SHIFTED problem.  An
         // offset, once there, stays (every later update is an increment), so ONE comparison at the end of the solve covers all of its iterates, the
         // saved best one included: the slacks of the last iterate (U at this point on every path into FINAL) against its freshly evaluated forms.
-        // Drift beyond KMPC_DRIFT_TOL * max(1, |bound|, |a_f^T U|) on any live form => KMPC_NUMERICAL_ERROR, never Optimal (tolerances: kmpc_common.h).
+        // Drift beyond KMPC_DRIFT_TOL * max(1, |bound|, |a_f^T U|) on any live form => KMPC_NUMERICAL_ERROR, never Optimal (tolerances: kmpc_tuning.h).
         if (mode == FINAL && status != 2) {
             s.forms_apply(U, w);
             T drifted = (T)0;
@@ -1064,7 +1064,7 @@ template <class SV> DEV void solve(SV &s, const KIO<typename SV::real> &io, int 
             const T phi0 = cs[C_PHI0];
             const T dphi = cs[C_DPHI], pred = -alpha * dphi;
             const bool armijo = phi - phi0 - (T)10 * Real<T>::eps() * fabs(phi0) <= -eta_phi * pred;
-            const bool below_noise = dphi <= (T)0 && pred <= (T)KMPC_NOISE_ACCEPT * Real<T>::eps() * fabs(phi0);   // (kmpc_common.h)
+            const bool below_noise = dphi <= (T)0 && pred <= (T)KMPC_NOISE_ACCEPT * Real<T>::eps() * fabs(phi0);   // (kmpc_tuning.h)
             if (!(okp && (armijo || below_noise))) {
                 // safeguard: the corrected direction is tried at the full step only; redo the step without the corrector term
                 if (corr_active) {
@@ -1192,8 +1192,8 @@ template <class SV> DEV void solve(SV &s, const KIO<typename SV::real> &io, int 
                 if (err0 <= tol || better) s.save_best(U);
                 if (err0 <= tol) have_best = true;
                 if (err0 <= tol) {
-                    if (gap <= gap_lim * sc || n_polish >= 1) done = true; else ++n_polish;
-                } else if (n_polish > 0 && ++n_polish > 1) done = true;
+                    if (gap <= gap_lim * sc || n_polish >= KMPC_MAX_POLISH) done = true; else ++n_polish;
+                } else if (n_polish > 0 && ++n_polish > KMPC_MAX_POLISH) done = true;
                 n_accept = err0 <= s.pt[PT_TOL_X100] ? n_accept + 1 : 0;
                 // rounding floor: the objective has not moved by more than 20 eps |J| for 12 iterations in a row -> the arithmetic cannot
                 // improve the iterate (fp32, large costs: the dual residual never settles below 100 tol); Optimal within 1e3 tol
@@ -1224,7 +1224,7 @@ template <class SV> DEV void solve(SV &s, const KIO<typename SV::real> &io, int 
                 // in shift mode the previous iteration's delta_w / 3 is the first trial (dropped below 1e-9 * max|H_jj|)
                 // ... and after two first-trial successes in a row the unshifted matrix is tried first again: a decaying shift slows the end game of the solves
                 // that have left the non-convex region
-                if (use_exact && indef == 1 && cs[C_DWS] > (T)0) { reg = cs[C_DWS] / (T)3; if (reg < (T)1e-9 * cs[C_HMAX] || n_first_ok >= 2) reg = 0; }
+                if (use_exact && indef == 1 && cs[C_DWS] > (T)0) { reg = cs[C_DWS] / (T)KMPC_DW_DECAY; if (reg < (T)1e-9 * cs[C_HMAX] || n_first_ok >= KMPC_ZERO_AFTER) reg = 0; }
                 first_attempt = true;
                 STAMP_AT(s, 2);
             }
@@ -1244,14 +1244,14 @@ template <class SV> DEV void solve(SV &s, const KIO<typename SV::real> &io, int 
                 if (!giveup) {
                     if (use_exact && indef == 1) {
                         const T hmax = cs[C_HMAX], dw_last = cs[C_DWL];
-                        if (reg == (T)0) reg = dw_last > (T)0 ? fmax((T)1e-10 * hmax, dw_last / (T)3) : (T)1e-2 * hmax;
+                        if (reg == (T)0) reg = dw_last > (T)0 ? fmax((T)1e-10 * hmax, dw_last / (T)KMPC_DW_DECAY) : (T)KMPC_DW_FIRST * hmax;
                         else reg *= dw_last > (T)0 ? (T)KMPC_DW_GROW : (T)10;
                         if (reg > (T)1e2 * hmax) { use_exact = false; reg = 0; s.drop_second_order(); }
                     } else if (use_exact) {
                         use_exact = false; gn_hold = 2; s.drop_second_order();
                         // (hybrid: shift mode from the first failure up to N = 28 on cold starts, from the second beyond and on warm starts -- pooled
                         // worst-of-4096 statistics; a warm start from a poor point begins at mu = 1e-6, where shift mode right away stalls)
-                        if (indef_cfg == 2 && ++n_fail >= ((N >= 32 || warm) ? 2 : 1)) { indef = 1; gn_hold = 0; }
+                        if (indef_cfg == 2 && ++n_fail >= KMPC_SHIFT_AFTER(N, warm)) { indef = 1; gn_hold = 0; }
                     } else reg = reg == (T)0 ? (T)1e-8 : reg * (T)100;  // last resort: shift the Gauss-Newton matrix
                     mode = REFACTOR;
                 } else { status = 3; mode = FINAL; final_reuse = true; }

@@ -1,10 +1,8 @@
 /*
  * oracle/kmpc_condensed.c -- TEST INFRASTRUCTURE (see kmpc_condensed.h).  PARITY UNPINNED.
  */
-#ifndef KMPC_NOISE_ACCEPT
-#define KMPC_NOISE_ACCEPT 100.0 /* same value as csrc/kmpc_common.h */
-#endif
 #include "kmpc_condensed.h"
+#include "kmpc_tuning.h" /* the tuned constants, shared with the kernels (oracle/Makefile: -I) */
 #include <math.h>
 #include <pthread.h>
 #include <stdlib.h>
@@ -25,6 +23,13 @@ void kmpc_opts_default(kmpc_opts *o)
     o->mu_strategy = -1;
     o->indef_strategy = -1;
     o->start = 0;
+    o->degen_theta = KMPC_DEGEN_THETA;
+    o->unstick = KMPC_UNSTICK;
+    o->noise_accept = KMPC_NOISE_ACCEPT;
+    o->dw_grow = KMPC_DW_GROW;
+    o->ikrd = KMPC_IKRD;
+    o->ikrd_nc = KMPC_IKRD_NC;
+    o->trace = 0;
 }
 
 /* ---- "forms": the 5N-2 distinct linear forms a_f^T U behind the 10N-4 one-sided rows.
@@ -458,63 +463,53 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
        one problem in six its last iteration -- mean 7.90 -> 7.77 at N = 20 -- with cost errors still <= 3.5e-8, but on flat problems the first
        input then moves by up to 5e-5 between two implementations that stop one iteration apart: kept at 1e-7, round 3) */
     const double gap_tol = 1e-7;
-    const int max_polish = getenv("KMPC_X_POLISH") ? atoi(getenv("KMPC_X_POLISH")) : 1;
     int gn_hold = 0;
     /* after a tiny fraction-to-the-boundary step the barrier floor applies without its cap at the current mean complementarity: a warm start from a wrong
        point (mu = 1e-7, slacks 1e-5 off the bounds) otherwise crawls to the iteration cap in steps of 1e-6 -- mu_cur can never grow (1 of 32 768 wrong-point
        warm starts at N = 8 and at N = 20; with the rule at most 20 / 34 iterations; warm starts from the own solution and cold starts unchanged; 1e-3 already
        costs the own-solution warm starts at N = 20 half an iteration) */
-    const double x_unstick = getenv("KMPC_X_UNSTICK") ? atof(getenv("KMPC_X_UNSTICK")) : 1e-4;
+    const double x_unstick = o->unstick;
     double alpha_last = 1.0;
     /* degenerate complementarity pairs (slack and multiplier vanish together; structurally the last acceleration input, tied to its neighbour by the
        rate cost only): Newton halves both per iteration (x0.375 with the corrector).  A side seen shrinking that way in an accepted (nearly) full step
        enters K -- and the recovery of its multiplier step -- with theta * lambda/s: the step of a double root (s+ = 0.13 s at theta = 0.6; below 0.45
        the corrected step overshoots the bound).  12 x 4096 seeded problems, N = 20: mean iterations 7.45 -> 7.10, E[worst of 4096] 21.7 -> 19.6;
        N = 8: 6.48 -> 6.13 / 13.5 -> 11.4; N = 12: 8.56 -> 7.76; N = 28: 7.70 -> 7.53; N = 50: 8.97 -> 8.84; same minima (costs to 2e-8).
-       KMPC_X_DEGEN = 1 switches it off. */
-    const double x_degen = getenv("KMPC_X_DEGEN") ? atof(getenv("KMPC_X_DEGEN")) : 0.6;
+       degen_theta = 1 switches it off. */
+    const double x_degen = o->degen_theta;
     double *thu = (double *)malloc((size_t)2 * nf * sizeof(double)), *thl = thu + nf;
     for (int f = 0; f < 2 * nf; ++f) thu[f] = 1.0;
     int *cand = (int *)calloc((size_t)nf, sizeof(int));
-    double dw_last = 0.0, dw_spec = 0.0, hmax_prev = 0.0, reg_final = 0.0;
+    double dw_last = 0.0, dw_spec = 0.0, hmax_prev = 0.0;
     /* Tuned on the pooled worst-of-4096 statistics of 48 seeded batches (the kernels carry the same values):
        after a failed first trial (= last/3) the shift grows x3 -- back to the one that worked last iteration -- instead of x8;
-       in shifted (non-convex) iterations the barrier floor is rd/100 instead of rd/1000.  Experiment overrides: KMPC_X_GROW, KMPC_X_KRDNC. */
-    const double dw_grow = getenv("KMPC_X_GROW") ? atof(getenv("KMPC_X_GROW")) : 3.0;
+       in shifted (non-convex) iterations the barrier floor is rd/100 (rd/40 since the first-failure switch) instead of rd/1000. */
+    const double dw_grow = o->dw_grow;
     /* A trial point is also accepted when the predicted decrease of phi_mu is below the noise of its evaluation (100 eps |phi|: the
        cost is a sum of C e^2 terms whose e = x - x_ref carries eps |x|, |x| >> |e|, so phi is resolved to ~50-70 eps |phi|, not to the
        10 eps of Ipopt's slack): near a low-cost optimum the Armijo test otherwise fails on rounding alone, the search backtracks max_ls
-       times and takes a 1e-5 step "by luck" -- ~100 wasted roll-outs per solve on ~0.25 % of the problems.  Experiment override: KMPC_X_NOISE. */
-    const double x_decay = getenv("KMPC_X_DECAY") ? atof(getenv("KMPC_X_DECAY")) : 3.0;
-    const int x_zero_after = getenv("KMPC_X_ZEROAFTER") ? atoi(getenv("KMPC_X_ZEROAFTER")) : 2;
-    int n_first_ok = 0, full_prev = 0;
-    const int x_leave = getenv("KMPC_X_LEAVE") ? atoi(getenv("KMPC_X_LEAVE")) : 0;
-    const double x_dw0 = getenv("KMPC_X_DW0") ? atof(getenv("KMPC_X_DW0")) : 1e-2;   /* experiment: first shift relative to max |sc H_jj| */
-    const double x_sigexp = getenv("KMPC_X_SIGEXP") ? atof(getenv("KMPC_X_SIGEXP")) : 3.0;   /* experiment knobs: Mehrotra exponent, fraction to the boundary */
-    const double x_tau = getenv("KMPC_X_TAU") ? atof(getenv("KMPC_X_TAU")) : tau_min;
-    const int x_gate = getenv("KMPC_X_GATE") ? atoi(getenv("KMPC_X_GATE")) : 2;
+       times and takes a 1e-5 step "by luck" -- ~100 wasted roll-outs per solve on ~0.25 % of the problems. */
+    const double k_noise = o->noise_accept;
+    int n_first_ok = 0;
     double err_p1 = INFINITY, err_p2 = INFINITY;
-    const double k_noise = getenv("KMPC_X_NOISE") ? atof(getenv("KMPC_X_NOISE")) : KMPC_NOISE_ACCEPT;
-    const double kappa_rd_nc = getenv("KMPC_X_KRDNC") ? atof(getenv("KMPC_X_KRDNC")) : 40.0;   /* (1e2 until the first-failure switch; re-measured: 10 ... 300) */
     /* 2 = hybrid: Gauss-Newton fallback until the exact Hessian has failed gn_switch times, delta_w shift from then on */
     const int indef_cfg = o->indef_strategy >= 0 ? o->indef_strategy : 2;
     int indef_strategy = indef_cfg == 2 ? 0 : indef_cfg, n_fail = 0;
     /* Round 3: one failure is enough up to N = 28 -- pooled worst-of-4096 iteration-equivalents 25.75 -> 23.52 at N = 20, 22.9 -> 20.6 at N = 12,
        30.5 -> 29.1 at N = 28 with the mean unchanged (+0.1 ... 0.5 %); at N = 50 the mean would rise 4.6 % for 5 % off the tail, and that
-       config is throughput-bound, so the long horizons keep two.  Experiment override: KMPC_X_GNSWITCH. */
-    const int gn_switch = getenv("KMPC_X_GNSWITCH") ? atoi(getenv("KMPC_X_GNSWITCH")) : ((N >= 32 || o->warm) ? 2 : 1);   /* (a warm start from a poor point begins at mu = 1e-6: shift mode right away stalls there --
-                                                                                                        3 of 32768 wrong-point warm starts hit the iteration cap, mean 10.7 -> 12.4 iterations; tools/warm_probe.py) */
+       config is throughput-bound, so the long horizons keep two.  (A warm start from a poor point begins at mu = 1e-6: shift mode right away stalls there --
+       3 of 32768 wrong-point warm starts hit the iteration cap, mean 10.7 -> 12.4 iterations; tools/warm_probe.py.) */
+    const int gn_switch = KMPC_SHIFT_AFTER(N, o->warm);
     /* Mehrotra safeguards: the barrier target may not drop below (scaled dual infeasibility)/kappa_rd while that exceeds the
        current complementarity (a Gauss-Newton step does not reduce the dual residual the way an LP/QP step does); and the
-       corrected direction is only tried at the full fraction-to-the-boundary step */
-    const double kappa_rd = getenv("KMPC_X_KRD") ? atof(getenv("KMPC_X_KRD")) : 1e3;
+       corrected direction is only tried at the full fraction-to-the-boundary step.  (The kernels multiply by KMPC_IKRD / KMPC_IKRD_NC; the port divides by
+       their reciprocals, exactly 1e3 and 40; 1e2 in shifted iterations until the first-failure switch, re-measured: 10 ... 300) */
+    const double kappa_rd = 1.0 / o->ikrd, kappa_rd_nc = 1.0 / o->ikrd_nc;
     /* ... but not while the solve is visibly converging: outside shift mode (two failed exact factorisations, or indef_strategy 1 from the
        start) the floor is dropped whenever the optimality error fell in each of the last two iterations.  There it only slowed the end game
        -- mean iterations 7.94 -> 7.45 (N = 20), 9.83 -> 8.97 (N = 50), 6.93 -> 6.48 (N = 8), worst-of-4096 statistics unchanged (pooled batches).
        Without ANY floor outside shift mode a rare problem cycles (N = 50 bench batch, #1010: mu collapses to 1e-8 at error 5, the next step is
-       3 % long, and so on to the iteration cap): its error never falls twice in a row, so it keeps the floor.  KMPC_X_GATE: 0 no gate (no floor
-       outside shift mode), 1 floor off after a full primal-dual step, 2 (default) the error rule; KMPC_X_KRD_EASY: floor used when the gate is open. */
-    const double kappa_rd_easy = getenv("KMPC_X_KRD_EASY") ? atof(getenv("KMPC_X_KRD_EASY")) : 1e300;
+       3 % long, and so on to the iteration cap): its error never falls twice in a row, so it keeps the floor. */
     int have_best = 0;
     double *Ubest = (double *)malloc((size_t)(n + 2 * nf) * sizeof(double));
     int n_polish = 0, n_accept = 0, n_tiny = 0, tiny_stop = 0, n_flat = 0;
@@ -582,7 +577,7 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
         /* Ipopt's scaled test, plus an UNSCALED duality-gap bound so that the cost is within
            gap_tol*max(1,|J|) of the optimum whatever the objective scaling was */
         const double gap_lim = gap_tol * fmax(1.0, fabs(J));
-        /* termination: Ipopt's test (+ the gap bound, pursued for at most max_polish further iterations once
+        /* termination: Ipopt's test (+ the gap bound, pursued for at most KMPC_MAX_POLISH further iterations once
            Ipopt's test has been met: below mu ~ 1e-11 round-off defeats the line search), or Ipopt's
            "acceptable level": error <= acceptable_tol (100*tol) for acceptable_iter (15) iterations in a row */
         if (err0 <= o->tol) { /* last iterate passing Ipopt's test (with its multipliers, for the certifier) */
@@ -592,9 +587,9 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
             have_best = 1;
         }
         if (err0 <= o->tol) {
-            if (gap / sc <= gap_lim || n_polish >= max_polish) { status = KMPC_OPTIMAL; break; }
+            if (gap / sc <= gap_lim || n_polish >= KMPC_MAX_POLISH) { status = KMPC_OPTIMAL; break; }
             ++n_polish;
-        } else if (n_polish > 0 && ++n_polish > max_polish) { status = KMPC_OPTIMAL; break; }
+        } else if (n_polish > 0 && ++n_polish > KMPC_MAX_POLISH) { status = KMPC_OPTIMAL; break; }
         n_accept = err0 <= 100.0 * o->tol ? n_accept + 1 : 0;
         if (n_accept >= 15) { status = KMPC_OPTIMAL; break; }
         /* rounding floor (the fp32 kernels meet it on large-cost problems: the dual residual is a difference of terms ~1e4 and never
@@ -633,13 +628,13 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
            non-convex region the delta_w = 0 attempt fails iteration after iteration -- up to 40 % of the factorisations of the
            slowest problems -- while a decaying shift costs nothing near the solution (dropped below 1e-9 * max|H_jj|) */
         if (!use_gn && indef_strategy == 1 && dw_spec > 0.0) {
-            reg = dw_spec / x_decay;
+            reg = dw_spec / KMPC_DW_DECAY;
             if (reg < 1e-9 * hmax_prev) reg = 0.0;
-            /* after two first-trial successes in a row the unshifted matrix is tried first again (KMPC_X_ZEROAFTER = k, 0 = never): a decaying shift
+            /* after two first-trial successes in a row the unshifted matrix is tried first again: a decaying shift
                slows the end game of the solves that left the non-convex region (error x8 per iteration over the last ten iterations of the slowest
                problem of the bench batch).  12 pooled batches: E[worst of 4096] 22.40 -> 21.71 at N = 20, 19.1 -> 18.2 (N = 12), 28.1 -> 27.3 (N = 28),
                39.3 -> 38.4 (N = 50); means unchanged or slightly lower */
-            if (x_zero_after > 0 && n_first_ok >= x_zero_after) reg = 0.0;
+            if (n_first_ok >= KMPC_ZERO_AFTER) reg = 0.0;
         }
         if (!use_gn && indef_strategy == 1) hmax_prev = hmax;
         for (int attempt = 0;; ++attempt) {
@@ -651,14 +646,11 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
             if (chol(K, n) == 0) {
                 if (!use_gn && reg > 0.0) dw_last = reg;
                 if (!use_gn) { dw_spec = reg; n_first_ok = attempt == 0 ? n_first_ok + 1 : 0; }
-                /* experiment KMPC_X_LEAVE: an unshifted exact factorisation succeeded in shift mode -> the region is convex again: leave shift mode */
-                if (x_leave && !use_gn && indef_cfg == 2 && indef_strategy == 1 && reg == 0.0 && attempt == 0) { indef_strategy = 0; n_fail = 0; }
-                reg_final = use_gn ? 0.0 : reg / fmax(hmax, 1e-300);
                 break;
             }
             ++n_refac;
             if (!use_gn && indef_strategy == 1) {
-                if (reg == 0.0) reg = dw_last > 0.0 ? fmax(1e-10 * hmax, dw_last / 3.0) : x_dw0 * hmax;
+                if (reg == 0.0) reg = dw_last > 0.0 ? fmax(1e-10 * hmax, dw_last / KMPC_DW_DECAY) : KMPC_DW_FIRST * hmax;
                 else reg *= (dw_last > 0.0 ? dw_grow : 10.0);
                 if (reg > 1e2 * hmax) { use_gn = 1; reg = 0.0; }
             } else if (!use_gn) {
@@ -698,15 +690,16 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
             }
             mucur /= 2.0 * nf;
             muaff /= 2.0 * nf;
-            const double r3 = muaff / mucur, sigma = fmin(1.0, x_sigexp == 3.0 ? r3 * r3 * r3 : pow(r3, x_sigexp));
+            const double r3 = muaff / mucur, sigma = fmin(1.0, r3 * r3 * r3);
             mu = fmax(mu_min, sigma * mucur);
             {
                 const int stuck = alpha_last < x_unstick;   /* the last accepted step was a tiny fraction-to-the-boundary step */
-                const double kap = (!use_gn && reg > 0.0) ? kappa_rd_nc : ((stuck || indef_strategy == 1 || !(x_gate == 1 ? full_prev : (x_gate == 2 ? (err0 < err_p1 && err_p1 < err_p2) : 1))) ? kappa_rd : kappa_rd_easy);
-                mu = fmax(mu, fmin(stuck ? 1e300 : mucur, rdmax / s_d / kap));
+                const int shifted = !use_gn && reg > 0.0, converging = err0 < err_p1 && err_p1 < err_p2;
+                if (shifted || stuck || indef_strategy == 1 || !converging)
+                    mu = fmax(mu, fmin(stuck ? 1e300 : mucur, rdmax / s_d / (shifted ? kappa_rd_nc : kappa_rd)));
             }
         }
-        const double tau = fmax(x_tau, 1.0 - mu);
+        const double tau = fmax(tau_min, 1.0 - mu);
         int accepted = 0;
         double alpha = 0.0, ap = 1.0, ad = 1.0;
         for (int pass = 0; pass < 2 && !accepted; ++pass) {
@@ -758,12 +751,12 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
                     phi -= mu * (log(a) + log(b));
                 }
                 /* small slack for round-off as in Ipopt (10 * eps * |phi|) */
-                if (getenv("KMPC_TRACE_LS")) fprintf(stderr, "   ls it %d pass %d l %d alpha %.3e ok %d phi-phi0 %.3e  alpha*dphi %.3e  (phi0 %.6e, sc %.3e)\n", it, pass, l, alpha, ok, phi - phi0, alpha * dphi, phi0, sc);
+                if (o->trace >= 2) fprintf(stderr, "   ls it %d pass %d l %d alpha %.3e ok %d phi-phi0 %.3e  alpha*dphi %.3e  (phi0 %.6e, sc %.3e)\n", it, pass, l, alpha, ok, phi - phi0, alpha * dphi, phi0, sc);
                 if (ok && (phi - phi0 - 10.0 * 2.2e-16 * fabs(phi0) <= eta_phi * alpha * dphi || (dphi <= 0.0 && -alpha * dphi <= k_noise * 2.2e-16 * fabs(phi0)))) { accepted = 1; break; }
             }
         }
         if (!accepted) { status = err0 <= 100.0 * o->tol ? KMPC_OPTIMAL : KMPC_NUMERICAL_ERROR; break; }  /* acceptable level reached */
-        if (getenv("KMPC_TRACE")) fprintf(stderr, "it %3d J %.10g err0 %.3e mu %.2e ap %.3g ad %.3g alpha %.3g rd %.3e comp %.3e gn %d reg/hmax %.2e\n", it, J, err0, mu, ap, ad, alpha, rdmax, cmax0, use_gn, reg / hmax);
+        if (o->trace) fprintf(stderr, "it %3d J %.10g err0 %.3e mu %.2e ap %.3g ad %.3g alpha %.3g rd %.3e comp %.3e gn %d reg/hmax %.2e\n", it, J, err0, mu, ap, ad, alpha, rdmax, cmax0, use_gn, reg / hmax);
         /* Ipopt's tiny-step rule (tiny_step_tol = 10 eps): two accepted steps in a row below 10 eps relative to the iterate mean the
            arithmetic cannot improve it -- stop; Optimal if the error is within 1e3 tol (the rounding floor of the fp32 kernels'
            dual residual sits there), else a numerical error */
@@ -773,7 +766,6 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
             n_tiny = stepn <= 10.0 * 2.2e-16 * umax ? n_tiny + 1 : 0;
         }
         alpha_last = alpha;
-        full_prev = alpha >= 1.0 && ad >= 1.0;   /* the accepted step was a full Newton step in the inputs and in the multipliers */
         memcpy(U, Ut, (size_t)n * sizeof(double));
         if (n_tiny >= 2) { status = err0 <= 1e3 * o->tol ? KMPC_OPTIMAL : KMPC_NUMERICAL_ERROR; tiny_stop = 1; break; }
         /* a candidate (marked where the step was computed, below the fraction-to-the-boundary rule) becomes a degenerate pair when the step was accepted
@@ -796,12 +788,12 @@ int kmpc_condensed_solve(const kmpc_params *p, const kmpc_problem *q_in, const k
 finish:
     /* Run-time guard of the slack iterates (same rule as ipm::solve in csrc/kmpc_ipm.h, round 4): the slacks are iterates and the termination test trusts
        them; an offset between a slack and b -/+ a_f^T U, once there, stays (every update is an increment), so one comparison of the LAST iterate's slacks
-       with its freshly evaluated forms covers every iterate of the solve, the saved best one included.  Beyond 1e-9 relative: Error, never Optimal. */
+       with its freshly evaluated forms covers every iterate of the solve, the saved best one included.  Beyond KMPC_DRIFT_TOL_F64 relative: Error, never Optimal. */
     if (status != KMPC_INFEASIBLE) {
         int drifted = 0;
         forms_apply(&F, U, au);
         for (int f = 0; f < nf; ++f) {
-            const double lim = 1e-9 * fmax(1.0, fmax(fmax(fabs(bu[f]), fabs(bl[f])), fabs(au[f])));
+            const double lim = KMPC_DRIFT_TOL_F64 * fmax(1.0, fmax(fmax(fabs(bu[f]), fabs(bl[f])), fabs(au[f])));
             if (!(fabs(su[f] - (bu[f] - au[f])) <= lim && fabs(sl[f] - (bl[f] + au[f])) <= lim)) drifted = 1;
         }
         if (drifted) { status = KMPC_NUMERICAL_ERROR; have_best = 0; }
@@ -841,7 +833,7 @@ finish:
         res->cost = kmpc_cost(p, q, U, Xl);
         res->viol = kmpc_max_violation(p, q, U);
         res->kkt = err0;
-        res->mu = getenv("KMPC_X_REGFINAL") ? reg_final : mu;
+        res->mu = mu;
     }
     free(mem);
     free(ref_local);

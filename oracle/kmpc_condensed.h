@@ -40,6 +40,14 @@ typedef struct kmpc_opts {
                             2 = hybrid (0 until the second failure, then 1), -1 (default) = 2 */
     int start;           /* cold-start point: 0 (default) = feed-forward guess inside the bounds; 1 = the reference's start, every input 0
                             (MKZMPCPathFollower.jl:65-72), moved inside the bounds where 0 is not strictly feasible */
+    /* the tuned constants a caller may vary (rule on / off tests, tools/pool_stats.py); defaults from csrc/kmpc_tuning.h, which explains each */
+    double degen_theta;  /* KMPC_DEGEN_THETA; outside (0, 1) switches the degenerate-pair rule off */
+    double unstick;      /* KMPC_UNSTICK; 0 switches the rule off */
+    double noise_accept; /* KMPC_NOISE_ACCEPT */
+    double dw_grow;      /* KMPC_DW_GROW */
+    double ikrd;         /* KMPC_IKRD: the solve divides by 1 / ikrd */
+    double ikrd_nc;      /* KMPC_IKRD_NC, likewise */
+    int trace;           /* 1: one line per iteration on stderr, 2: also one per line-search trial; 0 (default): silent */
 } kmpc_opts;
 
 typedef struct kmpc_result {

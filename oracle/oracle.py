@@ -35,7 +35,9 @@ class Opts(C.Structure):
     _fields_ = [("max_iter", C.c_int), ("tol", C.c_double), ("hessian", C.c_int),
                 ("mu_init", C.c_double), ("bound_relax", C.c_double), ("warm", C.c_int),
                 ("warm_push", C.c_double), ("warm_mu", C.c_double), ("max_ls", C.c_int), ("mu_strategy", C.c_int), ("indef_strategy", C.c_int),
-                ("start", C.c_int)]
+                ("start", C.c_int),
+                ("degen_theta", C.c_double), ("unstick", C.c_double), ("noise_accept", C.c_double), ("dw_grow", C.c_double),
+                ("ikrd", C.c_double), ("ikrd_nc", C.c_double), ("trace", C.c_int)]
 
 
 class Result(C.Structure):
@@ -47,6 +49,7 @@ def build(force=False):
     """Compile libkmpc_oracle.so with gcc (oracle/Makefile)."""
     so = os.path.join(_HERE, "libkmpc_oracle.so")
     srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".c", ".h"))]
+    srcs.append(os.path.join(_HERE, "..", "mkz_mpc_path_follower_amd", "csrc", "kmpc_tuning.h"))  # the tuned constants (oracle/Makefile: -I)
     if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call(["make", "-s", "-C", _HERE, "libkmpc_oracle.so"])
     return so

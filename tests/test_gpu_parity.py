@@ -600,7 +600,7 @@ def test_slack_guard_trips_on_a_corrupted_slack():
 
 
 @pytest.mark.parametrize("N,kv", [(8, 0), (8, 1), (20, 0), (50, 0)])
-def test_degenerate_pair_marks_survive_on_the_gpu(oracle, monkeypatch, N, kv):
+def test_degenerate_pair_marks_survive_on_the_gpu(oracle, N, kv):
     """the degenerate-pair rule's marks ride in mantissa bits (lowest bit of a side's reciprocal slack, two lowest bits of a_f^T du:
     kmpc_ipm.h) -- one refactor that recomputes a reciprocal without re-applying the mark would silently disable the rule.  The reference's
     module-load problem (MKZMPCPathFollower.jl:36-39,110-113,127; a standing start that accelerates at the limit to the end of the horizon: the
@@ -612,9 +612,7 @@ def test_degenerate_pair_marks_survive_on_the_gpu(oracle, monkeypatch, N, kv):
     p = O.params(N)
     args = (p, d["z0"], d["ref"], d["v_target"], d["u_prev"])
     ron = O.solve_condensed_batch(*args, nthreads=1)
-    monkeypatch.setenv("KMPC_X_DEGEN", "1")
-    roff = O.solve_condensed_batch(*args, nthreads=1)
-    monkeypatch.delenv("KMPC_X_DEGEN")
+    roff = O.solve_condensed_batch(*args, o=O.opts(degen_theta=1.0), nthreads=1)
     assert r["status"][0] == 0 and ron["status"][0] == 0 and roff["status"][0] == 0
     assert int(r["iters"][0]) == int(ron["iters"][0]) <= int(roff["iters"][0]) - 2, (r["iters"], ron["iters"], roff["iters"])
     if N == 8:
