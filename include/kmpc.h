@@ -273,6 +273,24 @@ int32_t kmpc_sim_advance_batch(int32_t device, int32_t B, void *state, const voi
 int32_t kmpc_command_batch(int32_t device, int32_t B, const void *u0, const int32_t *stop, uint8_t *stop_latch, void *u_prev, void *cmd,
                            void *stream);
 
+/* ---- Frenet reference from look-ahead waypoints: the step between kmpc_waypoints_batch and kmpc_solve_batch_frenet ----------------------
+ * Replaces, for B vehicles at once, what the Frenet node does with a received path before it solves
+ * (scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl): convert_msg_to_path_dict (:54-85: path in the vehicle frame, the origin (0, 0)
+ * at s = 0 put in front, s = cumulative chord length), get_reference_frenet (scripts/sim_path_utils/nav_msgs_path_frenet.py:76-86: fit_XY_s
+ * :62-73 -- np.interp every 0.5 m and two cubic least-squares fits --, compute_curvature_poly :44-59 -- K = (x'y'' - y'x'') / (x'^2 + y'^2)
+ * every 0.25 m and a cubic fit of K --, psi_start = atan2(Y'(0), X'(0)) :84) and update_init_cond(0, 0, -psi_start, v) (:128).
+ *   pose [B,3] fp64 DEVICE: x, y, yaw of the vehicle            ref [B,horizon+1,3] fp64 DEVICE: kmpc_waypoints_batch's output (x, y global; psi unused)
+ *   v [B] fp64 DEVICE or NULL: measured speed                   k_poly [B,4] out: K(s) coefficients, highest degree first (kmpc_solve_batch_frenet's order)
+ *   psi_start [B] out                                           z0 [B,4] out or NULL (needs v): (0, 0, -psi_start, v[b])
+ *   fit_status [B] int32 out: 0 fitted, 1 refused
+ * horizon 2..56.  fp64 only.  A vehicle is refused when its window has fewer than four 0.5 m resample points (s_end <= 1.5 m: np.polyfit is
+ * rank-deficient there), when any input or intermediate is non-finite, or when s_end > 8192 m (bounds the work per vehicle; the longest real
+ * window is 57 x 0.2 s x 20 m/s = 228 m); it gets fit_status 1, k_poly = 0, psi_start = 0, z0 = (0, 0, 0, v[b]) (0 for a non-finite v[b]).
+ * Every output is always written and always finite; a refused vehicle does not disturb any other.
+ * Asynchronous on `stream`.  Errors: negative code, text in kmpc_last_error(NULL). */
+int32_t kmpc_frenet_reference_batch(int32_t device, int32_t B, int32_t horizon, const double *pose, const double *ref, const double *v,
+                                    double *k_poly, double *psi_start, double *z0, int32_t *fit_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

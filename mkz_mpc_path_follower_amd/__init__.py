@@ -4,7 +4,7 @@ Drop-in for ONE path of govvijaycal/mkz_mpc_path_follower: the per-step nonlinea
 scripts/mpc_utils/MKZMPCPathFollower.jl as driven by scripts/mpc_cmd_pub.jl.  Importing the
 package does not touch the GPU; constructing a solver does, and fails loudly without one.
 """
-__all__ = ["BatchMPC", "KinematicMPC", "synthetic"]
+__all__ = ["BatchMPC", "KinematicMPC", "synthetic", "get_reference_frenet_batch", "ClosedLoopFrenet"]
 
 
 def __getattr__(name):
@@ -14,6 +14,12 @@ def __getattr__(name):
     if name == "KinematicMPC":
         from .kinematic_mpc import KinematicMPC
         return KinematicMPC
+    if name == "get_reference_frenet_batch":
+        from .kinematic_mpc_frenet import get_reference_frenet_batch
+        return get_reference_frenet_batch
+    if name == "ClosedLoopFrenet":
+        from .closed_loop import ClosedLoopFrenet
+        return ClosedLoopFrenet
     if name == "synthetic":
         from . import synthetic
         return synthetic

@@ -13,7 +13,10 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .kinematic_mpc_frenet import get_reference_frenet_batch
 from .solver import BatchMPC
+
+FRENET_WEIGHTS = (0.0, 9.0, 10.0, 0.5, 100.0, 1000.0, 0.0, 0.0)   # MKZMPCPathFollowerFrenet.jl:51-59 in update_cost's 8-slot layout (no x slot)
 
 
 class ClosedLoop:
@@ -73,3 +76,68 @@ class ClosedLoop:
         self.sim._update_vehicle_model(plant_updates)
         self.k += 1
         return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s)
+
+
+class ClosedLoopFrenet:
+    """One `step()` = one pass of the Frenet node's loop (gazebo_sim_mpc_cmd_pub_frenet.jl:112-153) for every vehicle, then 0.1 s of plant:
+    waypoints ahead of the vehicle at the target speed -> path in the vehicle frame, curvature polynomial and psi_start
+    (get_reference_frenet_batch; :54-85, :105) -> update_init_cond(0, 0, -psi_start, v) (:128) -> warm-started solve -> command stage -> plant.
+    Stop latch, rate-limit anchor and publish-whatever-the-status as in ClosedLoop.  Target-velocity mode only: the Frenet cost has no
+    along-path term and the node has a fixed des_speed (:38).  A vehicle whose fit is refused (fit_status 1: see get_reference_frenet_batch) solves
+    for a straight path with zero heading error -- in the loop that happens only to stop-latched vehicles, whose command is overridden."""
+
+    def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, **options):
+        if track_with_time or not target_vel > 0.0:
+            raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
+                             "track_with_time=%r)" % (target_vel, track_with_time))
+        if grt.traj_horizon != N:
+            raise ValueError("waypoint horizon %d != MPC horizon %d" % (grt.traj_horizon, N))
+        self.grt, self.sim, self.N = grt, sim, int(N)
+        self.B = sim.B
+        self.mpc = mpc if mpc is not None else BatchMPC(N=N, dtype=torch.float64, device=sim.device.index, weights=weights, model=1, **options)
+        if (self.mpc.dtype != torch.float64 or self.mpc.N != self.N or self.mpc.device != sim.device or sim.device.index is None
+                or self.mpc.cfg.model != 1):
+            raise ValueError("ClosedLoopFrenet needs a float64 model=1 BatchMPC with horizon %d on %s (got %s, model=%d, N=%d, %s)"
+                             % (self.N, sim.device, self.mpc.dtype, self.mpc.cfg.model, self.mpc.N, self.mpc.device))
+        if grt.device != sim.device:
+            raise ValueError("waypoint helper on %s, plant on %s: the loop runs on one device" % (grt.device, sim.device))
+        self.des_speed = float(target_vel)
+        dev = sim.device
+        self.v_target = torch.full((self.B,), self.des_speed, dtype=torch.float64, device=dev)
+        self.u_prev = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)
+        self.warm_U = torch.zeros((self.B, self.N, 2), dtype=torch.float64, device=dev)
+        self.command_stop = torch.zeros((self.B,), dtype=torch.bool, device=dev)
+        self._lib = _lib.load()
+        self.params = params
+        self.have_warm = False
+        self.out = None
+        self.k = 0
+
+    def step(self, plant_updates=10, time_solve=False):
+        """as ClosedLoop.step; the returned dict also carries `k_poly` [B,4] and `fit_status` [B]"""
+        import time
+        st = self.sim.state
+        pose = st[:, 0:3].contiguous()
+        ref, stop = self.grt.get_waypoints_batch(pose, self.v_target)
+        k_poly, _psi, z0, fit_status = get_reference_frenet_batch(pose, ref, st[:, 3].contiguous())
+        if time_solve:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        self.out = self.mpc.solve_frenet(z0, k_poly, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
+                                         params=self.params)
+        solve_s = None
+        if time_solve:
+            torch.cuda.synchronize()
+            solve_s = time.perf_counter() - t0
+        self.have_warm = True
+        cmd = self.sim.cmd
+        u0 = self.out["u0"]
+        assert u0.dtype == torch.float64 and u0.is_contiguous() and u0.device == cmd.device and u0.shape == (self.B, 2)
+        stream = C.c_void_p(torch.cuda.current_stream(cmd.device).cuda_stream)
+        _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
+                                                C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
+                                                C.c_void_p(cmd.data_ptr()), stream))
+        self.sim._update_vehicle_model(plant_updates)
+        self.k += 1
+        return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s,
+                    k_poly=k_poly, fit_status=fit_status)

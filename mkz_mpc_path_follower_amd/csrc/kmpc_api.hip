@@ -591,3 +591,19 @@ extern "C" int32_t kmpc_command_batch(int32_t device, int32_t B, const void *u0,
     if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_command_batch: %s", hipGetErrorString(e));
     return KMPC_OK;
 }
+
+// ---- Frenet reference from waypoints (kmpc_frenet_ref.hip) ----------------------------------------------------------
+extern "C" int32_t kmpc_frenet_reference_batch(int32_t device, int32_t B, int32_t horizon, const double *pose, const double *ref, const double *v,
+                                               double *k_poly, double *psi_start, double *z0, int32_t *fit_status, void *stream)
+{
+    if (B < 0 || horizon < 2 || horizon > 56) return fail(nullptr, KMPC_ERR_ARG, "kmpc_frenet_reference_batch: bad argument (B=%d, horizon=%d; horizon 2..56)", B, horizon);
+    if (B > 0 && (!pose || !ref || !k_poly || !psi_start || !fit_status)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_frenet_reference_batch: null required buffer");
+    if (z0 && !v) return fail(nullptr, KMPC_ERR_ARG, "kmpc_frenet_reference_batch: z0 needs v");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_frenet_reference_batch: hipSetDevice(%d) failed", device);
+    FR f;
+    f.B = B; f.H = horizon; f.pose = pose; f.ref = ref; f.v = v; f.k_poly = k_poly; f.psi = psi_start; f.z0 = z0; f.status = fit_status;
+    const hipError_t e = kmpc_launch_frenet_ref(f, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_frenet_reference_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}

@@ -107,4 +107,18 @@ struct WP {
     int32_t *closest;    // [B] or null (diagnostic)
 };
 hipError_t kmpc_launch_waypoints(const WP &w, hipStream_t st);
+
+// batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
+// scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)
+struct FR {
+    int B, H;            // vehicles, horizon (H+1 waypoints, 2 <= H <= 56)
+    const double *pose;  // [B,3] x, y, yaw
+    const double *ref;   // [B,H+1,3] x, y, psi (psi unused)
+    const double *v;     // [B] or null
+    double *k_poly;      // [B,4] highest degree first
+    double *psi;         // [B] psi_start
+    double *z0;          // [B,4] (0, 0, -psi_start, v) or null
+    int32_t *status;     // [B] 0 fitted, 1 refused
+};
+hipError_t kmpc_launch_frenet_ref(const FR &f, hipStream_t st);
 #endif

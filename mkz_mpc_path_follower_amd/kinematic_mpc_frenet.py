@@ -5,12 +5,17 @@ Same six functions, same argument orders: update_init_cond(s, ey, epsi, vel) (:1
 v_des) (:142-147), update_current_input(c_swa, c_acc) -- steer first (:151-154), update_cost(cey, cep, cev, cda, cdd, ca, cd)
 (:158-169), solve_model() -> (acc, d_f, status) (:173-183), get_solver_results() -> (s, ey, v, epsi, K, path_ref, d_f, acc)
 (:188-207, v before epsi, d_f before acc).  The solve runs on the MI355X (kmpc_solve_batch_frenet, B = 1); no CPU path.
+
+get_reference_frenet_batch is the fleet form of the fit: vehicle-frame path, curvature polynomial and initial condition for B vehicles in one
+kernel on the device (kmpc_frenet_reference_batch), from the waypoints kmpc_waypoints_batch wrote.
 """
+import ctypes as C
 import math
 
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import STATUS_NAMES
 from .solver import BatchMPC
 
@@ -43,6 +48,39 @@ def get_reference_frenet(path):
     K_coeffs = compute_curvature_poly(s_interp, x_coeffs, y_coeffs)
     psi_start = math.atan2(y_coeffs[2], x_coeffs[2])   # slopes of the two cubics at s = 0
     return K_coeffs, psi_start, x_interp, y_interp
+
+
+def get_reference_frenet_batch(pose, ref, v=None):
+    """gazebo_sim_mpc_cmd_pub_frenet.jl:54-85 (path in the vehicle frame, origin in front, cumulative chord length) + get_reference_frenet
+    (:76-86) + the arguments of update_init_cond (:128) for B vehicles on the device.
+    pose [B,3] (x, y, yaw), ref [B,H+1,3] (GPSRefTrajectory.get_waypoints_batch's output, H = 2..56), v [B] measured speeds or None
+    -> k_poly [B,4] (highest degree first), psi_start [B], z0 [B,4] = (0, 0, -psi_start, v) (None without v), fit_status [B] int32
+    (0 fitted; 1 refused: fewer than four 0.5 m resample points, a non-finite value, or a window longer than 8192 m -- zeros then).
+    float64 device tensors; asynchronous on torch's current stream.  No CPU fallback."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("get_reference_frenet_batch needs an MI355X; no CPU fallback")
+    ref = torch.as_tensor(ref, dtype=torch.float64)
+    dev = ref.device if ref.is_cuda else (pose.device if isinstance(pose, torch.Tensor) and pose.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    ref = ref.to(dev).contiguous()
+    pose = torch.as_tensor(pose, dtype=torch.float64, device=dev).contiguous()
+    if pose.dim() != 2 or pose.shape[1] != 3:
+        raise ValueError("pose: expected [B,3], got %s" % (tuple(pose.shape),))
+    B = pose.shape[0]
+    if ref.dim() != 3 or ref.shape[0] != B or ref.shape[2] != 3 or not 2 <= ref.shape[1] - 1 <= 56:
+        raise ValueError("ref: expected [%d,H+1,3] with H = 2..56, got %s" % (B, tuple(ref.shape)))
+    if v is not None:
+        v = torch.as_tensor(v, dtype=torch.float64, device=dev).contiguous()
+        if tuple(v.shape) != (B,):
+            raise ValueError("v: expected [%d], got %s" % (B, tuple(v.shape)))
+    k_poly = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    psi_start = torch.empty((B,), dtype=torch.float64, device=dev)
+    z0 = torch.empty((B, 4), dtype=torch.float64, device=dev) if v is not None else None
+    fit_status = torch.empty((B,), dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.load().kmpc_frenet_reference_batch(dev.index, B, ref.shape[1] - 1, p(pose), p(ref), p(v), p(k_poly), p(psi_start), p(z0),
+                                                       p(fit_status), stream))
+    return k_poly, psi_start, z0, fit_status
 
 
 class KinematicMPCFrenet:
