@@ -251,6 +251,37 @@ int32_t kmpc_waypoints_batch(kmpc_path *p, int32_t B, int32_t horizon, double tr
                              void *stream);
 const char *kmpc_path_last_error(kmpc_path *p);
 
+/* ---- fleets on several recorded paths: a path and a tracking mode per vehicle ---------------------------------------------------------
+ * The reference ships three recorded paths (the .mat files under paths/) and two tracking modes, and its launch file pairs each path with its own start pose
+ * (launch/sim_path_follow.launch:13, 22-30); one GPSRefTrajectory holds one path (ref_gps_traj.py:87-106) and one node runs one mode
+ * (mpc_cmd_pub.jl:99-112).  A kmpc_pathset holds P such paths in ONE device allocation, and kmpc_waypoints_fleet is get_waypoints (:131-142,
+ * 172-218) for B vehicles of which each follows its own path in its own mode: one launch for a fleet that mixes routes, modes and speeds. */
+typedef struct kmpc_pathset kmpc_pathset;
+
+/* HOST: M[P] sample counts; t, X, Y, psi, cdist concatenated in path order (sum of M doubles each; the columns kmpc_path_create takes, every
+ * path's cdist starting at 0, :95-100); copied to `device`.  P >= 1, every M[p] >= 2, sum of M < 2^31, else KMPC_ERR_ARG -- checked before
+ * any device call, so a machine without a GPU answers KMPC_ERR_ARG to bad arguments and KMPC_ERR_NODEVICE to good ones. */
+int32_t kmpc_pathset_create(int32_t device, int32_t P, const int32_t *M, const double *t, const double *X, const double *Y,
+                            const double *psi, const double *cdist, kmpc_pathset **out);
+int32_t kmpc_pathset_destroy(kmpc_pathset *ps);
+
+/* DEVICE pointers: pose [B,3] fp64 = (X_init, Y_init, yaw_init); path_id [B] int32; time_mode [B] uint8 or NULL; v_target [B] fp64 or NULL;
+ * ref_out [B,horizon+1,3], stop_out [B] int32 as kmpc_waypoints_batch; closest_out [B] int32 or NULL (index of the nearest sample within the
+ * vehicle's OWN path, -1 if refused).
+ * Modes: time_mode == NULL mirrors kmpc_waypoints_batch -- every vehicle in target-velocity mode (waypoints start ONE step ahead, :175) if
+ * v_target != NULL, every vehicle in time mode (start at the closest point, :191) if v_target == NULL.  time_mode != NULL needs v_target
+ * (KMPC_ERR_ARG otherwise); a non-zero entry puts that vehicle in time mode and its v_target[b] is then not read.
+ * Vehicle b's rows are, bit for bit, those of kmpc_waypoints_batch on path path_id[b] alone in b's mode; the stop flag (:182-184) compares with
+ * the last sample of b's own path, and no read leaves b's own segment.  A vehicle whose path_id is < 0 or >= P is refused: stop_out 1 (the node's
+ * stop latch brakes it, mpc_cmd_pub.jl:100-103, 148-153), closest_out -1, every waypoint row its own pose (x, y, yaw; a non-finite component
+ * becomes 0); it does not disturb any other vehicle.  A non-finite pose on a valid path gives closest index 0, as in kmpc_waypoints_batch.
+ * Same bounds on B, horizon and traj_dt as kmpc_waypoints_batch; B = 0 succeeds without a launch.  Asynchronous on `stream`; path_id and
+ * time_mode are read by the launch and not kept. */
+int32_t kmpc_waypoints_fleet(kmpc_pathset *ps, int32_t B, int32_t horizon, double traj_dt, const double *pose,
+                             const int32_t *path_id, const uint8_t *time_mode, const double *v_target,
+                             double *ref_out, int32_t *stop_out, int32_t *closest_out, void *stream);
+const char *kmpc_pathset_last_error(kmpc_pathset *ps);
+
 /* ---- closed-loop simulator --------------------------------------------------------
  * Replaces, for B simulated vehicles at once, `n_updates` passes of VehicleSimulator._update_vehicle_model
  * (scripts/vehicle_simulator.py:58-107: dynamic bicycle, linear tyres, 10 Euler sub-steps of 1 ms per pass, heading

@@ -33,7 +33,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_sim_advance_batch", "kmpc_solve_batch_frenet", "kmpc_debug_kkt", "kmpc_command_batch",
            "kmpc_record_bytes", "kmpc_pack_records", "kmpc_solve_batch_packed",
            "kmpc_get_problem_params", "kmpc_solve_batch_params", "kmpc_solve_batch_frenet_params",
-           "kmpc_frenet_reference_batch"]
+           "kmpc_frenet_reference_batch",
+           "kmpc_pathset_create", "kmpc_pathset_destroy", "kmpc_waypoints_fleet", "kmpc_pathset_last_error"]
 
 _lib = None
 
@@ -73,6 +74,11 @@ def load():
     L.kmpc_waypoints_batch.argtypes = [vp, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp]
     L.kmpc_path_last_error.argtypes = [vp]
     L.kmpc_path_last_error.restype = C.c_char_p
+    L.kmpc_pathset_create.argtypes = [i32, i32, C.POINTER(i32), dp, dp, dp, dp, dp, C.POINTER(vp)]
+    L.kmpc_pathset_destroy.argtypes = [vp]
+    L.kmpc_waypoints_fleet.argtypes = [vp, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.kmpc_pathset_last_error.argtypes = [vp]
+    L.kmpc_pathset_last_error.restype = C.c_char_p
     L.kmpc_sim_advance_batch.argtypes = [i32, i32, vp, vp, i32, vp]
     L.kmpc_command_batch.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp]
     L.kmpc_frenet_reference_batch.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -571,6 +571,79 @@ extern "C" int32_t kmpc_waypoints_batch(kmpc_path *p, int32_t B, int32_t horizon
 
 extern "C" const char *kmpc_path_last_error(kmpc_path *p) { return p ? p->err.c_str() : g_create_err.c_str(); }
 
+// ---- a set of recorded paths and a fleet that mixes them (kmpc_waypoints_fleet_kernel) ------------------------------
+struct kmpc_pathset {
+    int device, P, total;
+    double *d;      // one allocation: t | X | Y | psi | s, each `total` doubles with the paths concatenated, then off[P+1] int32
+    int32_t *off;   // points into d's allocation
+    std::string err;
+};
+
+extern "C" int32_t kmpc_pathset_create(int32_t device, int32_t P, const int32_t *M, const double *t, const double *X, const double *Y,
+                                       const double *psi, const double *cdist, kmpc_pathset **out)
+{
+    if (!out || P < 1 || !M || !t || !X || !Y || !psi || !cdist) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_create: bad argument");
+    std::vector<int32_t> off((size_t)P + 1, 0);
+    int64_t sum = 0;
+    for (int p = 0; p < P; ++p) {
+        if (M[p] < 2) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_create: path %d has %d samples (at least 2)", p, M[p]);
+        sum += M[p];
+        if (sum > INT32_MAX) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_create: more than 2^31 - 1 samples in all");
+        off[p + 1] = (int32_t)sum;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, KMPC_ERR_NODEVICE, "kmpc_pathset_create: no HIP device");
+    if (device < 0 || device >= ndev) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_create: device %d of %d", device, ndev);
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_pathset_create: hipSetDevice failed");
+    kmpc_pathset *ps = new kmpc_pathset();
+    const size_t n = (size_t)sum;
+    ps->device = device; ps->P = P; ps->total = (int)sum; ps->d = nullptr;
+    if (hipMalloc((void **)&ps->d, 5 * n * sizeof(double) + off.size() * sizeof(int32_t)) != hipSuccess) {
+        delete ps;
+        return fail(nullptr, KMPC_ERR_HIP, "kmpc_pathset_create: hipMalloc failed");
+    }
+    ps->off = (int32_t *)(ps->d + 5 * n);
+    const double *src[5] = {t, X, Y, psi, cdist};
+    bool ok = hipMemcpy(ps->off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    for (int i = 0; i < 5 && ok; ++i) ok = hipMemcpy(ps->d + i * n, src[i], n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipFree(ps->d); delete ps;
+        return fail(nullptr, KMPC_ERR_HIP, "kmpc_pathset_create: hipMemcpy failed");
+    }
+    *out = ps;
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_pathset_destroy(kmpc_pathset *ps)
+{
+    if (!ps) return KMPC_OK;
+    (void)hipSetDevice(ps->device);
+    (void)hipFree(ps->d);
+    delete ps;
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_waypoints_fleet(kmpc_pathset *ps, int32_t B, int32_t horizon, double traj_dt, const double *pose,
+                                        const int32_t *path_id, const uint8_t *time_mode, const double *v_target,
+                                        double *ref_out, int32_t *stop_out, int32_t *closest_out, void *stream)
+{
+    if (!ps) return KMPC_ERR_ARG;
+    if (B < 0 || horizon < 1 || horizon > 63 || !(traj_dt > 0)) { ps->err = "kmpc_waypoints_fleet: bad B / horizon / traj_dt"; return KMPC_ERR_ARG; }
+    if (time_mode && !v_target) { ps->err = "kmpc_waypoints_fleet: time_mode needs v_target"; return KMPC_ERR_ARG; }
+    if (B == 0) return KMPC_OK;
+    if (!pose || !path_id || !ref_out || !stop_out) { ps->err = "kmpc_waypoints_fleet: null required buffer"; return KMPC_ERR_ARG; }
+    if (hipSetDevice(ps->device) != hipSuccess) { ps->err = "hipSetDevice failed"; return KMPC_ERR_HIP; }
+    WPF w;
+    w.P = ps->P; w.B = B; w.H = horizon; w.total = ps->total; w.all_time = v_target ? 0 : 1; w.traj_dt = traj_dt;
+    w.d = ps->d; w.off = ps->off; w.path_id = path_id; w.time_mode = time_mode;
+    w.pose = pose; w.vt = v_target; w.ref = ref_out; w.stop = stop_out; w.closest = closest_out;
+    hipError_t e = kmpc_launch_waypoints_fleet(w, (hipStream_t)stream);
+    if (e != hipSuccess) { ps->err = std::string("fleet waypoints launch failed: ") + hipGetErrorString(e); return KMPC_ERR_HIP; }
+    return KMPC_OK;
+}
+
+extern "C" const char *kmpc_pathset_last_error(kmpc_pathset *ps) { return ps ? ps->err.c_str() : g_create_err.c_str(); }
+
 // ---- closed-loop simulator (kmpc_sim.hip) ------------------------------------------------------------------------
 extern "C" int32_t kmpc_sim_advance_batch(int32_t device, int32_t B, void *state, const void *cmd, int32_t n_updates, void *stream)
 {

@@ -108,6 +108,24 @@ struct WP {
 };
 hipError_t kmpc_launch_waypoints(const WP &w, hipStream_t st);
 
+// the same for a fleet on P recorded paths: a path and a tracking mode per vehicle (kmpc_waypoints_fleet_kernel)
+struct WPF {
+    int P, B, H;               // paths, vehicles, horizon (H+1 waypoints)
+    int total;                 // sum of the paths' sample counts = off[P]
+    int all_time;              // read only when time_mode is null: 1 every vehicle on the time grid, 0 every vehicle on the arclength grid
+    double traj_dt;
+    const double *d;           // t | X | Y | psi | s, each `total` doubles, the paths concatenated
+    const int32_t *off;        // [P+1] first sample of each path
+    const int32_t *path_id;    // [B]
+    const uint8_t *time_mode;  // [B] or null
+    const double *pose;        // [B,3] x, y, yaw
+    const double *vt;          // [B] or null (not read for a vehicle in time mode)
+    double *ref;               // [B,H+1,3] x, y, psi
+    int32_t *stop;             // [B]
+    int32_t *closest;          // [B] or null: index within the vehicle's own path, -1 if refused
+};
+hipError_t kmpc_launch_waypoints_fleet(const WPF &w, hipStream_t st);
+
 // batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
 // scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)
 struct FR {

@@ -12,20 +12,30 @@
 // vehicle and no HBM traffic beyond the first touch -- the kernel is L2-bandwidth bound.
 // Arithmetic mirrors numpy exactly (no FMA contraction in the distance and in np.interp's
 // slope*(x - xp[j]) + fp[j]) so that indices match bit for bit and values to the last ulp.
+//
+// Two kernels share one per-vehicle body: kmpc_waypoints_kernel (one path and one mode per launch) and kmpc_waypoints_fleet_kernel (a path and a
+// mode per vehicle, out of a set of paths held in one allocation).
 #include "kmpc_common.h"
 #include "kmpc_dispatch.h"
 #include "kmpc_interp.h"   // np_interp
 
-__global__ __launch_bounds__(64) void kmpc_waypoints_kernel(WP w)
+// one recorded path as the body sees it: five arrays of M samples
+struct PathView {
+    const double *t, *X, *Y, *psi, *s;
+    int M;
+};
+
+// One vehicle on one path, by one wavefront: shared by kmpc_waypoints_kernel (the launch's path and mode) and kmpc_waypoints_fleet_kernel (the
+// vehicle's own).  `pv` and `use_vtarget` are wave-uniform; vt is read only with use_vtarget.
+DEV void waypoints_vehicle(const PathView &pv, const int use_vtarget, const int b, const int lane, const int H, const double traj_dt,
+                           const double *pose, const double *vt, double *ref, int32_t *stop, int32_t *closest_out)
 {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    if (b >= w.B) return;
-    const double x = w.pose[3 * (size_t)b], y = w.pose[3 * (size_t)b + 1], yaw = w.pose[3 * (size_t)b + 2];
+    const double x = pose[3 * (size_t)b], y = pose[3 * (size_t)b + 1], yaw = pose[3 * (size_t)b + 2];
     // ---- closest recorded point: argmin (X-x)^2 + (Y-y)^2, first occurrence (np.argmin) ---------
     double best = INFINITY;
     int bi = 0x7fffffff;
-    for (int i = lane; i < w.M; i += 64) {
-        const double dx = __dsub_rn(w.X[i], x), dy = __dsub_rn(w.Y[i], y);
+    for (int i = lane; i < pv.M; i += 64) {
+        const double dx = __dsub_rn(pv.X[i], x), dy = __dsub_rn(pv.Y[i], y);
         const double d = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
         if (d < best) { best = d; bi = i; }
     }
@@ -34,24 +44,24 @@ __global__ __launch_bounds__(64) void kmpc_waypoints_kernel(WP w)
     int closest = (int)dpp_min(cand);
     // a non-finite pose (NaN or +-inf from the GPS / plant) makes every distance NaN or +inf: no lane records an index.  np.argmin
     // returns 0 then (first NaN / first of the equal minima), and so does this -- never an index outside the path arrays
-    closest = (unsigned)closest < (unsigned)w.M ? closest : 0;
+    closest = (unsigned)closest < (unsigned)pv.M ? closest : 0;
     // ---- look-ahead grid ---------------------------------------------------------------------------
     const int k = lane;
-    const bool act = k <= w.H;
-    const double *grid = w.use_vtarget ? w.s : w.t;
+    const bool act = k <= H;
+    const double *grid = use_vtarget ? pv.s : pv.t;
     const double start = grid[closest];
     double q;
-    if (w.use_vtarget) q = __dadd_rn(__dmul_rn(__dmul_rn((double)(k + 1), w.traj_dt), w.vt[b]), start);  // x*dt*v + start, x = 1..H+1
-    else q = __dadd_rn(__dmul_rn((double)k, w.traj_dt), start);                                            // h*dt + start, h = 0..H
+    if (use_vtarget) q = __dadd_rn(__dmul_rn(__dmul_rn((double)(k + 1), traj_dt), vt[b]), start);  // x*dt*v + start, x = 1..H+1
+    else q = __dadd_rn(__dmul_rn((double)k, traj_dt), start);                                      // h*dt + start, h = 0..H
     double xi = 0, yi = 0, pi_ = 0;
     if (act) {
-        xi = np_interp(q, grid, w.X, w.M);
-        yi = np_interp(q, grid, w.Y, w.M);
-        pi_ = np_interp(q, grid, w.psi, w.M);
+        xi = np_interp(q, grid, pv.X, pv.M);
+        yi = np_interp(q, grid, pv.Y, pv.M);
+        pi_ = np_interp(q, grid, pv.psi, pv.M);
     }
     // ---- heading wrap-around fix (:204-218) -------------------------------------------------------------
     const double pnext = dpp_mov0<0x130, 0xf>(pi_);  // lane k+1
-    const double dd = (k < w.H) ? fabs(__dsub_rn(pnext, pi_)) : 0.0;
+    const double dd = (k < H) ? fabs(__dsub_rn(pnext, pi_)) : 0.0;
     const double dc = act ? fabs(__dsub_rn(pi_, yaw)) : 0.0;
     const bool check1 = dpp_max(dd) < M_PI, check2 = dpp_max(dc) < M_PI;
     if (!(check1 && check2) && act) {
@@ -63,15 +73,62 @@ __global__ __launch_bounds__(64) void kmpc_waypoints_kernel(WP w)
         pi_ = bc;
     }
     if (act) {
-        double *o = w.ref + ((size_t)b * (w.H + 1) + k) * 3;
+        double *o = ref + ((size_t)b * (H + 1) + k) * 3;
         o[0] = xi; o[1] = yi; o[2] = pi_;
     }
-    if (k == w.H) w.stop[b] = (xi == w.X[w.M - 1] && yi == w.Y[w.M - 1]) ? 1 : 0;  // :182-184
-    if (lane == 0 && w.closest) w.closest[b] = closest;
+    if (k == H) stop[b] = (xi == pv.X[pv.M - 1] && yi == pv.Y[pv.M - 1]) ? 1 : 0;  // :182-184, the last sample of the vehicle's own path
+    if (lane == 0 && closest_out) closest_out[b] = closest;
+}
+
+__global__ __launch_bounds__(64) void kmpc_waypoints_kernel(WP w)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= w.B) return;
+    const PathView pv = {w.t, w.X, w.Y, w.psi, w.s, w.M};
+    waypoints_vehicle(pv, w.use_vtarget, b, lane, w.H, w.traj_dt, w.pose, w.vt, w.ref, w.stop, w.closest);
+}
+
+// A fleet on P recorded paths (the reference ships three, the .mat files under paths/, and pairs each with its own start pose in launch/sim_path_follow.launch:13,22-30):
+// vehicle b follows path path_id[b], on the time grid if time_mode[b] != 0 (ref_gps_traj.py:191) and on the arclength grid at v_target[b] otherwise (:175).
+// Both are wave-uniform, read once and made scalar, so the segment's base pointers, its sample count and the grid selection live in SGPRs and the argmin
+// loop bound and the mode branch are scalar; from there on the vehicle runs waypoints_vehicle on a view of its own segment and reads nothing outside it.
+// A path_id outside [0, P) is contained: stop 1 (the loop brakes the vehicle), closest -1, every waypoint row the vehicle's own pose with non-finite
+// components replaced by 0; no table entry and no path sample is read for it.
+__global__ __launch_bounds__(64) void kmpc_waypoints_fleet_kernel(WPF w)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= w.B) return;
+    const int pid = __builtin_amdgcn_readfirstlane(w.path_id[b]);
+    if ((unsigned)pid >= (unsigned)w.P) {
+        if (lane <= w.H) {
+            double *o = w.ref + ((size_t)b * (w.H + 1) + lane) * 3;
+            for (int c = 0; c < 3; ++c) {
+                const double v = w.pose[3 * (size_t)b + c];
+                o[c] = isfinite(v) ? v : 0.0;
+            }
+        }
+        if (lane == 0) {
+            w.stop[b] = 1;
+            if (w.closest) w.closest[b] = -1;
+        }
+        return;
+    }
+    const int o0 = __builtin_amdgcn_readfirstlane(w.off[pid]), o1 = __builtin_amdgcn_readfirstlane(w.off[pid + 1]);
+    const bool time_mode = w.time_mode ? __builtin_amdgcn_readfirstlane((int)w.time_mode[b]) != 0 : w.all_time != 0;
+    const double *seg = w.d + o0;
+    const size_t n = (size_t)w.total;
+    const PathView pv = {seg, seg + n, seg + 2 * n, seg + 3 * n, seg + 4 * n, o1 - o0};
+    waypoints_vehicle(pv, time_mode ? 0 : 1, b, lane, w.H, w.traj_dt, w.pose, w.vt, w.ref, w.stop, w.closest);
 }
 
 hipError_t kmpc_launch_waypoints(const WP &w, hipStream_t st)
 {
     hipLaunchKernelGGL(kmpc_waypoints_kernel, dim3(w.B), dim3(64), 0, st, w);
+    return hipGetLastError();
+}
+
+hipError_t kmpc_launch_waypoints_fleet(const WPF &w, hipStream_t st)
+{
+    hipLaunchKernelGGL(kmpc_waypoints_fleet_kernel, dim3(w.B), dim3(64), 0, st, w);
     return hipGetLastError();
 }

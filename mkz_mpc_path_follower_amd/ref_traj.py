@@ -5,7 +5,8 @@ the cumulative arclength -- ref_gps_traj.py:33-52, 87-106) and the same
 `get_waypoints(X_init, Y_init, yaw_init, v_target=None)` call (:131-142), but the rosparams
 (lat0, lon0, yaw0, is_heading_info) are constructor arguments (defaults: launch/path_follow.launch:15-21)
 and the look-ahead itself runs on the MI355X for B vehicles at once (kmpc_waypoints_batch);
-`get_waypoints` is the B = 1 case.  No CPU fallback.
+`get_waypoints` is the B = 1 case.  FleetRefTrajectory holds several recorded paths and gives every vehicle
+a path and a tracking mode of its own (kmpc_waypoints_fleet).  No CPU fallback.
 """
 import ctypes as C
 import math
@@ -103,3 +104,85 @@ class GPSRefTrajectory:
         ref, stop = self.get_waypoints_batch([[X_init, Y_init, yaw_init]], None if v_target is None else [v_target])
         r = ref[0].cpu().numpy()
         return r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy(), bool(stop[0].item())
+
+
+class FleetRefTrajectory:
+    """B vehicles on several recorded paths: vehicle b follows paths[path_id[b]], on the time grid (ref_gps_traj.py:191) if time_mode[b] != 0 and on
+    the arclength grid at its own v_target[b] (:175) otherwise -- one kmpc_waypoints_fleet launch for the whole fleet.
+
+    paths: a list of what GPSRefTrajectory takes for ONE path -- a .mat file name, or an `arrays` dict with t, lat, lon, psi and optionally lat0, lon0
+    (the projection origin of that path; launch/path_follow.launch:19-20 by default).  trajectories[p] is path p's [M_p,7] array (:106).
+    path_id (int32, [B]) and time_mode (uint8, [B], or None) are device tensors and public: the launch reads them as they are, so the caller may edit
+    them in place between steps (re-route a vehicle, switch its mode).  time_mode = None mirrors GPSRefTrajectory: every vehicle in target-velocity
+    mode when get_waypoints_batch is given v_target, every vehicle in time mode when it is not.
+    A vehicle whose path_id is outside [0, len(paths)) is refused by the kernel: stop flag 1, closest index -1, every waypoint its own pose."""
+
+    def __init__(self, paths, path_id, time_mode=None, traj_horizon=8, traj_dt=0.2, device=0):
+        if not len(paths):
+            raise ValueError("FleetRefTrajectory: at least one path")
+        self.traj_horizon, self.traj_dt = int(traj_horizon), float(traj_dt)
+        self.trajectories = []
+        for src in paths:
+            if isinstance(src, str):
+                import scipy.io as sio
+                dd = sio.loadmat(src)  # :88
+                src = dict(t=dd["t"], lat=dd["lat"], lon=dd["lon"], psi=dd["psi"])
+            cols = path_arrays(src["t"], src["lat"], src["lon"], src["psi"], float(src.get("lat0", LAT0)), float(src.get("lon0", LON0)))
+            self.trajectories.append(np.column_stack(cols))  # :106
+        self._lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise RuntimeError("FleetRefTrajectory needs an MI355X; no CPU fallback")
+        self.device = torch.device("cuda", device)
+        self.path_id = torch.as_tensor(path_id, device=self.device).to(torch.int32).contiguous()
+        if self.path_id.dim() != 1:
+            raise ValueError("path_id: expected [B], got %s" % (tuple(self.path_id.shape),))
+        self.time_mode = None
+        if time_mode is not None:
+            self.time_mode = torch.as_tensor(time_mode, device=self.device).to(torch.uint8).contiguous()
+            if self.time_mode.shape != self.path_id.shape:
+                raise ValueError("time_mode: expected %s, got %s" % (tuple(self.path_id.shape), tuple(self.time_mode.shape)))
+        M = np.array([len(tr) for tr in self.trajectories], dtype=np.int32)
+        cols = [np.ascontiguousarray(np.concatenate([tr[:, i] for tr in self.trajectories])) for i in (0, 4, 5, 3, 6)]
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        h = C.c_void_p()
+        rc = self._lib.kmpc_pathset_create(int(device), len(M), M.ctypes.data_as(C.POINTER(C.c_int32)), dp(cols[0]), dp(cols[1]), dp(cols[2]),
+                                           dp(cols[3]), dp(cols[4]), C.byref(h))
+        if rc != 0:
+            raise _lib.KmpcError(self._lib.kmpc_pathset_last_error(None).decode())
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.kmpc_pathset_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def get_waypoints_batch(self, pose, v_target=None, want_closest=False):
+        """pose [B,3], v_target [B] or None -> ref [B,H+1,3] (device), stop [B] int32 [, closest [B] int32: index within the vehicle's own path]"""
+        pose = torch.as_tensor(pose, dtype=torch.float64, device=self.device).contiguous()
+        B = self.path_id.shape[0]
+        if tuple(pose.shape) != (B, 3):
+            raise ValueError("pose: expected [%d,3], got %s" % (B, tuple(pose.shape)))
+        vt = None if v_target is None else torch.as_tensor(v_target, dtype=torch.float64, device=self.device).contiguous()
+        if vt is not None and tuple(vt.shape) != (B,):
+            raise ValueError("v_target: expected [%d], got %s" % (B, tuple(vt.shape)))
+        tm = self.time_mode
+        if tm is not None:
+            if vt is None:
+                raise ValueError("a fleet with per-vehicle modes needs v_target (it is not read for the vehicles in time mode)")
+            if not (tm.dtype == torch.uint8 and tuple(tm.shape) == (B,) and tm.is_contiguous() and tm.device == self.device):
+                raise ValueError("time_mode must stay a contiguous uint8 tensor [%d] on %s (write into it in place)" % (B, self.device))
+        pid = self.path_id   # a plain attribute: what reaches the kernel is a raw pointer
+        if not (pid.dtype == torch.int32 and tuple(pid.shape) == (B,) and pid.is_contiguous() and pid.device == self.device):
+            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, self.device))
+        ref = torch.empty((B, self.traj_horizon + 1, 3), dtype=torch.float64, device=self.device)
+        stop = torch.empty((B,), dtype=torch.int32, device=self.device)
+        closest = torch.empty((B,), dtype=torch.int32, device=self.device) if want_closest else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.kmpc_waypoints_fleet(self._h, B, self.traj_horizon, self.traj_dt, p(pose), p(pid), p(tm), p(vt), p(ref), p(stop),
+                                            p(closest), stream)
+        if rc != 0:
+            raise _lib.KmpcError(self._lib.kmpc_pathset_last_error(self._h).decode())
+        return (ref, stop, closest) if want_closest else (ref, stop)
