@@ -282,6 +282,66 @@ int32_t kmpc_waypoints_fleet(kmpc_pathset *ps, int32_t B, int32_t horizon, doubl
                              double *ref_out, int32_t *stop_out, int32_t *closest_out, void *stream);
 const char *kmpc_pathset_last_error(kmpc_pathset *ps);
 
+/* ---- tracking errors on the recorded paths and a running score per vehicle -----------------------------------------------------------------
+ * Replaces, for B vehicles at once and on the device, the numerical part of scripts/analysis/plot_path_tracking_error.py: compute_path_errors
+ * (:21-34, nearest recorded sample and the distance to it) and the yaw error there through fix_heading (:36-43, :155-162); it adds the signed
+ * distance to the POLYLINE through the samples and, in `score`, the figures of a closed-loop run (rms and largest errors, settle index, live
+ * periods, largest command steps, the period of the stop latch) without a device -> host copy per period.
+ *   state  DEVICE fp64, row b at state + b * state_stride doubles, X, Y, psi first: the plant's state [B,8] of kmpc_sim_advance_batch
+ *          (state_stride 8) or a pose [B,3] (state_stride 3); state_stride >= 3
+ *   settle_tol  finite, >= 0 [m]
+ * Command side of the period, DEVICE, all four or all NULL (NULL: a geometry-only call, as for the initial state):
+ *   status [B] int32, iters [B] int32 (kmpc_solve_batch's), cmd [B,2] fp64 (kmpc_command_batch's), stop_latch [B] uint8 (after it)
+ * Outputs of the call, DEVICE, each optional (NULL to skip):
+ *   err_out [B,4] fp64: e_ct   signed distance to the polyline: nearest point over the segments i -> i+1 with w = p - P_i, d = P_{i+1} - P_i,
+ *                              s = clamp(w.d / max(|d|^2, 1e-18), 0, 1), e = |w - s d|; the sign is that of d x w on the winning segment (>= 0
+ *                              counts as positive): positive when the vehicle is to the LEFT of the direction of travel
+ *                       e_near distance to the nearest sample (error_xy, :30-32)
+ *                       e_psi  psi_path[closest] - psi through fix_heading: the first of p, p + 2 pi, p - 2 pi of smallest magnitude
+ *                       s_along cdist[seg] + s (cdist[seg+1] - cdist[seg])
+ *   seg_out [B] int32: the winning segment, 0 .. M-2 (the lowest index among exactly equal distances)
+ *   closest_out [B] int32: nearest sample, bit-identical to kmpc_waypoints_batch's closest_out
+ * score [B,16] fp64 DEVICE in/out or NULL: the running record, 128 bytes per vehicle.  Over every scored state: */
+enum {
+    KMPC_SCORE_N = 0,             /* states scored */
+    KMPC_SCORE_SUM_ECT2 = 1,      /* sum of e_ct^2 */
+    KMPC_SCORE_MAX_ECT = 2,       /* max |e_ct| */
+    KMPC_SCORE_SUM_EPSI2 = 3,     /* sum of e_psi^2 */
+    KMPC_SCORE_MAX_EPSI = 4,      /* max |e_psi| */
+    KMPC_SCORE_MAX_ENEAR = 5,     /* max e_near */
+    KMPC_SCORE_SETTLE_INDEX = 6,  /* 1 + index (count of states scored before it) of the last scored state with |e_ct| >= settle_tol, 0 if none */
+    KMPC_SCORE_N_REFUSED = 7,     /* refused states */
+    /* over live periods only: command side given and stop_latch[b] == 0 */
+    KMPC_SCORE_N_LIVE = 8,        /* live periods */
+    KMPC_SCORE_N_NONOPT = 9,      /* ... with status != KMPC_OPTIMAL */
+    KMPC_SCORE_SUM_ITERS = 10,    /* sum of iters */
+    KMPC_SCORE_MAX_DACC = 11,     /* max |acc - last live acc|; the first live command is compared with (0, 0) */
+    KMPC_SCORE_MAX_DDF = 12,      /* max |d_f - last live d_f| */
+    KMPC_SCORE_LAST_ACC = 13,     /* the last live command: the record is self-contained */
+    KMPC_SCORE_LAST_DF = 14,
+    KMPC_SCORE_LATCH_INDEX = 15,  /* live periods scored before the first period with stop_latch[b] != 0: the index of that period (when no
+                                     state of the vehicle was refused before it); -1 until then */
+    KMPC_SCORE_WORDS = 16
+};
+/* s_along of the last scored state is not a word of the record: it is the last call's err_out[b][3].
+ * A fresh record is all zeros except KMPC_SCORE_LATCH_INDEX = -1: kmpc_track_score_init writes B of them to HOST memory (copy them to the device),
+ * or write the constant yourself; no kernel is needed.
+ * Refused states: a path_id outside [0, P), a non-finite X, Y or psi, and (never with finite paths and kmpc_command_batch's commands) a
+ * non-finite error or live command.  err_out row 0, seg_out = closest_out = -1, only KMPC_SCORE_N_REFUSED moves; no sample and no table entry is
+ * read for a bad path_id; no other vehicle's outputs change.  Every word written is finite.
+ * Argument checks come before any use of the handle and any device call: a NULL path / set, B < 0, state_stride < 3, settle_tol not finite or
+ * < 0, a command side only partly given, and with B > 0 a NULL state (or path_id) return KMPC_ERR_ARG, text in kmpc_last_error(NULL), also on a
+ * machine without a GPU.  B = 0 succeeds without a launch.  Asynchronous on `stream`. */
+int32_t kmpc_track_score_init(double *score_host, int32_t B);
+int32_t kmpc_track_score_batch(kmpc_path *p, int32_t B, const double *state, int32_t state_stride, double settle_tol,
+                               const int32_t *status, const int32_t *iters, const double *cmd, const uint8_t *stop_latch,
+                               double *err_out, int32_t *seg_out, int32_t *closest_out, double *score, void *stream);
+/* the same for a fleet: vehicle b on path path_id[b] [B] int32 DEVICE of the set; its rows are, bit for bit, kmpc_track_score_batch's on that path alone */
+int32_t kmpc_track_score_fleet(kmpc_pathset *ps, int32_t B, const double *state, int32_t state_stride, const int32_t *path_id,
+                               double settle_tol, const int32_t *status, const int32_t *iters, const double *cmd,
+                               const uint8_t *stop_latch, double *err_out, int32_t *seg_out, int32_t *closest_out, double *score,
+                               void *stream);
+
 /* ---- closed-loop simulator --------------------------------------------------------
  * Replaces, for B simulated vehicles at once, `n_updates` passes of VehicleSimulator._update_vehicle_model
  * (scripts/vehicle_simulator.py:58-107: dynamic bicycle, linear tyres, 10 Euler sub-steps of 1 ms per pass, heading

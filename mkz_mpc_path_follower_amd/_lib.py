@@ -34,7 +34,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_record_bytes", "kmpc_pack_records", "kmpc_solve_batch_packed",
            "kmpc_get_problem_params", "kmpc_solve_batch_params", "kmpc_solve_batch_frenet_params",
            "kmpc_frenet_reference_batch",
-           "kmpc_pathset_create", "kmpc_pathset_destroy", "kmpc_waypoints_fleet", "kmpc_pathset_last_error"]
+           "kmpc_pathset_create", "kmpc_pathset_destroy", "kmpc_waypoints_fleet", "kmpc_pathset_last_error",
+           "kmpc_track_score_init", "kmpc_track_score_batch", "kmpc_track_score_fleet"]
 
 _lib = None
 
@@ -79,6 +80,9 @@ def load():
     L.kmpc_waypoints_fleet.argtypes = [vp, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
     L.kmpc_pathset_last_error.argtypes = [vp]
     L.kmpc_pathset_last_error.restype = C.c_char_p
+    L.kmpc_track_score_init.argtypes = [dp, i32]
+    L.kmpc_track_score_batch.argtypes = [vp, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.kmpc_track_score_fleet.argtypes = [vp, i32, vp, i32, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.kmpc_sim_advance_batch.argtypes = [i32, i32, vp, vp, i32, vp]
     L.kmpc_command_batch.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp]
     L.kmpc_frenet_reference_batch.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -12,14 +12,19 @@ Fleets on several recorded paths: `grt` may be a ref_traj.FleetRefTrajectory, wh
 `target_vel` may be a length-B sequence.  The loops then always hand the helper `v_target`; the helper owns the modes.  Re-routing a vehicle
 (editing grt.path_id[b]) does NOT clear its stop latch: a vehicle that latched at the end of its old path stays braked until the caller clears
 `loop.command_stop[b]`.
+
+Episodes and scores: `run(steps)` runs `steps` periods without a host synchronisation or a device -> host copy and scores every state on the device
+(ref_traj.track_score_batch: tracking errors on the vehicle's recorded path and a running record per vehicle, `loop.score` [B,16]);
+`score_summary()` downloads the record once.  `step()` alone never scores.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
 from .kinematic_mpc_frenet import get_reference_frenet_batch
-from .ref_traj import FleetRefTrajectory
+from .ref_traj import SCORE_FIELDS, FleetRefTrajectory, fresh_score
 from .solver import BatchMPC
 
 FRENET_WEIGHTS = (0.0, 9.0, 10.0, 0.5, 100.0, 1000.0, 0.0, 0.0)   # MKZMPCPathFollowerFrenet.jl:51-59 in update_cost's 8-slot layout (no x slot)
@@ -40,7 +45,77 @@ def _target_speeds(target_vel, B, device):
     return tuple(tv.tolist()), tv.to(device)
 
 
-class ClosedLoop:
+class _ScoredLoop:
+    """run() / score / score_summary() of both loops.  A loop provides _period(plant_updates, time_solve) -> step()'s dict: one control period."""
+
+    def _init_score(self):
+        self.score = fresh_score(self.B, self.sim.device)   # [B,16], layout KMPC_SCORE_* of include/kmpc.h (ref_traj.SCORE_FIELDS)
+        self.track = None                                   # err [B,4], seg [B], closest [B] of the last scored state
+        self._score_fresh = True
+
+    def reset_score(self):
+        """a fresh record for every vehicle (the next run() from k == 0 scores the initial state again)"""
+        self._init_score()
+
+    def _score_state(self, o, settle_tol):
+        side = {} if o is None else dict(status=o["status"], iters=o["iters"], cmd=o["cmd"], stop_latch=self.command_stop)
+        self.track = self.grt.track_score_batch(self.sim.state, score=self.score, settle_tol=settle_tol, out=self.track, **side)
+        self._score_fresh = False
+
+    def run(self, steps, score=True, settle_tol=0.5, history=False, plant_updates=10):
+        """`steps` control periods back to back: no host synchronisation and no device -> host copy in here.
+        score=True: the initial state is scored geometry-only when the loop has not stepped (k == 0) and its record is fresh; then every
+        period's new state is scored with that period's status, iters, command and stop latch.  history=True also records, on the device,
+        state [steps+1,B,8] (the state before the first period first), cmd [steps,B,2], status [steps,B] and latch [steps,B].
+        -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
+        the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError("steps >= 0")
+        dev = self.sim.device
+        hist = None
+        if history:
+            hist = dict(state=torch.empty((steps + 1, self.B, 8), dtype=torch.float64, device=dev),
+                        cmd=torch.empty((steps, self.B, 2), dtype=torch.float64, device=dev),
+                        status=torch.empty((steps, self.B), dtype=torch.int32, device=dev),
+                        latch=torch.empty((steps, self.B), dtype=torch.bool, device=dev))
+            hist["state"][0].copy_(self.sim.state)
+        if score and self.k == 0 and self._score_fresh:
+            self._score_state(None, settle_tol)
+        o = None
+        for j in range(steps):
+            o = self._period(plant_updates, False)
+            if score:
+                self._score_state(o, settle_tol)
+            if history:
+                hist["cmd"][j].copy_(o["cmd"]); hist["status"][j].copy_(o["status"])
+                hist["latch"][j].copy_(self.command_stop); hist["state"][j + 1].copy_(self.sim.state)
+        out = dict(score=self.score, last=o)
+        if score and self.track is not None:
+            out.update(self.track)
+        if history:
+            out.update(hist)
+        return out
+
+    def score_summary(self, dt=0.1):
+        """the record as named numpy fields [B] (one synchronising download): ref_traj.SCORE_FIELDS, plus rms_ect and rms_epsi (already divided by
+        the number of states scored; 0 where none was), t_settle = settle_index * dt, mean_iters over the live periods, and s_along of the last
+        scored state (nan before the first)."""
+        B = self.B
+        tail = self.track["err"][:, 3:4] if self.track is not None else torch.full((B, 1), float("nan"), dtype=torch.float64, device=self.score.device)
+        a = torch.cat([self.score, tail], 1).cpu().numpy()
+        out = {k: a[:, i].copy() for i, k in enumerate(SCORE_FIELDS)}
+        for k in ("n", "settle_index", "n_refused", "n_live", "n_nonopt", "sum_iters", "latch_index"):
+            out[k] = out[k].astype(np.int64)
+        n = np.maximum(out["n"], 1)
+        out["rms_ect"], out["rms_epsi"] = np.sqrt(out["sum_ect2"] / n), np.sqrt(out["sum_epsi2"] / n)
+        out["t_settle"] = out["settle_index"] * dt
+        out["mean_iters"] = out["sum_iters"] / np.maximum(out["n_live"], 1)
+        out["s_along"] = a[:, len(SCORE_FIELDS)].copy()
+        return out
+
+
+class ClosedLoop(_ScoredLoop):
     """`grt`: a GPSRefTrajectory (one path; `track_with_time` picks the mode for the whole fleet) or a FleetRefTrajectory (a path and a mode per
     vehicle; `track_with_time` must stay False).  `target_vel`: a scalar or one target speed per vehicle -- vehicle b's waypoint spacing and its solver's
     v_des.  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
@@ -73,9 +148,13 @@ class ClosedLoop:
         self.have_warm = False
         self.out = None
         self.k = 0
+        self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
         """time_solve=True brackets the solve with device synchronisations and returns its wall time (`solve_s`)"""
+        return self._period(plant_updates, time_solve)
+
+    def _period(self, plant_updates, time_solve):
         import time
         st = self.sim.state
         pose = st[:, 0:3].contiguous()
@@ -104,7 +183,7 @@ class ClosedLoop:
         return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s)
 
 
-class ClosedLoopFrenet:
+class ClosedLoopFrenet(_ScoredLoop):
     """One `step()` = one pass of the Frenet node's loop (gazebo_sim_mpc_cmd_pub_frenet.jl:112-153) for every vehicle, then 0.1 s of plant:
     waypoints ahead of the vehicle at the target speed -> path in the vehicle frame, curvature polynomial and psi_start
     (get_reference_frenet_batch; :54-85, :105) -> update_init_cond(0, 0, -psi_start, v) (:128) -> warm-started solve -> command stage -> plant.
@@ -142,9 +221,13 @@ class ClosedLoopFrenet:
         self.have_warm = False
         self.out = None
         self.k = 0
+        self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
         """as ClosedLoop.step; the returned dict also carries `k_poly` [B,4] and `fit_status` [B]"""
+        return self._period(plant_updates, time_solve)
+
+    def _period(self, plant_updates, time_solve):
         import time
         st = self.sim.state
         pose = st[:, 0:3].contiguous()

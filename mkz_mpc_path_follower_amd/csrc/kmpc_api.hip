@@ -644,6 +644,58 @@ extern "C" int32_t kmpc_waypoints_fleet(kmpc_pathset *ps, int32_t B, int32_t hor
 
 extern "C" const char *kmpc_pathset_last_error(kmpc_pathset *ps) { return ps ? ps->err.c_str() : g_create_err.c_str(); }
 
+// ---- tracking errors and the running score record (kmpc_track_score.hip) ----------------------------------------------
+extern "C" int32_t kmpc_track_score_init(double *score_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !score_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_track_score_init: bad argument (B=%d)", B);
+    for (size_t i = 0; i < (size_t)B * KMPC_SCORE_WORDS; ++i) score_host[i] = i % KMPC_SCORE_WORDS == KMPC_SCORE_LATCH_INDEX ? -1.0 : 0.0;
+    return KMPC_OK;
+}
+
+// the checks both entry points share, before the handle is touched; 1 = nothing to do (B = 0)
+static int track_score_args(const char *fn, const void *handle, int B, const double *state, int stride, const int32_t *path_id, bool fleet,
+                            double settle_tol, const int32_t *status, const int32_t *iters, const double *cmd, const uint8_t *latch)
+{
+    if (!handle) return fail(nullptr, KMPC_ERR_ARG, "%s: null path handle", fn);
+    if (B < 0 || stride < 3) return fail(nullptr, KMPC_ERR_ARG, "%s: bad B / state_stride (B=%d, state_stride=%d; state_stride >= 3)", fn, B, stride);
+    if (!std::isfinite(settle_tol) || settle_tol < 0) return fail(nullptr, KMPC_ERR_ARG, "%s: settle_tol must be finite and >= 0", fn);
+    const int given = (status != nullptr) + (iters != nullptr) + (cmd != nullptr) + (latch != nullptr);
+    if (given != 0 && given != 4) return fail(nullptr, KMPC_ERR_ARG, "%s: status, iters, cmd and stop_latch are given all together or all NULL", fn);
+    if (B > 0 && (!state || (fleet && !path_id))) return fail(nullptr, KMPC_ERR_ARG, "%s: null required buffer", fn);
+    return B == 0 ? 1 : KMPC_OK;
+}
+
+extern "C" int32_t kmpc_track_score_batch(kmpc_path *p, int32_t B, const double *state, int32_t state_stride, double settle_tol,
+                                          const int32_t *status, const int32_t *iters, const double *cmd, const uint8_t *stop_latch,
+                                          double *err_out, int32_t *seg_out, int32_t *closest_out, double *score, void *stream)
+{
+    const int rc = track_score_args("kmpc_track_score_batch", p, B, state, state_stride, nullptr, false, settle_tol, status, iters, cmd, stop_latch);
+    if (rc != KMPC_OK) return rc < 0 ? rc : KMPC_OK;
+    if (hipSetDevice(p->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_track_score_batch: hipSetDevice(%d) failed", p->device);
+    TSB k;
+    k.w = {B, state_stride, settle_tol, state, status, iters, cmd, stop_latch, err_out, seg_out, closest_out, score};
+    k.M = p->M; k.X = p->d + p->M; k.Y = p->d + 2 * (size_t)p->M; k.psi = p->d + 3 * (size_t)p->M; k.s = p->d + 4 * (size_t)p->M;
+    const hipError_t e = kmpc_launch_track_score(k, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_track_score_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_track_score_fleet(kmpc_pathset *ps, int32_t B, const double *state, int32_t state_stride, const int32_t *path_id,
+                                          double settle_tol, const int32_t *status, const int32_t *iters, const double *cmd,
+                                          const uint8_t *stop_latch, double *err_out, int32_t *seg_out, int32_t *closest_out, double *score,
+                                          void *stream)
+{
+    const int rc = track_score_args("kmpc_track_score_fleet", ps, B, state, state_stride, path_id, true, settle_tol, status, iters, cmd, stop_latch);
+    if (rc != KMPC_OK) return rc < 0 ? rc : KMPC_OK;
+    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_track_score_fleet: hipSetDevice(%d) failed", ps->device);
+    TSF k;
+    k.w = {B, state_stride, settle_tol, state, status, iters, cmd, stop_latch, err_out, seg_out, closest_out, score};
+    k.P = ps->P; k.total = ps->total; k.d = ps->d; k.off = ps->off; k.path_id = path_id;
+    const hipError_t e = kmpc_launch_track_score_fleet(k, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_track_score_fleet: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 // ---- closed-loop simulator (kmpc_sim.hip) ------------------------------------------------------------------------
 extern "C" int32_t kmpc_sim_advance_batch(int32_t device, int32_t B, void *state, const void *cmd, int32_t n_updates, void *stream)
 {

@@ -126,6 +126,35 @@ struct WPF {
 };
 hipError_t kmpc_launch_waypoints_fleet(const WPF &w, hipStream_t st);
 
+// tracking errors and the running score record (kmpc_track_score.hip; scripts/analysis/plot_path_tracking_error.py:21-43, 155-162)
+struct TS {
+    int B, stride;             // vehicles; doubles between two rows of `state` (>= 3)
+    double settle_tol;
+    const double *state;       // row b: X, Y, psi first (the plant's state [B,8], or pose [B,3])
+    const int32_t *status;     // [B]   } the period's command side: all four or none
+    const int32_t *iters;      // [B]   }
+    const double *cmd;         // [B,2] }
+    const uint8_t *latch;      // [B]   }
+    double *err;               // [B,4] e_ct, e_near, e_psi, s_along, or null
+    int32_t *seg;              // [B] or null
+    int32_t *closest;          // [B] or null
+    double *score;             // [B,16] in/out or null (layout: include/kmpc.h)
+};
+struct TSB {                   // one path
+    TS w;
+    int M;
+    const double *X, *Y, *psi, *s;
+};
+struct TSF {                   // a set of paths, a path per vehicle
+    TS w;
+    int P, total;
+    const double *d;           // t | X | Y | psi | s, each `total` doubles
+    const int32_t *off;        // [P+1]
+    const int32_t *path_id;    // [B]
+};
+hipError_t kmpc_launch_track_score(const TSB &k, hipStream_t st);
+hipError_t kmpc_launch_track_score_fleet(const TSF &k, hipStream_t st);
+
 // batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
 // scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)
 struct FR {

@@ -42,6 +42,55 @@ def path_arrays(tms, lats, lons, yaws, lat0=LAT0, lon0=LON0):
     return tms, lats, lons, yaws, X, Y, cd
 
 
+SCORE_WORDS = 16
+SCORE_FIELDS = ("n", "sum_ect2", "max_ect", "sum_epsi2", "max_epsi", "max_enear", "settle_index", "n_refused",
+                "n_live", "n_nonopt", "sum_iters", "max_dacc", "max_ddf", "last_acc", "last_df", "latch_index")   # KMPC_SCORE_* of include/kmpc.h, in order
+
+
+def fresh_score(B, device):
+    """[B,16] float64 on `device`: B fresh score records (kmpc_track_score_init: zeros, latch index -1)"""
+    rec = np.empty((int(B), SCORE_WORDS))
+    _lib.check(_lib.load().kmpc_track_score_init(rec.ctypes.data_as(C.POINTER(C.c_double)), int(B)))
+    return torch.from_numpy(rec).to(device)
+
+
+def _track_score(lib, entry, handle, device, B_fixed, path_id, state, score, status, iters, cmd, stop_latch, settle_tol, out):
+    """argument marshalling shared by GPSRefTrajectory.track_score_batch and FleetRefTrajectory.track_score_batch"""
+    st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=device)
+    if not (st.dtype == torch.float64 and st.device == device and st.dim() == 2 and st.shape[1] >= 3 and (st.shape[0] == 0 or st.stride(1) == 1)
+            and st.stride(0) >= 3):
+        st = torch.as_tensor(st, dtype=torch.float64, device=device).contiguous()
+        if st.dim() != 2 or st.shape[1] < 3:
+            raise ValueError("state: expected [B,W] with X, Y, psi in the first three columns, got %s" % (tuple(st.shape),))
+    B = st.shape[0]
+    if B_fixed is not None and B != B_fixed:
+        raise ValueError("state: expected %d rows, got %d" % (B_fixed, B))
+    given = [a is not None for a in (status, iters, cmd, stop_latch)]
+    if any(given) and not all(given):
+        raise ValueError("status, iters, cmd and stop_latch are given all together or not at all")
+
+    def buf(t, shape, dtypes, name):
+        if t is None:
+            return None
+        if not (type(t) is torch.Tensor and t.dtype in dtypes and tuple(t.shape) == shape and t.is_contiguous() and t.device == device):
+            raise ValueError("%s: expected a contiguous %s tensor %s on %s" % (name, dtypes[0], shape, device))
+        return t
+    status, iters = buf(status, (B,), (torch.int32,), "status"), buf(iters, (B,), (torch.int32,), "iters")
+    cmd = buf(cmd, (B, 2), (torch.float64,), "cmd")
+    stop_latch = buf(stop_latch, (B,), (torch.uint8, torch.bool), "stop_latch")
+    score = buf(score, (B, SCORE_WORDS), (torch.float64,), "score")
+    o = {} if out is None else out
+    for k, shape, dt in (("err", (B, 4), torch.float64), ("seg", (B,), torch.int32), ("closest", (B,), torch.int32)):
+        if buf(o.get(k), shape, (dt,), k) is None:
+            o[k] = torch.empty(shape, dtype=dt, device=device)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    args = (handle, B, p(st), int(st.stride(0)) if B else 3) + (() if path_id is None else (p(path_id),)) + \
+        (float(settle_tol), p(status), p(iters), p(cmd), p(stop_latch), p(o["err"]), p(o["seg"]), p(o["closest"]), p(score), stream)
+    _lib.check(entry(*args))
+    return o
+
+
 class GPSRefTrajectory:
     def __init__(self, mat_filename=None, traj_horizon=8, traj_dt=0.2, lat0=LAT0, lon0=LON0, yaw0=YAW0,
                  use_heading=False, arrays=None, device=0):
@@ -98,6 +147,14 @@ class GPSRefTrajectory:
         if rc != 0:
             raise _lib.KmpcError(self._lib.kmpc_path_last_error(self._h).decode())
         return (ref, stop, closest) if want_closest else (ref, stop)
+
+    def track_score_batch(self, state, score=None, status=None, iters=None, cmd=None, stop_latch=None, settle_tol=0.5, out=None):
+        """Tracking errors of B vehicles on this path and, with `score` [B,16] (fresh_score), the running record (kmpc_track_score_batch).
+        state: device tensor [B,W], X, Y, psi first -- the plant's state [B,8] as it is (no copy) or a pose [B,3].  status, iters (int32 [B]),
+        cmd [B,2], stop_latch (uint8 / bool [B]): the period's command side, all or none.  -> dict err [B,4] (e_ct, e_near, e_psi, s_along),
+        seg [B], closest [B] (int32); `out` may carry these tensors from an earlier call.  Asynchronous on torch's current stream."""
+        return _track_score(self._lib, self._lib.kmpc_track_score_batch, self._h, self.device, None, None, state, score, status, iters, cmd,
+                            stop_latch, settle_tol, out)
 
     # :131-142 -- same signature and return tuple as the reference
     def get_waypoints(self, X_init, Y_init, yaw_init, v_target=None):
@@ -186,3 +243,13 @@ class FleetRefTrajectory:
         if rc != 0:
             raise _lib.KmpcError(self._lib.kmpc_pathset_last_error(self._h).decode())
         return (ref, stop, closest) if want_closest else (ref, stop)
+
+    def track_score_batch(self, state, score=None, status=None, iters=None, cmd=None, stop_latch=None, settle_tol=0.5, out=None):
+        """GPSRefTrajectory.track_score_batch for the fleet: vehicle b against paths[path_id[b]] (kmpc_track_score_fleet).  A vehicle whose
+        path_id is outside the set, or whose X, Y or psi is not finite, is refused: err row 0, seg = closest = -1, only its refused count moves."""
+        pid = self.path_id
+        B = pid.shape[0]
+        if not (pid.dtype == torch.int32 and pid.dim() == 1 and pid.is_contiguous() and pid.device == self.device):
+            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, self.device))
+        return _track_score(self._lib, self._lib.kmpc_track_score_fleet, self._h, self.device, B, pid, state, score, status, iters, cmd,
+                            stop_latch, settle_tol, out)
