@@ -353,6 +353,65 @@ int32_t kmpc_track_score_fleet(kmpc_pathset *ps, int32_t B, const double *state,
  * Asynchronous on `stream` (NULL = the device's default stream).  Errors: negative code, text in kmpc_last_error(NULL). */
 int32_t kmpc_sim_advance_batch(int32_t device, int32_t B, void *state, const void *cmd, int32_t n_updates, void *stream);
 
+/* ---- a plant per vehicle, with a command delay ------------------------------------------------------------------------------------------
+ * kmpc_sim_advance_batch with the simulator's constants (vehicle_simulator.py:61-67, :112-113) read per vehicle: a closed-loop fleet whose
+ * vehicles differ in mass, geometry, tyres and actuators, and whose commands arrive late.
+ *   state [B,8], cmd [B,2]   exactly as in kmpc_sim_advance_batch
+ *   plant [B,8] fp64 DEVICE, 64 bytes per vehicle, row of vehicle b: */
+enum {
+    KMPC_PLANT_LF = 0,         /* lf: centre of gravity -> front axle [m] (:61) */
+    KMPC_PLANT_LR = 1,         /* lr: centre of gravity -> rear axle [m] (:62) */
+    KMPC_PLANT_M = 2,          /* m: mass [kg] (:64) */
+    KMPC_PLANT_IZ = 3,         /* Iz: yaw inertia [kg m^2] (:65) */
+    KMPC_PLANT_C_ALPHA_F = 4,  /* front cornering stiffness [N/rad] (:66) */
+    KMPC_PLANT_C_ALPHA_R = 5,  /* rear cornering stiffness [N/rad] (:67) */
+    KMPC_PLANT_K_ACC = 6,      /* gain of the acceleration lag [1/s] (:112) */
+    KMPC_PLANT_K_DF = 7,       /* gain of the steering lag [1/s] (:113) */
+    KMPC_PLANT_WORDS = 8
+};
+/*   cmd_delay [B] int32 DEVICE or NULL (= 0 for every vehicle): the command's latency in model updates of 10 ms
+ *   cmd_held  [B,2] fp64 DEVICE in/out, required with cmd_delay (optional without it): the command in force before this call
+ * Vehicle b runs its first d = min(max(cmd_delay[b], 0), n_updates) updates towards cmd_held[b] and the remaining n_updates - d towards
+ * cmd[b]; cmd[b] is then stored into cmd_held[b] (when cmd_held is given).  d == n_updates is a full-period latency.  Delays LONGER than one
+ * call are out of scope: there is one held command per vehicle, not a queue.
+ * Arithmetic: operation for operation kmpc_sim_advance_batch's, the literals replaced by the row's values; 1 / m and 1 / Iz are divided once per
+ * call and multiplied as the source does.  A row written by kmpc_plant_default with no delay gives kmpc_sim_advance_batch's state bit for bit.
+ * The reference's two quirks stay: the rear slip angle uses lf (:77) and vx has no Fyf sin(df) / m term (:84 under Python 2).
+ * Row contents cannot be checked from the host: a non-finite or non-positive m or Iz (and any non-finite word) poisons that vehicle's state
+ * alone -- one thread per vehicle, no lane reads another's row.  Validate rows where they are written (Python: vehicle_sim.plant_params).
+ * Argument checks as kmpc_sim_advance_batch, before any device call: B < 0, n_updates < 0, and with B > 0 a NULL state, cmd or plant, or a
+ * cmd_delay without cmd_held, return KMPC_ERR_ARG (text in kmpc_last_error(NULL)); B == 0 or n_updates == 0 succeeds without a launch (cmd_held
+ * is then left as it was).  Asynchronous on `stream`. */
+int32_t kmpc_plant_default(double *row8);   /* HOST: the reference's constants in row order (lag gains 5.0); KMPC_ERR_ARG for NULL */
+int32_t kmpc_sim_advance_plant(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay,
+                               void *cmd_held, int32_t n_updates, void *stream);
+
+/* ---- measurement stage: what the controller sees of the plant ------------------------------------------------------------------------------
+ * The reference's vehicle builds state_est from a GPS fix, an IMU yaw and the steering report's speed (scripts/state_publisher.py); its simulator
+ * publishes the truth (vehicle_simulator.py:40-48).  kmpc_sense_batch puts additive Gaussian noise and a bias on the four channels the MPC reads.
+ *   state  [B,8] fp64 DEVICE: the plant's state (X, Y, psi, vx first)
+ *   sensor [B,8] fp64 DEVICE, row of vehicle b: */
+enum {
+    KMPC_SENSOR_SIGMA_X = 0, KMPC_SENSOR_SIGMA_Y = 1, KMPC_SENSOR_SIGMA_PSI = 2, KMPC_SENSOR_SIGMA_V = 3,   /* standard deviations [m, m, rad, m/s] */
+    KMPC_SENSOR_BIAS_X = 4, KMPC_SENSOR_BIAS_Y = 5, KMPC_SENSOR_BIAS_PSI = 6, KMPC_SENSOR_BIAS_V = 7,
+    KMPC_SENSOR_WORDS = 8
+};
+/*   est [B,4] fp64 DEVICE out: x, y, psi, v with est_c = (truth_c + bias_c) + sigma_c * n_c; a channel whose sigma is 0 skips the noise term, so
+ *                              est_c = truth_c + bias_c bit for bit.  psi outside [-pi, pi) is wrapped into it as the plant wraps (:101); a psi
+ *                              inside passes unchanged.  v is floored at 0.
+ * The normals are a pure function of (seed, id_base + b, period): not of B, the launch geometry or the shard a vehicle runs in (a shard's
+ * id_base is its first vehicle's index in the whole fleet).  To reproduce them:
+ *   generator  Philox4x32-10 (Salmon et al., SC'11; Random123), key (seed & 0xffffffff, seed >> 32),
+ *              counter (gid lo, gid hi, period lo, period hi) with gid = id_base + b  ->  words w0..w3
+ *   uniforms   u_i = (w_i + 0.5) * 2^-32  (exact in fp64, never 0 or 1)
+ *   normals    n0 = sqrt(-2 ln u0) cos(t), n1 = sqrt(-2 ln u0) sin(t), t = 6.283185307179586 * u1  ->  x, y;   n2, n3 from (u2, u3)  ->  psi, v
+ * log / sqrt / cos / sin are the device library's (a few ulp from another libm's).  A non-finite state or row word gives a non-finite (or, for v,
+ * 0) estimate of that vehicle alone.
+ * Argument checks before any device call: B, period or id_base < 0, and with B > 0 a NULL state, sensor or est, return KMPC_ERR_ARG (text in
+ * kmpc_last_error(NULL)); B == 0 succeeds without a launch.  Asynchronous on `stream`. */
+int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period, int64_t id_base,
+                         void *est, void *stream);
+
 /* ---- command stage of the node's loop, for B vehicles (scripts/mpc_cmd_pub.jl) --------------------------------------
  * What the loop does between solve_model() and the publish: the waypoint helper's stop flag latches (:100-103); a latched vehicle is
  * commanded accel -1.0 / steer 0.0 (:148-153) and keeps its rate-limit anchor; every other vehicle publishes the solver's first input

@@ -16,6 +16,11 @@ Fleets on several recorded paths: `grt` may be a ref_traj.FleetRefTrajectory, wh
 Episodes and scores: `run(steps)` runs `steps` periods without a host synchronisation or a device -> host copy and scores every state on the device
 (ref_traj.track_score_batch: tracking errors on the vehicle's recorded path and a running record per vehicle, `loop.score` [B,16]);
 `score_summary()` downloads the record once.  `step()` alone never scores.
+
+Monte-Carlo runs: `sensor=vehicle_sim.SensorModel(...)` puts a measurement stage between the plant and the controller.  Waypoints, the Frenet fit
+and the solve's initial state then read `loop.est` [B,4] (the plant's x, y, psi, v as sensed in period `loop.k`: bias + seeded Gaussian noise per
+vehicle) instead of `sim.state`; scoring, the history's `state` and the plant stay on the truth.  A plant per vehicle and a command delay belong
+to the simulator (VehicleSimulator(plant=, cmd_delay=)).  Without a sensor the loops take exactly the code path they always took.
 """
 import ctypes as C
 
@@ -48,6 +53,17 @@ def _target_speeds(target_vel, B, device):
 class _ScoredLoop:
     """run() / score / score_summary() of both loops.  A loop provides _period(plant_updates, time_solve) -> step()'s dict: one control period."""
 
+    def _init_sensor(self, sensor):
+        if sensor is not None and (sensor.B != self.B or sensor.device != self.sim.device):
+            raise ValueError("sensor for %d vehicles on %s, plant with %d on %s" % (sensor.B, sensor.device, self.B, self.sim.device))
+        self.sensor = sensor
+        self.est = None   # [B,4] x, y, psi, v as sensed in the last period (sensor given)
+
+    def _sense(self):
+        """this period's measurement of the plant -> loop.est [B,4]: what waypoints, fit and solve read in place of sim.state[:, 0:4]"""
+        self.est = self.sensor.sense(self.sim.state, self.k, out=self.est)
+        return self.est
+
     def _init_score(self):
         self.score = fresh_score(self.B, self.sim.device)   # [B,16], layout KMPC_SCORE_* of include/kmpc.h (ref_traj.SCORE_FIELDS)
         self.track = None                                   # err [B,4], seg [B], closest [B] of the last scored state
@@ -66,7 +82,8 @@ class _ScoredLoop:
         """`steps` control periods back to back: no host synchronisation and no device -> host copy in here.
         score=True: the initial state is scored geometry-only when the loop has not stepped (k == 0) and its record is fresh; then every
         period's new state is scored with that period's status, iters, command and stop latch.  history=True also records, on the device,
-        state [steps+1,B,8] (the state before the first period first), cmd [steps,B,2], status [steps,B] and latch [steps,B].
+        state [steps+1,B,8] (the state before the first period first), cmd [steps,B,2], status [steps,B], latch [steps,B] and, with a sensor, est [steps,B,4]
+        (what the controller saw of state[j] in period j).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -79,6 +96,8 @@ class _ScoredLoop:
                         cmd=torch.empty((steps, self.B, 2), dtype=torch.float64, device=dev),
                         status=torch.empty((steps, self.B), dtype=torch.int32, device=dev),
                         latch=torch.empty((steps, self.B), dtype=torch.bool, device=dev))
+            if self.sensor is not None:
+                hist["est"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
             hist["state"][0].copy_(self.sim.state)
         if score and self.k == 0 and self._score_fresh:
             self._score_state(None, settle_tol)
@@ -90,6 +109,8 @@ class _ScoredLoop:
             if history:
                 hist["cmd"][j].copy_(o["cmd"]); hist["status"][j].copy_(o["status"])
                 hist["latch"][j].copy_(self.command_stop); hist["state"][j + 1].copy_(self.sim.state)
+                if self.sensor is not None:
+                    hist["est"][j].copy_(self.est)
         out = dict(score=self.score, last=o)
         if score and self.track is not None:
             out.update(self.track)
@@ -121,7 +142,7 @@ class ClosedLoop(_ScoredLoop):
     v_des.  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
-                 mpc=None, params=None, **options):
+                 mpc=None, params=None, sensor=None, **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -148,6 +169,7 @@ class ClosedLoop(_ScoredLoop):
         self.have_warm = False
         self.out = None
         self.k = 0
+        self._init_sensor(sensor)
         self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
@@ -156,7 +178,7 @@ class ClosedLoop(_ScoredLoop):
 
     def _period(self, plant_updates, time_solve):
         import time
-        st = self.sim.state
+        st = self.sim.state if self.sensor is None else self._sense()
         pose = st[:, 0:3].contiguous()
         ref, stop = self.grt.get_waypoints_batch(pose, None if self.track_with_time else self.v_target)
         z0 = st[:, 0:4].contiguous()                                                # x, y, psi, v = vx  (state_est, :43-46 of the simulator)
@@ -193,7 +215,7 @@ class ClosedLoopFrenet(_ScoredLoop):
     `grt` may be a FleetRefTrajectory and `target_vel` one speed per vehicle, as in ClosedLoop; a fleet helper with a vehicle in time mode is refused
     (checked once, here).  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
-    def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, **options):
+    def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -221,6 +243,7 @@ class ClosedLoopFrenet(_ScoredLoop):
         self.have_warm = False
         self.out = None
         self.k = 0
+        self._init_sensor(sensor)
         self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
@@ -229,7 +252,7 @@ class ClosedLoopFrenet(_ScoredLoop):
 
     def _period(self, plant_updates, time_solve):
         import time
-        st = self.sim.state
+        st = self.sim.state if self.sensor is None else self._sense()
         pose = st[:, 0:3].contiguous()
         ref, stop = self.grt.get_waypoints_batch(pose, self.v_target)
         k_poly, _psi, z0, fit_status = get_reference_frenet_batch(pose, ref, st[:, 3].contiguous())

@@ -707,6 +707,42 @@ extern "C" int32_t kmpc_sim_advance_batch(int32_t device, int32_t B, void *state
     return KMPC_OK;
 }
 
+// the reference's plant constants (vehicle_simulator.py:61-67, :112-113): the one place they exist for the per-vehicle plant
+extern "C" int32_t kmpc_plant_default(double *row8)
+{
+    if (!row8) return fail(nullptr, KMPC_ERR_ARG, "kmpc_plant_default: null row");
+    row8[KMPC_PLANT_LF] = 1.152; row8[KMPC_PLANT_LR] = 1.693; row8[KMPC_PLANT_M] = 1840.0; row8[KMPC_PLANT_IZ] = 3477.0;
+    row8[KMPC_PLANT_C_ALPHA_F] = 4.0703e4; row8[KMPC_PLANT_C_ALPHA_R] = 6.4495e4; row8[KMPC_PLANT_K_ACC] = 5.0; row8[KMPC_PLANT_K_DF] = 5.0;
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_sim_advance_plant(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay,
+                                          void *cmd_held, int32_t n_updates, void *stream)
+{
+    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_plant: bad argument (B=%d, n_updates=%d)", B, n_updates);
+    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_plant: null plant rows");
+    if (B > 0 && cmd_delay && !cmd_held) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_plant: cmd_delay needs cmd_held");
+    if (B == 0 || n_updates == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_plant: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_sim_plant(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_held, n_updates,
+                                               (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_plant: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period, int64_t id_base,
+                                    void *est, void *stream)
+{
+    if (B < 0 || period < 0 || id_base < 0 || (B > 0 && (!state || !sensor || !est)))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_batch: bad argument (B=%d, period=%lld, id_base=%lld)", B, (long long)period, (long long)id_base);
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_sense(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, (double *)est,
+                                           (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 extern "C" int32_t kmpc_command_batch(int32_t device, int32_t B, const void *u0, const int32_t *stop, uint8_t *stop_latch, void *u_prev, void *cmd, void *stream)
 {
     if (B < 0 || (B > 0 && (!u0 || !stop || !stop_latch || !u_prev || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_command_batch: bad argument (B=%d)", B);

@@ -92,6 +92,10 @@ template <typename T> hipError_t kmpc_launch_schedule(int B, int N, double dt, c
 template <typename T> hipError_t kmpc_launch_pack(int B, int N, int stride, const T *z0, const T *ref, const T *vt, const T *up, T *rec, hipStream_t st);
 // closed-loop simulator (kmpc_sim.hip)
 hipError_t kmpc_launch_sim(int B, double *state, const double *cmd, int n_updates, hipStream_t st);
+hipError_t kmpc_launch_sim_plant(int B, double *state, const double *cmd, const double *plant, const int32_t *cmd_delay, double *cmd_held,
+                                 int n_updates, hipStream_t st);
+hipError_t kmpc_launch_sense(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base, double *est,
+                             hipStream_t st);
 hipError_t kmpc_launch_command(int B, const double *u0, const int32_t *stop, uint8_t *latch, double *u_prev, double *cmd, hipStream_t st);
 
 // batched waypoint generation (kmpc_waypoints.hip; scripts/gps_utils/ref_gps_traj.py)

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/kmpc.h"   // KMPC_PLANT_*, KMPC_SENSOR_*: the row layouts
 #include "kmpc_dispatch.h"
 
 #pragma clang fp contract(off)
@@ -129,6 +130,142 @@ __global__ __launch_bounds__(256) void kmpc_sim_kernel(int B, double *__restrict
 hipError_t kmpc_launch_sim(int B, double *state, const double *cmd, int n_updates, hipStream_t st)
 {
     hipLaunchKernelGGL(kmpc_sim_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, state, cmd, n_updates);
+    return hipGetLastError();
+}
+
+// A plant per vehicle (kmpc_sim_advance_plant): kmpc_sim_kernel's sub-step, operation for operation, with the eight literals read from the
+// vehicle's row `plant` [B,8] (KMPC_PLANT_*) and kept in registers across all sub-steps -- 64 B more read per vehicle and call.  The polynomials'
+// ranges are statements about the state, not about the parameters, so the same wave-uniform test picks between them and the library.  1 / m and
+// 1 / Iz are divided once (correctly rounded, as the compiler folds 1.0 / 1840.0 above) and multiplied as the source does: a row holding
+// kmpc_plant_default's values gives kmpc_sim_kernel's results bit for bit.
+// Command delay: the first d = clamp(cmd_delay[i], 0, n_updates) updates (10 sub-steps each) run towards cmd_held[i], the rest towards cmd[i];
+// the target is a select per update, so lanes with different delays stay in one loop.  cmd[i] is then written to cmd_held[i].
+__global__ __launch_bounds__(256) void kmpc_sim_plant_kernel(int B, double *__restrict__ state, const double *__restrict__ cmd,
+                                                             const double *__restrict__ plant, const int32_t *__restrict__ cmd_delay,
+                                                             double *__restrict__ cmd_held, int n_updates)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const double *pr = plant + KMPC_PLANT_WORDS * (size_t)i;
+    const double lf = pr[KMPC_PLANT_LF], lr = pr[KMPC_PLANT_LR], m = pr[KMPC_PLANT_M], Iz = pr[KMPC_PLANT_IZ];
+    const double C_alpha_f = pr[KMPC_PLANT_C_ALPHA_F], C_alpha_r = pr[KMPC_PLANT_C_ALPHA_R];
+    const double k_acc = pr[KMPC_PLANT_K_ACC], k_df = pr[KMPC_PLANT_K_DF];
+    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;
+    const double deltaT = 0.01 / 10.0;
+    const double pi = 3.141592653589793;
+    double *s = state + 8 * (size_t)i;
+    double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
+    const double acc_new = cmd[2 * (size_t)i], df_new = cmd[2 * (size_t)i + 1];
+    int d = 0;
+    double acc_old = acc_new, df_old = df_new;
+    if (cmd_delay) {
+        d = min(max(cmd_delay[i], 0), n_updates);
+        acc_old = cmd_held[2 * (size_t)i]; df_old = cmd_held[2 * (size_t)i + 1];
+    }
+    for (int up = 0; up < n_updates; ++up) {
+        const double acc_des = up < d ? acc_old : acc_new, df_des = up < d ? df_old : df_new;   // the target changes between updates only
+#pragma unroll 1
+        for (int it = 0; it < 10; ++it) {
+            const bool moving = fabs(vx) > 1e-6;
+            const double yf = vy + lf * wz, yr = vy - lf * wz;          // lf where lr is expected -- as in the reference
+            const double rvx = sim_rcp(vx);
+            const double tf = yf * rvx, tr = yr * rvx;
+            const bool in_range = (!moving || (vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) && fabs(df) <= 0.6 && fabs(psi) <= 4.0;
+            double af = sim_atan_poly(tf), ar = sim_atan_poly(tr), cd = sim_cos_poly(df * df), sp, cp;
+            sim_sincos_poly(psi, &sp, &cp);
+            if (__any(!in_range)) {
+                if (moving && !(vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) { af = atan2(yf, vx); ar = atan2(yr, vx); }
+                if (!(fabs(df) <= 0.6)) cd = cos(df);
+                if (!(fabs(psi) <= 4.0)) sincos(psi, &sp, &cp);
+            }
+            const double alpha_f = moving ? df - af : 0.0;
+            const double alpha_r = moving ? -ar : 0.0;
+            const double Fyf = C_alpha_f * alpha_f, Fyr = C_alpha_r * alpha_r;
+            const double vx_n = fmax(0.0, vx + deltaT * (acc + wz * vy));   // no Fyf * sin(df) / m term -- as in the reference
+            const bool fwd = vx_n > 1e-6;
+            const double vy_c = vy + deltaT * (inv_m * (Fyf * cd + Fyr) - wz * vx);
+            const double wz_c = wz + deltaT * (inv_Iz * (lf * Fyf * cd - lr * Fyr));
+            const double vy_n = fwd ? vy_c : 0.0, wz_n = fwd ? wz_c : 0.0;
+            const double psi_n = psi + deltaT * wz;
+            const double X_n = X + deltaT * (vx * cp - vy * sp);
+            const double Y_n = Y + deltaT * (vx * sp + vy * cp);
+            X = X_n; Y = Y_n;
+            const double a = psi_n + pi, p2 = 2.0 * pi;
+            double md = a;
+            const bool wrap = !(a >= 0.0 && a < p2);
+            if (__any(wrap)) {
+                if (wrap) {
+                    md = fmod(a, p2);
+                    if (md < 0.0) md += p2;
+                }
+            }
+            psi = md - pi;
+            vx = vx_n; vy = vy_n; wz = wz_n;
+            acc = k_acc * (acc_des - acc) * deltaT + acc;
+            df = k_df * (df_des - df) * deltaT + df;
+        }
+    }
+    s[0] = X; s[1] = Y; s[2] = psi; s[3] = vx; s[4] = vy; s[5] = wz; s[6] = acc; s[7] = df;
+    if (cmd_held) { cmd_held[2 * (size_t)i] = acc_new; cmd_held[2 * (size_t)i + 1] = df_new; }
+}
+
+hipError_t kmpc_launch_sim_plant(int B, double *state, const double *cmd, const double *plant, const int32_t *cmd_delay, double *cmd_held,
+                                 int n_updates, hipStream_t st)
+{
+    hipLaunchKernelGGL(kmpc_sim_plant_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, state, cmd, plant, cmd_delay, cmd_held, n_updates);
+    return hipGetLastError();
+}
+
+// The measurement stage (kmpc_sense_batch): est = truth + bias + sigma * n on the four state_est channels the MPC reads, one thread per vehicle.
+// The normals are a pure function of (seed, id_base + b, period) -- Philox4x32-10 keyed by the seed, counter = (vehicle id, period), Box-Muller
+// on the four words (include/kmpc.h has the specification) -- so a vehicle's noise does not depend on B, on the launch geometry or on the shard
+// that simulates it.  A channel with sigma == 0 skips the noise term: est = truth + bias bit for bit.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4])
+{
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+__global__ __launch_bounds__(256) void kmpc_sense_kernel(int B, const double *__restrict__ state, const double *__restrict__ sensor, uint64_t seed,
+                                                         uint64_t period, uint64_t id_base, double *__restrict__ est)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const uint64_t gid = id_base + (uint64_t)i;
+    uint32_t w[4];
+    philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)period, (uint32_t)(period >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    const double *sr = sensor + KMPC_SENSOR_WORDS * (size_t)i, *st = state + 8 * (size_t)i;
+    double e[4];
+    for (int c = 0; c < 4; ++c) e[c] = st[c] + sr[KMPC_SENSOR_BIAS_X + c];
+    for (int h = 0; h < 2; ++h) {
+        const double sg0 = sr[KMPC_SENSOR_SIGMA_X + 2 * h], sg1 = sr[KMPC_SENSOR_SIGMA_X + 2 * h + 1];
+        if (sg0 != 0.0 || sg1 != 0.0) {
+            const double u0 = ((double)w[2 * h] + 0.5) * 0x1p-32, u1 = ((double)w[2 * h + 1] + 0.5) * 0x1p-32;
+            const double r = sqrt(-2.0 * log(u0)), a = 6.283185307179586 * u1;
+            if (sg0 != 0.0) e[2 * h] = e[2 * h] + sg0 * (r * cos(a));
+            if (sg1 != 0.0) e[2 * h + 1] = e[2 * h + 1] + sg1 * (r * sin(a));
+        }
+    }
+    const double pi = 3.141592653589793, p2 = 2.0 * pi;
+    if (!(e[2] >= -pi && e[2] < pi)) {   // the plant's wrap (:101), only where there is something to wrap: a heading in range passes unchanged
+        double md = fmod(e[2] + pi, p2);
+        if (md < 0.0) md += p2;
+        e[2] = md - pi;
+    }
+    e[3] = fmax(0.0, e[3]);              // the steering report's speed is not negative
+    double *o = est + 4 * (size_t)i;
+    o[0] = e[0]; o[1] = e[1]; o[2] = e[2]; o[3] = e[3];
+}
+
+hipError_t kmpc_launch_sense(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base, double *est,
+                             hipStream_t st)
+{
+    hipLaunchKernelGGL(kmpc_sense_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, state, sensor, seed, period, id_base, est);
     return hipGetLastError();
 }
 

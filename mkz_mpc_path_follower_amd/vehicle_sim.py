@@ -2,9 +2,14 @@
 sim_path_follow.launch runs against the MPC node.  Attribute names and update methods follow the reference
 (X, Y, psi, vx, vy, wz, acc, df, acc_des, df_des; `_mpc_cmd_callback`, `_update_vehicle_model`), but every
 attribute is a length-B device tensor and the ODE runs on the MI355X (kmpc_sim_advance_batch).  No CPU fallback.
+
+Monte-Carlo runs: `plant=plant_params(B, m=..., C_alpha_f=...)` gives every vehicle its own constants and `cmd_delay` a command latency in
+model updates of 10 ms (kmpc_sim_advance_plant); `SensorModel` is the measurement stage between the plant and the controller
+(kmpc_sense_batch).  Without them the simulator runs the kernel and computes the results it always did.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -12,11 +17,58 @@ from .messages import StateEst
 
 X0, Y0, PSI0 = -300.0, -450.0, 1.0  # vehicle_simulator.py:28-30 (rosparam defaults)
 
+PLANT_FIELDS = ("lf", "lr", "m", "Iz", "C_alpha_f", "C_alpha_r", "k_acc", "k_df")   # KMPC_PLANT_* of include/kmpc.h, in row order
+SENSOR_FIELDS = ("sigma_x", "sigma_y", "sigma_psi", "sigma_v", "bias_x", "bias_y", "bias_psi", "bias_v")   # KMPC_SENSOR_*
+
+
+def _device(device):
+    return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+
+
+def plant_default():
+    """the reference's constants (vehicle_simulator.py:61-67, :112-113) as a numpy row [8], from kmpc_plant_default: they live in the library"""
+    row = np.zeros(8)
+    _lib.check(_lib.load().kmpc_plant_default(row.ctypes.data_as(C.POINTER(C.c_double))))
+    return row
+
+
+def check_plant_rows(rows):
+    """[B,8] host rows -> ValueError unless all are finite, lf, lr, m, Iz, C_alpha_f, C_alpha_r > 0 and the lag gains >= 0 (the kernel cannot
+    refuse a row: a bad m or Iz poisons that vehicle's state)"""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 8:
+        raise ValueError("plant rows: [B,8] (%s), got %s" % (", ".join(PLANT_FIELDS), rows.shape))
+    if not np.isfinite(rows).all():
+        raise ValueError("plant rows: non-finite value in vehicle(s) %s" % np.flatnonzero(~np.isfinite(rows).all(1))[:8].tolist())
+    if not (rows[:, 0:6] > 0.0).all():
+        raise ValueError("plant rows: lf, lr, m, Iz, C_alpha_f, C_alpha_r must be > 0 (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 0:6] > 0.0).all(1))[:8].tolist())
+    if not (rows[:, 6:8] >= 0.0).all():
+        raise ValueError("plant rows: the lag gains k_acc, k_df must be >= 0 (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 6:8] >= 0.0).all(1))[:8].tolist())
+    return rows
+
+
+def plant_params(B, device=0, **overrides):
+    """[B,8] float64 plant rows on `device`: the reference's constants, with each override (`m=`, `C_alpha_f=`, ... : PLANT_FIELDS) a scalar or
+    one value per vehicle.  Validated on the host (check_plant_rows) before anything reaches the device."""
+    rows = np.tile(plant_default(), (int(B), 1))
+    for k, v in overrides.items():
+        if k not in PLANT_FIELDS:
+            raise ValueError("plant_params: unknown parameter %r (one of %s)" % (k, ", ".join(PLANT_FIELDS)))
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
+            raise ValueError("plant_params: %s is a scalar or one value per vehicle [%d], got %s" % (k, B, v.shape))
+        rows[:, PLANT_FIELDS.index(k)] = v
+    return torch.as_tensor(check_plant_rows(rows)).to(_device(device))
+
 
 class VehicleSimulator:
     dt_model = 0.01  # :24
 
-    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0):
+    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None):
+        """plant: [B,8] rows (plant_params) -- a plant per vehicle; cmd_delay: a scalar or one per vehicle, model updates of 10 ms by which a new
+        command takes effect late (clamped to one call's n_updates; the command in force until then is `cmd_held`, 0 at the start).  Giving
+        either runs kmpc_sim_advance_plant (the other defaults to the reference's constants / no delay); `plant`, `cmd_delay` (int32 [B]) and
+        `cmd_held` [B,2] are then plain device tensors the caller may edit between steps.  Giving neither changes nothing."""
         self._lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("VehicleSimulator needs an MI355X; no CPU fallback")
@@ -28,6 +80,20 @@ class VehicleSimulator:
         self.state[:, 1] = torch.as_tensor(Y0, dtype=torch.float64, device=self.device)
         self.state[:, 2] = torch.as_tensor(Psi0, dtype=torch.float64, device=self.device)
         self.cmd = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)  # acc_des, df_des (:21-22)
+        self.plant = self.cmd_delay = self.cmd_held = None
+        if plant is not None or cmd_delay is not None:
+            if plant is None:
+                self.plant = plant_params(self.B, self.device)
+            else:
+                rows = plant.detach().cpu().numpy() if isinstance(plant, torch.Tensor) else plant
+                if np.shape(rows) != (self.B, 8):
+                    raise ValueError("plant: [%d,8] rows (plant_params), got %s" % (self.B, np.shape(rows)))
+                self.plant = torch.as_tensor(check_plant_rows(rows)).to(self.device).contiguous()
+            d = torch.as_tensor(0 if cmd_delay is None else cmd_delay).detach().cpu()
+            if d.is_floating_point() or d.dim() > 1 or (d.dim() == 1 and d.shape[0] != self.B):
+                raise ValueError("cmd_delay: an integer or one per vehicle [%d] (model updates of 10 ms)" % self.B)
+            self.cmd_delay = d.to(torch.int32).expand(self.B).contiguous().to(self.device)
+            self.cmd_held = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
 
     # views named as in the reference
     X = property(lambda s: s.state[:, 0]); Y = property(lambda s: s.state[:, 1]); psi = property(lambda s: s.state[:, 2])
@@ -45,11 +111,54 @@ class VehicleSimulator:
             if not (t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
                 raise ValueError("state [B,8] / cmd [B,2] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.kmpc_sim_advance_batch(self.device.index, self.B, C.c_void_p(self.state.data_ptr()),
-                                              C.c_void_p(self.cmd.data_ptr()), int(n_updates), stream)
+        if self.plant is None:
+            rc = self._lib.kmpc_sim_advance_batch(self.device.index, self.B, C.c_void_p(self.state.data_ptr()),
+                                                  C.c_void_p(self.cmd.data_ptr()), int(n_updates), stream)
+        else:
+            for t, shape, dt in ((self.plant, (self.B, 8), torch.float64), (self.cmd_delay, (self.B,), torch.int32), (self.cmd_held, (self.B, 2), torch.float64)):
+                if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+                    raise ValueError("plant [B,8] / cmd_held [B,2] float64 and cmd_delay [B] int32 must stay contiguous tensors on %s "
+                                     "(write into them with copy_)" % self.device)
+            rc = self._lib.kmpc_sim_advance_plant(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
+                                                  C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
+                                                  C.c_void_p(self.cmd_held.data_ptr()), int(n_updates), stream)
         _lib.check(rc)
 
     def state_est(self, i=0):
         """the state_est message of vehicle i (:40-48)"""
         s = self.state[i].cpu().numpy()
         return StateEst(x=float(s[0]), y=float(s[1]), psi=float(s[2]), v=float(s[3]), a=float(s[6]), df=float(s[7]))
+
+
+class SensorModel:
+    """The measurement stage between the plant and the controller: est = truth + bias + sigma * n on x, y, psi, v (kmpc_sense_batch), what
+    scripts/state_publisher.py's GPS fix, IMU yaw and steering-report speed do to state_est on the real vehicle.  `sigma`, `bias`: a scalar,
+    four values (x, y, psi, v) or [B,4].  `params` [B,8] (SENSOR_FIELDS) is a plain device tensor the caller may edit between calls.  Vehicle b's
+    noise depends only on (seed, id_base + b, period): a shard of a larger fleet passes its first vehicle's index (dist.shard_range's lo) as id_base."""
+
+    def __init__(self, B, sigma=0.0, bias=0.0, seed=0, id_base=0, device=0):
+        self._lib = _lib.load()
+        self.B, self.seed, self.id_base = int(B), int(seed), int(id_base)
+        if not (0 <= self.seed < 2 ** 64 and 0 <= self.id_base and self.id_base + self.B < 2 ** 63):
+            raise ValueError("SensorModel: seed in [0, 2^64), id_base >= 0")
+        rows = np.zeros((self.B, 8))
+        for name, v, c0 in (("sigma", sigma, 0), ("bias", bias, 4)):
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape not in ((), (4,), (self.B, 4)):
+                raise ValueError("SensorModel: %s is a scalar, four values (x, y, psi, v) or [%d,4], got %s" % (name, self.B, v.shape))
+            rows[:, c0:c0 + 4] = v
+        if not np.isfinite(rows).all() or not (rows[:, 0:4] >= 0.0).all():
+            raise ValueError("SensorModel: sigma and bias must be finite, sigma >= 0")
+        self.device = _device(device)
+        self.params = torch.as_tensor(rows).to(self.device)
+
+    def sense(self, state, period, out=None):
+        """state [B,8] (the plant's) -> est [B,4] = x, y, psi (wrapped to [-pi, pi)), v (>= 0) as measured in control period `period`"""
+        est = out if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
+        for t, w in ((state, 8), (self.params, 8), (est, 4)):
+            if not (t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+                raise ValueError("state [B,8], params [B,8] and est [B,4] must be contiguous float64 tensors on %s" % self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_sense_batch(self.device.index, self.B, C.c_void_p(state.data_ptr()), C.c_void_p(self.params.data_ptr()),
+                                              self.seed, int(period), self.id_base, C.c_void_p(est.data_ptr()), stream))
+        return est

@@ -1,0 +1,89 @@
+"""What the path follower tolerates: one closed-loop run of 4096 vehicles over a grid of plant mismatch, GPS noise and command latency, scored on the
+device (-> profiles/robustness_sweep.txt).  An example of the Monte-Carlo surface (vehicle_sim.plant_params / SensorModel / cmd_delay and the loops'
+`sensor=`), not a test: the numbers are findings.
+
+Grid, 4 x 4 x 4 x 4 = 256 cells of 16 vehicles: mass x (0.85, 1.0, 1.15, 1.3); both cornering stiffnesses x (0.6, 0.8, 1.0, 1.2); GPS sigma on x and y
+(0, 0.1, 0.2, 0.5) m; command delay (0, 2, 4, 8) model updates of 10 ms.  The 16 vehicles of a cell are spread over the three recorded paths of
+tests/golden at 6 m/s (target-velocity mode, N = 8, the node's weights), starting on the path at speed.
+
+usage: python tools/robustness_sweep.py [out.txt] [steps]
+"""
+import itertools
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
+from mkz_mpc_path_follower_amd.ref_traj import FleetRefTrajectory  # noqa: E402
+from mkz_mpc_path_follower_amd.vehicle_sim import SensorModel, VehicleSimulator, plant_default, plant_params  # noqa: E402
+
+MASS, STIFF, SIGMA, DELAY = (0.85, 1.0, 1.15, 1.3), (0.6, 0.8, 1.0, 1.2), (0.0, 0.1, 0.2, 0.5), (0, 2, 4, 8)
+PER_CELL, VT = 16, 6.0
+LINES = []
+
+
+def say(s):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def main():
+    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 150
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    cells = list(itertools.product(range(4), repeat=4))
+    B = len(cells) * PER_CELL
+    cell = np.repeat(np.arange(len(cells)), PER_CELL)
+    ix = np.array(cells)[cell]                      # [B,4] grid indices: mass, stiffness, sigma, delay
+    rng = np.random.default_rng(0)
+    pid = np.tile(np.arange(PER_CELL) % 3, len(cells))
+    fleet = FleetRefTrajectory(paths, pid, traj_horizon=8, traj_dt=0.2)
+    frac = np.tile(rng.uniform(0.02, 0.45, PER_CELL), len(cells))     # the same 16 starts in every cell
+    pose = np.empty((B, 3))
+    for b in range(B):
+        tr = fleet.trajectories[pid[b]]
+        i = int(frac[b] * len(tr))
+        pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+    d0 = plant_default()
+    st = np.array(STIFF)[ix[:, 1]]
+    sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2],
+                           plant=plant_params(B, m=d0[2] * np.array(MASS)[ix[:, 0]], C_alpha_f=d0[4] * st, C_alpha_r=d0[5] * st),
+                           cmd_delay=np.array(DELAY)[ix[:, 3]])
+    sim.state[:, 3] = VT
+    sigma = np.zeros((B, 4))
+    sigma[:, 0] = sigma[:, 1] = np.array(SIGMA)[ix[:, 2]]
+    loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, sensor=SensorModel(B, sigma=sigma, seed=2024))
+    loop.run(steps)
+    s = loop.score_summary()
+    finite = bool(torch.isfinite(sim.state).all().item())
+    say("%s: %d vehicles, %d periods of 0.1 s at %.0f m/s on three paths; every state finite: %s; latched vehicles: %d"
+        % (torch.cuda.get_device_name(0), B, steps, VT, finite, int((s["latch_index"] >= 0).sum())))
+    say("per factor level, over all other factors: median / 95th percentile of rms e_ct [m], largest |e_ct| [m], periods not Optimal per 1000")
+
+    def row(label, sel):
+        say("   %-28s %7.3f %7.3f %8.3f %8.2f" % (label, np.median(s["rms_ect"][sel]), np.percentile(s["rms_ect"][sel], 95), s["max_ect"][sel].max(),
+                                                1000.0 * s["n_nonopt"][sel].sum() / max(1, s["n_live"][sel].sum())))
+    for f, (name, levels, fmt) in enumerate((("mass x", MASS, "%.2f"), ("cornering stiffness x", STIFF, "%.1f"), ("GPS sigma [m]", SIGMA, "%.1f"),
+                                             ("delay [10 ms updates]", DELAY, "%d"))):
+        for lv in range(4):
+            row("%s %s" % (name, fmt % levels[lv]), ix[:, f] == lv)
+    say("cells (mass x, stiffness x, sigma, delay): the nominal one, then the five with the largest median rms e_ct")
+    med = np.array([np.median(s["rms_ect"][cell == c]) for c in range(len(cells))])
+    nominal = cells.index((1, 2, 0, 0))
+    for c in [nominal] + list(np.argsort(-med)[:5]):
+        m, k, g, dl = cells[c]
+        row("(%.2f, %.1f, %.1f, %d)" % (MASS[m], STIFF[k], SIGMA[g], DELAY[dl]), cell == c)
+    if len(sys.argv) > 1:
+        with open(sys.argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()
