@@ -412,6 +412,67 @@ enum {
 int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period, int64_t id_base,
                          void *est, void *stream);
 
+/* ---- state estimator: between the measurement stage and the solver ---------------------------------------------------------------------------
+ * The reference hands the MPC raw measurements (scripts/state_publisher.py republishes the GPS fix, the IMU yaw and the steering report's speed).
+ * kmpc_estimate_batch filters them: one call is one period of an extended Kalman filter on the SOLVER's model (MKZMPCPathFollower.jl's Euler
+ * bicycle, with L_a and L_b of the solver's kmpc_config) for every vehicle, H = I, R diagonal.  One thread per vehicle, fp64, no FP contraction.
+ *   rec [B,16] fp64 DEVICE in/out, 128 bytes per vehicle, record of vehicle b: */
+enum {
+    KMPC_EST_X = 0, KMPC_EST_Y = 1, KMPC_EST_PSI = 2, KMPC_EST_V = 3,      /* the estimate xh [m, m, rad in [-pi, pi), m/s >= 0] */
+    KMPC_EST_PXX = 4, KMPC_EST_PXY = 5, KMPC_EST_PXPSI = 6, KMPC_EST_PXV = 7,   /* upper triangle of the covariance P, row-major */
+    KMPC_EST_PYY = 8, KMPC_EST_PYPSI = 9, KMPC_EST_PYV = 10,
+    KMPC_EST_PPSIPSI = 11, KMPC_EST_PPSIV = 12,
+    KMPC_EST_PVV = 13,
+    KMPC_EST_COUNT = 14,       /* calls that updated the record; 0 = fresh */
+    KMPC_EST_SKIPPED = 15,     /* channel measurements skipped so far */
+    KMPC_EST_WORDS = 16
+};
+/*   A fresh record is all zeros (hipMemset); word 14 == 0 is what makes it fresh.
+ *   params [B,8] fp64 DEVICE, row of vehicle b: standard deviations, squared by the kernel (q2_c = q_c * q_c, r2_c = r_c * r_c) */
+enum {
+    KMPC_ESTPAR_Q_X = 0, KMPC_ESTPAR_Q_Y = 1, KMPC_ESTPAR_Q_PSI = 2, KMPC_ESTPAR_Q_V = 3,   /* process noise per call [m, m, rad, m/s] */
+    KMPC_ESTPAR_R_X = 4, KMPC_ESTPAR_R_Y = 5, KMPC_ESTPAR_R_PSI = 6, KMPC_ESTPAR_R_V = 7,   /* measurement noise [m, m, rad, m/s] */
+    KMPC_ESTPAR_WORDS = 8
+};
+enum {   /* flags_out bits */
+    KMPC_EST_FLAG_SKIP_X = 1, KMPC_EST_FLAG_SKIP_Y = 2, KMPC_EST_FLAG_SKIP_PSI = 4, KMPC_EST_FLAG_SKIP_V = 8,   /* bit c: channel c skipped */
+    KMPC_EST_FLAG_INIT = 16,   /* the record was initialised by this call */
+    KMPC_EST_FLAG_RESET = 32   /* the record held or produced a non-finite word and was reset to fresh */
+};
+/*   z [B,4] fp64 DEVICE: the measurement x, y, psi, v (kmpc_sense_batch's est, or the truth); a non-finite word is a dropout of that channel
+ *   u fp64 DEVICE, row b at u + b * u_stride doubles (u_stride >= 2): (acc, d_f) in force since the last call -- sim.state + 6 with stride 8 (the
+ *     actuator states state_est publishes) or a [B,2] command buffer with stride 2
+ *   dt, L_a, L_b, gate: fleet-wide; dt the time between calls [s] (> 0), L_a, L_b the solver model's axle distances [m] (> 0), gate >= 0 the
+ *     innovation gate in standard deviations (0 = no gate)
+ *   est_out [B,4] fp64 DEVICE out (may be z itself)     innov_out [B,4] fp64 DEVICE out or NULL     flags_out [B] int32 DEVICE out or NULL
+ * Arithmetic, every operation rounded on its own, sums left to right, wrap(a) = a when -pi <= a < pi, else fmod(a + pi, 2 pi) (+ 2 pi when
+ * negative) - pi with pi = 3.141592653589793 (the plant's and the sensor's wrap); tan / atan / sin / cos / sqrt are the device library's:
+ *   FIRST CALL (word 14 == 0): no predict.  All four z finite: xh = z and P = diag(r2) bit for bit (off-diagonals 0), word 14 = 1, word 15 = 0,
+ *     est_out = z, innov_out = 0, flags = INIT.  Otherwise the record is written as all zeros (it stays fresh), est_out = z, innov_out = 0 and
+ *     flags carries bit c for every non-finite z_c.
+ *   PREDICT  beta = atan(L_b / (L_a + L_b) * tan(d_f)); s = sin(psi + beta), c = cos(psi + beta), sb = sin(beta)   (psi, v: before the step)
+ *     F = I + {F_x,psi = -(dt * (v * s)), F_x,v = dt * c, F_y,psi = dt * (v * c), F_y,v = dt * s, F_psi,v = dt * (sb / L_b)}
+ *     x += dt * (v * c);  y += dt * (v * s);  psi = wrap(psi + dt * (v / L_b * sb));  v = v + dt * acc, 0 when that is < 0
+ *     A = F P: A_ij = P_ij + F_i,psi * P_psi,j + F_i,v * P_v,j (the terms F has), then P_ij = A_ij + F_j,psi * A_i,psi + F_j,v * A_i,v for i <= j
+ *     only, and P_cc += q2_c last.  The lower triangle is never formed: P is symmetric by construction.
+ *   UPDATE, channels c = x, y, psi, v in this order, each on the result of the one before:
+ *     nu = z_c - xh_c (c = psi: wrap(nu));  S = P_cc + r2_c
+ *     skipped -- bit c set, word 15 += 1, innov_out_c = 0, nothing else changes -- when z_c is non-finite, when S is not a finite number > 0, or
+ *     when gate > 0 and nu * nu > gate * gate * S; otherwise
+ *     K_i = P_ic / S (IEEE division, P_ic before this channel);  xh_i += K_i * nu;  P_ij -= K_i * P_cj for i <= j (P_cj before this channel);
+ *     innov_out_c = nu / sqrt(S)
+ *     After v: psi = wrap(psi); v = 0 when v < 0; word 14 += 1.
+ *   CONTAINMENT  if any word of the record is then non-finite, the record is written as all zeros (fresh: the next call initialises from its z),
+ *     est_out = z, innov_out = 0 and flags = the skipped bits | RESET.  A record that arrives with a non-finite word ends here too.  One thread
+ *     per vehicle, no lane reads another vehicle's words: a poisoned record, row or measurement costs that vehicle one re-initialisation.
+ *   est_out = xh otherwise.
+ * Row contents cannot be checked from the host; validate them where they are written (Python: vehicle_sim.Estimator: finite, q >= 0, r > 0).
+ * Argument checks before any device call: B < 0, u_stride < 2, dt, L_a or L_b not finite and > 0, gate not finite and >= 0, and with B > 0 a
+ * NULL rec, z, u, params or est_out return KMPC_ERR_ARG (text in kmpc_last_error(NULL)); B == 0 succeeds without a launch.  Asynchronous on
+ * `stream`. */
+int32_t kmpc_estimate_batch(int32_t device, int32_t B, void *rec, const void *z, const void *u, int32_t u_stride, const void *params, double dt,
+                            double L_a, double L_b, double gate, void *est_out, void *innov_out, int32_t *flags_out, void *stream);
+
 /* ---- command stage of the node's loop, for B vehicles (scripts/mpc_cmd_pub.jl) --------------------------------------
  * What the loop does between solve_model() and the publish: the waypoint helper's stop flag latches (:100-103); a latched vehicle is
  * commanded accel -1.0 / steer 0.0 (:148-153) and keeps its rate-limit anchor; every other vehicle publishes the solver's first input

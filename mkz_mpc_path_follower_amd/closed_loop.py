@@ -21,6 +21,12 @@ Monte-Carlo runs: `sensor=vehicle_sim.SensorModel(...)` puts a measurement stage
 and the solve's initial state then read `loop.est` [B,4] (the plant's x, y, psi, v as sensed in period `loop.k`: bias + seeded Gaussian noise per
 vehicle) instead of `sim.state`; scoring, the history's `state` and the plant stay on the truth.  A plant per vehicle and a command delay belong
 to the simulator (VehicleSimulator(plant=, cmd_delay=)).  Without a sensor the loops take exactly the code path they always took.
+
+State estimation: `estimator=vehicle_sim.Estimator(...)` puts an extended Kalman filter per vehicle between the measurement (the sensor's `loop.est`,
+or the truth without a sensor) and the controller.  Waypoints, fit and solve then read `loop.est_filt` [B,4]; `loop.est` stays the raw measurement.
+`estimator_input` names the (acc, d_f) the filter predicts with: "actuator" -- `sim.state[:, 6:8]`, the a and df that state_est publishes -- or
+"command", the command sent in the previous period (`sim.cmd` before this period's command stage overwrites it).  The estimator's `dt` must be the
+control period (plant_updates x 10 ms) and its L_a, L_b the solver's.  Without an estimator nothing changes.
 """
 import ctypes as C
 
@@ -59,6 +65,21 @@ class _ScoredLoop:
         self.sensor = sensor
         self.est = None   # [B,4] x, y, psi, v as sensed in the last period (sensor given)
 
+    def _init_estimator(self, estimator, estimator_input):
+        if estimator_input not in ("actuator", "command"):
+            raise ValueError("estimator_input: 'actuator' or 'command', got %r" % (estimator_input,))
+        if estimator is not None and (estimator.B != self.B or estimator.device != self.sim.device):
+            raise ValueError("estimator for %d vehicles on %s, plant with %d on %s" % (estimator.B, estimator.device, self.B, self.sim.device))
+        self.estimator, self.estimator_input = estimator, estimator_input
+        self.est_filt = None   # [B,4] the filtered x, y, psi, v of the last period (estimator given)
+
+    def _filter(self, st):
+        """this period's measurement `st` (loop.est, or the plant's state without a sensor) -> loop.est_filt [B,4]"""
+        z = st if st.shape[1] == 4 else st[:, 0:4].contiguous()
+        u = self.sim.state[:, 6:8] if self.estimator_input == "actuator" else self.sim.cmd
+        self.est_filt = self.estimator.update(z, u, out=self.est_filt)
+        return self.est_filt
+
     def _sense(self):
         """this period's measurement of the plant -> loop.est [B,4]: what waypoints, fit and solve read in place of sim.state[:, 0:4]"""
         self.est = self.sensor.sense(self.sim.state, self.k, out=self.est)
@@ -83,7 +104,8 @@ class _ScoredLoop:
         score=True: the initial state is scored geometry-only when the loop has not stepped (k == 0) and its record is fresh; then every
         period's new state is scored with that period's status, iters, command and stop latch.  history=True also records, on the device,
         state [steps+1,B,8] (the state before the first period first), cmd [steps,B,2], status [steps,B], latch [steps,B] and, with a sensor, est [steps,B,4]
-        (what the controller saw of state[j] in period j).
+        (what was measured of state[j] in period j: what the controller saw, unless an estimator follows) and, with an estimator, est_filt [steps,B,4]
+        (what the controller saw then).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -98,6 +120,8 @@ class _ScoredLoop:
                         latch=torch.empty((steps, self.B), dtype=torch.bool, device=dev))
             if self.sensor is not None:
                 hist["est"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
+            if self.estimator is not None:
+                hist["est_filt"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
             hist["state"][0].copy_(self.sim.state)
         if score and self.k == 0 and self._score_fresh:
             self._score_state(None, settle_tol)
@@ -111,6 +135,8 @@ class _ScoredLoop:
                 hist["latch"][j].copy_(self.command_stop); hist["state"][j + 1].copy_(self.sim.state)
                 if self.sensor is not None:
                     hist["est"][j].copy_(self.est)
+                if self.estimator is not None:
+                    hist["est_filt"][j].copy_(self.est_filt)
         out = dict(score=self.score, last=o)
         if score and self.track is not None:
             out.update(self.track)
@@ -142,7 +168,7 @@ class ClosedLoop(_ScoredLoop):
     v_des.  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
-                 mpc=None, params=None, sensor=None, **options):
+                 mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -170,6 +196,7 @@ class ClosedLoop(_ScoredLoop):
         self.out = None
         self.k = 0
         self._init_sensor(sensor)
+        self._init_estimator(estimator, estimator_input)
         self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
@@ -179,6 +206,8 @@ class ClosedLoop(_ScoredLoop):
     def _period(self, plant_updates, time_solve):
         import time
         st = self.sim.state if self.sensor is None else self._sense()
+        if self.estimator is not None:
+            st = self._filter(st)
         pose = st[:, 0:3].contiguous()
         ref, stop = self.grt.get_waypoints_batch(pose, None if self.track_with_time else self.v_target)
         z0 = st[:, 0:4].contiguous()                                                # x, y, psi, v = vx  (state_est, :43-46 of the simulator)
@@ -215,7 +244,8 @@ class ClosedLoopFrenet(_ScoredLoop):
     `grt` may be a FleetRefTrajectory and `target_vel` one speed per vehicle, as in ClosedLoop; a fleet helper with a vehicle in time mode is refused
     (checked once, here).  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
-    def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, **options):
+    def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, estimator=None,
+                 estimator_input="actuator", **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -244,6 +274,7 @@ class ClosedLoopFrenet(_ScoredLoop):
         self.out = None
         self.k = 0
         self._init_sensor(sensor)
+        self._init_estimator(estimator, estimator_input)
         self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
@@ -253,6 +284,8 @@ class ClosedLoopFrenet(_ScoredLoop):
     def _period(self, plant_updates, time_solve):
         import time
         st = self.sim.state if self.sensor is None else self._sense()
+        if self.estimator is not None:
+            st = self._filter(st)
         pose = st[:, 0:3].contiguous()
         ref, stop = self.grt.get_waypoints_batch(pose, self.v_target)
         k_poly, _psi, z0, fit_status = get_reference_frenet_batch(pose, ref, st[:, 3].contiguous())

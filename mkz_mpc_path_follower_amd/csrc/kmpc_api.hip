@@ -743,6 +743,24 @@ extern "C" int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state
     return KMPC_OK;
 }
 
+// ---- state estimator (kmpc_estimator.hip) --------------------------------------------------------------------------
+extern "C" int32_t kmpc_estimate_batch(int32_t device, int32_t B, void *rec, const void *z, const void *u, int32_t u_stride, const void *params,
+                                       double dt, double L_a, double L_b, double gate, void *est_out, void *innov_out, int32_t *flags_out,
+                                       void *stream)
+{
+    const auto pos = [](double a) { return a > 0.0 && a <= 1.7976931348623157e308; };   // finite and > 0
+    if (B < 0 || u_stride < 2 || !pos(dt) || !pos(L_a) || !pos(L_b) || !(gate == 0.0 || pos(gate)))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_estimate_batch: bad argument (B=%d, u_stride=%d, dt=%g, L_a=%g, L_b=%g, gate=%g)", B, u_stride, dt, L_a,
+                    L_b, gate);
+    if (B > 0 && (!rec || !z || !u || !params || !est_out)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_estimate_batch: null required buffer");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_estimate_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_estimate(B, (double *)rec, (const double *)z, (const double *)u, u_stride, (const double *)params, dt, L_a, L_b,
+                                              gate, (double *)est_out, (double *)innov_out, flags_out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_estimate_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 extern "C" int32_t kmpc_command_batch(int32_t device, int32_t B, const void *u0, const int32_t *stop, uint8_t *stop_latch, void *u_prev, void *cmd, void *stream)
 {
     if (B < 0 || (B > 0 && (!u0 || !stop || !stop_latch || !u_prev || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_command_batch: bad argument (B=%d)", B);

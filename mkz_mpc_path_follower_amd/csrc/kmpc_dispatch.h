@@ -96,6 +96,9 @@ hipError_t kmpc_launch_sim_plant(int B, double *state, const double *cmd, const 
                                  int n_updates, hipStream_t st);
 hipError_t kmpc_launch_sense(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base, double *est,
                              hipStream_t st);
+// state estimator (kmpc_estimator.hip)
+hipError_t kmpc_launch_estimate(int B, double *rec, const double *z, const double *u, int u_stride, const double *params, double dt, double L_a,
+                                double L_b, double gate, double *est_out, double *innov_out, int32_t *flags_out, hipStream_t st);
 hipError_t kmpc_launch_command(int B, const double *u0, const int32_t *stop, uint8_t *latch, double *u_prev, double *cmd, hipStream_t st);
 
 // batched waypoint generation (kmpc_waypoints.hip; scripts/gps_utils/ref_gps_traj.py)

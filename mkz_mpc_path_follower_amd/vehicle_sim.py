@@ -5,7 +5,8 @@ attribute is a length-B device tensor and the ODE runs on the MI355X (kmpc_sim_a
 
 Monte-Carlo runs: `plant=plant_params(B, m=..., C_alpha_f=...)` gives every vehicle its own constants and `cmd_delay` a command latency in
 model updates of 10 ms (kmpc_sim_advance_plant); `SensorModel` is the measurement stage between the plant and the controller
-(kmpc_sense_batch).  Without them the simulator runs the kernel and computes the results it always did.
+(kmpc_sense_batch).  Without them the simulator runs the kernel and computes the results it always did.  `Estimator` is the stage after the
+sensor: an extended Kalman filter per vehicle on the solver's model (kmpc_estimate_batch), so that the controller is fed a filtered state.
 """
 import ctypes as C
 
@@ -19,6 +20,9 @@ X0, Y0, PSI0 = -300.0, -450.0, 1.0  # vehicle_simulator.py:28-30 (rosparam defau
 
 PLANT_FIELDS = ("lf", "lr", "m", "Iz", "C_alpha_f", "C_alpha_r", "k_acc", "k_df")   # KMPC_PLANT_* of include/kmpc.h, in row order
 SENSOR_FIELDS = ("sigma_x", "sigma_y", "sigma_psi", "sigma_v", "bias_x", "bias_y", "bias_psi", "bias_v")   # KMPC_SENSOR_*
+ESTIMATOR_FIELDS = ("x", "y", "psi", "v", "pxx", "pxy", "pxpsi", "pxv", "pyy", "pypsi", "pyv", "ppsipsi", "ppsiv", "pvv", "count", "skipped")   # KMPC_EST_*
+ESTIMATOR_PARAM_FIELDS = ("q_x", "q_y", "q_psi", "q_v", "r_x", "r_y", "r_psi", "r_v")   # KMPC_ESTPAR_*
+EST_SKIP_X, EST_SKIP_Y, EST_SKIP_PSI, EST_SKIP_V, EST_INIT, EST_RESET = 1, 2, 4, 8, 16, 32   # KMPC_EST_FLAG_*
 
 
 def _device(device):
@@ -161,4 +165,70 @@ class SensorModel:
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         _lib.check(self._lib.kmpc_sense_batch(self.device.index, self.B, C.c_void_p(state.data_ptr()), C.c_void_p(self.params.data_ptr()),
                                               self.seed, int(period), self.id_base, C.c_void_p(est.data_ptr()), stream))
+        return est
+
+
+class Estimator:
+    """The stage between the sensor and the controller: one extended Kalman filter per vehicle on the solver's kinematic model
+    (kmpc_estimate_batch; include/kmpc.h states the arithmetic).  `q`: process standard deviations PER CALL of x, y, psi, v; `r`: measurement
+    standard deviations -- each a scalar, four values or [B,4].  `gate` > 0 skips a channel whose innovation exceeds `gate` standard deviations
+    (0: no gate); a non-finite measurement is a dropout and the filter coasts.  `dt` is the time between calls (the loops' control period),
+    `L_a`, `L_b` the solver model's axle distances (kmpc_config's defaults).
+    `params` [B,8] (ESTIMATOR_PARAM_FIELDS), `record` [B,16] (ESTIMATOR_FIELDS; all zeros = fresh) and `flags` [B] int32 (EST_* bits of the last
+    call) are plain device tensors the caller may edit between calls; `innov` [B,4] holds the last call's normalised innovations nu / sqrt(S)."""
+
+    def __init__(self, B, q=(0.02, 0.02, 0.01, 0.1), r=(0.2, 0.2, 0.02, 0.1), gate=0.0, dt=0.1, L_a=1.108, L_b=1.742, device=0):
+        self._lib = _lib.load()
+        self.B = int(B)
+        rows = np.zeros((self.B, 8))
+        for name, v, c0 in (("q", q, 0), ("r", r, 4)):
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape not in ((), (4,), (self.B, 4)):
+                raise ValueError("Estimator: %s is a scalar, four values (x, y, psi, v) or [%d,4], got %s" % (name, self.B, v.shape))
+            rows[:, c0:c0 + 4] = v
+        if not np.isfinite(rows).all() or not (rows[:, 0:4] >= 0.0).all() or not (rows[:, 4:8] > 0.0).all():
+            raise ValueError("Estimator: q and r must be finite, q >= 0, r > 0")
+        self.gate, self.dt, self.L_a, self.L_b = float(gate), float(dt), float(L_a), float(L_b)
+        if not (np.isfinite([self.gate, self.dt, self.L_a, self.L_b]).all() and self.gate >= 0.0 and self.dt > 0.0 and self.L_a > 0.0 and self.L_b > 0.0):
+            raise ValueError("Estimator: gate >= 0, dt > 0, L_a > 0, L_b > 0, all finite (got %r, %r, %r, %r)" % (gate, dt, L_a, L_b))
+        self.device = _device(device)
+        self.params = torch.as_tensor(rows).to(self.device)
+        self.record = torch.zeros((self.B, 16), dtype=torch.float64, device=self.device)
+        self.flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        self.innov = torch.zeros((self.B, 4), dtype=torch.float64, device=self.device)
+
+    @classmethod
+    def from_sensor(cls, sensor, q=(0.02, 0.02, 0.01, 0.1), r_floor=(1e-3, 1e-3, 1e-4, 1e-3), **kw):
+        """r = the sensor's sigma per vehicle and channel, floored at `r_floor` (a noiseless channel still needs r > 0); B and device are the
+        sensor's.  Reads sensor.params once, here (one download)."""
+        floor = np.asarray(r_floor, dtype=np.float64)
+        if floor.shape not in ((), (4,)) or not np.isfinite(floor).all() or not (floor > 0.0).all():
+            raise ValueError("Estimator.from_sensor: r_floor is a positive scalar or four positive values")
+        sigma = sensor.params[:, 0:4].detach().cpu().numpy()
+        return cls(sensor.B, q=q, r=np.maximum(sigma, floor), device=sensor.device, **kw)
+
+    def reset(self):
+        """every record fresh: the next update initialises from its measurement"""
+        self.record.zero_()
+        self.flags.zero_()
+        self.innov.zero_()
+
+    def update(self, z, u, out=None):
+        """z [B,4]: this period's measurement x, y, psi, v; u [B,2]: (acc, d_f) in force since the last call -- a contiguous [B,2] tensor or a
+        column view such as sim.state[:, 6:8] (rows any fixed distance >= 2 apart: no copy is made) -> est [B,4], the filtered state"""
+        est = out if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
+        for t, w in ((z, 4), (self.params, 8), (self.record, 16), (est, 4), (self.innov, 4)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+                raise ValueError("z [B,4], params [B,8], record [B,16], est [B,4] and innov [B,4] must be contiguous float64 tensors on %s" % self.device)
+        if not (self.flags.dtype == torch.int32 and tuple(self.flags.shape) == (self.B,) and self.flags.is_contiguous() and self.flags.device == self.device):
+            raise ValueError("flags must stay a contiguous int32 tensor [B] on %s" % self.device)
+        if not (isinstance(u, torch.Tensor) and u.dtype == torch.float64 and tuple(u.shape) == (self.B, 2) and u.device == self.device
+                and (self.B == 0 or (u.stride(1) == 1 and (self.B == 1 or u.stride(0) >= 2)))):
+            raise ValueError("u: float64 [B,2] on %s with unit column stride and rows >= 2 apart (a [B,2] buffer or sim.state[:, 6:8])" % self.device)
+        stride = u.stride(0) if self.B > 1 else 2
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_estimate_batch(self.device.index, self.B, C.c_void_p(self.record.data_ptr()), C.c_void_p(z.data_ptr()),
+                                                 C.c_void_p(u.data_ptr()), int(stride), C.c_void_p(self.params.data_ptr()), self.dt, self.L_a, self.L_b,
+                                                 self.gate, C.c_void_p(est.data_ptr()), C.c_void_p(self.innov.data_ptr()),
+                                                 C.c_void_p(self.flags.data_ptr()), stream))
         return est

@@ -6,7 +6,10 @@ Grid, 4 x 4 x 4 x 4 = 256 cells of 16 vehicles: mass x (0.85, 1.0, 1.15, 1.3); b
 (0, 0.1, 0.2, 0.5) m; command delay (0, 2, 4, 8) model updates of 10 ms.  The 16 vehicles of a cell are spread over the three recorded paths of
 tests/golden at 6 m/s (target-velocity mode, N = 8, the node's weights), starting on the path at speed.
 
-usage: python tools/robustness_sweep.py [out.txt] [steps]
+--estimator puts vehicle_sim.Estimator (an extended Kalman filter per vehicle, r = the sensor's sigma) between the sensor and the controller
+(-> profiles/robustness_sweep_estimator.txt) and also prints, per GPS sigma, the rms position error of what the controller saw against the truth.
+
+usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
 """
 import itertools
 import os
@@ -20,7 +23,7 @@ sys.path.insert(0, ROOT)
 
 from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
 from mkz_mpc_path_follower_amd.ref_traj import FleetRefTrajectory  # noqa: E402
-from mkz_mpc_path_follower_amd.vehicle_sim import SensorModel, VehicleSimulator, plant_default, plant_params  # noqa: E402
+from mkz_mpc_path_follower_amd.vehicle_sim import Estimator, SensorModel, VehicleSimulator, plant_default, plant_params  # noqa: E402
 
 MASS, STIFF, SIGMA, DELAY = (0.85, 1.0, 1.15, 1.3), (0.6, 0.8, 1.0, 1.2), (0.0, 0.1, 0.2, 0.5), (0, 2, 4, 8)
 PER_CELL, VT = 16, 6.0
@@ -33,7 +36,9 @@ def say(s):
 
 
 def main():
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 150
+    use_estimator = "--estimator" in sys.argv[1:]
+    argv = [a for a in sys.argv if a != "--estimator"]
+    steps = int(argv[2]) if len(argv) > 2 else 150
     paths = []
     for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
         d = np.load(os.path.join(ROOT, "tests", "golden", name))
@@ -59,8 +64,13 @@ def main():
     sim.state[:, 3] = VT
     sigma = np.zeros((B, 4))
     sigma[:, 0] = sigma[:, 1] = np.array(SIGMA)[ix[:, 2]]
-    loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, sensor=SensorModel(B, sigma=sigma, seed=2024))
-    loop.run(steps)
+    sensor = SensorModel(B, sigma=sigma, seed=2024)
+    if use_estimator:
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, sensor=sensor, estimator=Estimator.from_sensor(sensor))
+        hist = loop.run(steps, history=True)
+    else:
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, sensor=sensor)
+        loop.run(steps)
     s = loop.score_summary()
     finite = bool(torch.isfinite(sim.state).all().item())
     say("%s: %d vehicles, %d periods of 0.1 s at %.0f m/s on three paths; every state finite: %s; latched vehicles: %d"
@@ -80,8 +90,17 @@ def main():
     for c in [nominal] + list(np.argsort(-med)[:5]):
         m, k, g, dl = cells[c]
         row("(%.2f, %.1f, %.1f, %d)" % (MASS[m], STIFF[k], SIGMA[g], DELAY[dl]), cell == c)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if use_estimator:
+        truth = hist["state"][:steps, :, 0:2]
+        e_raw = ((hist["est"][:, :, 0:2] - truth) ** 2).sum(2).mean(0).sqrt().cpu().numpy()
+        e_filt = ((hist["est_filt"][:, :, 0:2] - truth) ** 2).sum(2).mean(0).sqrt().cpu().numpy()
+        say("with the estimator (q = 0.02 m, 0.02 m, 0.01 rad, 0.1 m/s per period, r = sigma floored at 1e-3 m): median rms position error of the measurement "
+            "-> of what the controller saw [m]; filter resets: %d" % int((loop.estimator.flags & 32).sum().item()))
+        for lv in range(4):
+            sel = ix[:, 2] == lv
+            say("   GPS sigma [m] %.1f              %7.3f -> %7.3f" % (SIGMA[lv], np.median(e_raw[sel]), np.median(e_filt[sel])))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
             f.write("\n".join(LINES) + "\n")
 
 
