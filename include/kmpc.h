@@ -373,7 +373,7 @@ enum {
  *   cmd_held  [B,2] fp64 DEVICE in/out, required with cmd_delay (optional without it): the command in force before this call
  * Vehicle b runs its first d = min(max(cmd_delay[b], 0), n_updates) updates towards cmd_held[b] and the remaining n_updates - d towards
  * cmd[b]; cmd[b] is then stored into cmd_held[b] (when cmd_held is given).  d == n_updates is a full-period latency.  Delays LONGER than one
- * call are out of scope: there is one held command per vehicle, not a queue.
+ * call need a queue: kmpc_sim_advance_queue below (here there is one held command per vehicle).
  * Arithmetic: operation for operation kmpc_sim_advance_batch's, the literals replaced by the row's values; 1 / m and 1 / Iz are divided once per
  * call and multiplied as the source does.  A row written by kmpc_plant_default with no delay gives kmpc_sim_advance_batch's state bit for bit.
  * The reference's two quirks stay: the rear slip angle uses lf (:77) and vx has no Fyf sin(df) / m term (:84 under Python 2).
@@ -385,6 +385,29 @@ enum {
 int32_t kmpc_plant_default(double *row8);   /* HOST: the reference's constants in row order (lag gains 5.0); KMPC_ERR_ARG for NULL */
 int32_t kmpc_sim_advance_plant(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay,
                                void *cmd_held, int32_t n_updates, void *stream);
+
+/* ---- latency in the closed loops: definitions ---------------------------------------------------------------------------------------------
+ * An UPDATE is 10 ms of plant time; a PERIOD is one call of the plant, n = n_updates updates (10 in the loops); the ABSOLUTE update of update
+ * `up` of period p is tau = p n + up.  The command issued in period j under a command delay of d updates acts from absolute update j n + d
+ * on, so the command IN FORCE at tau is that of period
+ *     j(tau, d) = floor((tau - d) / n)          (floor towards -infinity)
+ * and j < 0 means (0, 0), the simulator's command before the first period (vehicle_simulator.py:21-22).
+ * A RING [D,B,2] (or [D,B,4]) is fp64 DEVICE memory in which slot j mod D -- the B rows at ring + (j mod D) * B * 2 (or 4) doubles -- holds
+ * period j: one thread per vehicle reads and writes it coalesced.  Rings need no initial contents: no slot is read before it was written.
+ *
+ * ---- plant with a command queue: delays longer than one call ------------------------------------------------------------------------------
+ * kmpc_sim_advance_plant with its one held command replaced by a ring of the last `depth` periods' commands.
+ *   state, cmd, plant, cmd_delay, n_updates   exactly as in kmpc_sim_advance_plant (cmd_delay NULL = 0 for every vehicle)
+ *   cmd_queue [depth,B,2] ring, in/out         period: the index of this call (>= 0); the caller counts one per call, from 0
+ * Per vehicle b: cmd[b] is stored into slot period mod depth; d = min(max(cmd_delay[b], 0), (depth - 1) n), q = d / n, r = d % n (integer);
+ * update `up` runs towards the command of period  period - q - (up < r ? 1 : 0)  -- that is j(period n + up, d) -- and towards (0, 0) where that
+ * period is negative.  The sub-step arithmetic is kmpc_sim_advance_plant's, operation for operation: the call leaves the state that
+ * kmpc_sim_advance_plant leaves when given cmd = the command of period - q, cmd_held = that of period - q - 1 and a delay of r, bit for bit; with
+ * depth = 2 and every delay <= n it is kmpc_sim_advance_plant on the same arguments, call after call.
+ * Argument checks as kmpc_sim_advance_plant's, before any device call, and depth < 2, period < 0 or a NULL cmd_queue return KMPC_ERR_ARG;
+ * B == 0 or n_updates == 0 succeeds without a launch (the queue is then not written).  Asynchronous on `stream`. */
+int32_t kmpc_sim_advance_queue(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay,
+                               void *cmd_queue, int32_t depth, int64_t period, int32_t n_updates, void *stream);
 
 /* ---- measurement stage: what the controller sees of the plant ------------------------------------------------------------------------------
  * The reference's vehicle builds state_est from a GPS fix, an IMU yaw and the steering report's speed (scripts/state_publisher.py); its simulator
@@ -411,6 +434,51 @@ enum {
  * kmpc_last_error(NULL)); B == 0 succeeds without a launch.  Asynchronous on `stream`. */
 int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period, int64_t id_base,
                          void *est, void *stream);
+
+/* ---- stale fixes: kmpc_sense_batch on the truth of an earlier period ------------------------------------------------------------------------
+ *   state, sensor, seed, period, id_base, est   exactly as in kmpc_sense_batch
+ *   meas_delay [B] int32 DEVICE: the age of the fix in WHOLE control periods      truth_ring [depth,B,4] ring, in/out (depth >= 1)
+ * Per vehicle b: this period's truth x, y, psi, vx (state words 0..3) is stored into slot period mod depth; L = min(max(meas_delay[b], 0),
+ * min(depth - 1, period)); the truth of period period - L is measured: est_c = (truth_c + bias_c) + sigma_c * n_c with THIS period's bias and
+ * normals -- the Philox counter stays (id_base + b, period): noise belongs to the moment of emission -- then kmpc_sense_batch's wrap and floor.
+ * Before the ring is filled (period < meas_delay) a vehicle sees period 0's state.  L = 0 is kmpc_sense_batch bit for bit.  The caller passes
+ * consecutive periods from 0 (a gap leaves slots of other periods in the ring).  Latency INSIDE a period (a fix some updates old) is out of
+ * scope: the plant's state exists between calls only.
+ * Argument checks as kmpc_sense_batch's, and depth < 1 or, with B > 0, a NULL meas_delay or truth_ring return KMPC_ERR_ARG.  Asynchronous. */
+int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period,
+                                 int64_t id_base, const int32_t *meas_delay, void *truth_ring, int32_t depth, void *est, void *stream);
+
+/* ---- delay compensation: the controller's side -------------------------------------------------------------------------------------------
+ * The controller keeps a log of the commands it sent and its own ASSUMED delays -- buffers of its own, not the plant's or the sensor's, so that
+ * a run can have a delay mismatch.
+ *   cmd_hist [depth,B,2] ring: period p's command is written (by the caller: a [B,2] copy into slot p mod depth) AFTER the command stage of
+ *                              period p, so a call in period p sees periods p - depth ... p - 1
+ *   cmd_delay [B] int32 DEVICE: assumed command delay in updates       meas_delay [B] int32 DEVICE: assumed age of the measurement in periods
+ *   max_cmd_delay, max_meas_delay >= 0: caps.  Per vehicle d = min(max(cmd_delay[b], 0), max_cmd_delay) and
+ *                              Lm = min(max(meas_delay[b], 0), min(max_meas_delay, period))
+ *   depth >= max_meas_delay + ceil(max_cmd_delay / n) + 1, else KMPC_ERR_ARG: then no slot is read that the log does not hold
+ *   period >= 0, n = n_updates >= 1
+ * kmpc_cmd_in_force_batch -> u_out [B,2]: the input of the estimator's predict step in period p.  The measurement belongs to update (p - Lm) n,
+ *   the filter steps over the period before that update, and u_out is the command in force at that period's midpoint:
+ *   tau = (p - Lm - 1) n + n / 2 (integer division), u_out = the logged command of period j(tau, d), (0, 0) for j < 0.  A pure selection: exact.
+ * kmpc_predict_ahead_batch -> z_out [B,4] (may be z itself): z [B,4] is the estimate x, y, psi, v, valid at update tau0 = (p - Lm) n.  For
+ *   tau = tau0 ... p n + d - 1, in this order, one Euler step of the solver's bicycle (the PREDICT state equations of kmpc_estimate_batch below,
+ *   with dt = h = 0.01) under (acc, d_f) = the logged command of period j(tau, d):
+ *     beta = atan(L_b / (L_a + L_b) * tan(d_f)); sb = sin(beta)      -- recomputed only when j(tau, d) differs from the step before
+ *     s = sin(psi + beta), c = cos(psi + beta)                        (psi, v: before the step)
+ *     x += h * (v * c);  y += h * (v * s);  psi = wrap(psi + h * (v / L_b * sb));  v = v + h * acc, 0 when that is < 0
+ *   Every operation is rounded on its own (no FP contraction); wrap as in kmpc_estimate_batch; tan / atan / sin / cos are the device library's.
+ *   That is Lm n + d steps: z_out is the state at the update from which THIS period's command acts.  Lm = d = 0 copies z bit for bit.  A
+ *   non-finite z (or logged command) poisons that vehicle's z_out alone: one thread per vehicle.
+ * Argument checks before any device call: B < 0, period < 0, n_updates < 1, a negative cap, depth too small, L_a or L_b not finite and > 0
+ * (predict-ahead), and with B > 0 a NULL buffer return KMPC_ERR_ARG (text in kmpc_last_error(NULL)); B == 0 succeeds without a launch.
+ * Asynchronous on `stream`. */
+int32_t kmpc_cmd_in_force_batch(int32_t device, int32_t B, const void *cmd_hist, int32_t depth, int64_t period, int32_t n_updates,
+                                const int32_t *cmd_delay, const int32_t *meas_delay, int32_t max_cmd_delay, int32_t max_meas_delay, void *u_out,
+                                void *stream);
+int32_t kmpc_predict_ahead_batch(int32_t device, int32_t B, const void *z, const void *cmd_hist, int32_t depth, int64_t period,
+                                 int32_t n_updates, const int32_t *cmd_delay, const int32_t *meas_delay, int32_t max_cmd_delay,
+                                 int32_t max_meas_delay, double L_a, double L_b, void *z_out, void *stream);
 
 /* ---- state estimator: between the measurement stage and the solver ---------------------------------------------------------------------------
  * The reference hands the MPC raw measurements (scripts/state_publisher.py republishes the GPS fix, the IMU yaw and the steering report's speed).

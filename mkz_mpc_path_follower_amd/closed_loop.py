@@ -27,6 +27,14 @@ or the truth without a sensor) and the controller.  Waypoints, fit and solve the
 `estimator_input` names the (acc, d_f) the filter predicts with: "actuator" -- `sim.state[:, 6:8]`, the a and df that state_est publishes -- or
 "command", the command sent in the previous period (`sim.cmd` before this period's command stage overwrites it).  The estimator's `dt` must be the
 control period (plant_updates x 10 ms) and its L_a, L_b the solver's.  Without an estimator nothing changes.
+
+Latency: the plant's command queue and the sensor's stale fixes belong to the simulator and the sensor (VehicleSimulator(cmd_queue_depth=),
+SensorModel(meas_delay=)).  `compensator=vehicle_sim.LatencyCompensator(...)` is the controller's side: the period's state passes
+sense -> filter -> compensator.predict and becomes `loop.est_pred` [B,4], the state at the update from which this period's command will act (under the
+compensator's ASSUMED delays and its log of sent commands); waypoints, fit and solve read it.  After the command stage `compensator.push(sim.cmd, k)`
+logs the command.  `estimator_input="history"` feeds the filter `compensator.filter_input(k)`, the logged command in force over the period the filter
+steps across (refused without a compensator).  Scoring, the history's `state` and the plant stay on the truth; nothing synchronises.  The
+compensator's n_updates must be the loop's plant_updates (checked every period).  Without a compensator the loops take exactly the path they took.
 """
 import ctypes as C
 
@@ -65,9 +73,16 @@ class _ScoredLoop:
         self.sensor = sensor
         self.est = None   # [B,4] x, y, psi, v as sensed in the last period (sensor given)
 
-    def _init_estimator(self, estimator, estimator_input):
-        if estimator_input not in ("actuator", "command"):
-            raise ValueError("estimator_input: 'actuator' or 'command', got %r" % (estimator_input,))
+    def _init_estimator(self, estimator, estimator_input, compensator=None):
+        if estimator_input not in ("actuator", "command", "history"):
+            raise ValueError("estimator_input: 'actuator', 'command' or 'history', got %r" % (estimator_input,))
+        if estimator_input == "history" and compensator is None:
+            raise ValueError("estimator_input='history' reads the compensator's command log: give compensator=")
+        if compensator is not None and (compensator.B != self.B or compensator.device != self.sim.device):
+            raise ValueError("compensator for %d vehicles on %s, plant with %d on %s" % (compensator.B, compensator.device, self.B, self.sim.device))
+        self.compensator = compensator
+        self.est_pred = None   # [B,4] the state predicted ahead to where this period's command acts (compensator given)
+        self._u_hist = None
         if estimator is not None and (estimator.B != self.B or estimator.device != self.sim.device):
             raise ValueError("estimator for %d vehicles on %s, plant with %d on %s" % (estimator.B, estimator.device, self.B, self.sim.device))
         self.estimator, self.estimator_input = estimator, estimator_input
@@ -76,9 +91,20 @@ class _ScoredLoop:
     def _filter(self, st):
         """this period's measurement `st` (loop.est, or the plant's state without a sensor) -> loop.est_filt [B,4]"""
         z = st if st.shape[1] == 4 else st[:, 0:4].contiguous()
-        u = self.sim.state[:, 6:8] if self.estimator_input == "actuator" else self.sim.cmd
+        if self.estimator_input == "history":
+            u = self._u_hist = self.compensator.filter_input(self.k, out=self._u_hist)
+        else:
+            u = self.sim.state[:, 6:8] if self.estimator_input == "actuator" else self.sim.cmd
         self.est_filt = self.estimator.update(z, u, out=self.est_filt)
         return self.est_filt
+
+    def _predict(self, st, plant_updates):
+        """what the controller holds of this period (measurement, estimate or the plant's state) -> loop.est_pred [B,4], predicted ahead"""
+        if self.compensator.n_updates != int(plant_updates):
+            raise ValueError("the compensator counts %d updates per period, this period has %d" % (self.compensator.n_updates, plant_updates))
+        z = st if st.shape[1] == 4 else st[:, 0:4].contiguous()
+        self.est_pred = self.compensator.predict(z, self.k, out=self.est_pred)
+        return self.est_pred
 
     def _sense(self):
         """this period's measurement of the plant -> loop.est [B,4]: what waypoints, fit and solve read in place of sim.state[:, 0:4]"""
@@ -105,7 +131,7 @@ class _ScoredLoop:
         period's new state is scored with that period's status, iters, command and stop latch.  history=True also records, on the device,
         state [steps+1,B,8] (the state before the first period first), cmd [steps,B,2], status [steps,B], latch [steps,B] and, with a sensor, est [steps,B,4]
         (what was measured of state[j] in period j: what the controller saw, unless an estimator follows) and, with an estimator, est_filt [steps,B,4]
-        (what the controller saw then).
+        (what the controller saw then, unless a compensator follows) and, with a compensator, est_pred [steps,B,4] (what the controller saw then).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -122,6 +148,8 @@ class _ScoredLoop:
                 hist["est"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
             if self.estimator is not None:
                 hist["est_filt"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
+            if self.compensator is not None:
+                hist["est_pred"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
             hist["state"][0].copy_(self.sim.state)
         if score and self.k == 0 and self._score_fresh:
             self._score_state(None, settle_tol)
@@ -137,6 +165,8 @@ class _ScoredLoop:
                     hist["est"][j].copy_(self.est)
                 if self.estimator is not None:
                     hist["est_filt"][j].copy_(self.est_filt)
+                if self.compensator is not None:
+                    hist["est_pred"][j].copy_(self.est_pred)
         out = dict(score=self.score, last=o)
         if score and self.track is not None:
             out.update(self.track)
@@ -168,7 +198,7 @@ class ClosedLoop(_ScoredLoop):
     v_des.  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
-                 mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", **options):
+                 mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -196,7 +226,7 @@ class ClosedLoop(_ScoredLoop):
         self.out = None
         self.k = 0
         self._init_sensor(sensor)
-        self._init_estimator(estimator, estimator_input)
+        self._init_estimator(estimator, estimator_input, compensator)
         self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
@@ -208,6 +238,8 @@ class ClosedLoop(_ScoredLoop):
         st = self.sim.state if self.sensor is None else self._sense()
         if self.estimator is not None:
             st = self._filter(st)
+        if self.compensator is not None:
+            st = self._predict(st, plant_updates)
         pose = st[:, 0:3].contiguous()
         ref, stop = self.grt.get_waypoints_batch(pose, None if self.track_with_time else self.v_target)
         z0 = st[:, 0:4].contiguous()                                                # x, y, psi, v = vx  (state_est, :43-46 of the simulator)
@@ -229,6 +261,8 @@ class ClosedLoop(_ScoredLoop):
         _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
                                                 C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
                                                 C.c_void_p(cmd.data_ptr()), stream))
+        if self.compensator is not None:
+            self.compensator.push(cmd, self.k)
         self.sim._update_vehicle_model(plant_updates)
         self.k += 1
         return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s)
@@ -245,7 +279,7 @@ class ClosedLoopFrenet(_ScoredLoop):
     (checked once, here).  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, estimator=None,
-                 estimator_input="actuator", **options):
+                 estimator_input="actuator", compensator=None, **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -274,7 +308,7 @@ class ClosedLoopFrenet(_ScoredLoop):
         self.out = None
         self.k = 0
         self._init_sensor(sensor)
-        self._init_estimator(estimator, estimator_input)
+        self._init_estimator(estimator, estimator_input, compensator)
         self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
@@ -286,6 +320,8 @@ class ClosedLoopFrenet(_ScoredLoop):
         st = self.sim.state if self.sensor is None else self._sense()
         if self.estimator is not None:
             st = self._filter(st)
+        if self.compensator is not None:
+            st = self._predict(st, plant_updates)
         pose = st[:, 0:3].contiguous()
         ref, stop = self.grt.get_waypoints_batch(pose, self.v_target)
         k_poly, _psi, z0, fit_status = get_reference_frenet_batch(pose, ref, st[:, 3].contiguous())
@@ -306,6 +342,8 @@ class ClosedLoopFrenet(_ScoredLoop):
         _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
                                                 C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
                                                 C.c_void_p(cmd.data_ptr()), stream))
+        if self.compensator is not None:
+            self.compensator.push(cmd, self.k)
         self.sim._update_vehicle_model(plant_updates)
         self.k += 1
         return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s,

@@ -743,6 +743,84 @@ extern "C" int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state
     return KMPC_OK;
 }
 
+extern "C" int32_t kmpc_sim_advance_queue(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay,
+                                          void *cmd_queue, int32_t depth, int64_t period, int32_t n_updates, void *stream)
+{
+    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_queue: bad argument (B=%d, n_updates=%d)", B, n_updates);
+    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_queue: null plant rows");
+    if (depth < 2 || period < 0 || !cmd_queue)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_queue: bad queue (depth=%d, at least 2; period=%lld, at least 0; cmd_queue %s)", depth,
+                    (long long)period, cmd_queue ? "given" : "NULL");
+    if (B == 0 || n_updates == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_queue: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_sim_queue(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_queue, depth,
+                                               (long long)period, n_updates, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_queue: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period,
+                                            int64_t id_base, const int32_t *meas_delay, void *truth_ring, int32_t depth, void *est, void *stream)
+{
+    if (B < 0 || period < 0 || id_base < 0 || (B > 0 && (!state || !sensor || !est)))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_delayed_batch: bad argument (B=%d, period=%lld, id_base=%lld)", B, (long long)period, (long long)id_base);
+    if (depth < 1 || (B > 0 && (!meas_delay || !truth_ring)))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_delayed_batch: bad ring (depth=%d, at least 1; meas_delay and truth_ring are required)", depth);
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_delayed_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_sense_delayed(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, meas_delay,
+                                                   (double *)truth_ring, depth, (double *)est, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_delayed_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+// ---- delay compensation (kmpc_latency.hip) ---------------------------------------------------------------------------
+static int32_t latency_args(const char *fn, int32_t B, const void *cmd_hist, int32_t depth, int64_t period, int32_t n_updates, const int32_t *cmd_delay,
+                            const int32_t *meas_delay, int32_t max_cmd_delay, int32_t max_meas_delay)
+{
+    if (B < 0 || period < 0 || n_updates < 1 || max_cmd_delay < 0 || max_meas_delay < 0)
+        return fail(nullptr, KMPC_ERR_ARG, "%s: bad argument (B=%d, period=%lld, n_updates=%d, max_cmd_delay=%d, max_meas_delay=%d)", fn, B,
+                    (long long)period, n_updates, max_cmd_delay, max_meas_delay);
+    const int64_t need = (int64_t)max_meas_delay + ((int64_t)max_cmd_delay + n_updates - 1) / n_updates + 1;
+    if ((int64_t)depth < need)
+        return fail(nullptr, KMPC_ERR_ARG, "%s: depth=%d, but max_meas_delay=%d periods + max_cmd_delay=%d updates of %d per period reach back %lld periods",
+                    fn, depth, max_meas_delay, max_cmd_delay, n_updates, (long long)need);
+    if (B > 0 && (!cmd_hist || !cmd_delay || !meas_delay)) return fail(nullptr, KMPC_ERR_ARG, "%s: null required buffer", fn);
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_cmd_in_force_batch(int32_t device, int32_t B, const void *cmd_hist, int32_t depth, int64_t period, int32_t n_updates,
+                                           const int32_t *cmd_delay, const int32_t *meas_delay, int32_t max_cmd_delay, int32_t max_meas_delay,
+                                           void *u_out, void *stream)
+{
+    const int32_t rc = latency_args("kmpc_cmd_in_force_batch", B, cmd_hist, depth, period, n_updates, cmd_delay, meas_delay, max_cmd_delay, max_meas_delay);
+    if (rc != KMPC_OK) return rc;
+    if (B > 0 && !u_out) return fail(nullptr, KMPC_ERR_ARG, "kmpc_cmd_in_force_batch: null u_out");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_cmd_in_force_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_cmd_in_force(B, (const double *)cmd_hist, depth, (long long)period, n_updates, cmd_delay, meas_delay, max_cmd_delay,
+                                                  max_meas_delay, (double *)u_out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_cmd_in_force_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_predict_ahead_batch(int32_t device, int32_t B, const void *z, const void *cmd_hist, int32_t depth, int64_t period,
+                                            int32_t n_updates, const int32_t *cmd_delay, const int32_t *meas_delay, int32_t max_cmd_delay,
+                                            int32_t max_meas_delay, double L_a, double L_b, void *z_out, void *stream)
+{
+    const int32_t rc = latency_args("kmpc_predict_ahead_batch", B, cmd_hist, depth, period, n_updates, cmd_delay, meas_delay, max_cmd_delay, max_meas_delay);
+    if (rc != KMPC_OK) return rc;
+    const auto pos = [](double a) { return a > 0.0 && a <= 1.7976931348623157e308; };   // finite and > 0
+    if (!pos(L_a) || !pos(L_b)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_predict_ahead_batch: L_a=%g, L_b=%g must be finite and > 0", L_a, L_b);
+    if (B > 0 && (!z || !z_out)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_predict_ahead_batch: null z or z_out");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_predict_ahead_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_predict_ahead(B, (const double *)z, (const double *)cmd_hist, depth, (long long)period, n_updates, cmd_delay, meas_delay,
+                                                   max_cmd_delay, max_meas_delay, L_a, L_b, (double *)z_out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_predict_ahead_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 // ---- state estimator (kmpc_estimator.hip) --------------------------------------------------------------------------
 extern "C" int32_t kmpc_estimate_batch(int32_t device, int32_t B, void *rec, const void *z, const void *u, int32_t u_stride, const void *params,
                                        double dt, double L_a, double L_b, double gate, void *est_out, void *innov_out, int32_t *flags_out,

@@ -96,6 +96,16 @@ hipError_t kmpc_launch_sim_plant(int B, double *state, const double *cmd, const 
                                  int n_updates, hipStream_t st);
 hipError_t kmpc_launch_sense(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base, double *est,
                              hipStream_t st);
+hipError_t kmpc_launch_sim_queue(int B, double *state, const double *cmd, const double *plant, const int32_t *cmd_delay, double *cmd_queue, int depth,
+                                 long long period, int n_updates, hipStream_t st);
+hipError_t kmpc_launch_sense_delayed(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base,
+                                     const int32_t *meas_delay, double *truth_ring, int depth, double *est, hipStream_t st);
+// delay compensation (kmpc_latency.hip)
+hipError_t kmpc_launch_cmd_in_force(int B, const double *hist, int depth, long long period, int n, const int32_t *cmd_delay, const int32_t *meas_delay,
+                                    int max_cmd_delay, int max_meas_delay, double *u_out, hipStream_t st);
+hipError_t kmpc_launch_predict_ahead(int B, const double *z, const double *hist, int depth, long long period, int n, const int32_t *cmd_delay,
+                                     const int32_t *meas_delay, int max_cmd_delay, int max_meas_delay, double L_a, double L_b, double *z_out,
+                                     hipStream_t st);
 // state estimator (kmpc_estimator.hip)
 hipError_t kmpc_launch_estimate(int B, double *rec, const double *z, const double *u, int u_stride, const double *params, double dt, double L_a,
                                 double L_b, double gate, double *est_out, double *innov_out, int32_t *flags_out, hipStream_t st);

@@ -290,3 +290,160 @@ hipError_t kmpc_launch_command(int B, const double *u0, const int32_t *stop, uin
     hipLaunchKernelGGL(kmpc_command_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, u0, stop, latch, u_prev, cmd);
     return hipGetLastError();
 }
+
+// A command queue (kmpc_sim_advance_queue): kmpc_sim_plant_kernel with the one held command replaced by a ring of the last `depth` periods' commands,
+// cmd_queue [depth,B,2] (slot j mod depth holds period j; consecutive lanes read consecutive 16 B), so that a command may take effect several
+// control periods late.  With d = clamp(cmd_delay, 0, (depth - 1) n) = q n + r the update `up` of period p runs towards the command of period
+// p - q - (up < r): only two commands are in play per call, fetched before the loop -- the loop is kmpc_sim_plant_kernel's with its two targets
+// substituted, and the sub-step below is a COPY of that kernel's, operation for operation (the two existing kernels are not touched: a shared body
+// would have to be shown not to move their instruction streams, a copy cannot).  A period before the first (j < 0) commands (0, 0).
+__global__ __launch_bounds__(256) void kmpc_sim_queue_kernel(int B, double *__restrict__ state, const double *__restrict__ cmd,
+                                                             const double *__restrict__ plant, const int32_t *__restrict__ cmd_delay,
+                                                             double *cmd_queue, int depth, long long period, int n_updates)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const double *pr = plant + KMPC_PLANT_WORDS * (size_t)i;
+    const double lf = pr[KMPC_PLANT_LF], lr = pr[KMPC_PLANT_LR], m = pr[KMPC_PLANT_M], Iz = pr[KMPC_PLANT_IZ];
+    const double C_alpha_f = pr[KMPC_PLANT_C_ALPHA_F], C_alpha_r = pr[KMPC_PLANT_C_ALPHA_R];
+    const double k_acc = pr[KMPC_PLANT_K_ACC], k_df = pr[KMPC_PLANT_K_DF];
+    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;
+    const double deltaT = 0.01 / 10.0;
+    const double pi = 3.141592653589793;
+    double *s = state + 8 * (size_t)i;
+    double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
+    const double acc_now = cmd[2 * (size_t)i], df_now = cmd[2 * (size_t)i + 1];
+    const size_t slot_words = 2 * (size_t)B;
+    {
+        double *own = cmd_queue + (size_t)(period % depth) * slot_words + 2 * (size_t)i;
+        own[0] = acc_now; own[1] = df_now;
+    }
+    int d = cmd_delay ? cmd_delay[i] : 0;
+    const long long dmax = (long long)(depth - 1) * n_updates;   // n_updates >= 1 here (the host returns before a launch otherwise)
+    d = d < 0 ? 0 : ((long long)d > dmax ? (int)dmax : d);
+    const int q = d / n_updates, r = d % n_updates;
+    // period p - q (the later of the two) and p - q - 1 (the earlier, needed only when r > 0; with q == depth - 1, r is 0 and its slot is this period's)
+    double acc_new = acc_now, df_new = df_now, acc_old = 0.0, df_old = 0.0;
+    const long long jn = period - q, jo = jn - 1;
+    if (q > 0) {
+        acc_new = 0.0; df_new = 0.0;
+        if (jn >= 0) {
+            const double *e = cmd_queue + (size_t)(jn % depth) * slot_words + 2 * (size_t)i;
+            acc_new = e[0]; df_new = e[1];
+        }
+    }
+    if (r > 0 && jo >= 0) {
+        const double *e = cmd_queue + (size_t)(jo % depth) * slot_words + 2 * (size_t)i;
+        acc_old = e[0]; df_old = e[1];
+    }
+    for (int up = 0; up < n_updates; ++up) {
+        const double acc_des = up < r ? acc_old : acc_new, df_des = up < r ? df_old : df_new;   // the target changes between updates only
+#pragma unroll 1
+        for (int it = 0; it < 10; ++it) {
+            const bool moving = fabs(vx) > 1e-6;
+            const double yf = vy + lf * wz, yr = vy - lf * wz;          // lf where lr is expected -- as in the reference
+            const double rvx = sim_rcp(vx);
+            const double tf = yf * rvx, tr = yr * rvx;
+            const bool in_range = (!moving || (vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) && fabs(df) <= 0.6 && fabs(psi) <= 4.0;
+            double af = sim_atan_poly(tf), ar = sim_atan_poly(tr), cd = sim_cos_poly(df * df), sp, cp;
+            sim_sincos_poly(psi, &sp, &cp);
+            if (__any(!in_range)) {
+                if (moving && !(vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) { af = atan2(yf, vx); ar = atan2(yr, vx); }
+                if (!(fabs(df) <= 0.6)) cd = cos(df);
+                if (!(fabs(psi) <= 4.0)) sincos(psi, &sp, &cp);
+            }
+            const double alpha_f = moving ? df - af : 0.0;
+            const double alpha_r = moving ? -ar : 0.0;
+            const double Fyf = C_alpha_f * alpha_f, Fyr = C_alpha_r * alpha_r;
+            const double vx_n = fmax(0.0, vx + deltaT * (acc + wz * vy));   // no Fyf * sin(df) / m term -- as in the reference
+            const bool fwd = vx_n > 1e-6;
+            const double vy_c = vy + deltaT * (inv_m * (Fyf * cd + Fyr) - wz * vx);
+            const double wz_c = wz + deltaT * (inv_Iz * (lf * Fyf * cd - lr * Fyr));
+            const double vy_n = fwd ? vy_c : 0.0, wz_n = fwd ? wz_c : 0.0;
+            const double psi_n = psi + deltaT * wz;
+            const double X_n = X + deltaT * (vx * cp - vy * sp);
+            const double Y_n = Y + deltaT * (vx * sp + vy * cp);
+            X = X_n; Y = Y_n;
+            const double a = psi_n + pi, p2 = 2.0 * pi;
+            double md = a;
+            const bool wrap = !(a >= 0.0 && a < p2);
+            if (__any(wrap)) {
+                if (wrap) {
+                    md = fmod(a, p2);
+                    if (md < 0.0) md += p2;
+                }
+            }
+            psi = md - pi;
+            vx = vx_n; vy = vy_n; wz = wz_n;
+            acc = k_acc * (acc_des - acc) * deltaT + acc;
+            df = k_df * (df_des - df) * deltaT + df;
+        }
+    }
+    s[0] = X; s[1] = Y; s[2] = psi; s[3] = vx; s[4] = vy; s[5] = wz; s[6] = acc; s[7] = df;
+}
+
+hipError_t kmpc_launch_sim_queue(int B, double *state, const double *cmd, const double *plant, const int32_t *cmd_delay, double *cmd_queue, int depth,
+                                 long long period, int n_updates, hipStream_t st)
+{
+    hipLaunchKernelGGL(kmpc_sim_queue_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, state, cmd, plant, cmd_delay, cmd_queue, depth, period,
+                       n_updates);
+    return hipGetLastError();
+}
+
+// Stale fixes (kmpc_sense_delayed_batch): kmpc_sense_kernel measuring the truth of period - L instead of this period's.  This period's x, y, psi, vx go
+// into slot period mod depth of truth_ring [depth,B,4] (consecutive lanes write consecutive 32 B) and the measured truth comes out of slot
+// (period - L) mod depth, L = clamp(meas_delay, 0, min(depth - 1, period)); bias and noise are this period's (counter = (vehicle id, period)): noise
+// belongs to the moment of emission.  The arithmetic after the fetch is kmpc_sense_kernel's, operation for operation (a copy: that kernel stays).
+__global__ __launch_bounds__(256) void kmpc_sense_delayed_kernel(int B, const double *__restrict__ state, const double *__restrict__ sensor, uint64_t seed,
+                                                                 uint64_t period, uint64_t id_base, const int32_t *__restrict__ meas_delay,
+                                                                 double *truth_ring, int depth, double *__restrict__ est)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const uint64_t gid = id_base + (uint64_t)i;
+    uint32_t w[4];
+    philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)period, (uint32_t)(period >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    const double *sr = sensor + KMPC_SENSOR_WORDS * (size_t)i, *st = state + 8 * (size_t)i;
+    const size_t slot_words = 4 * (size_t)B;
+    double t[4];
+    for (int c = 0; c < 4; ++c) t[c] = st[c];
+    {
+        double *own = truth_ring + (size_t)(period % (uint64_t)depth) * slot_words + 4 * (size_t)i;
+        for (int c = 0; c < 4; ++c) own[c] = t[c];
+    }
+    const uint64_t lmax = period < (uint64_t)(depth - 1) ? period : (uint64_t)(depth - 1);
+    const int lraw = meas_delay[i];
+    const uint64_t L = lraw <= 0 ? 0 : ((uint64_t)lraw > lmax ? lmax : (uint64_t)lraw);
+    if (L > 0) {
+        const double *old = truth_ring + (size_t)((period - L) % (uint64_t)depth) * slot_words + 4 * (size_t)i;
+        for (int c = 0; c < 4; ++c) t[c] = old[c];
+    }
+    double e[4];
+    for (int c = 0; c < 4; ++c) e[c] = t[c] + sr[KMPC_SENSOR_BIAS_X + c];
+    for (int h = 0; h < 2; ++h) {
+        const double sg0 = sr[KMPC_SENSOR_SIGMA_X + 2 * h], sg1 = sr[KMPC_SENSOR_SIGMA_X + 2 * h + 1];
+        if (sg0 != 0.0 || sg1 != 0.0) {
+            const double u0 = ((double)w[2 * h] + 0.5) * 0x1p-32, u1 = ((double)w[2 * h + 1] + 0.5) * 0x1p-32;
+            const double r = sqrt(-2.0 * log(u0)), a = 6.283185307179586 * u1;
+            if (sg0 != 0.0) e[2 * h] = e[2 * h] + sg0 * (r * cos(a));
+            if (sg1 != 0.0) e[2 * h + 1] = e[2 * h + 1] + sg1 * (r * sin(a));
+        }
+    }
+    const double pi = 3.141592653589793, p2 = 2.0 * pi;
+    if (!(e[2] >= -pi && e[2] < pi)) {
+        double md = fmod(e[2] + pi, p2);
+        if (md < 0.0) md += p2;
+        e[2] = md - pi;
+    }
+    e[3] = fmax(0.0, e[3]);
+    double *o = est + 4 * (size_t)i;
+    o[0] = e[0]; o[1] = e[1]; o[2] = e[2]; o[3] = e[3];
+}
+
+hipError_t kmpc_launch_sense_delayed(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base,
+                                     const int32_t *meas_delay, double *truth_ring, int depth, double *est, hipStream_t st)
+{
+    hipLaunchKernelGGL(kmpc_sense_delayed_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, state, sensor, seed, period, id_base, meas_delay,
+                       truth_ring, depth, est);
+    return hipGetLastError();
+}

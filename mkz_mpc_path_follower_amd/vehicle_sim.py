@@ -7,6 +7,11 @@ Monte-Carlo runs: `plant=plant_params(B, m=..., C_alpha_f=...)` gives every vehi
 model updates of 10 ms (kmpc_sim_advance_plant); `SensorModel` is the measurement stage between the plant and the controller
 (kmpc_sense_batch).  Without them the simulator runs the kernel and computes the results it always did.  `Estimator` is the stage after the
 sensor: an extended Kalman filter per vehicle on the solver's model (kmpc_estimate_batch), so that the controller is fed a filtered state.
+
+Latency: `VehicleSimulator(cmd_queue_depth=D)` keeps the last D periods' commands, so that `cmd_delay` may exceed one call (kmpc_sim_advance_queue);
+`SensorModel(meas_delay=, depth=)` measures the truth of an earlier period (kmpc_sense_delayed_batch); `LatencyCompensator` is the controller's
+answer: a log of the commands sent and assumed delays of its own, from which it picks the filter's input and predicts the estimate ahead to the
+moment the next command acts (kmpc_cmd_in_force_batch, kmpc_predict_ahead_batch).
 """
 import ctypes as C
 
@@ -27,6 +32,17 @@ EST_SKIP_X, EST_SKIP_Y, EST_SKIP_PSI, EST_SKIP_V, EST_INIT, EST_RESET = 1, 2, 4,
 
 def _device(device):
     return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+
+
+def _int_per_vehicle(name, v, B, lo, hi=None):
+    """a scalar or one integer per vehicle within [lo, hi] -> int32 [B] on the host (ValueError otherwise)"""
+    d = torch.as_tensor(v).detach().cpu()
+    if d.is_floating_point() or d.dtype == torch.bool or d.dim() > 1 or (d.dim() == 1 and d.shape[0] != B):
+        raise ValueError("%s: an integer or one per vehicle [%d], got %r" % (name, B, v))
+    d = d.to(torch.int64).expand(B)
+    if B and (int(d.min()) < lo or (hi is not None and int(d.max()) > hi)):
+        raise ValueError("%s: within %d ... %s, got %d ... %d" % (name, lo, "any" if hi is None else hi, int(d.min()), int(d.max())))
+    return d.to(torch.int32).contiguous()
 
 
 def plant_default():
@@ -68,11 +84,19 @@ def plant_params(B, device=0, **overrides):
 class VehicleSimulator:
     dt_model = 0.01  # :24
 
-    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None):
+    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None, cmd_queue_depth=None):
         """plant: [B,8] rows (plant_params) -- a plant per vehicle; cmd_delay: a scalar or one per vehicle, model updates of 10 ms by which a new
         command takes effect late (clamped to one call's n_updates; the command in force until then is `cmd_held`, 0 at the start).  Giving
         either runs kmpc_sim_advance_plant (the other defaults to the reference's constants / no delay); `plant`, `cmd_delay` (int32 [B]) and
-        `cmd_held` [B,2] are then plain device tensors the caller may edit between steps.  Giving neither changes nothing."""
+        `cmd_held` [B,2] are then plain device tensors the caller may edit between steps.  Giving neither changes nothing.
+        cmd_queue_depth=D (an integer >= 2): a ring `cmd_queue` [D,B,2] of the last D periods' commands replaces `cmd_held`
+        (kmpc_sim_advance_queue), so that cmd_delay may exceed one call: it is clamped to (D - 1) n_updates.  The simulator then counts its calls
+        in `period` (slot period mod D holds that call's command); every call of a run must use the same n_updates."""
+        self.cmd_queue_depth = None
+        if cmd_queue_depth is not None:   # checked first: a bad depth is a ValueError on any machine
+            if isinstance(cmd_queue_depth, bool) or not isinstance(cmd_queue_depth, (int, np.integer)) or cmd_queue_depth < 2:
+                raise ValueError("cmd_queue_depth: an integer >= 2 (periods of commands kept), got %r" % (cmd_queue_depth,))
+            self.cmd_queue_depth = int(cmd_queue_depth)
         self._lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("VehicleSimulator needs an MI355X; no CPU fallback")
@@ -84,8 +108,9 @@ class VehicleSimulator:
         self.state[:, 1] = torch.as_tensor(Y0, dtype=torch.float64, device=self.device)
         self.state[:, 2] = torch.as_tensor(Psi0, dtype=torch.float64, device=self.device)
         self.cmd = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)  # acc_des, df_des (:21-22)
-        self.plant = self.cmd_delay = self.cmd_held = None
-        if plant is not None or cmd_delay is not None:
+        self.plant = self.cmd_delay = self.cmd_held = self.cmd_queue = None
+        self.period = 0
+        if plant is not None or cmd_delay is not None or cmd_queue_depth is not None:
             if plant is None:
                 self.plant = plant_params(self.B, self.device)
             else:
@@ -97,7 +122,10 @@ class VehicleSimulator:
             if d.is_floating_point() or d.dim() > 1 or (d.dim() == 1 and d.shape[0] != self.B):
                 raise ValueError("cmd_delay: an integer or one per vehicle [%d] (model updates of 10 ms)" % self.B)
             self.cmd_delay = d.to(torch.int32).expand(self.B).contiguous().to(self.device)
-            self.cmd_held = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
+            if self.cmd_queue_depth is None:
+                self.cmd_held = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
+            else:
+                self.cmd_queue = torch.zeros((self.cmd_queue_depth, self.B, 2), dtype=torch.float64, device=self.device)
 
     # views named as in the reference
     X = property(lambda s: s.state[:, 0]); Y = property(lambda s: s.state[:, 1]); psi = property(lambda s: s.state[:, 2])
@@ -118,6 +146,17 @@ class VehicleSimulator:
         if self.plant is None:
             rc = self._lib.kmpc_sim_advance_batch(self.device.index, self.B, C.c_void_p(self.state.data_ptr()),
                                                   C.c_void_p(self.cmd.data_ptr()), int(n_updates), stream)
+        elif self.cmd_queue_depth is not None:
+            for t, shape, dt in ((self.plant, (self.B, 8), torch.float64), (self.cmd_delay, (self.B,), torch.int32),
+                                 (self.cmd_queue, (self.cmd_queue_depth, self.B, 2), torch.float64)):
+                if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+                    raise ValueError("plant [B,8] / cmd_queue [D,B,2] float64 and cmd_delay [B] int32 must stay contiguous tensors on %s "
+                                     "(write into them with copy_)" % self.device)
+            rc = self._lib.kmpc_sim_advance_queue(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
+                                                  C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
+                                                  C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth, int(self.period), int(n_updates), stream)
+            if rc == 0 and int(n_updates) > 0:
+                self.period += 1
         else:
             for t, shape, dt in ((self.plant, (self.B, 8), torch.float64), (self.cmd_delay, (self.B,), torch.int32), (self.cmd_held, (self.B, 2), torch.float64)):
                 if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
@@ -138,9 +177,13 @@ class SensorModel:
     """The measurement stage between the plant and the controller: est = truth + bias + sigma * n on x, y, psi, v (kmpc_sense_batch), what
     scripts/state_publisher.py's GPS fix, IMU yaw and steering-report speed do to state_est on the real vehicle.  `sigma`, `bias`: a scalar,
     four values (x, y, psi, v) or [B,4].  `params` [B,8] (SENSOR_FIELDS) is a plain device tensor the caller may edit between calls.  Vehicle b's
-    noise depends only on (seed, id_base + b, period): a shard of a larger fleet passes its first vehicle's index (dist.shard_range's lo) as id_base."""
+    noise depends only on (seed, id_base + b, period): a shard of a larger fleet passes its first vehicle's index (dist.shard_range's lo) as id_base.
+    `meas_delay` (an integer or one per vehicle, whole control periods, 0 ... depth - 1): the fix is that old when it is read
+    (kmpc_sense_delayed_batch: the truth of period - meas_delay with this period's noise; period 0's state until the ring is filled); `depth`
+    (default: the largest meas_delay + 1) sizes `truth_ring` [depth,B,4].  `meas_delay` [B] int32 is then a plain device tensor too, and sense()
+    must be called once per period with consecutive periods from 0.  Without meas_delay the stage is what it was."""
 
-    def __init__(self, B, sigma=0.0, bias=0.0, seed=0, id_base=0, device=0):
+    def __init__(self, B, sigma=0.0, bias=0.0, seed=0, id_base=0, device=0, meas_delay=None, depth=None):
         self._lib = _lib.load()
         self.B, self.seed, self.id_base = int(B), int(seed), int(id_base)
         if not (0 <= self.seed < 2 ** 64 and 0 <= self.id_base and self.id_base + self.B < 2 ** 63):
@@ -155,6 +198,19 @@ class SensorModel:
             raise ValueError("SensorModel: sigma and bias must be finite, sigma >= 0")
         self.device = _device(device)
         self.params = torch.as_tensor(rows).to(self.device)
+        self.meas_delay = self.truth_ring = self.depth = None
+        if meas_delay is None and depth is not None:
+            raise ValueError("SensorModel: depth belongs to meas_delay")
+        if meas_delay is not None:
+            d = _int_per_vehicle("SensorModel: meas_delay", meas_delay, self.B, 0)
+            need = (int(d.max()) if self.B else 0) + 1
+            if depth is None:
+                depth = need
+            if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or depth < need:
+                raise ValueError("SensorModel: depth is an integer >= the largest meas_delay + 1 = %d, got %r" % (need, depth))
+            self.depth = int(depth)
+            self.meas_delay = d.to(self.device)
+            self.truth_ring = torch.zeros((self.depth, self.B, 4), dtype=torch.float64, device=self.device)
 
     def sense(self, state, period, out=None):
         """state [B,8] (the plant's) -> est [B,4] = x, y, psi (wrapped to [-pi, pi)), v (>= 0) as measured in control period `period`"""
@@ -163,6 +219,14 @@ class SensorModel:
             if not (t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
                 raise ValueError("state [B,8], params [B,8] and est [B,4] must be contiguous float64 tensors on %s" % self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.meas_delay is not None:
+            for t, shape, dt in ((self.meas_delay, (self.B,), torch.int32), (self.truth_ring, (self.depth, self.B, 4), torch.float64)):
+                if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+                    raise ValueError("meas_delay [B] int32 and truth_ring [depth,B,4] float64 must stay contiguous tensors on %s" % self.device)
+            _lib.check(self._lib.kmpc_sense_delayed_batch(self.device.index, self.B, C.c_void_p(state.data_ptr()), C.c_void_p(self.params.data_ptr()),
+                                                          self.seed, int(period), self.id_base, C.c_void_p(self.meas_delay.data_ptr()),
+                                                          C.c_void_p(self.truth_ring.data_ptr()), self.depth, C.c_void_p(est.data_ptr()), stream))
+            return est
         _lib.check(self._lib.kmpc_sense_batch(self.device.index, self.B, C.c_void_p(state.data_ptr()), C.c_void_p(self.params.data_ptr()),
                                               self.seed, int(period), self.id_base, C.c_void_p(est.data_ptr()), stream))
         return est
@@ -232,3 +296,76 @@ class Estimator:
                                                  self.gate, C.c_void_p(est.data_ptr()), C.c_void_p(self.innov.data_ptr()),
                                                  C.c_void_p(self.flags.data_ptr()), stream))
         return est
+
+
+class LatencyCompensator:
+    """The controller's answer to dead time (kmpc_cmd_in_force_batch, kmpc_predict_ahead_batch; include/kmpc.h states the rules).  It keeps a log
+    of the commands it sent, `cmd_hist` [depth,B,2] (slot p mod depth: period p's command, written by push() after the command stage), and its own
+    ASSUMED delays: `cmd_delay` [B] int32 in model updates of 10 ms and `meas_delay` [B] int32 in whole control periods -- separate tensors from the
+    plant's and the sensor's, so that a run can have a delay mismatch.  All three are plain device tensors the caller may edit between periods;
+    the delays are clamped into `max_cmd_delay` / `max_meas_delay`, the largest values given here (plain ints; raise them only as far as
+    depth >= max_meas_delay + ceil(max_cmd_delay / n_updates) + 1 allows: the library refuses more).  `depth` defaults to exactly that.
+    `n_updates`: plant updates per control period; `L_a`, `L_b`: the solver model's axle distances (kmpc_config's defaults).
+      filter_input(period)   -> u [B,2]: the command in force over the period before the measurement's moment: the estimator's predict input
+      predict(z, period)     -> z [B,4] carried from the measurement's moment, update (period - meas_delay) n, to update period n + cmd_delay, where
+                                this period's command begins to act; zero delays return z bit for bit
+      push(cmd, period)      logs period's command [B,2]"""
+
+    def __init__(self, B, cmd_delay=0, meas_delay=0, n_updates=10, depth=None, L_a=1.108, L_b=1.742, device=0):
+        self._lib = _lib.load()
+        self.B = int(B)
+        if isinstance(n_updates, bool) or not isinstance(n_updates, (int, np.integer)) or n_updates < 1:
+            raise ValueError("LatencyCompensator: n_updates is an integer >= 1, got %r" % (n_updates,))
+        self.n_updates = int(n_updates)
+        cd = _int_per_vehicle("LatencyCompensator: cmd_delay (model updates of 10 ms)", cmd_delay, self.B, 0)
+        md = _int_per_vehicle("LatencyCompensator: meas_delay (control periods)", meas_delay, self.B, 0)
+        self.max_cmd_delay, self.max_meas_delay = (int(cd.max()), int(md.max())) if self.B else (0, 0)
+        need = self.max_meas_delay + -(-self.max_cmd_delay // self.n_updates) + 1
+        if depth is None:
+            depth = need
+        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or depth < need:
+            raise ValueError("LatencyCompensator: depth is an integer >= max meas_delay + ceil(max cmd_delay / n_updates) + 1 = %d, got %r" % (need, depth))
+        self.depth = int(depth)
+        self.L_a, self.L_b = float(L_a), float(L_b)
+        if not (np.isfinite([self.L_a, self.L_b]).all() and self.L_a > 0.0 and self.L_b > 0.0):
+            raise ValueError("LatencyCompensator: L_a > 0, L_b > 0, finite (got %r, %r)" % (L_a, L_b))
+        self.device = _device(device)
+        self.cmd_delay, self.meas_delay = cd.to(self.device), md.to(self.device)
+        self.cmd_hist = torch.zeros((self.depth, self.B, 2), dtype=torch.float64, device=self.device)
+
+    def _check(self, period):
+        for t, shape, dt in ((self.cmd_delay, (self.B,), torch.int32), (self.meas_delay, (self.B,), torch.int32),
+                             (self.cmd_hist, (self.depth, self.B, 2), torch.float64)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+                raise ValueError("cmd_delay, meas_delay [B] int32 and cmd_hist [depth,B,2] float64 must stay contiguous tensors on %s" % self.device)
+        if int(period) < 0:
+            raise ValueError("period >= 0")
+
+    def _buf(self, t, w, name):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+            raise ValueError("%s must be a contiguous float64 tensor [B,%d] on %s" % (name, w, self.device))
+        return t
+
+    def filter_input(self, period, out=None):
+        self._check(period)
+        u = self._buf(out, 2, "out") if out is not None else torch.empty((self.B, 2), dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_cmd_in_force_batch(self.device.index, self.B, C.c_void_p(self.cmd_hist.data_ptr()), self.depth, int(period),
+                                                     self.n_updates, C.c_void_p(self.cmd_delay.data_ptr()), C.c_void_p(self.meas_delay.data_ptr()),
+                                                     int(self.max_cmd_delay), int(self.max_meas_delay), C.c_void_p(u.data_ptr()), stream))
+        return u
+
+    def predict(self, z, period, out=None):
+        self._check(period)
+        self._buf(z, 4, "z")
+        zo = self._buf(out, 4, "out") if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_predict_ahead_batch(self.device.index, self.B, C.c_void_p(z.data_ptr()), C.c_void_p(self.cmd_hist.data_ptr()),
+                                                      self.depth, int(period), self.n_updates, C.c_void_p(self.cmd_delay.data_ptr()),
+                                                      C.c_void_p(self.meas_delay.data_ptr()), int(self.max_cmd_delay), int(self.max_meas_delay),
+                                                      self.L_a, self.L_b, C.c_void_p(zo.data_ptr()), stream))
+        return zo
+
+    def push(self, cmd, period):
+        self._check(period)
+        self.cmd_hist[int(period) % self.depth].copy_(self._buf(cmd, 2, "cmd"))
