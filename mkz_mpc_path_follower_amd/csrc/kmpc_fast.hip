@@ -389,12 +389,15 @@ template <typename T, int N, int MODEL = 0> struct FastSolver {
                 for (int k = 0; k < 4; ++k) a[t][k] = pan[4 * (16 * t + c) + k];
             const ipm::Chol4<T> c4 = ipm::factor_diag4(dd);
             if (!c4.ok) return false;  // not positive definite (wave-uniform)
-            if (lane == 0) c4.store_inv(sinvb + 16 * jb);
-            // column kk of inv, for this lane's component of L~: read back from the block just stored (4 LDS reads instead of 9 selects;
-            // they feed only the L~ stores, which are off the panel -> MFMA critical path)
-            WFENCE();
-            const T *sqc = sinvb + 16 * jb + kk;
-            const T c0 = sqc[0], c1 = sqc[4], c2 = sqc[8], c3 = sqc[12];
+            // column kk of inv, for this lane's component of L~, computed where it is used (Chol4::inv_col); the first lane of each
+            // 16-lane row stores it for diag_solve (the zeros above the diagonal included: what the buffer holds there from construction)
+            T ic[4];
+            c4.inv_col(kk, ic);
+            if (c == 0) {
+                T *sqc = sinvb + 16 * jb + kk;
+                sqc[0] = ic[0]; sqc[4] = ic[1]; sqc[8] = ic[2]; sqc[12] = ic[3];
+            }
+            const T c0 = ic[0], c1 = ic[1], c2 = ic[2], c3 = ic[3];
             T pf[NTF];
             const int jc = j0 + kk;
             T *colL = Lc + offc_rt(jc < n ? jc : 0);

@@ -737,6 +737,24 @@ template <typename T> struct Chol4 {
     {
         sq[0] = r0; sq[4] = i10; sq[5] = r1; sq[8] = i20; sq[9] = i21; sq[10] = r2; sq[12] = i30; sq[13] = i31; sq[14] = i32; sq[15] = r3;
     }
+    // Column kk of inv (c[m] = inv[m][kk], +0 above the diagonal) in the lane that uses it: forward substitution against e_kk, 9 products instead of the 16
+    // of the whole inverse, and no store -> fence -> read-back.  Every entry is the bit pattern factor_diag4 gives i10 .. i32 (same products, same order):
+    // the column starts at its own pivot, so the terms a zero-padded substitution would add are replaced by -0.0 (x + -0.0 == x for every x, signed zeros
+    // included), and the entries above the diagonal are selected to +0, not computed (l * 0 carries the sign of l).  A caller that only uses inv_col leaves
+    // i10 .. i32 dead.
+    DEV void inv_col(int kk, T (&c)[4]) const
+    {
+        const bool k0 = kk == 0, k1 = kk == 1, k2 = kk == 2;
+        const T nz = -(T)0;
+        c[0] = k0 ? r0 : (T)0;
+        const T c1 = -l10 * c[0] * r1;                                    // kk == 0: i10
+        c[1] = k0 ? c1 : (k1 ? r1 : (T)0);
+        const T c2 = -fma(l21, c[1], k0 ? l20 * c[0] : nz) * r2;          // kk == 0: i20, kk == 1: i21
+        c[2] = (k0 || k1) ? c2 : (k2 ? r2 : (T)0);
+        const T s3 = fma(l31, c[1], k0 ? l30 * c[0] : nz);                // kk == 0: l31 i10 + l30 r0, kk == 1: l31 r1
+        const T c3 = -fma(l32, c[2], (k0 || k1) ? s3 : nz) * r3;          // kk == 0: i30, kk == 1: i31, kk == 2: i32
+        c[3] = kk == 3 ? r3 : c3;
+    }
 };
 template <typename T> DEV Chol4<T> factor_diag4(const Diag4<T> &d)
 {
@@ -1227,11 +1245,26 @@ template <class SV> DEV void solve(SV &s, const KIO<typename SV::real> &io, int 
                 if (use_exact && indef == 1 && cs[C_DWS] > (T)0) { reg = cs[C_DWS] / (T)KMPC_DW_DECAY; if (reg < (T)1e-9 * cs[C_HMAX] || n_first_ok >= KMPC_ZERO_AFTER) reg = 0; }
                 first_attempt = true;
                 STAMP_AT(s, 2);
-            }
-            // K = sc*H + A^T Sigma A with the affine right-hand side -sc*g riding along
+                // form weights of this iteration, staged once (one wave per problem: the one-wave and the generic kernel): a REFACTOR pass finds them where they are -- lu, isu, ll, isl have not
+                // moved, and nothing between the failed attempt and the re-entry writes wb or cb[0 .. N) (the tile assembly and the diagonal staging read them
+                // and write cub / clb or their own staging rows, the factorisation writes its panel, sinvb and Lc, drop_second_order the stage records) -- so a
+                // retry pays no LDS exchange, suffix scan and second exchange.  Placed in this block, not behind a test of its own: as a separate region,
+                // next to the block step's inv_col, the same skip took <double,20> from 79 to 87 SGPR spills.
+                if (NTH == 64) {
 #pragma unroll
-            for (int i = 0; i < NF; ++i) w[i] = DG_U(i) * lu[i] * isu[i] + DG_L(i) * ll[i] * isl[i];
-            s.stage_form_weights(w);
+                    for (int i = 0; i < NF; ++i) w[i] = DG_U(i) * lu[i] * isu[i] + DG_L(i) * ll[i] * isl[i];
+                    s.stage_form_weights(w);
+                }
+            }
+            // K = sc*H + A^T Sigma A with the affine right-hand side -sc*g riding along.  The four-wave back-end stages the form weights on every pass, REFACTOR
+            // included: its staging ends in the workgroup barrier that also keeps a wave that has left a failed factorisation from assembling into the panel
+            // buffers a slower wave still reads.  So does the four-problems-per-wave kernel, whose rows take this path under diverged exec masks: moving the
+            // staging there changes the register allocation of its Frenet build (scratch 68 -> 40 B, a pinned and certified figure).
+            if (NTH != 64) {
+#pragma unroll
+                for (int i = 0; i < NF; ++i) w[i] = DG_U(i) * lu[i] * isu[i] + DG_L(i) * ll[i] * isl[i];
+                s.stage_form_weights(w);
+            }
             STAMP_AT(s, 6);
             const bool factored = s.kkt_factor(sc, reg, use_exact && indef == 1 && first_attempt);
             first_attempt = false;
