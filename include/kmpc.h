@@ -409,6 +409,66 @@ int32_t kmpc_sim_advance_plant(int32_t device, int32_t B, void *state, const voi
 int32_t kmpc_sim_advance_queue(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay,
                                void *cmd_queue, int32_t depth, int64_t period, int32_t n_updates, void *stream);
 
+/* ---- grip and road: tyre limits, bank, grade, steering offset ------------------------------------------------------------------------------
+ * kmpc_sim_advance_queue with a ROAD ROW per vehicle and grip bookkeeping.  The reference's tyres are linear and unbounded
+ * (vehicle_simulator.py:80-81: Fy = C_alpha * alpha), its road is flat and level and its steering has no offset; a plant that cannot run out of
+ * grip cannot show what a controller does when the road does not deliver the lateral force a corner asks for.
+ *   state, cmd, plant, cmd_delay, cmd_queue, depth, period, n_updates   exactly as in kmpc_sim_advance_queue, with its clamping and checks
+ *   road [B,8] fp64 DEVICE, 64 bytes per vehicle, row of vehicle b: */
+enum {
+    KMPC_ROAD_MU_F = 0,        /* friction coefficient at the front axle; +inf = no limit */
+    KMPC_ROAD_MU_R = 1,        /* friction coefficient at the rear axle; +inf = no limit */
+    KMPC_ROAD_A_LONG = 2,      /* specific force along the body x axis [m/s^2]: a grade theta gives -g sin(theta) */
+    KMPC_ROAD_A_LAT = 3,       /* specific force along the body y axis, left positive [m/s^2]: bank, steady crosswind */
+    KMPC_ROAD_DF_OFFSET = 4,   /* added to the actuator's tyre angle where the tyre model reads it [rad]: misalignment */
+    KMPC_ROAD_ACC_GAIN = 5,    /* the acceleration that acts is gain x the actuator state acc */
+                               /* words 6 and 7 are read by nobody */
+    KMPC_ROAD_WORDS = 8
+};
+/*   road_stat [B,4] fp64 DEVICE in/out, or NULL: accumulated over calls (the caller zeroes it), row of vehicle b: */
+enum {
+    KMPC_ROAD_STAT_SAT_F = 0,  /* sub-steps in which the front force was clipped */
+    KMPC_ROAD_STAT_SAT_R = 1,  /* the same for the rear */
+    KMPC_ROAD_STAT_UTIL_F = 2, /* the largest front utilisation |C_alpha_f alpha_f| / lim_f so far */
+    KMPC_ROAD_STAT_UTIL_R = 3, /* the same for the rear */
+    KMPC_ROAD_STAT_WORDS = 4
+};
+/* The neutral row is (inf, inf, 0, 0, 0, 1, 0, 0): kmpc_road_default writes it.
+ * Arithmetic: each sub-step is kmpc_sim_advance_queue's (that is kmpc_sim_advance_plant's), operation for operation, with these changes only
+ * (g = 9.81 as a literal; no product and sum are contracted into one rounding anywhere in the plant):
+ *   before the loop, once per call like 1 / m:
+ *       lim_f = MU_F * (m * 9.81 * lr / (lf + lr))        lim_r = MU_R * (m * 9.81 * lf / (lf + lr))         (mu x the static axle loads)
+ *   in the sub-step:
+ *       dfe  = df + DF_OFFSET      replaces df in alpha_f = dfe - atan2(vy + lf wz, vx), in cos(dfe), and in the range test fabs(dfe) <= 0.6 that
+ *                                  picks between the short polynomial and the library's cos
+ *       acce = ACC_GAIN * acc      replaces acc in vx's derivative
+ *       Fyf  = clip(C_alpha_f * alpha_f, lim_f),  Fyr = clip(C_alpha_r * alpha_r, lim_r)  with
+ *       clip(x, lim) = x > lim ? lim : (x < -lim ? -lim : x)     compare-and-select: inside the limit x keeps its own bits, and a NaN passes through
+ *                                                                 (fmin / fmax would swallow it)
+ *   the two specific forces enter as statements of their own, after the parent's expressions have been rounded as they are today:
+ *       vx0 = vx + deltaT * (acce + wz * vy);                                vx_n = fmax(0, vx0 + deltaT * A_LONG)
+ *       vy0 = vy + deltaT * (1/m * (Fyf * cos(dfe) + Fyr) - wz * vx);        vy_c = vy0 + deltaT * A_LAT
+ *     so a zero term adds nothing; the standstill rule (vy, wz = 0 unless vx_n > 1e-6) follows as before.  The actuator lags act on acc and df
+ *     themselves, not on acce and dfe.
+ *   bookkeeping: a sub-step counts as clipped at an axle when x > lim or x < -lim held there; the utilisation of a call is the largest |x| of its
+ *     sub-steps divided by lim (the same number as the largest |x| / lim: division by one positive limit is monotone; an infinite limit gives 0
+ *     by the division itself), and road_stat keeps  count + this call's count  and  the larger of its word and this call's utilisation (a NaN
+ *     utilisation is not larger).  road_stat is read and written once per call, after the last sub-step.
+ * The reference's two quirks stay: lf in the rear slip angle and no Fyf sin(df) / m term in vx.
+ * Not modelled: a longitudinal grip limit and combined slip (the solver's a_max is 1 m/s^2, far inside mu g for any mu worth sweeping), load
+ * transfer (the axle loads are the static ones), a limit that varies along the path, random gusts.  The rows are plain device memory: a caller
+ * who wants a wet patch edits `road` between periods.
+ * Contract: with the neutral row in every vehicle the call leaves the state that kmpc_sim_advance_queue leaves on the same arguments, bit for
+ * bit, and road_stat untouched (count + 0, and 0 is not larger).  A row cannot be checked from the host: a non-finite word, a mu <= 0 or a NaN
+ * anywhere poisons that vehicle's state or statistics alone -- one thread per vehicle, no lane reads another's row.  Validate rows where they
+ * are written (Python: vehicle_sim.road_params).
+ * Argument checks as kmpc_sim_advance_queue's, before any device call, and with B > 0 a NULL road returns KMPC_ERR_ARG (text in
+ * kmpc_last_error(NULL)); B == 0 or n_updates == 0 succeeds without a launch.  Asynchronous on `stream`. */
+int32_t kmpc_road_default(double *row8);   /* HOST: the neutral row (inf, inf, 0, 0, 0, 1, 0, 0); KMPC_ERR_ARG for NULL */
+int32_t kmpc_sim_advance_road(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const void *road,
+                              const int32_t *cmd_delay, void *cmd_queue, int32_t depth, int64_t period, int32_t n_updates, void *road_stat,
+                              void *stream);
+
 /* ---- measurement stage: what the controller sees of the plant ------------------------------------------------------------------------------
  * The reference's vehicle builds state_est from a GPS fix, an IMU yaw and the steering report's speed (scripts/state_publisher.py); its simulator
  * publishes the truth (vehicle_simulator.py:40-48).  kmpc_sense_batch puts additive Gaussian noise and a bias on the four channels the MPC reads.

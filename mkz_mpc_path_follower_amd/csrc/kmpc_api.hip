@@ -2,6 +2,7 @@
 // The library has no CPU fallback: every entry point that computes launches the HIP kernels
 // of kmpc_kernels.hip and fails with KMPC_ERR_NODEVICE / KMPC_ERR_HIP when it cannot.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -756,6 +757,33 @@ extern "C" int32_t kmpc_sim_advance_queue(int32_t device, int32_t B, void *state
     const hipError_t e = kmpc_launch_sim_queue(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_queue, depth,
                                                (long long)period, n_updates, (hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_queue: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+// the neutral road row: no grip limit, a flat and level road, no steering offset, the acceleration as commanded
+extern "C" int32_t kmpc_road_default(double *row8)
+{
+    if (!row8) return fail(nullptr, KMPC_ERR_ARG, "kmpc_road_default: null row");
+    row8[KMPC_ROAD_MU_F] = INFINITY; row8[KMPC_ROAD_MU_R] = INFINITY; row8[KMPC_ROAD_A_LONG] = 0.0; row8[KMPC_ROAD_A_LAT] = 0.0;
+    row8[KMPC_ROAD_DF_OFFSET] = 0.0; row8[KMPC_ROAD_ACC_GAIN] = 1.0; row8[6] = 0.0; row8[7] = 0.0;
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_sim_advance_road(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const void *road,
+                                         const int32_t *cmd_delay, void *cmd_queue, int32_t depth, int64_t period, int32_t n_updates, void *road_stat,
+                                         void *stream)
+{
+    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_road: bad argument (B=%d, n_updates=%d)", B, n_updates);
+    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_road: null plant rows");
+    if (B > 0 && !road) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_road: null road rows");
+    if (depth < 2 || period < 0 || !cmd_queue)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_road: bad queue (depth=%d, at least 2; period=%lld, at least 0; cmd_queue %s)", depth,
+                    (long long)period, cmd_queue ? "given" : "NULL");
+    if (B == 0 || n_updates == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_road: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_sim_road(B, (double *)state, (const double *)cmd, (const double *)plant, (const double *)road, cmd_delay,
+                                              (double *)cmd_queue, depth, (long long)period, n_updates, (double *)road_stat, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_road: %s", hipGetErrorString(e));
     return KMPC_OK;
 }
 

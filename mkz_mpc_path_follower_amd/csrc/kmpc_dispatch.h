@@ -100,6 +100,8 @@ hipError_t kmpc_launch_sim_queue(int B, double *state, const double *cmd, const 
                                  long long period, int n_updates, hipStream_t st);
 hipError_t kmpc_launch_sense_delayed(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base,
                                      const int32_t *meas_delay, double *truth_ring, int depth, double *est, hipStream_t st);
+hipError_t kmpc_launch_sim_road(int B, double *state, const double *cmd, const double *plant, const double *road, const int32_t *cmd_delay,
+                                double *cmd_queue, int depth, long long period, int n_updates, double *road_stat, hipStream_t st);
 // delay compensation (kmpc_latency.hip)
 hipError_t kmpc_launch_cmd_in_force(int B, const double *hist, int depth, long long period, int n, const int32_t *cmd_delay, const int32_t *meas_delay,
                                     int max_cmd_delay, int max_meas_delay, double *u_out, hipStream_t st);

@@ -390,6 +390,131 @@ hipError_t kmpc_launch_sim_queue(int B, double *state, const double *cmd, const 
     return hipGetLastError();
 }
 
+// Grip and road (kmpc_sim_advance_road): kmpc_sim_queue_kernel with a road row per vehicle, `road` [B,8] (KMPC_ROAD_*), kept in registers like the plant
+// row -- 64 B more read per vehicle and call.  The sub-step is a COPY of the queue kernel's, operation for operation, with the changes include/kmpc.h
+// lists: the tyre model reads dfe = df + DF_OFFSET, vx's derivative acce = ACC_GAIN * acc, each axle's force is clipped at mu times its static load
+// (compare-and-select: inside the limit the force keeps its own bits, a NaN passes), and the two specific forces are added in statements of their own
+// after the parent's expressions, so a neutral row (inf, inf, 0, 0, 0, 1) leaves the queue kernel's state bit for bit.
+// Grip bookkeeping: per axle the number of clipped sub-steps and the largest |C_alpha alpha| of the call stay in registers (4 VGPRs + 2 counters);
+// the utilisation is that maximum divided by the limit ONCE after the loop (a correctly rounded division by one positive number is monotone: the
+// quotient of the maximum is the maximum of the quotients, bit for bit), so the sub-step carries no division.  road_stat [B,4] is read and
+// written once, after the loop, and only when given.
+__global__ __launch_bounds__(256) void kmpc_sim_road_kernel(int B, double *__restrict__ state, const double *__restrict__ cmd,
+                                                            const double *__restrict__ plant, const double *__restrict__ road,
+                                                            const int32_t *__restrict__ cmd_delay, double *cmd_queue, int depth, long long period,
+                                                            int n_updates, double *__restrict__ road_stat)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const double *pr = plant + KMPC_PLANT_WORDS * (size_t)i;
+    const double lf = pr[KMPC_PLANT_LF], lr = pr[KMPC_PLANT_LR], m = pr[KMPC_PLANT_M], Iz = pr[KMPC_PLANT_IZ];
+    const double C_alpha_f = pr[KMPC_PLANT_C_ALPHA_F], C_alpha_r = pr[KMPC_PLANT_C_ALPHA_R];
+    const double k_acc = pr[KMPC_PLANT_K_ACC], k_df = pr[KMPC_PLANT_K_DF];
+    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;
+    const double *rr = road + KMPC_ROAD_WORDS * (size_t)i;
+    const double a_long = rr[KMPC_ROAD_A_LONG], a_lat = rr[KMPC_ROAD_A_LAT], df_offset = rr[KMPC_ROAD_DF_OFFSET], acc_gain = rr[KMPC_ROAD_ACC_GAIN];
+    const double lim_f = rr[KMPC_ROAD_MU_F] * (m * 9.81 * lr / (lf + lr));   // mu x the static axle loads, divided once per call
+    const double lim_r = rr[KMPC_ROAD_MU_R] * (m * 9.81 * lf / (lf + lr));
+    const double deltaT = 0.01 / 10.0;
+    const double pi = 3.141592653589793;
+    double *s = state + 8 * (size_t)i;
+    double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
+    const double acc_now = cmd[2 * (size_t)i], df_now = cmd[2 * (size_t)i + 1];
+    const size_t slot_words = 2 * (size_t)B;
+    {
+        double *own = cmd_queue + (size_t)(period % depth) * slot_words + 2 * (size_t)i;
+        own[0] = acc_now; own[1] = df_now;
+    }
+    int d = cmd_delay ? cmd_delay[i] : 0;
+    const long long dmax = (long long)(depth - 1) * n_updates;   // n_updates >= 1 here (the host returns before a launch otherwise)
+    d = d < 0 ? 0 : ((long long)d > dmax ? (int)dmax : d);
+    const int q = d / n_updates, r = d % n_updates;
+    double acc_new = acc_now, df_new = df_now, acc_old = 0.0, df_old = 0.0;
+    const long long jn = period - q, jo = jn - 1;
+    if (q > 0) {
+        acc_new = 0.0; df_new = 0.0;
+        if (jn >= 0) {
+            const double *e = cmd_queue + (size_t)(jn % depth) * slot_words + 2 * (size_t)i;
+            acc_new = e[0]; df_new = e[1];
+        }
+    }
+    if (r > 0 && jo >= 0) {
+        const double *e = cmd_queue + (size_t)(jo % depth) * slot_words + 2 * (size_t)i;
+        acc_old = e[0]; df_old = e[1];
+    }
+    int sat_f = 0, sat_r = 0;           // clipped sub-steps of this call
+    double peak_f = 0.0, peak_r = 0.0;  // largest |C_alpha alpha| of this call [N]
+    for (int up = 0; up < n_updates; ++up) {
+        const double acc_des = up < r ? acc_old : acc_new, df_des = up < r ? df_old : df_new;   // the target changes between updates only
+#pragma unroll 1
+        for (int it = 0; it < 10; ++it) {
+            const bool moving = fabs(vx) > 1e-6;
+            const double yf = vy + lf * wz, yr = vy - lf * wz;          // lf where lr is expected -- as in the reference
+            const double rvx = sim_rcp(vx);
+            const double tf = yf * rvx, tr = yr * rvx;
+            const double dfe = df + df_offset;                          // the tyre angle the tyre model reads
+            const double acce = acc_gain * acc;                         // the acceleration that acts
+            const bool in_range = (!moving || (vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) && fabs(dfe) <= 0.6 && fabs(psi) <= 4.0;
+            double af = sim_atan_poly(tf), ar = sim_atan_poly(tr), cd = sim_cos_poly(dfe * dfe), sp, cp;
+            sim_sincos_poly(psi, &sp, &cp);
+            if (__any(!in_range)) {
+                if (moving && !(vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) { af = atan2(yf, vx); ar = atan2(yr, vx); }
+                if (!(fabs(dfe) <= 0.6)) cd = cos(dfe);
+                if (!(fabs(psi) <= 4.0)) sincos(psi, &sp, &cp);
+            }
+            const double alpha_f = moving ? dfe - af : 0.0;
+            const double alpha_r = moving ? -ar : 0.0;
+            const double Ff = C_alpha_f * alpha_f, Fr = C_alpha_r * alpha_r;   // what the linear tyre asks for
+            const double Fyf = Ff > lim_f ? lim_f : (Ff < -lim_f ? -lim_f : Ff);
+            const double Fyr = Fr > lim_r ? lim_r : (Fr < -lim_r ? -lim_r : Fr);
+            sat_f += (Ff > lim_f || Ff < -lim_f) ? 1 : 0;
+            sat_r += (Fr > lim_r || Fr < -lim_r) ? 1 : 0;
+            peak_f = fabs(Ff) > peak_f ? fabs(Ff) : peak_f;
+            peak_r = fabs(Fr) > peak_r ? fabs(Fr) : peak_r;
+            const double vx0 = vx + deltaT * (acce + wz * vy);          // no Fyf * sin(df) / m term -- as in the reference
+            const double vx_n = fmax(0.0, vx0 + deltaT * a_long);
+            const bool fwd = vx_n > 1e-6;
+            const double vy0 = vy + deltaT * (inv_m * (Fyf * cd + Fyr) - wz * vx);
+            const double vy_c = vy0 + deltaT * a_lat;
+            const double wz_c = wz + deltaT * (inv_Iz * (lf * Fyf * cd - lr * Fyr));
+            const double vy_n = fwd ? vy_c : 0.0, wz_n = fwd ? wz_c : 0.0;
+            const double psi_n = psi + deltaT * wz;
+            const double X_n = X + deltaT * (vx * cp - vy * sp);
+            const double Y_n = Y + deltaT * (vx * sp + vy * cp);
+            X = X_n; Y = Y_n;
+            const double a = psi_n + pi, p2 = 2.0 * pi;
+            double md = a;
+            const bool wrap = !(a >= 0.0 && a < p2);
+            if (__any(wrap)) {
+                if (wrap) {
+                    md = fmod(a, p2);
+                    if (md < 0.0) md += p2;
+                }
+            }
+            psi = md - pi;
+            vx = vx_n; vy = vy_n; wz = wz_n;
+            acc = k_acc * (acc_des - acc) * deltaT + acc;
+            df = k_df * (df_des - df) * deltaT + df;
+        }
+    }
+    s[0] = X; s[1] = Y; s[2] = psi; s[3] = vx; s[4] = vy; s[5] = wz; s[6] = acc; s[7] = df;
+    if (road_stat) {
+        double *rs = road_stat + KMPC_ROAD_STAT_WORDS * (size_t)i;
+        const double c_f = rs[KMPC_ROAD_STAT_SAT_F], c_r = rs[KMPC_ROAD_STAT_SAT_R], u_f = rs[KMPC_ROAD_STAT_UTIL_F], u_r = rs[KMPC_ROAD_STAT_UTIL_R];
+        const double n_f = peak_f / lim_f, n_r = peak_r / lim_r;   // an infinite limit: 0 by the division itself
+        rs[KMPC_ROAD_STAT_SAT_F] = c_f + (double)sat_f; rs[KMPC_ROAD_STAT_SAT_R] = c_r + (double)sat_r;
+        rs[KMPC_ROAD_STAT_UTIL_F] = n_f > u_f ? n_f : u_f; rs[KMPC_ROAD_STAT_UTIL_R] = n_r > u_r ? n_r : u_r;
+    }
+}
+
+hipError_t kmpc_launch_sim_road(int B, double *state, const double *cmd, const double *plant, const double *road, const int32_t *cmd_delay,
+                                double *cmd_queue, int depth, long long period, int n_updates, double *road_stat, hipStream_t st)
+{
+    hipLaunchKernelGGL(kmpc_sim_road_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, state, cmd, plant, road, cmd_delay, cmd_queue, depth, period,
+                       n_updates, road_stat);
+    return hipGetLastError();
+}
+
 // Stale fixes (kmpc_sense_delayed_batch): kmpc_sense_kernel measuring the truth of period - L instead of this period's.  This period's x, y, psi, vx go
 // into slot period mod depth of truth_ring [depth,B,4] (consecutive lanes write consecutive 32 B) and the measured truth comes out of slot
 // (period - L) mod depth, L = clamp(meas_delay, 0, min(depth - 1, period)); bias and noise are this period's (counter = (vehicle id, period)): noise

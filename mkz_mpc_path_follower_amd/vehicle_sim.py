@@ -12,6 +12,10 @@ Latency: `VehicleSimulator(cmd_queue_depth=D)` keeps the last D periods' command
 `SensorModel(meas_delay=, depth=)` measures the truth of an earlier period (kmpc_sense_delayed_batch); `LatencyCompensator` is the controller's
 answer: a log of the commands sent and assumed delays of its own, from which it picks the filter's input and predicts the estimate ahead to the
 moment the next command acts (kmpc_cmd_in_force_batch, kmpc_predict_ahead_batch).
+
+Grip and road: `VehicleSimulator(road=road_params(B, mu=0.5, a_lat=1.5, ...))` gives every vehicle a road row -- friction limits per axle, specific
+forces of grade and bank, a steering offset, an acceleration gain (kmpc_sim_advance_road) -- and counts, per vehicle and axle, the sub-steps in
+which the tyre force was clipped (`road_stat`, `road_summary()`).  The neutral row computes what the command-queue plant computes, bit for bit.
 """
 import ctypes as C
 
@@ -25,6 +29,7 @@ X0, Y0, PSI0 = -300.0, -450.0, 1.0  # vehicle_simulator.py:28-30 (rosparam defau
 
 PLANT_FIELDS = ("lf", "lr", "m", "Iz", "C_alpha_f", "C_alpha_r", "k_acc", "k_df")   # KMPC_PLANT_* of include/kmpc.h, in row order
 SENSOR_FIELDS = ("sigma_x", "sigma_y", "sigma_psi", "sigma_v", "bias_x", "bias_y", "bias_psi", "bias_v")   # KMPC_SENSOR_*
+ROAD_FIELDS = ("mu_f", "mu_r", "a_long", "a_lat", "df_offset", "acc_gain")   # KMPC_ROAD_* words 0 ... 5, in row order (6 and 7 are read by nobody)
 ESTIMATOR_FIELDS = ("x", "y", "psi", "v", "pxx", "pxy", "pxpsi", "pxv", "pyy", "pypsi", "pyv", "ppsipsi", "ppsiv", "pvv", "count", "skipped")   # KMPC_EST_*
 ESTIMATOR_PARAM_FIELDS = ("q_x", "q_y", "q_psi", "q_v", "r_x", "r_y", "r_psi", "r_v")   # KMPC_ESTPAR_*
 EST_SKIP_X, EST_SKIP_Y, EST_SKIP_PSI, EST_SKIP_V, EST_INIT, EST_RESET = 1, 2, 4, 8, 16, 32   # KMPC_EST_FLAG_*
@@ -81,17 +86,70 @@ def plant_params(B, device=0, **overrides):
     return torch.as_tensor(check_plant_rows(rows)).to(_device(device))
 
 
+def road_default():
+    """the neutral road row (inf, inf, 0, 0, 0, 1, 0, 0) as a numpy row [8], from kmpc_road_default"""
+    row = np.zeros(8)
+    _lib.check(_lib.load().kmpc_road_default(row.ctypes.data_as(C.POINTER(C.c_double))))
+    return row
+
+
+def check_road_rows(rows):
+    """[B,8] host rows -> ValueError unless no word is NaN, mu_f, mu_r > 0 (+inf: no limit), every other word is finite and acc_gain > 0 (the
+    kernel cannot refuse a row: a bad one poisons that vehicle)"""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 8:
+        raise ValueError("road rows: [B,8] (%s, two unused words), got %s" % (", ".join(ROAD_FIELDS), rows.shape))
+    if np.isnan(rows).any():
+        raise ValueError("road rows: NaN in vehicle(s) %s" % np.flatnonzero(np.isnan(rows).any(1))[:8].tolist())
+    if not (rows[:, 0:2] > 0.0).all():
+        raise ValueError("road rows: mu_f, mu_r must be > 0 (+inf: no limit) (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 0:2] > 0.0).all(1))[:8].tolist())
+    if not np.isfinite(rows[:, 2:8]).all():
+        raise ValueError("road rows: only mu_f, mu_r may be infinite (vehicle(s) %s)" % np.flatnonzero(~np.isfinite(rows[:, 2:8]).all(1))[:8].tolist())
+    if not (rows[:, 5] > 0.0).all():
+        raise ValueError("road rows: acc_gain must be > 0 (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 5] > 0.0))[:8].tolist())
+    return rows
+
+
+def road_params(B, device=0, **overrides):
+    """[B,8] float64 road rows on `device`: the neutral row, with each override (`mu=` for both axles, `mu_f=`, `mu_r=`, `a_long=`, `a_lat=`,
+    `df_offset=`, `acc_gain=`) a scalar or one value per vehicle.  Validated on the host (check_road_rows) before anything reaches the device."""
+    rows = np.tile(road_default(), (int(B), 1))
+    for k, v in overrides.items():
+        if k != "mu" and k not in ROAD_FIELDS:
+            raise ValueError("road_params: unknown parameter %r (mu or one of %s)" % (k, ", ".join(ROAD_FIELDS)))
+        if k == "mu" and ("mu_f" in overrides or "mu_r" in overrides):
+            raise ValueError("road_params: mu= sets both axles; give mu_f= and mu_r= instead of combining them with it")
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
+            raise ValueError("road_params: %s is a scalar or one value per vehicle [%d], got %s" % (k, B, v.shape))
+        for w in ((0, 1) if k == "mu" else (ROAD_FIELDS.index(k),)):
+            rows[:, w] = v
+    return torch.as_tensor(check_road_rows(rows)).to(_device(device))
+
+
 class VehicleSimulator:
     dt_model = 0.01  # :24
 
-    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None, cmd_queue_depth=None):
+    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None, cmd_queue_depth=None, road=None):
         """plant: [B,8] rows (plant_params) -- a plant per vehicle; cmd_delay: a scalar or one per vehicle, model updates of 10 ms by which a new
         command takes effect late (clamped to one call's n_updates; the command in force until then is `cmd_held`, 0 at the start).  Giving
         either runs kmpc_sim_advance_plant (the other defaults to the reference's constants / no delay); `plant`, `cmd_delay` (int32 [B]) and
         `cmd_held` [B,2] are then plain device tensors the caller may edit between steps.  Giving neither changes nothing.
         cmd_queue_depth=D (an integer >= 2): a ring `cmd_queue` [D,B,2] of the last D periods' commands replaces `cmd_held`
         (kmpc_sim_advance_queue), so that cmd_delay may exceed one call: it is clamped to (D - 1) n_updates.  The simulator then counts its calls
-        in `period` (slot period mod D holds that call's command); every call of a run must use the same n_updates."""
+        in `period` (slot period mod D holds that call's command); every call of a run must use the same n_updates.
+        road: [B,8] rows (road_params) -- grip limits, grade, bank, steering offset and acceleration gain per vehicle (kmpc_sim_advance_road).  It
+        implies the queue path (cmd_queue_depth defaults to 2, which equals the held-command plant call after call) and allocates `road_stat` [B,4];
+        `road` and `road_stat` are plain device tensors the caller may edit between steps (a wet patch: write `road` between periods), and
+        road_summary() downloads the grip bookkeeping."""
+        road_rows = None
+        if road is not None:   # checked before the GPU is touched, like the depth
+            road_rows = road.detach().cpu().numpy() if isinstance(road, torch.Tensor) else road
+            if np.shape(road_rows) != (int(B), 8):
+                raise ValueError("road: [%d,8] rows (road_params), got %s" % (int(B), np.shape(road_rows)))
+            road_rows = check_road_rows(road_rows)
+            if cmd_queue_depth is None:
+                cmd_queue_depth = 2
         self.cmd_queue_depth = None
         if cmd_queue_depth is not None:   # checked first: a bad depth is a ValueError on any machine
             if isinstance(cmd_queue_depth, bool) or not isinstance(cmd_queue_depth, (int, np.integer)) or cmd_queue_depth < 2:
@@ -108,7 +166,7 @@ class VehicleSimulator:
         self.state[:, 1] = torch.as_tensor(Y0, dtype=torch.float64, device=self.device)
         self.state[:, 2] = torch.as_tensor(Psi0, dtype=torch.float64, device=self.device)
         self.cmd = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)  # acc_des, df_des (:21-22)
-        self.plant = self.cmd_delay = self.cmd_held = self.cmd_queue = None
+        self.plant = self.cmd_delay = self.cmd_held = self.cmd_queue = self.road = self.road_stat = None
         self.period = 0
         if plant is not None or cmd_delay is not None or cmd_queue_depth is not None:
             if plant is None:
@@ -126,6 +184,9 @@ class VehicleSimulator:
                 self.cmd_held = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
             else:
                 self.cmd_queue = torch.zeros((self.cmd_queue_depth, self.B, 2), dtype=torch.float64, device=self.device)
+            if road_rows is not None:
+                self.road = torch.as_tensor(road_rows).to(self.device).contiguous()
+                self.road_stat = torch.zeros((self.B, 4), dtype=torch.float64, device=self.device)
 
     # views named as in the reference
     X = property(lambda s: s.state[:, 0]); Y = property(lambda s: s.state[:, 1]); psi = property(lambda s: s.state[:, 2])
@@ -152,9 +213,20 @@ class VehicleSimulator:
                 if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
                     raise ValueError("plant [B,8] / cmd_queue [D,B,2] float64 and cmd_delay [B] int32 must stay contiguous tensors on %s "
                                      "(write into them with copy_)" % self.device)
-            rc = self._lib.kmpc_sim_advance_queue(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
-                                                  C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
-                                                  C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth, int(self.period), int(n_updates), stream)
+            if self.road is not None:
+                for t, w in ((self.road, 8), (self.road_stat, 4)):
+                    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous()
+                            and t.device == self.device):
+                        raise ValueError("road [B,8] / road_stat [B,4] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
+                rc = self._lib.kmpc_sim_advance_road(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
+                                                     C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.road.data_ptr()),
+                                                     C.c_void_p(self.cmd_delay.data_ptr()), C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth,
+                                                     int(self.period), int(n_updates), C.c_void_p(self.road_stat.data_ptr()), stream)
+            else:
+                rc = self._lib.kmpc_sim_advance_queue(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
+                                                      C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
+                                                      C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth, int(self.period), int(n_updates),
+                                                      stream)
             if rc == 0 and int(n_updates) > 0:
                 self.period += 1
         else:
@@ -166,6 +238,14 @@ class VehicleSimulator:
                                                   C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
                                                   C.c_void_p(self.cmd_held.data_ptr()), int(n_updates), stream)
         _lib.check(rc)
+
+    def road_summary(self):
+        """the grip bookkeeping so far, one download -> dict of numpy arrays [B]: sat_f, sat_r (sub-steps in which the front / rear force was
+        clipped) and util_f, util_r (the largest |C_alpha alpha| / limit); None without road="""
+        if self.road_stat is None:
+            return None
+        st = self.road_stat.detach().cpu().numpy()
+        return dict(sat_f=st[:, 0].astype(np.int64), sat_r=st[:, 1].astype(np.int64), util_f=st[:, 2].copy(), util_r=st[:, 3].copy())
 
     def state_est(self, i=0):
         """the state_est message of vehicle i (:40-48)"""

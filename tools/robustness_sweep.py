@@ -13,8 +13,13 @@ tests/golden at 6 m/s (target-velocity mode, N = 8, the node's weights), startin
 updates x age of the fix (0, 1, 2) periods, each cell once as it is and once with vehicle_sim.LatencyCompensator assuming the true delays
 (the estimator fed from the command log, the estimate predicted ahead to where the command acts).
 
+--road is a sweep of its own too (-> profiles/robustness_sweep_road.txt): nominal plant, no noise, no delay, the truth fed to the controller; the
+road row of vehicle_sim.road_params per vehicle: friction coefficient (inf, 1.0, 0.7, 0.5, 0.35, 0.25) on both axles x target speed (6, 8) m/s x
+lateral specific force (0, 0.75, 1.5) m/s^2 (bank) x steering offset (0, 0.015, 0.03) rad.
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
        python tools/robustness_sweep.py --latency [out.txt] [steps]
+       python tools/robustness_sweep.py --road [out.txt] [steps]
 """
 import itertools
 import os
@@ -29,6 +34,7 @@ sys.path.insert(0, ROOT)
 from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
 from mkz_mpc_path_follower_amd.ref_traj import FleetRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import Estimator, LatencyCompensator, SensorModel, VehicleSimulator, plant_default, plant_params  # noqa: E402
+from mkz_mpc_path_follower_amd.vehicle_sim import road_params  # noqa: E402
 
 MASS, STIFF, SIGMA, DELAY = (0.85, 1.0, 1.15, 1.3), (0.6, 0.8, 1.0, 1.2), (0.0, 0.1, 0.2, 0.5), (0, 2, 4, 8)
 PER_CELL, VT = 16, 6.0
@@ -163,8 +169,73 @@ def latency_main():
             f.write("\n".join(LINES) + "\n")
 
 
+ROAD_MU, ROAD_VT, ROAD_LAT, ROAD_OFFSET, ROAD_PER_CELL = (float("inf"), 1.0, 0.7, 0.5, 0.35, 0.25), (6.0, 8.0), (0.0, 0.75, 1.5), (0.0, 0.015, 0.03), 48
+
+
+def road_main():
+    """one loop of 6 x 2 x 3 x 3 cells of 48 vehicles, each cell the same 48 starts: on the path, heading along it, already at the cell's speed"""
+    argv = [a for a in sys.argv if a != "--road"]
+    steps = int(argv[2]) if len(argv) > 2 else 150
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    cells = list(itertools.product(range(6), range(2), range(3), range(3)))
+    B = len(cells) * ROAD_PER_CELL
+    cell = np.repeat(np.arange(len(cells)), ROAD_PER_CELL)
+    ix = np.array(cells)[cell]                      # [B,4] grid indices: mu, speed, lateral force, steering offset
+    rng = np.random.default_rng(0)
+    pid = np.tile(np.arange(ROAD_PER_CELL) % 3, len(cells))
+    fleet = FleetRefTrajectory(paths, pid, traj_horizon=8, traj_dt=0.2)
+    frac = np.tile(rng.uniform(0.02, 0.45, ROAD_PER_CELL), len(cells))
+    pose = np.empty((B, 3))
+    for b in range(B):
+        tr = fleet.trajectories[pid[b]]
+        i = int(frac[b] * len(tr))
+        pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+    vt = np.array(ROAD_VT)[ix[:, 1]]
+    sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2],
+                           road=road_params(B, mu=np.array(ROAD_MU)[ix[:, 0]], a_lat=np.array(ROAD_LAT)[ix[:, 2]], df_offset=np.array(ROAD_OFFSET)[ix[:, 3]]))
+    sim.state[:, 3] = torch.as_tensor(vt, device=sim.device)
+    loop = ClosedLoop(fleet, sim, N=8, target_vel=vt)
+    loop.run(steps)
+    s, grip = loop.score_summary(), sim.road_summary()
+    slid = (grip["sat_f"] + grip["sat_r"]) > 0
+    finite = bool(torch.isfinite(sim.state).all().item())
+    say("%s: %d vehicles, %d periods of 0.1 s on three paths, nominal plant, no noise, no delay; every state finite: %s; latched vehicles: %d"
+        % (torch.cuda.get_device_name(0), B, steps, finite, int((s["latch_index"] >= 0).sum())))
+    head = "median / 95th percentile of rms e_ct [m], largest |e_ct| [m], share of vehicles that ever saturated [%], periods not Optimal per 1000"
+
+    def row(label, sel):
+        say("   %-44s %7.3f %7.3f %8.3f %7.1f %8.2f" % (label, np.median(s["rms_ect"][sel]), np.percentile(s["rms_ect"][sel], 95), s["max_ect"][sel].max(),
+                                                        100.0 * slid[sel].mean(), 1000.0 * s["n_nonopt"][sel].sum() / max(1, s["n_live"][sel].sum())))
+    say("per factor level, over all other factors: " + head)
+    for f, (name, levels, fmt) in enumerate((("mu", ROAD_MU, "%.2f"), ("target speed [m/s]", ROAD_VT, "%.0f"), ("lateral force [m/s^2]", ROAD_LAT, "%.2f"),
+                                             ("steering offset [rad]", ROAD_OFFSET, "%.3f"))):
+        for lv in range(len(levels)):
+            row("%s %s" % (name, fmt % levels[lv]), ix[:, f] == lv)
+    say("mu x target speed on a level road without offset (%d vehicles per line): " % ROAD_PER_CELL + head)
+    for v in range(2):
+        for m in range(6):
+            row("mu %.2f at %.0f m/s" % (ROAD_MU[m], ROAD_VT[v]), (ix[:, 0] == m) & (ix[:, 1] == v) & (ix[:, 2] == 0) & (ix[:, 3] == 0))
+    say("lateral force x steering offset without a grip limit, both speeds (%d vehicles per line): " % (2 * ROAD_PER_CELL) + head)
+    for a in range(3):
+        for o in range(3):
+            row("%.2f m/s^2, %.3f rad" % (ROAD_LAT[a], ROAD_OFFSET[o]), (ix[:, 0] == 0) & (ix[:, 2] == a) & (ix[:, 3] == o))
+    say("largest utilisation |C_alpha alpha| / limit, median per mu at 6 and 8 m/s (level road, no offset), front / rear")
+    for m in range(1, 6):
+        sel = [(ix[:, 0] == m) & (ix[:, 1] == v) & (ix[:, 2] == 0) & (ix[:, 3] == 0) for v in range(2)]
+        say("   mu %.2f   %6.2f / %-6.2f   %6.2f / %-6.2f" % (ROAD_MU[m], np.median(grip["util_f"][sel[0]]), np.median(grip["util_r"][sel[0]]),
+                                                           np.median(grip["util_f"][sel[1]]), np.median(grip["util_r"][sel[1]])))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 if __name__ == "__main__":
-    if "--latency" in sys.argv[1:]:
+    if "--road" in sys.argv[1:]:
+        road_main()
+    elif "--latency" in sys.argv[1:]:
         latency_main()
     else:
         main()
