@@ -601,6 +601,86 @@ enum {   /* flags_out bits */
 int32_t kmpc_estimate_batch(int32_t device, int32_t B, void *rec, const void *z, const void *u, int32_t u_stride, const void *params, double dt,
                             double L_a, double L_b, double gate, void *est_out, void *innov_out, int32_t *flags_out, void *stream);
 
+/* ---- disturbance observer and command offset: offset-free closed loops -----------------------------------------------------------------------
+ * A bank, a steering offset or a grade is a CONSTANT error of the solver's model; kmpc_estimate_batch trusts that model and is dragged along.
+ * kmpc_observe_batch is kmpc_estimate_batch's filter on the model augmented with three constant disturbances, seven states
+ *   xh = (x, y, psi, v, dpsi, ddelta, da):  dpsi  the course offset [rad]: direction of travel - heading - beta (crab angle under bank, yaw-sensor bias)
+ *                                           ddelta the steering offset [rad], added to the input d_f
+ *                                           da    the acceleration offset [m/s^2], added to the input acc (grade; gain error at steady state)
+ * and kmpc_cmd_offset_batch subtracts the two input disturbances from the command on its way to the plant.  No solve kernel is involved: the
+ * correction enters through est_out (the state waypoints, fit and solve read) and through the command.
+ *   rec [B,40] fp64 DEVICE in/out, 320 bytes per vehicle, record of vehicle b: */
+enum {
+    KMPC_OBS_X = 0, KMPC_OBS_Y = 1, KMPC_OBS_PSI = 2, KMPC_OBS_V = 3,   /* as KMPC_EST_X ... KMPC_EST_V */
+    KMPC_OBS_DPSI = 4, KMPC_OBS_DDELTA = 5, KMPC_OBS_DA = 6,            /* the disturbance estimates */
+    KMPC_OBS_P = 7,            /* words 7 ... 34: upper triangle of the 7 x 7 covariance, row-major: P_ij (i <= j) at 7 + 7 i - i (i - 1) / 2 + (j - i) */
+    KMPC_OBS_COUNT = 35,       /* calls that updated the record; 0 = fresh */
+    KMPC_OBS_SKIPPED = 36,     /* channel measurements skipped so far */
+                               /* words 37 ... 39 are written 0 and read by nobody */
+    KMPC_OBS_WORDS = 40
+};
+/*   A fresh record is all zeros (hipMemset); word 35 == 0 is what makes it fresh.
+ *   params [B,16] fp64 DEVICE, row of vehicle b: standard deviations, squared by the kernel (q2_i = q_i * q_i, r2_c = r_c * r_c, p02 = p0 * p0) */
+enum {
+    KMPC_OBSPAR_Q_X = 0, KMPC_OBSPAR_Q_Y = 1, KMPC_OBSPAR_Q_PSI = 2, KMPC_OBSPAR_Q_V = 3,   /* process noise per call [m, m, rad, m/s] */
+    KMPC_OBSPAR_Q_DPSI = 4, KMPC_OBSPAR_Q_DDELTA = 5, KMPC_OBSPAR_Q_DA = 6,                 /* random walk of the disturbances per call */
+    KMPC_OBSPAR_R_X = 7, KMPC_OBSPAR_R_Y = 8, KMPC_OBSPAR_R_PSI = 9, KMPC_OBSPAR_R_V = 10,  /* measurement noise [m, m, rad, m/s] */
+    KMPC_OBSPAR_P0_DPSI = 11, KMPC_OBSPAR_P0_DDELTA = 12, KMPC_OBSPAR_P0_DA = 13,           /* initial standard deviation of the disturbances */
+                               /* words 14 and 15 are read by nobody */
+    KMPC_OBSPAR_WORDS = 16
+};
+/*   z, u, u_stride, dt, L_a, L_b, gate, innov_out, flags_out (KMPC_EST_FLAG_* bits, same values): exactly as in kmpc_estimate_batch.  u is what
+ *     the ACTUATORS got (sim.state + 6, stride 8) or the command as sent, after kmpc_cmd_offset_batch: then "input + d" is what acted.
+ *   v_min >= 0 [m/s]: below it dpsi and ddelta are frozen (see PREDICT)       psi_cap >= 0 [rad]: cap on the course offset handed to the solver
+ *   est_out [B,4] fp64 DEVICE out (may be z itself) = (x, y, wrap(psi + clip(dpsi, psi_cap)), v): the heading the solver's model needs to travel
+ *     where the vehicle travels; psi_cap = 0 gives psi itself.  clip(a, cap) = a > cap ? cap : (a < -cap ? -cap : a), compare-and-select as the
+ *     road kernel's.            dist_out [B,3] fp64 DEVICE out or NULL = dpsi, ddelta, da (0, 0, 0 when the record leaves the call fresh)
+ * Arithmetic: kmpc_estimate_batch's, operation for operation, with every new term APPENDED after the terms stated there; every operation rounded
+ * on its own, sums left to right, the same wrap.  Indices: 0 x, 1 y, 2 psi, 3 v, 4 dpsi, 5 ddelta, 6 da.
+ *   FIRST CALL (word 35 == 0): no predict.  All four z finite: xh = (z, 0, 0, 0), P = diag(r2_x, r2_y, r2_psi, r2_v, p02_dpsi, p02_ddelta, p02_da)
+ *     (off-diagonals 0), word 35 = 1, word 36 = 0, est_out = z bit for bit, dist_out = 0, innov_out = 0, flags = INIT.  Otherwise the record is
+ *     written as all zeros, est_out = z, dist_out = 0, innov_out = 0 and flags carries bit c for every non-finite z_c.
+ *   PREDICT  (psi, v, dpsi, ddelta, da: before the step)
+ *     de = d_f + ddelta;  t = tan(de);  k = L_b / (L_a + L_b);  beta = atan(k * t);  sb = sin(beta);  cb = cos(beta)
+ *     th = (psi + dpsi) + beta;  s = sin(th), c = cos(th)
+ *     bp = k * (1 + t * t) / (1 + (k * t) * (k * t))                                                       (d beta / d de)
+ *     F = I + {F_x,psi = -(dt * (v * s)), F_x,v = dt * c, F_y,psi = dt * (v * c), F_y,v = dt * s, F_psi,v = dt * (sb / L_b),      (the estimator's)
+ *              F_x,dpsi = F_x,psi, F_y,dpsi = F_y,psi, F_x,ddelta = F_x,psi * bp, F_y,ddelta = F_y,psi * bp,
+ *              F_psi,ddelta = dt * (v / L_b * (cb * bp)), F_v,da = dt}
+ *     x += dt * (v * c);  y += dt * (v * s);  psi = wrap(psi + dt * (v / L_b * sb));  v = v + dt * (acc + da), 0 when that is < 0;
+ *     dpsi, ddelta, da unchanged
+ *     A = F P, rows x, y, psi, v (rows 4 ... 6 of F are identity: A_ij = P_ij there):
+ *       A_ij = P_ij + sum over k = psi, v, dpsi, ddelta, da, in this order, of F_i,k * P_k,j, the terms F has in row i only
+ *     P_ij = A_ij + sum over k = psi, v, dpsi, ddelta, da, in this order, of F_j,k * A_i,k, the terms F has in row j only, for i <= j <= 3;
+ *     P_ij = A_ij for j >= 4;  then P_ii += q2_i last, i = 0 ... 6 -- except that q2_dpsi and q2_ddelta are NOT added when v (before the step) is
+ *     < v_min: neither is observable at rest, and P must not grow without bound at a stop line.  The lower triangle is never formed.
+ *   UPDATE, channels c = x, y, psi, v as in kmpc_estimate_batch (nu, S, the skip rules, innov_out_c), over seven states:
+ *     K_i = P_ic / S;  xh_i += K_i * nu;  P_ij -= K_i * P_cj for i <= j, i, j = 0 ... 6 (P_ic, P_cj before this channel).
+ *     After v: psi = wrap(psi); v = 0 when v < 0; word 35 += 1.
+ *   CONTAINMENT as kmpc_estimate_batch's, over words 0 ... 36: a record that holds or produces a non-finite word is written as all zeros,
+ *     est_out = z, dist_out = 0, innov_out = 0, flags = the skipped bits | RESET.  One thread per vehicle: it costs that vehicle alone.
+ * Contract: with p0 = q_dpsi = q_ddelta = q_da = 0 the disturbances and their covariance words stay 0 and every appended term is a product with 0:
+ *   words 0 ... 3, the ten words of the 4 x 4 block of P, est_out (any psi_cap), innov_out, flags and both counters equal kmpc_estimate_batch's
+ *   on the same inputs AS NUMBERS (a -0 may become +0), call after call.
+ * Argument checks before any device call: kmpc_estimate_batch's, and v_min or psi_cap not finite and >= 0 return KMPC_ERR_ARG; with B > 0 a NULL
+ * rec, z, u, params or est_out returns KMPC_ERR_ARG (text in kmpc_last_error(NULL)); B == 0 succeeds without a launch.  Asynchronous on `stream`.
+ * Row contents cannot be checked from the host (Python: vehicle_sim.DisturbanceObserver validates them: finite, q, q_dist, p0 >= 0, r > 0). */
+int32_t kmpc_observe_batch(int32_t device, int32_t B, void *rec, const void *z, const void *u, int32_t u_stride, const void *params, double dt,
+                           double L_a, double L_b, double gate, double v_min, double psi_cap, void *est_out, void *dist_out, void *innov_out,
+                           int32_t *flags_out, void *stream);
+
+/* kmpc_cmd_offset_batch: between kmpc_command_batch and the plant, in place on cmd [B,2] fp64 DEVICE (accel, steer).
+ *   rec [B,40]: kmpc_observe_batch's records, read only (words 5, 6 and 35)      stop_latch [B] uint8 DEVICE or NULL (= none latched)
+ *   acc_cap, df_cap >= 0: caps on the two corrections [m/s^2, rad]
+ * Per vehicle: ca = clip(da, acc_cap), cd = clip(ddelta, df_cap) (compare-and-select, as above); acc = acc - ca when ca != 0, steer = steer - cd
+ * when cd != 0 -- a zero correction leaves the word's bits, so caps of 0 leave cmd as it is.  Skipped, cmd[b] untouched: a latched vehicle (its
+ * command is the brake override, not the solver's), a fresh record (word 35 == 0), a non-finite da or ddelta.  The solver's rate-limit anchor
+ * u_prev is kmpc_command_batch's and stays the solver's own command.
+ * Argument checks before any device call: B < 0, a cap not finite and >= 0, with B > 0 a NULL rec or cmd return KMPC_ERR_ARG; B == 0 succeeds
+ * without a launch.  Asynchronous on `stream`. */
+int32_t kmpc_cmd_offset_batch(int32_t device, int32_t B, const void *rec, const uint8_t *stop_latch, double acc_cap, double df_cap, void *cmd,
+                              void *stream);
+
 /* ---- command stage of the node's loop, for B vehicles (scripts/mpc_cmd_pub.jl) --------------------------------------
  * What the loop does between solve_model() and the publish: the waypoint helper's stop flag latches (:100-103); a latched vehicle is
  * commanded accel -1.0 / steer 0.0 (:148-153) and keeps its rate-limit anchor; every other vehicle publishes the solver's first input

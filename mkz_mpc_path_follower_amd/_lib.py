@@ -38,7 +38,7 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_track_score_init", "kmpc_track_score_batch", "kmpc_track_score_fleet",
            "kmpc_plant_default", "kmpc_sim_advance_plant", "kmpc_sense_batch", "kmpc_estimate_batch",
            "kmpc_sim_advance_queue", "kmpc_sense_delayed_batch", "kmpc_cmd_in_force_batch", "kmpc_predict_ahead_batch",
-           "kmpc_road_default", "kmpc_sim_advance_road"]
+           "kmpc_road_default", "kmpc_sim_advance_road", "kmpc_observe_batch", "kmpc_cmd_offset_batch"]
 
 _lib = None
 
@@ -91,6 +91,8 @@ def load():
     L.kmpc_sim_advance_plant.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, vp]
     L.kmpc_sense_batch.argtypes = [i32, i32, vp, vp, C.c_uint64, C.c_int64, C.c_int64, vp, vp]
     L.kmpc_estimate_batch.argtypes = [i32, i32, vp, vp, vp, i32, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    L.kmpc_observe_batch.argtypes = [i32, i32, vp, vp, vp, i32, vp] + [C.c_double] * 6 + [vp, vp, vp, vp, vp]
+    L.kmpc_cmd_offset_batch.argtypes = [i32, i32, vp, vp, C.c_double, C.c_double, vp, vp]
     L.kmpc_sim_advance_queue.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, C.c_int64, i32, vp]
     L.kmpc_road_default.argtypes = [dp]
     L.kmpc_sim_advance_road.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, C.c_int64, i32, vp, vp]

@@ -28,6 +28,12 @@ or the truth without a sensor) and the controller.  Waypoints, fit and solve the
 "command", the command sent in the previous period (`sim.cmd` before this period's command stage overwrites it).  The estimator's `dt` must be the
 control period (plant_updates x 10 ms) and its L_a, L_b the solver's.  Without an estimator nothing changes.
 
+Offset-free loops: `observer=vehicle_sim.DisturbanceObserver(...)` takes the estimator's place in the period -- waypoints, fit and solve read its
+`loop.est_filt` [B,4] (the heading shifted by the estimated course offset), `loop.dist` [B,3] is the estimate of (dpsi, ddelta, da) -- and its
+`offset()` runs between the command stage and the plant, in place on `sim.cmd`: the plant (and `estimator_input="command"`) sees the corrected
+command, the solver's rate-limit anchor `u_prev` stays the solver's own.  `observer=` together with `estimator=` or `compensator=` is refused.
+Without an observer the loops run the code they ran before.
+
 Latency: the plant's command queue and the sensor's stale fixes belong to the simulator and the sensor (VehicleSimulator(cmd_queue_depth=),
 SensorModel(meas_delay=)).  `compensator=vehicle_sim.LatencyCompensator(...)` is the controller's side: the period's state passes
 sense -> filter -> compensator.predict and becomes `loop.est_pred` [B,4], the state at the update from which this period's command will act (under the
@@ -73,7 +79,14 @@ class _ScoredLoop:
         self.sensor = sensor
         self.est = None   # [B,4] x, y, psi, v as sensed in the last period (sensor given)
 
-    def _init_estimator(self, estimator, estimator_input, compensator=None):
+    def _init_estimator(self, estimator, estimator_input, compensator=None, observer=None):
+        if observer is not None:
+            if estimator is not None or compensator is not None:
+                raise ValueError("observer= takes the estimator's place and has no prediction ahead yet: give neither estimator= nor compensator=")
+            if observer.B != self.B or observer.device != self.sim.device:
+                raise ValueError("observer for %d vehicles on %s, plant with %d on %s" % (observer.B, observer.device, self.B, self.sim.device))
+        self.observer = observer
+        self.dist = None       # [B,3] the estimated dpsi, ddelta, da of the last period (observer given): the observer's own tensor
         if estimator_input not in ("actuator", "command", "history"):
             raise ValueError("estimator_input: 'actuator', 'command' or 'history', got %r" % (estimator_input,))
         if estimator_input == "history" and compensator is None:
@@ -95,6 +108,10 @@ class _ScoredLoop:
             u = self._u_hist = self.compensator.filter_input(self.k, out=self._u_hist)
         else:
             u = self.sim.state[:, 6:8] if self.estimator_input == "actuator" else self.sim.cmd
+        if self.observer is not None:
+            self.est_filt = self.observer.update(z, u, out=self.est_filt)
+            self.dist = self.observer.dist
+            return self.est_filt
         self.est_filt = self.estimator.update(z, u, out=self.est_filt)
         return self.est_filt
 
@@ -131,7 +148,7 @@ class _ScoredLoop:
         period's new state is scored with that period's status, iters, command and stop latch.  history=True also records, on the device,
         state [steps+1,B,8] (the state before the first period first), cmd [steps,B,2], status [steps,B], latch [steps,B] and, with a sensor, est [steps,B,4]
         (what was measured of state[j] in period j: what the controller saw, unless an estimator follows) and, with an estimator, est_filt [steps,B,4]
-        (what the controller saw then, unless a compensator follows) and, with a compensator, est_pred [steps,B,4] (what the controller saw then).
+        (what the controller saw then, unless a compensator follows; an observer's est_filt likewise, with dist [steps,B,3]) and, with a compensator, est_pred [steps,B,4] (what the controller saw then).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -146,8 +163,10 @@ class _ScoredLoop:
                         latch=torch.empty((steps, self.B), dtype=torch.bool, device=dev))
             if self.sensor is not None:
                 hist["est"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
-            if self.estimator is not None:
+            if self.estimator is not None or self.observer is not None:
                 hist["est_filt"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
+            if self.observer is not None:
+                hist["dist"] = torch.empty((steps, self.B, 3), dtype=torch.float64, device=dev)
             if self.compensator is not None:
                 hist["est_pred"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
             hist["state"][0].copy_(self.sim.state)
@@ -163,8 +182,10 @@ class _ScoredLoop:
                 hist["latch"][j].copy_(self.command_stop); hist["state"][j + 1].copy_(self.sim.state)
                 if self.sensor is not None:
                     hist["est"][j].copy_(self.est)
-                if self.estimator is not None:
+                if self.estimator is not None or self.observer is not None:
                     hist["est_filt"][j].copy_(self.est_filt)
+                if self.observer is not None:
+                    hist["dist"][j].copy_(self.dist)
                 if self.compensator is not None:
                     hist["est_pred"][j].copy_(self.est_pred)
         out = dict(score=self.score, last=o)
@@ -198,7 +219,7 @@ class ClosedLoop(_ScoredLoop):
     v_des.  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
-                 mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, **options):
+                 mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, observer=None, **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -226,7 +247,7 @@ class ClosedLoop(_ScoredLoop):
         self.out = None
         self.k = 0
         self._init_sensor(sensor)
-        self._init_estimator(estimator, estimator_input, compensator)
+        self._init_estimator(estimator, estimator_input, compensator, observer)
         self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
@@ -236,7 +257,7 @@ class ClosedLoop(_ScoredLoop):
     def _period(self, plant_updates, time_solve):
         import time
         st = self.sim.state if self.sensor is None else self._sense()
-        if self.estimator is not None:
+        if self.estimator is not None or self.observer is not None:
             st = self._filter(st)
         if self.compensator is not None:
             st = self._predict(st, plant_updates)
@@ -261,6 +282,8 @@ class ClosedLoop(_ScoredLoop):
         _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
                                                 C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
                                                 C.c_void_p(cmd.data_ptr()), stream))
+        if self.observer is not None:
+            self.observer.offset(cmd, self.command_stop)
         if self.compensator is not None:
             self.compensator.push(cmd, self.k)
         self.sim._update_vehicle_model(plant_updates)
@@ -279,7 +302,7 @@ class ClosedLoopFrenet(_ScoredLoop):
     (checked once, here).  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, estimator=None,
-                 estimator_input="actuator", compensator=None, **options):
+                 estimator_input="actuator", compensator=None, observer=None, **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -308,7 +331,7 @@ class ClosedLoopFrenet(_ScoredLoop):
         self.out = None
         self.k = 0
         self._init_sensor(sensor)
-        self._init_estimator(estimator, estimator_input, compensator)
+        self._init_estimator(estimator, estimator_input, compensator, observer)
         self._init_score()
 
     def step(self, plant_updates=10, time_solve=False):
@@ -318,7 +341,7 @@ class ClosedLoopFrenet(_ScoredLoop):
     def _period(self, plant_updates, time_solve):
         import time
         st = self.sim.state if self.sensor is None else self._sense()
-        if self.estimator is not None:
+        if self.estimator is not None or self.observer is not None:
             st = self._filter(st)
         if self.compensator is not None:
             st = self._predict(st, plant_updates)
@@ -342,6 +365,8 @@ class ClosedLoopFrenet(_ScoredLoop):
         _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
                                                 C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
                                                 C.c_void_p(cmd.data_ptr()), stream))
+        if self.observer is not None:
+            self.observer.offset(cmd, self.command_stop)
         if self.compensator is not None:
             self.compensator.push(cmd, self.k)
         self.sim._update_vehicle_model(plant_updates)

@@ -867,6 +867,40 @@ extern "C" int32_t kmpc_estimate_batch(int32_t device, int32_t B, void *rec, con
     return KMPC_OK;
 }
 
+// ---- disturbance observer and command offset (kmpc_observer.hip) ---------------------------------------------------
+extern "C" int32_t kmpc_observe_batch(int32_t device, int32_t B, void *rec, const void *z, const void *u, int32_t u_stride, const void *params,
+                                      double dt, double L_a, double L_b, double gate, double v_min, double psi_cap, void *est_out, void *dist_out,
+                                      void *innov_out, int32_t *flags_out, void *stream)
+{
+    const auto pos = [](double a) { return a > 0.0 && a <= 1.7976931348623157e308; };   // finite and > 0
+    const auto nonneg = [](double a) { return a >= 0.0 && a <= 1.7976931348623157e308; };   // finite and >= 0
+    if (B < 0 || u_stride < 2 || !pos(dt) || !pos(L_a) || !pos(L_b) || !nonneg(gate) || !nonneg(v_min) || !nonneg(psi_cap))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_observe_batch: bad argument (B=%d, u_stride=%d, dt=%g, L_a=%g, L_b=%g, gate=%g, v_min=%g, psi_cap=%g)", B,
+                    u_stride, dt, L_a, L_b, gate, v_min, psi_cap);
+    if (B > 0 && (!rec || !z || !u || !params || !est_out)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_observe_batch: null required buffer");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_observe_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_observe(B, (double *)rec, (const double *)z, (const double *)u, u_stride, (const double *)params, dt, L_a, L_b,
+                                             gate, v_min, psi_cap, (double *)est_out, (double *)dist_out, (double *)innov_out, flags_out,
+                                             (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_observe_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_cmd_offset_batch(int32_t device, int32_t B, const void *rec, const uint8_t *stop_latch, double acc_cap, double df_cap,
+                                         void *cmd, void *stream)
+{
+    const auto nonneg = [](double a) { return a >= 0.0 && a <= 1.7976931348623157e308; };   // finite and >= 0
+    if (B < 0 || !nonneg(acc_cap) || !nonneg(df_cap))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_cmd_offset_batch: bad argument (B=%d, acc_cap=%g, df_cap=%g)", B, acc_cap, df_cap);
+    if (B > 0 && (!rec || !cmd)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_cmd_offset_batch: null required buffer");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_cmd_offset_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_cmd_offset(B, (const double *)rec, stop_latch, acc_cap, df_cap, (double *)cmd, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_cmd_offset_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 extern "C" int32_t kmpc_command_batch(int32_t device, int32_t B, const void *u0, const int32_t *stop, uint8_t *stop_latch, void *u_prev, void *cmd, void *stream)
 {
     if (B < 0 || (B > 0 && (!u0 || !stop || !stop_latch || !u_prev || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_command_batch: bad argument (B=%d)", B);

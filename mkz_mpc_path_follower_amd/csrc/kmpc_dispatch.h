@@ -111,6 +111,11 @@ hipError_t kmpc_launch_predict_ahead(int B, const double *z, const double *hist,
 // state estimator (kmpc_estimator.hip)
 hipError_t kmpc_launch_estimate(int B, double *rec, const double *z, const double *u, int u_stride, const double *params, double dt, double L_a,
                                 double L_b, double gate, double *est_out, double *innov_out, int32_t *flags_out, hipStream_t st);
+// disturbance observer and command offset (kmpc_observer.hip)
+hipError_t kmpc_launch_observe(int B, double *rec, const double *z, const double *u, int u_stride, const double *params, double dt, double L_a,
+                               double L_b, double gate, double v_min, double psi_cap, double *est_out, double *dist_out, double *innov_out,
+                               int32_t *flags_out, hipStream_t st);
+hipError_t kmpc_launch_cmd_offset(int B, const double *rec, const uint8_t *latch, double acc_cap, double df_cap, double *cmd, hipStream_t st);
 hipError_t kmpc_launch_command(int B, const double *u0, const int32_t *stop, uint8_t *latch, double *u_prev, double *cmd, hipStream_t st);
 
 // batched waypoint generation (kmpc_waypoints.hip; scripts/gps_utils/ref_gps_traj.py)

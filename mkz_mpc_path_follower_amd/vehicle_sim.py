@@ -13,6 +13,9 @@ Latency: `VehicleSimulator(cmd_queue_depth=D)` keeps the last D periods' command
 answer: a log of the commands sent and assumed delays of its own, from which it picks the filter's input and predicts the estimate ahead to the
 moment the next command acts (kmpc_cmd_in_force_batch, kmpc_predict_ahead_batch).
 
+Offset-free loops: `DisturbanceObserver` takes the estimator's place: the same filter on the model augmented with a course offset, a steering offset
+and an acceleration offset (kmpc_observe_batch), and `offset()` takes the two input offsets out of the command (kmpc_cmd_offset_batch).
+
 Grip and road: `VehicleSimulator(road=road_params(B, mu=0.5, a_lat=1.5, ...))` gives every vehicle a road row -- friction limits per axle, specific
 forces of grade and bank, a steering offset, an acceleration gain (kmpc_sim_advance_road) -- and counts, per vehicle and axle, the sub-steps in
 which the tyre force was clipped (`road_stat`, `road_summary()`).  The neutral row computes what the command-queue plant computes, bit for bit.
@@ -32,6 +35,8 @@ SENSOR_FIELDS = ("sigma_x", "sigma_y", "sigma_psi", "sigma_v", "bias_x", "bias_y
 ROAD_FIELDS = ("mu_f", "mu_r", "a_long", "a_lat", "df_offset", "acc_gain")   # KMPC_ROAD_* words 0 ... 5, in row order (6 and 7 are read by nobody)
 ESTIMATOR_FIELDS = ("x", "y", "psi", "v", "pxx", "pxy", "pxpsi", "pxv", "pyy", "pypsi", "pyv", "ppsipsi", "ppsiv", "pvv", "count", "skipped")   # KMPC_EST_*
 ESTIMATOR_PARAM_FIELDS = ("q_x", "q_y", "q_psi", "q_v", "r_x", "r_y", "r_psi", "r_v")   # KMPC_ESTPAR_*
+OBSERVER_FIELDS = ("x", "y", "psi", "v", "dpsi", "ddelta", "da")   # KMPC_OBS_* words 0 ... 6; 7 ... 34 the covariance, 35 count, 36 skipped
+OBSERVER_PARAM_FIELDS = ("q_x", "q_y", "q_psi", "q_v", "q_dpsi", "q_ddelta", "q_da", "r_x", "r_y", "r_psi", "r_v", "p0_dpsi", "p0_ddelta", "p0_da")   # KMPC_OBSPAR_*
 EST_SKIP_X, EST_SKIP_Y, EST_SKIP_PSI, EST_SKIP_V, EST_INIT, EST_RESET = 1, 2, 4, 8, 16, 32   # KMPC_EST_FLAG_*
 
 
@@ -376,6 +381,94 @@ class Estimator:
                                                  self.gate, C.c_void_p(est.data_ptr()), C.c_void_p(self.innov.data_ptr()),
                                                  C.c_void_p(self.flags.data_ptr()), stream))
         return est
+
+
+class DisturbanceObserver:
+    """The estimator's filter on the solver's model augmented with three constant disturbances (kmpc_observe_batch; include/kmpc.h states the
+    arithmetic): a course offset dpsi (crab angle under bank, yaw bias), a steering offset ddelta and an acceleration offset da (grade).  A bank, a
+    misaligned steering or a grade is a constant model error that no weight of the controller removes and that `Estimator` makes worse; this stage
+    estimates it, hands the solver the heading along which the vehicle really travels (`psi + clip(dpsi, psi_cap)`) and, in `offset()`, takes
+    ddelta and da out of the command (kmpc_cmd_offset_batch, capped at `df_cap`, `acc_cap`).
+    `q`, `r`: as Estimator's; `q_dist`: random-walk standard deviations PER CALL of dpsi, ddelta, da; `p0`: their initial standard deviations -- a
+    scalar, three values or [B,3].  `v_min`: below this estimated speed dpsi and ddelta are frozen (unobservable at rest).
+    The defaults are those of the CPU prototype loop (path3 at 6 m/s): with them a bank of 1.5 m/s^2 plus a steering offset of 0.03 rad leaves
+    0.022 m beside the path instead of 0.60 m; a larger q_dist follows a change faster and mistakes more of a corner's tyre slip for a disturbance.
+    `params` [B,16] (OBSERVER_PARAM_FIELDS), `record` [B,40] (all zeros = fresh), `dist` [B,3] (dpsi, ddelta, da of the last call), `innov` [B,4] and
+    `flags` [B] int32 (EST_* bits) are plain device tensors the caller may edit between calls."""
+
+    def __init__(self, B, q=(0.02, 0.02, 0.01, 0.1), q_dist=(0.002, 0.002, 0.02), r=(0.2, 0.2, 0.02, 0.1), p0=(0.05, 0.05, 0.5), gate=0.0, dt=0.1,
+                 v_min=1.0, psi_cap=0.2, acc_cap=0.5, df_cap=0.1, L_a=1.108, L_b=1.742, device=0):
+        self._lib = _lib.load()
+        self.B = int(B)
+        rows = np.zeros((self.B, 16))
+        for name, v, c0, w in (("q", q, 0, 4), ("q_dist", q_dist, 4, 3), ("r", r, 7, 4), ("p0", p0, 11, 3)):
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape not in ((), (w,), (self.B, w)):
+                raise ValueError("DisturbanceObserver: %s is a scalar, %d values or [%d,%d], got %s" % (name, w, self.B, w, v.shape))
+            rows[:, c0:c0 + w] = v
+        if not np.isfinite(rows).all() or not (rows[:, 0:7] >= 0.0).all() or not (rows[:, 7:11] > 0.0).all() or not (rows[:, 11:14] >= 0.0).all():
+            raise ValueError("DisturbanceObserver: q, q_dist, r and p0 must be finite, q >= 0, q_dist >= 0, r > 0, p0 >= 0")
+        self.gate, self.dt, self.L_a, self.L_b = float(gate), float(dt), float(L_a), float(L_b)
+        self.v_min, self.psi_cap, self.acc_cap, self.df_cap = float(v_min), float(psi_cap), float(acc_cap), float(df_cap)
+        if not (np.isfinite([self.gate, self.dt, self.L_a, self.L_b]).all() and self.gate >= 0.0 and self.dt > 0.0 and self.L_a > 0.0 and self.L_b > 0.0):
+            raise ValueError("DisturbanceObserver: gate >= 0, dt > 0, L_a > 0, L_b > 0, all finite (got %r, %r, %r, %r)" % (gate, dt, L_a, L_b))
+        caps = [self.v_min, self.psi_cap, self.acc_cap, self.df_cap]
+        if not (np.isfinite(caps).all() and min(caps) >= 0.0):
+            raise ValueError("DisturbanceObserver: v_min, psi_cap, acc_cap, df_cap >= 0, all finite (got %r, %r, %r, %r)" % (v_min, psi_cap, acc_cap, df_cap))
+        self.device = _device(device)
+        self.params = torch.as_tensor(rows).to(self.device)
+        self.record = torch.zeros((self.B, 40), dtype=torch.float64, device=self.device)
+        self.flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        self.innov = torch.zeros((self.B, 4), dtype=torch.float64, device=self.device)
+        self.dist = torch.zeros((self.B, 3), dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        """every record fresh: the next update initialises from its measurement, with zero disturbances"""
+        self.record.zero_()
+        self.flags.zero_()
+        self.innov.zero_()
+        self.dist.zero_()
+
+    def _own(self):
+        for t, w in ((self.params, 16), (self.record, 40)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+                raise ValueError("params [B,16] and record [B,40] must stay contiguous float64 tensors on %s" % self.device)
+
+    def update(self, z, u, out=None):
+        """z [B,4]: this period's measurement x, y, psi, v; u [B,2]: the (acc, d_f) that acted since the last call -- sim.state[:, 6:8] or the command
+        as sent, after offset() (as Estimator.update: a column view is not copied) -> est [B,4]: x, y, psi + clip(dpsi, psi_cap), v"""
+        est = out if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
+        self._own()
+        for t, w in ((z, 4), (est, 4), (self.innov, 4), (self.dist, 3)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+                raise ValueError("z [B,4], est [B,4], innov [B,4] and dist [B,3] must be contiguous float64 tensors on %s" % self.device)
+        if not (self.flags.dtype == torch.int32 and tuple(self.flags.shape) == (self.B,) and self.flags.is_contiguous() and self.flags.device == self.device):
+            raise ValueError("flags must stay a contiguous int32 tensor [B] on %s" % self.device)
+        if not (isinstance(u, torch.Tensor) and u.dtype == torch.float64 and tuple(u.shape) == (self.B, 2) and u.device == self.device
+                and (self.B == 0 or (u.stride(1) == 1 and (self.B == 1 or u.stride(0) >= 2)))):
+            raise ValueError("u: float64 [B,2] on %s with unit column stride and rows >= 2 apart (a [B,2] buffer or sim.state[:, 6:8])" % self.device)
+        stride = u.stride(0) if self.B > 1 else 2
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_observe_batch(self.device.index, self.B, C.c_void_p(self.record.data_ptr()), C.c_void_p(z.data_ptr()),
+                                                C.c_void_p(u.data_ptr()), int(stride), C.c_void_p(self.params.data_ptr()), self.dt, self.L_a, self.L_b,
+                                                self.gate, self.v_min, self.psi_cap, C.c_void_p(est.data_ptr()), C.c_void_p(self.dist.data_ptr()),
+                                                C.c_void_p(self.innov.data_ptr()), C.c_void_p(self.flags.data_ptr()), stream))
+        return est
+
+    def offset(self, cmd, stop_latch=None):
+        """cmd [B,2] (accel, steer), in place: accel -= clip(da, acc_cap), steer -= clip(ddelta, df_cap); a vehicle whose `stop_latch` [B] (bool or
+        uint8) is set, whose record is fresh or whose estimate is not finite keeps its command -> cmd"""
+        self._own()
+        if not (isinstance(cmd, torch.Tensor) and cmd.dtype == torch.float64 and tuple(cmd.shape) == (self.B, 2) and cmd.is_contiguous() and cmd.device == self.device):
+            raise ValueError("cmd must be a contiguous float64 tensor [B,2] on %s" % self.device)
+        if stop_latch is not None and not (isinstance(stop_latch, torch.Tensor) and stop_latch.dtype in (torch.bool, torch.uint8)
+                                           and tuple(stop_latch.shape) == (self.B,) and stop_latch.is_contiguous() and stop_latch.device == self.device):
+            raise ValueError("stop_latch must be a contiguous bool or uint8 tensor [B] on %s" % self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_cmd_offset_batch(self.device.index, self.B, C.c_void_p(self.record.data_ptr()),
+                                                   None if stop_latch is None else C.c_void_p(stop_latch.data_ptr()), self.acc_cap, self.df_cap,
+                                                   C.c_void_p(cmd.data_ptr()), stream))
+        return cmd
 
 
 class LatencyCompensator:

@@ -17,7 +17,12 @@ updates x age of the fix (0, 1, 2) periods, each cell once as it is and once wit
 road row of vehicle_sim.road_params per vehicle: friction coefficient (inf, 1.0, 0.7, 0.5, 0.35, 0.25) on both axles x target speed (6, 8) m/s x
 lateral specific force (0, 0.75, 1.5) m/s^2 (bank) x steering offset (0, 0.015, 0.03) rad.
 
+--observer is the road sweep's bank / offset / grade cells once more (-> profiles/robustness_sweep_observer.txt): no grip limit, 6 m/s, lateral
+specific force (0, 0.75, 1.5) m/s^2 x steering offset (0, 0.015, 0.03) rad x longitudinal specific force (0, -0.5) m/s^2, each cell once as it is and
+once with vehicle_sim.DisturbanceObserver (its defaults) in the loop: the existing figure next to the observer's.
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
+       python tools/robustness_sweep.py --observer [out.txt] [steps]
        python tools/robustness_sweep.py --latency [out.txt] [steps]
        python tools/robustness_sweep.py --road [out.txt] [steps]
 """
@@ -35,6 +40,7 @@ from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
 from mkz_mpc_path_follower_amd.ref_traj import FleetRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import Estimator, LatencyCompensator, SensorModel, VehicleSimulator, plant_default, plant_params  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import road_params  # noqa: E402
+from mkz_mpc_path_follower_amd.vehicle_sim import DisturbanceObserver  # noqa: E402
 
 MASS, STIFF, SIGMA, DELAY = (0.85, 1.0, 1.15, 1.3), (0.6, 0.8, 1.0, 1.2), (0.0, 0.1, 0.2, 0.5), (0, 2, 4, 8)
 PER_CELL, VT = 16, 6.0
@@ -232,8 +238,70 @@ def road_main():
             f.write("\n".join(LINES) + "\n")
 
 
+OBS_LONG = (0.0, -0.5)
+
+
+def observer_main():
+    """two loops of 3 x 3 x 2 cells of 48 vehicles (the road sweep's starts, all at 6 m/s, no grip limit): without and with observer=.  Each loop is
+    scored in two halves: the whole run carries the start and the corners, the second half is what stays."""
+    argv = [a for a in sys.argv if a != "--observer"]
+    steps = int(argv[2]) if len(argv) > 2 else 200
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    cells = list(itertools.product(range(3), range(3), range(2)))
+    B = len(cells) * ROAD_PER_CELL
+    ix = np.array(cells)[np.repeat(np.arange(len(cells)), ROAD_PER_CELL)]     # [B,3] grid indices: lateral force, steering offset, longitudinal force
+    rng = np.random.default_rng(0)
+    pid = np.tile(np.arange(ROAD_PER_CELL) % 3, len(cells))
+    fleet = FleetRefTrajectory(paths, pid, traj_horizon=8, traj_dt=0.2)
+    frac = np.tile(rng.uniform(0.02, 0.45, ROAD_PER_CELL), len(cells))
+    pose = np.empty((B, 3))
+    for b in range(B):
+        tr = fleet.trajectories[pid[b]]
+        i = int(frac[b] * len(tr))
+        pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+    res = {}
+    for with_observer in (False, True):
+        sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2],
+                               road=road_params(B, a_lat=np.array(ROAD_LAT)[ix[:, 0]], df_offset=np.array(ROAD_OFFSET)[ix[:, 1]], a_long=np.array(OBS_LONG)[ix[:, 2]]))
+        sim.state[:, 3] = VT
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, observer=DisturbanceObserver(B) if with_observer else None)
+        loop.run(steps // 2)
+        first = loop.score_summary()
+        loop.reset_score()
+        loop.run(steps - steps // 2)
+        second = loop.score_summary()
+        n1, n2 = first["n"], second["n"]
+        res[with_observer] = dict(rms=np.sqrt((first["sum_ect2"] + second["sum_ect2"]) / np.maximum(n1 + n2, 1)), rms2=second["rms_ect"],
+                                  max=np.maximum(first["max_ect"], second["max_ect"]), nonopt=first["n_nonopt"] + second["n_nonopt"],
+                                  live=first["n_live"] + second["n_live"], v=sim.state[:, 3].cpu().numpy(),
+                                  dist=loop.dist.cpu().numpy() if with_observer else None, finite=bool(torch.isfinite(sim.state).all().item()),
+                                  latched=int((second["latch_index"] >= 0).sum()))
+    say("%s: 2 x %d vehicles, %d periods of 0.1 s on three paths at %.0f m/s, nominal plant, no noise, no delay, no grip limit; every state finite: %s / %s; "
+        "latched vehicles: %d / %d (without / with the observer)" % (torch.cuda.get_device_name(0), B, steps, VT, res[False]["finite"], res[True]["finite"],
+                                                                  res[False]["latched"], res[True]["latched"]))
+    say("per cell (%d vehicles), without | with DisturbanceObserver: median rms e_ct over the run [m], over its second half [m], largest |e_ct| [m], periods "
+        "not Optimal per 1000, median speed at the end [m/s]; then the medians of dpsi-hat [rad], ddelta-hat [rad], da-hat [m/s^2]" % ROAD_PER_CELL)
+    for c, (a, o, g) in enumerate(cells):
+        sel = (ix[:, 0] == a) & (ix[:, 1] == o) & (ix[:, 2] == g)
+        part = []
+        for w in (False, True):
+            r = res[w]
+            part.append("%6.3f %6.3f %6.3f %6.2f %6.3f" % (np.median(r["rms"][sel]), np.median(r["rms2"][sel]), r["max"][sel].max(),
+                                                          1000.0 * r["nonopt"][sel].sum() / max(1, r["live"][sel].sum()), np.median(r["v"][sel])))
+        d = np.median(res[True]["dist"][sel], 0)
+        say("   %.2f m/s^2, %.3f rad, %+.1f m/s^2   %s | %s   %+.4f %+.4f %+.4f" % (ROAD_LAT[a], ROAD_OFFSET[o], OBS_LONG[g], part[0], part[1], d[0], d[1], d[2]))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 if __name__ == "__main__":
-    if "--road" in sys.argv[1:]:
+    if "--observer" in sys.argv[1:]:
+        observer_main()
+    elif "--road" in sys.argv[1:]:
         road_main()
     elif "--latency" in sys.argv[1:]:
         latency_main()
