@@ -681,6 +681,39 @@ int32_t kmpc_observe_batch(int32_t device, int32_t B, void *rec, const void *z, 
 int32_t kmpc_cmd_offset_batch(int32_t device, int32_t B, const void *rec, const uint8_t *stop_latch, double acc_cap, double df_cap, void *cmd,
                               void *stream);
 
+/* ---- prediction ahead under estimated disturbances: observer and delay compensation together --------------------------------------------------
+ * kmpc_predict_ahead_batch steps the solver's UNDISTURBED bicycle: behind kmpc_observe_batch it forgets over the dead time what the observer
+ * learnt (a steering offset of 0.05 rad turns the heading by about 0.035 rad over 0.35 s).  kmpc_predict_ahead_dist_batch is that prediction on
+ * the observer's augmented model, started from the observer's record.  One thread per vehicle, fp64, no FP contraction.
+ *   rec [B,40] fp64 DEVICE: kmpc_observe_batch's records, read only (words 0 ... 6 and 35)
+ *   est [B,4] fp64 DEVICE: the observer's est_out of this period         z_out [B,4] fp64 DEVICE out (may be est itself)
+ *   cmd_hist, depth, period, n_updates, cmd_delay, meas_delay, max_cmd_delay, max_meas_delay, L_a, L_b: exactly as in kmpc_predict_ahead_batch,
+ *     and so are Lm, d, tau0 = (p - Lm) n, the steps tau = tau0 ... p n + d - 1 and the log lookup j(tau, d).  The log holds the commands AS SENT,
+ *     after kmpc_cmd_offset_batch: then "logged command + disturbance" is what acted.
+ *   psi_cap >= 0 [rad]: kmpc_observe_batch's, the cap on the course offset handed to the solver
+ * START  a live record (word 35 != 0): (x, y, psi, v, dpsi, ddelta, da) = words 0 ... 6 -- psi is the record's heading, NOT est_out's shifted one.
+ *   A fresh record (word 35 == 0) has nothing to predict from: z_out = est bit for bit, no step is taken.
+ * PER STEP, h = 0.01, (psi, v: before the step), with (acc, d_f) = the logged command of period j(tau, d):
+ *     de = d_f + ddelta;  beta = atan(L_b / (L_a + L_b) * tan(de));  sb = sin(beta)    -- recomputed only when j(tau, d) differs from the step before
+ *     th = (psi + dpsi) + beta;  s = sin(th), c = cos(th)
+ *     x += h * (v * c);  y += h * (v * s);  psi = wrap(psi + h * (v / L_b * sb));  v = v + h * (acc + da), 0 when that is < 0
+ *   dpsi, ddelta and da stay constant and UNCLIPPED inside the model (the observer's own predict does not clip them either); kmpc_observe_batch's
+ *   freeze rule (v < v_min) concerns the covariance only and has no part here.  Every operation is rounded on its own; wrap and clip are
+ *   kmpc_observe_batch's; tan / atan / sin / cos are the device library's.
+ * OUTPUT  z_out = (x, y, wrap(psi + clip(dpsi, psi_cap)), v): the heading convention of est_out.
+ * Contracts: (a) with Lm = d = 0 no step is taken and z_out is the est_out kmpc_observe_batch wrote with this record, bit for bit (a record
+ *   initialised by that very call: as numbers when z_psi was outside [-pi, pi) or -0); a fresh record returns est bit for bit at any delay.
+ *   (b) With dpsi = ddelta = da = 0 in a live record, z_out equals kmpc_predict_ahead_batch on words 0 ... 3 AS NUMBERS (a -0 may become +0): every
+ *   added term is a sum with 0.  (c) A non-finite word among words 0 ... 6 and 35 of a vehicle's record, or in its logged commands, poisons that
+ *   vehicle's z_out alone: one thread per vehicle, no lane reads another vehicle's words.
+ * Argument checks before any device call: kmpc_predict_ahead_batch's, and psi_cap not finite and >= 0 returns KMPC_ERR_ARG; with B > 0 a NULL rec,
+ * est, cmd_hist, cmd_delay, meas_delay or z_out returns KMPC_ERR_ARG (text in kmpc_last_error(NULL)); B == 0 succeeds without a launch.
+ * Asynchronous on `stream`. */
+int32_t kmpc_predict_ahead_dist_batch(int32_t device, int32_t B, const void *rec, const void *est, const void *cmd_hist, int32_t depth,
+                                      int64_t period, int32_t n_updates, const int32_t *cmd_delay, const int32_t *meas_delay,
+                                      int32_t max_cmd_delay, int32_t max_meas_delay, double L_a, double L_b, double psi_cap, void *z_out,
+                                      void *stream);
+
 /* ---- command stage of the node's loop, for B vehicles (scripts/mpc_cmd_pub.jl) --------------------------------------
  * What the loop does between solve_model() and the publish: the waypoint helper's stop flag latches (:100-103); a latched vehicle is
  * commanded accel -1.0 / steer 0.0 (:148-153) and keeps its rate-limit anchor; every other vehicle publishes the solver's first input

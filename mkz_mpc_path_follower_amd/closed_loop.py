@@ -31,8 +31,17 @@ control period (plant_updates x 10 ms) and its L_a, L_b the solver's.  Without a
 Offset-free loops: `observer=vehicle_sim.DisturbanceObserver(...)` takes the estimator's place in the period -- waypoints, fit and solve read its
 `loop.est_filt` [B,4] (the heading shifted by the estimated course offset), `loop.dist` [B,3] is the estimate of (dpsi, ddelta, da) -- and its
 `offset()` runs between the command stage and the plant, in place on `sim.cmd`: the plant (and `estimator_input="command"`) sees the corrected
-command, the solver's rate-limit anchor `u_prev` stays the solver's own.  `observer=` together with `estimator=` or `compensator=` is refused.
+command, the solver's rate-limit anchor `u_prev` stays the solver's own.  `observer=` together with `estimator=` is refused.
 Without an observer the loops run the code they ran before.
+
+Offset-free loops under dead time: `observer=` together with `compensator=vehicle_sim.LatencyCompensator(..., disturbances=True)`.  The period is
+sense -> observer.update(z, u) -> compensator.predict_disturbed(observer, est_filt, k) -> `loop.est_pred` -> waypoints / fit / solve -> command ->
+observer.offset -> compensator.push: the prediction runs on the observer's augmented model (kmpc_predict_ahead_dist_batch: travel along
+psi + dpsi + beta, steering d_f + ddelta, acceleration acc + da), and the log holds the command AS SENT, after the offset, so that "logged command +
+disturbance" is what acted.  `estimator_input="history"` then feeds the observer the logged command in force (the choice under dead time; it
+ignores the actuator lag, which reaches the observer as a small disturbance).  A plain LatencyCompensator with `observer=` stays refused, and so
+does `disturbances=True` without `observer=`.  The observer's q_dist must shrink as the dead time grows: about 0.25 x the default at 0.35 s, the
+default up to 0.1 s; no automatic rule is built.  `run(history=True)` carries est_filt, dist and est_pred together.
 
 Latency: the plant's command queue and the sensor's stale fixes belong to the simulator and the sensor (VehicleSimulator(cmd_queue_depth=),
 SensorModel(meas_delay=)).  `compensator=vehicle_sim.LatencyCompensator(...)` is the controller's side: the period's state passes
@@ -81,10 +90,17 @@ class _ScoredLoop:
 
     def _init_estimator(self, estimator, estimator_input, compensator=None, observer=None):
         if observer is not None:
-            if estimator is not None or compensator is not None:
-                raise ValueError("observer= takes the estimator's place and has no prediction ahead yet: give neither estimator= nor compensator=")
+            if estimator is not None:
+                raise ValueError("observer= takes the estimator's place: give no estimator=")
+            if compensator is not None and not getattr(compensator, "disturbances", False):
+                raise ValueError("observer= with compensator= needs LatencyCompensator(..., disturbances=True): the prediction ahead must run on "
+                                 "the observer's model")
             if observer.B != self.B or observer.device != self.sim.device:
                 raise ValueError("observer for %d vehicles on %s, plant with %d on %s" % (observer.B, observer.device, self.B, self.sim.device))
+            if compensator is not None:
+                compensator.check_observer(observer)
+        elif compensator is not None and getattr(compensator, "disturbances", False):
+            raise ValueError("LatencyCompensator(disturbances=True) predicts on a DisturbanceObserver's model: give observer=")
         self.observer = observer
         self.dist = None       # [B,3] the estimated dpsi, ddelta, da of the last period (observer given): the observer's own tensor
         if estimator_input not in ("actuator", "command", "history"):
@@ -120,6 +136,9 @@ class _ScoredLoop:
         if self.compensator.n_updates != int(plant_updates):
             raise ValueError("the compensator counts %d updates per period, this period has %d" % (self.compensator.n_updates, plant_updates))
         z = st if st.shape[1] == 4 else st[:, 0:4].contiguous()
+        if self.observer is not None:   # on the observer's augmented model, from its record; z is its est_out
+            self.est_pred = self.compensator.predict_disturbed(self.observer, z, self.k, out=self.est_pred)
+            return self.est_pred
         self.est_pred = self.compensator.predict(z, self.k, out=self.est_pred)
         return self.est_pred
 

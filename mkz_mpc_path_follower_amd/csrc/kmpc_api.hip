@@ -901,6 +901,30 @@ extern "C" int32_t kmpc_cmd_offset_batch(int32_t device, int32_t B, const void *
     return KMPC_OK;
 }
 
+// ---- prediction ahead under estimated disturbances (kmpc_predict_dist.hip) -------------------------------------------
+extern "C" int32_t kmpc_predict_ahead_dist_batch(int32_t device, int32_t B, const void *rec, const void *est, const void *cmd_hist, int32_t depth,
+                                                 int64_t period, int32_t n_updates, const int32_t *cmd_delay, const int32_t *meas_delay,
+                                                 int32_t max_cmd_delay, int32_t max_meas_delay, double L_a, double L_b, double psi_cap, void *z_out,
+                                                 void *stream)
+{
+    const int32_t rc = latency_args("kmpc_predict_ahead_dist_batch", B, cmd_hist, depth, period, n_updates, cmd_delay, meas_delay, max_cmd_delay,
+                                    max_meas_delay);
+    if (rc != KMPC_OK) return rc;
+    const auto pos = [](double a) { return a > 0.0 && a <= 1.7976931348623157e308; };   // finite and > 0
+    const auto nonneg = [](double a) { return a >= 0.0 && a <= 1.7976931348623157e308; };   // finite and >= 0
+    if (!pos(L_a) || !pos(L_b) || !nonneg(psi_cap))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_predict_ahead_dist_batch: L_a=%g, L_b=%g must be finite and > 0, psi_cap=%g finite and >= 0", L_a, L_b,
+                    psi_cap);
+    if (B > 0 && (!rec || !est || !z_out)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_predict_ahead_dist_batch: null rec, est or z_out");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_predict_ahead_dist_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_predict_ahead_dist(B, (const double *)rec, (const double *)est, (const double *)cmd_hist, depth, (long long)period,
+                                                        n_updates, cmd_delay, meas_delay, max_cmd_delay, max_meas_delay, L_a, L_b, psi_cap,
+                                                        (double *)z_out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_predict_ahead_dist_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 extern "C" int32_t kmpc_command_batch(int32_t device, int32_t B, const void *u0, const int32_t *stop, uint8_t *stop_latch, void *u_prev, void *cmd, void *stream)
 {
     if (B < 0 || (B > 0 && (!u0 || !stop || !stop_latch || !u_prev || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_command_batch: bad argument (B=%d)", B);

@@ -116,6 +116,10 @@ hipError_t kmpc_launch_observe(int B, double *rec, const double *z, const double
                                double L_b, double gate, double v_min, double psi_cap, double *est_out, double *dist_out, double *innov_out,
                                int32_t *flags_out, hipStream_t st);
 hipError_t kmpc_launch_cmd_offset(int B, const double *rec, const uint8_t *latch, double acc_cap, double df_cap, double *cmd, hipStream_t st);
+// prediction ahead under estimated disturbances (kmpc_predict_dist.hip)
+hipError_t kmpc_launch_predict_ahead_dist(int B, const double *rec, const double *est, const double *hist, int depth, long long period, int n,
+                                          const int32_t *cmd_delay, const int32_t *meas_delay, int max_cmd_delay, int max_meas_delay, double L_a,
+                                          double L_b, double psi_cap, double *z_out, hipStream_t st);
 hipError_t kmpc_launch_command(int B, const double *u0, const int32_t *stop, uint8_t *latch, double *u_prev, double *cmd, hipStream_t st);
 
 // batched waypoint generation (kmpc_waypoints.hip; scripts/gps_utils/ref_gps_traj.py)

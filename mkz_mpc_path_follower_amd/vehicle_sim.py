@@ -15,6 +15,8 @@ moment the next command acts (kmpc_cmd_in_force_batch, kmpc_predict_ahead_batch)
 
 Offset-free loops: `DisturbanceObserver` takes the estimator's place: the same filter on the model augmented with a course offset, a steering offset
 and an acceleration offset (kmpc_observe_batch), and `offset()` takes the two input offsets out of the command (kmpc_cmd_offset_batch).
+Under dead time its partner is `LatencyCompensator(disturbances=True)`, whose `predict_disturbed()` predicts ahead on that augmented model from the
+observer's record (kmpc_predict_ahead_dist_batch).
 
 Grip and road: `VehicleSimulator(road=road_params(B, mu=0.5, a_lat=1.5, ...))` gives every vehicle a road row -- friction limits per axle, specific
 forces of grade and bank, a steering offset, an acceleration gain (kmpc_sim_advance_road) -- and counts, per vehicle and axle, the sub-steps in
@@ -482,9 +484,19 @@ class LatencyCompensator:
       filter_input(period)   -> u [B,2]: the command in force over the period before the measurement's moment: the estimator's predict input
       predict(z, period)     -> z [B,4] carried from the measurement's moment, update (period - meas_delay) n, to update period n + cmd_delay, where
                                 this period's command begins to act; zero delays return z bit for bit
-      push(cmd, period)      logs period's command [B,2]"""
+      push(cmd, period)      logs period's command [B,2]
+    `disturbances=True` makes it the partner of a DisturbanceObserver (kmpc_predict_ahead_dist_batch): the closed loops accept observer= together
+    with compensator= only then, and
+      predict_disturbed(observer, est, period) -> z [B,4]: the same steps on the observer's augmented model, from the observer's record: travel
+                                along psi + dpsi + beta, steering d_f + ddelta, acceleration acc + da, the three held constant; the heading
+                                returned is est_out's, psi + clip(dpsi, psi_cap).  `est` [B,4] (the observer's est_out) is what a vehicle with a
+                                fresh record gets back; zero delays return est_out bit for bit.
+    The observer's random walk must slow as the dead time grows (about 0.25 x the default q_dist at 0.35 s)."""
 
-    def __init__(self, B, cmd_delay=0, meas_delay=0, n_updates=10, depth=None, L_a=1.108, L_b=1.742, device=0):
+    def __init__(self, B, cmd_delay=0, meas_delay=0, n_updates=10, depth=None, L_a=1.108, L_b=1.742, device=0, disturbances=False):
+        if not isinstance(disturbances, (bool, np.bool_)):
+            raise ValueError("LatencyCompensator: disturbances is True or False, got %r" % (disturbances,))
+        self.disturbances = bool(disturbances)
         self._lib = _lib.load()
         self.B = int(B)
         if isinstance(n_updates, bool) or not isinstance(n_updates, (int, np.integer)) or n_updates < 1:
@@ -537,6 +549,30 @@ class LatencyCompensator:
                                                       self.depth, int(period), self.n_updates, C.c_void_p(self.cmd_delay.data_ptr()),
                                                       C.c_void_p(self.meas_delay.data_ptr()), int(self.max_cmd_delay), int(self.max_meas_delay),
                                                       self.L_a, self.L_b, C.c_void_p(zo.data_ptr()), stream))
+        return zo
+
+    def check_observer(self, observer):
+        """refuse an observer this compensator cannot predict for: another fleet size, device or model geometry"""
+        if not self.disturbances:
+            raise ValueError("LatencyCompensator: predict_disturbed needs LatencyCompensator(..., disturbances=True)")
+        if not isinstance(observer, DisturbanceObserver):
+            raise ValueError("LatencyCompensator: observer is a vehicle_sim.DisturbanceObserver, got %r" % (type(observer).__name__,))
+        if observer.B != self.B or observer.device != self.device or observer.L_a != self.L_a or observer.L_b != self.L_b:
+            raise ValueError("LatencyCompensator: the observer has B=%d on %s with L_a=%r, L_b=%r, the compensator B=%d on %s with L_a=%r, L_b=%r: "
+                             "they must agree" % (observer.B, observer.device, observer.L_a, observer.L_b, self.B, self.device, self.L_a, self.L_b))
+
+    def predict_disturbed(self, observer, est, period, out=None):
+        self.check_observer(observer)
+        self._check(period)
+        observer._own()
+        self._buf(est, 4, "est")
+        zo = self._buf(out, 4, "out") if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_predict_ahead_dist_batch(self.device.index, self.B, C.c_void_p(observer.record.data_ptr()),
+                                                           C.c_void_p(est.data_ptr()), C.c_void_p(self.cmd_hist.data_ptr()), self.depth, int(period),
+                                                           self.n_updates, C.c_void_p(self.cmd_delay.data_ptr()),
+                                                           C.c_void_p(self.meas_delay.data_ptr()), int(self.max_cmd_delay), int(self.max_meas_delay),
+                                                           self.L_a, self.L_b, observer.psi_cap, C.c_void_p(zo.data_ptr()), stream))
         return zo
 
     def push(self, cmd, period):

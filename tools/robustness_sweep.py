@@ -21,8 +21,13 @@ lateral specific force (0, 0.75, 1.5) m/s^2 (bank) x steering offset (0, 0.015, 
 specific force (0, 0.75, 1.5) m/s^2 x steering offset (0, 0.015, 0.03) rad x longitudinal specific force (0, -0.5) m/s^2, each cell once as it is and
 once with vehicle_sim.DisturbanceObserver (its defaults) in the loop: the existing figure next to the observer's.
 
+--observer-latency is the observer sweep's cells under dead time (-> profiles/robustness_sweep_observer_latency.txt): total dead time 0.1 / 0.2 /
+0.35 s (command delay 10 / 10 / 25 updates, fix 0 / 1 / 1 periods old) x the observer's q_dist at 1 / 0.5 / 0.25 of its default, each cell three ways:
+Estimator + LatencyCompensator, DisturbanceObserver alone, and DisturbanceObserver + LatencyCompensator(disturbances=True).
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
        python tools/robustness_sweep.py --observer [out.txt] [steps]
+       python tools/robustness_sweep.py --observer-latency [out.txt] [steps]
        python tools/robustness_sweep.py --latency [out.txt] [steps]
        python tools/robustness_sweep.py --road [out.txt] [steps]
 """
@@ -298,8 +303,94 @@ def observer_main():
             f.write("\n".join(LINES) + "\n")
 
 
+OL_DEAD = ((10, 0), (10, 1), (25, 1))     # command delay [updates], age of the fix [periods]: 0.1, 0.2, 0.35 s
+OL_SCALE = (1.0, 0.5, 0.25)
+OL_PER_CELL = 12
+OL_WAYS = ("estimator + compensator", "observer alone", "observer + compensator")
+
+
+def observer_latency_main():
+    """three loops of 3 x 3 x 2 road cells x 3 dead times x 3 q_dist scales of 12 vehicles (the road sweep's first 12 starts, all at 6 m/s, no grip
+    limit): the plant's queue and the sensor's stale fix per vehicle, the controller assuming the true delays.  Scored in two halves as --observer."""
+    argv = [a for a in sys.argv if a != "--observer-latency"]
+    steps = int(argv[2]) if len(argv) > 2 else 200
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    cells = list(itertools.product(range(3), range(3), range(2), range(3), range(3)))
+    B = len(cells) * OL_PER_CELL
+    ix = np.array(cells)[np.repeat(np.arange(len(cells)), OL_PER_CELL)]     # [B,5]: lateral force, steering offset, longitudinal force, dead time, q_dist scale
+    rng = np.random.default_rng(0)
+    pid = np.tile(np.arange(OL_PER_CELL) % 3, len(cells))
+    fleet = FleetRefTrajectory(paths, pid, traj_horizon=8, traj_dt=0.2)
+    frac = np.tile(rng.uniform(0.02, 0.45, ROAD_PER_CELL)[:OL_PER_CELL], len(cells))
+    pose = np.empty((B, 3))
+    for b in range(B):
+        tr = fleet.trajectories[pid[b]]
+        i = int(frac[b] * len(tr))
+        pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+    cd, md = np.array(OL_DEAD)[ix[:, 3], 0], np.array(OL_DEAD)[ix[:, 3], 1]
+    q_dist = np.array(OL_SCALE)[ix[:, 4]][:, None] * np.array((0.002, 0.002, 0.02))[None, :]      # DisturbanceObserver's default, scaled per vehicle
+    res = {}
+    for way in OL_WAYS:
+        sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2], cmd_delay=cd, cmd_queue_depth=4,
+                               road=road_params(B, a_lat=np.array(ROAD_LAT)[ix[:, 0]], df_offset=np.array(ROAD_OFFSET)[ix[:, 1]], a_long=np.array(OBS_LONG)[ix[:, 2]]))
+        sim.state[:, 3] = VT
+        sensor = SensorModel(B, meas_delay=md)
+        if way == "estimator + compensator":
+            kw = dict(estimator=Estimator.from_sensor(sensor), compensator=LatencyCompensator(B, cmd_delay=cd, meas_delay=md), estimator_input="history")
+        elif way == "observer alone":
+            kw = dict(observer=DisturbanceObserver(B, q_dist=q_dist))
+        else:
+            kw = dict(observer=DisturbanceObserver(B, q_dist=q_dist), compensator=LatencyCompensator(B, cmd_delay=cd, meas_delay=md, disturbances=True),
+                      estimator_input="history")
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, sensor=sensor, **kw)
+        loop.run(steps // 2)
+        first = loop.score_summary()
+        loop.reset_score()
+        loop.run(steps - steps // 2)
+        second = loop.score_summary()
+        n1, n2 = first["n"], second["n"]
+        res[way] = dict(rms=np.sqrt((first["sum_ect2"] + second["sum_ect2"]) / np.maximum(n1 + n2, 1)), rms2=second["rms_ect"],
+                        max=np.maximum(first["max_ect"], second["max_ect"]), nonopt=first["n_nonopt"] + second["n_nonopt"],
+                        live=first["n_live"] + second["n_live"], finite=bool(torch.isfinite(sim.state).all().item()),
+                        latched=int((second["latch_index"] >= 0).sum()))
+    say("%s: 3 x %d vehicles, %d periods of 0.1 s on three paths at %.0f m/s, nominal plant, no noise, no grip limit; the controller assumes the true delays; "
+        "every state finite: %s; latched vehicles: %s; periods not Optimal per 1000: %s (%s)"
+        % (torch.cuda.get_device_name(0), B, steps, VT, " / ".join(str(res[w]["finite"]) for w in OL_WAYS), " / ".join(str(res[w]["latched"]) for w in OL_WAYS),
+           " / ".join("%.2f" % (1000.0 * res[w]["nonopt"].sum() / max(1, res[w]["live"].sum())) for w in OL_WAYS), " / ".join(OL_WAYS)))
+    head = "median rms e_ct over the run [m], over its second half [m], largest |e_ct| [m]: " + " | ".join(OL_WAYS)
+
+    def row(label, sel):
+        say("   %-52s %s" % (label, " | ".join("%6.3f %6.3f %7.3f" % (np.median(res[w]["rms"][sel]), np.median(res[w]["rms2"][sel]), res[w]["max"][sel].max())
+                                               for w in OL_WAYS)))
+    dead = ["%.2f s" % (0.01 * c + 0.1 * m) for c, m in OL_DEAD]
+    say("dead time x q_dist scale, over all road cells (%d vehicles per line; the estimator's lines differ by nothing but the cell): " % (18 * OL_PER_CELL) + head)
+    for t in range(3):
+        for q in range(3):
+            row("%s, q_dist x %.2f" % (dead[t], OL_SCALE[q]), (ix[:, 3] == t) & (ix[:, 4] == q))
+    say("dead time x q_dist scale, the disturbed corner 1.50 m/s^2 with 0.030 rad, level and on the grade (%d vehicles per line): " % (2 * OL_PER_CELL) + head)
+    for t in range(3):
+        for q in range(3):
+            row("%s, q_dist x %.2f" % (dead[t], OL_SCALE[q]), (ix[:, 0] == 2) & (ix[:, 1] == 2) & (ix[:, 3] == t) & (ix[:, 4] == q))
+    say("per road cell at 0.35 s and q_dist x 0.25 (%d vehicles per line): " % OL_PER_CELL + head)
+    for a, o, g in itertools.product(range(3), range(3), range(2)):
+        row("%.2f m/s^2, %.3f rad, %+.1f m/s^2" % (ROAD_LAT[a], ROAD_OFFSET[o], OBS_LONG[g]),
+            (ix[:, 0] == a) & (ix[:, 1] == o) & (ix[:, 2] == g) & (ix[:, 3] == 2) & (ix[:, 4] == 2))
+    say("per road cell at 0.10 s and q_dist x 1.00 (%d vehicles per line): " % OL_PER_CELL + head)
+    for a, o, g in itertools.product(range(3), range(3), range(2)):
+        row("%.2f m/s^2, %.3f rad, %+.1f m/s^2" % (ROAD_LAT[a], ROAD_OFFSET[o], OBS_LONG[g]),
+            (ix[:, 0] == a) & (ix[:, 1] == o) & (ix[:, 2] == g) & (ix[:, 3] == 0) & (ix[:, 4] == 0))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 if __name__ == "__main__":
-    if "--observer" in sys.argv[1:]:
+    if "--observer-latency" in sys.argv[1:]:
+        observer_latency_main()
+    elif "--observer" in sys.argv[1:]:
         observer_main()
     elif "--road" in sys.argv[1:]:
         road_main()
