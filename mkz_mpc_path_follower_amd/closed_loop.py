@@ -52,6 +52,7 @@ steps across (refused without a compensator).  Scoring, the history's `state` an
 compensator's n_updates must be the loop's plant_updates (checked every period).  Without a compensator the loops take exactly the path they took.
 """
 import ctypes as C
+import time
 
 import numpy as np
 import torch
@@ -80,7 +81,61 @@ def _target_speeds(target_vel, B, device):
 
 
 class _ScoredLoop:
-    """run() / score / score_summary() of both loops.  A loop provides _period(plant_updates, time_solve) -> step()'s dict: one control period."""
+    """The control period, run() / score / score_summary() of both loops.  A loop provides the one step in which they differ,
+    _reference(st) -> (ref, stop, solve, extra): the reference built from the controller's state `st`, the helper's stop flags, the solve as a
+    call without arguments -> the solver's output dict, and the entries the loop adds to step()'s dict."""
+
+    def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer):
+        """what both loops own beside grt, sim, N, B, mpc and the target speeds: buffers, the stop latch, the library, and the stages"""
+        dev = self.sim.device
+        self.u_prev = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)       # (acc, d_f): update_current_input starts at 0
+        self.warm_U = torch.zeros((self.B, self.N, 2), dtype=torch.float64, device=dev)
+        self.command_stop = torch.zeros((self.B,), dtype=torch.bool, device=dev)   # the stop latch (one byte per vehicle: kmpc_command_batch's uint8)
+        self._lib = _lib.load()
+        # per-vehicle weights and limits [B,16] (BatchMPC.problem_params), owned by the caller: it may be edited between steps (gain scheduling,
+        # a new speed limit); None = the solver handle's values for every vehicle
+        self.params = params
+        self.have_warm = False
+        self.out = None
+        self.k = 0
+        self._init_sensor(sensor)
+        self._init_estimator(estimator, estimator_input, compensator, observer)
+        self._init_score()
+
+    def _period(self, plant_updates, time_solve):
+        """one control period -> step()'s dict: sense -> filter -> predict -> reference and solve (the loop's own) -> command stage -> offset ->
+        log -> plant"""
+        st = self.sim.state if self.sensor is None else self._sense()
+        if self.estimator is not None or self.observer is not None:
+            st = self._filter(st)
+        if self.compensator is not None:
+            st = self._predict(st, plant_updates)
+        ref, stop, solve, extra = self._reference(st)
+        if time_solve:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        self.out = solve()
+        solve_s = None
+        if time_solve:
+            torch.cuda.synchronize()
+            solve_s = time.perf_counter() - t0
+        self.have_warm = True
+        # stop latch (:100-103), command selection (:148-153) and update_current_input (:140, only on the solve branch): one kernel, straight
+        # into the plant's command buffer
+        cmd = self.sim.cmd
+        u0 = self.out["u0"]
+        assert u0.dtype == torch.float64 and u0.is_contiguous() and u0.device == cmd.device and u0.shape == (self.B, 2)
+        stream = C.c_void_p(torch.cuda.current_stream(cmd.device).cuda_stream)
+        _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
+                                                C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
+                                                C.c_void_p(cmd.data_ptr()), stream))
+        if self.observer is not None:
+            self.observer.offset(cmd, self.command_stop)
+        if self.compensator is not None:
+            self.compensator.push(cmd, self.k)
+        self.sim._update_vehicle_model(plant_updates)
+        self.k += 1
+        return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s, **extra)
 
     def _init_sensor(self, sensor):
         if sensor is not None and (sensor.B != self.B or sensor.device != self.sim.device):
@@ -253,61 +308,19 @@ class ClosedLoop(_ScoredLoop):
         if track_with_time and isinstance(grt, FleetRefTrajectory):
             raise ValueError("a FleetRefTrajectory owns the tracking modes (its time_mode): track_with_time must stay False")
         self.track_with_time = track_with_time
-        dev = sim.device
-        self.des_speed, self.v_target = _target_speeds(target_vel, self.B, dev)  # mpc_cmd_pub.jl:58-62
-        self.u_prev = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)       # (acc, d_f): update_current_input starts at 0
-        self.warm_U = torch.zeros((self.B, self.N, 2), dtype=torch.float64, device=dev)
-        self.command_stop = torch.zeros((self.B,), dtype=torch.bool, device=dev)   # the stop latch (one byte per vehicle: kmpc_command_batch's uint8)
-        self._lib = _lib.load()
-        # per-vehicle weights and limits [B,16] (BatchMPC.problem_params), owned by the caller: it may be edited between steps (gain scheduling,
-        # a new speed limit); None = the solver handle's values for every vehicle
-        self.params = params
-        self.have_warm = False
-        self.out = None
-        self.k = 0
-        self._init_sensor(sensor)
-        self._init_estimator(estimator, estimator_input, compensator, observer)
-        self._init_score()
+        self.des_speed, self.v_target = _target_speeds(target_vel, self.B, sim.device)  # mpc_cmd_pub.jl:58-62
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer)
 
     def step(self, plant_updates=10, time_solve=False):
         """time_solve=True brackets the solve with device synchronisations and returns its wall time (`solve_s`)"""
         return self._period(plant_updates, time_solve)
 
-    def _period(self, plant_updates, time_solve):
-        import time
-        st = self.sim.state if self.sensor is None else self._sense()
-        if self.estimator is not None or self.observer is not None:
-            st = self._filter(st)
-        if self.compensator is not None:
-            st = self._predict(st, plant_updates)
+    def _reference(self, st):
         pose = st[:, 0:3].contiguous()
         ref, stop = self.grt.get_waypoints_batch(pose, None if self.track_with_time else self.v_target)
         z0 = st[:, 0:4].contiguous()                                                # x, y, psi, v = vx  (state_est, :43-46 of the simulator)
-        if time_solve:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-        self.out = self.mpc.solve(z0, ref, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out, params=self.params)
-        solve_s = None
-        if time_solve:
-            torch.cuda.synchronize()
-            solve_s = time.perf_counter() - t0
-        self.have_warm = True
-        # stop latch (:100-103), command selection (:148-153) and update_current_input (:140, only on the solve branch): one kernel, straight
-        # into the plant's command buffer
-        cmd = self.sim.cmd
-        u0 = self.out["u0"]
-        assert u0.dtype == torch.float64 and u0.is_contiguous() and u0.device == cmd.device and u0.shape == (self.B, 2)
-        stream = C.c_void_p(torch.cuda.current_stream(cmd.device).cuda_stream)
-        _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
-                                                C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
-                                                C.c_void_p(cmd.data_ptr()), stream))
-        if self.observer is not None:
-            self.observer.offset(cmd, self.command_stop)
-        if self.compensator is not None:
-            self.compensator.push(cmd, self.k)
-        self.sim._update_vehicle_model(plant_updates)
-        self.k += 1
-        return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s)
+        return ref, stop, lambda: self.mpc.solve(z0, ref, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
+                                                 params=self.params), {}
 
 
 class ClosedLoopFrenet(_ScoredLoop):
@@ -340,55 +353,15 @@ class ClosedLoopFrenet(_ScoredLoop):
         if grt.device != sim.device:
             raise ValueError("waypoint helper on %s, plant on %s: the loop runs on one device" % (grt.device, sim.device))
         self.des_speed, self.v_target = des_speed, v_target
-        dev = sim.device
-        self.u_prev = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)
-        self.warm_U = torch.zeros((self.B, self.N, 2), dtype=torch.float64, device=dev)
-        self.command_stop = torch.zeros((self.B,), dtype=torch.bool, device=dev)
-        self._lib = _lib.load()
-        self.params = params
-        self.have_warm = False
-        self.out = None
-        self.k = 0
-        self._init_sensor(sensor)
-        self._init_estimator(estimator, estimator_input, compensator, observer)
-        self._init_score()
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer)
 
     def step(self, plant_updates=10, time_solve=False):
         """as ClosedLoop.step; the returned dict also carries `k_poly` [B,4] and `fit_status` [B]"""
         return self._period(plant_updates, time_solve)
 
-    def _period(self, plant_updates, time_solve):
-        import time
-        st = self.sim.state if self.sensor is None else self._sense()
-        if self.estimator is not None or self.observer is not None:
-            st = self._filter(st)
-        if self.compensator is not None:
-            st = self._predict(st, plant_updates)
+    def _reference(self, st):
         pose = st[:, 0:3].contiguous()
         ref, stop = self.grt.get_waypoints_batch(pose, self.v_target)
         k_poly, _psi, z0, fit_status = get_reference_frenet_batch(pose, ref, st[:, 3].contiguous())
-        if time_solve:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-        self.out = self.mpc.solve_frenet(z0, k_poly, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
-                                         params=self.params)
-        solve_s = None
-        if time_solve:
-            torch.cuda.synchronize()
-            solve_s = time.perf_counter() - t0
-        self.have_warm = True
-        cmd = self.sim.cmd
-        u0 = self.out["u0"]
-        assert u0.dtype == torch.float64 and u0.is_contiguous() and u0.device == cmd.device and u0.shape == (self.B, 2)
-        stream = C.c_void_p(torch.cuda.current_stream(cmd.device).cuda_stream)
-        _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
-                                                C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
-                                                C.c_void_p(cmd.data_ptr()), stream))
-        if self.observer is not None:
-            self.observer.offset(cmd, self.command_stop)
-        if self.compensator is not None:
-            self.compensator.push(cmd, self.k)
-        self.sim._update_vehicle_model(plant_updates)
-        self.k += 1
-        return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s,
-                    k_poly=k_poly, fit_status=fit_status)
+        return ref, stop, lambda: self.mpc.solve_frenet(z0, k_poly, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
+                                                        params=self.params), dict(k_poly=k_poly, fit_status=fit_status)

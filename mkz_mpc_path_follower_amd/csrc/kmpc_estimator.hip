@@ -11,24 +11,11 @@
 
 #include "../../include/kmpc.h"   // KMPC_EST_*, KMPC_ESTPAR_*: record and row layouts
 #include "kmpc_dispatch.h"
+#include "kmpc_stage.h"   // wrap, finite
 
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ bool est_finite(double a) { return fabs(a) <= 1.7976931348623157e308; }   // false for NaN and +-inf
-
-// the plant's and the sensor's wrap (vehicle_simulator.py:101), only where there is something to wrap: an angle inside [-pi, pi) passes unchanged
-__device__ __forceinline__ double est_wrap(double a)
-{
-    const double pi = 3.141592653589793, p2 = 2.0 * pi;
-    if (!(a >= -pi && a < pi)) {
-        double md = fmod(a + pi, p2);
-        if (md < 0.0) md += p2;
-        a = md - pi;
-    }
-    return a;
-}
 
 // index of P_ij (i <= j) in the row-major upper triangle: xx xy xs xv | yy ys yv | ss sv | vv
 __device__ __forceinline__ constexpr int tri(int i, int j) { return i * 4 - (i * (i - 1)) / 2 + (j - i); }
@@ -64,7 +51,7 @@ __global__ __launch_bounds__(256) void kmpc_estimate_kernel(int B, double *__res
         bool ok = true;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            if (!est_finite(zz[c])) { ok = false; flags |= 1 << c; }
+            if (!stage::finite(zz[c])) { ok = false; flags |= 1 << c; }
         }
         if (ok) {
 #pragma unroll
@@ -86,7 +73,7 @@ __global__ __launch_bounds__(256) void kmpc_estimate_kernel(int B, double *__res
         const double fxp = -(dt * (v * sa)), fxv = dt * ca, fyp = dt * (v * ca), fyv = dt * sa, fpv = dt * (sb / L_b);
         xh[0] = xh[0] + dt * (v * ca);
         xh[1] = xh[1] + dt * (v * sa);
-        xh[2] = est_wrap(xh[2] + dt * (v / L_b * sb));
+        xh[2] = stage::wrap(xh[2] + dt * (v / L_b * sb));
         const double vn = v + dt * acc;
         xh[3] = vn < 0.0 ? 0.0 : vn;
         // A = F P (the entries the upper triangle of A F^T needs), then P <- A F^T + diag(q^2); sums left to right
@@ -110,9 +97,9 @@ __global__ __launch_bounds__(256) void kmpc_estimate_kernel(int B, double *__res
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             double nu = zz[c] - xh[c];
-            if (c == 2) nu = est_wrap(nu);
+            if (c == 2) nu = stage::wrap(nu);
             const double S = P[tri(c, c)] + r2[c];
-            const bool skip = !est_finite(zz[c]) || !(S > 0.0 && est_finite(S)) || (gate > 0.0 && nu * nu > gate * gate * S);
+            const bool skip = !stage::finite(zz[c]) || !(S > 0.0 && stage::finite(S)) || (gate > 0.0 && nu * nu > gate * gate * S);
             if (skip) {
                 flags |= 1 << c;
                 ++nskip;
@@ -131,16 +118,16 @@ __global__ __launch_bounds__(256) void kmpc_estimate_kernel(int B, double *__res
                 nu_out[c] = nu / sqrt(S);
             }
         }
-        xh[2] = est_wrap(xh[2]);
+        xh[2] = stage::wrap(xh[2]);
         xh[3] = xh[3] < 0.0 ? 0.0 : xh[3];
         count = count + 1.0;
         skipped = skipped + (double)nskip;
         // ---- containment: a record with a non-finite word does not survive the call
-        bool ok = est_finite(count) && est_finite(skipped);
+        bool ok = stage::finite(count) && stage::finite(skipped);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) ok = ok && est_finite(xh[c]);
+        for (int c = 0; c < 4; ++c) ok = ok && stage::finite(xh[c]);
 #pragma unroll
-        for (int k = 0; k < 10; ++k) ok = ok && est_finite(P[k]);
+        for (int k = 0; k < 10; ++k) ok = ok && stage::finite(P[k]);
         if (!ok) {
             fresh_out = true;
             flags |= KMPC_EST_FLAG_RESET;

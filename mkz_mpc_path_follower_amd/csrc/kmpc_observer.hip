@@ -12,29 +12,13 @@
 
 #include "../../include/kmpc.h"   // KMPC_OBS_*, KMPC_OBSPAR_*, KMPC_EST_FLAG_*: record and row layouts
 #include "kmpc_dispatch.h"
+#include "kmpc_stage.h"   // wrap, clip, finite
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int NS = 7, NP = 28;   // states, words of the upper triangle
-
-__device__ __forceinline__ bool obs_finite(double a) { return fabs(a) <= 1.7976931348623157e308; }   // false for NaN and +-inf
-
-// kmpc_estimate_batch's wrap: an angle inside [-pi, pi) passes unchanged
-__device__ __forceinline__ double obs_wrap(double a)
-{
-    const double pi = 3.141592653589793, p2 = 2.0 * pi;
-    if (!(a >= -pi && a < pi)) {
-        double md = fmod(a + pi, p2);
-        if (md < 0.0) md += p2;
-        a = md - pi;
-    }
-    return a;
-}
-
-// compare-and-select, as the road kernel's: inside the cap a keeps its own bits
-__device__ __forceinline__ double obs_clip(double a, double cap) { return a > cap ? cap : (a < -cap ? -cap : a); }
 
 // index of P_ij in the row-major upper triangle, either order of i and j
 __device__ __forceinline__ constexpr int tri(int i, int j) { return i <= j ? i * NS - (i * (i - 1)) / 2 + (j - i) : j * NS - (j * (j - 1)) / 2 + (i - j); }
@@ -85,7 +69,7 @@ __global__ __launch_bounds__(256) void kmpc_observe_kernel(int B, double *__rest
         bool ok = true;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            if (!obs_finite(zz[c])) { ok = false; flags |= 1 << c; }
+            if (!stage::finite(zz[c])) { ok = false; flags |= 1 << c; }
         }
         if (ok) {
 #pragma unroll
@@ -120,7 +104,7 @@ __global__ __launch_bounds__(256) void kmpc_observe_kernel(int B, double *__rest
         F[2][5] = dt * (v / L_b * (cb * bp)); F[3][6] = dt;
         xh[0] = xh[0] + dt * (v * c);
         xh[1] = xh[1] + dt * (v * s);
-        xh[2] = obs_wrap(xh[2] + dt * (v / L_b * sb));
+        xh[2] = stage::wrap(xh[2] + dt * (v / L_b * sb));
         const double vn = v + dt * (acc + xh[6]);
         xh[3] = vn < 0.0 ? 0.0 : vn;
         // P <- F P F^T on the upper triangle, a row of A = F P at a time (header comment); sums left to right, the estimator's terms first
@@ -159,9 +143,9 @@ __global__ __launch_bounds__(256) void kmpc_observe_kernel(int B, double *__rest
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) {
             double nu = zz[ch] - xh[ch];
-            if (ch == 2) nu = obs_wrap(nu);
+            if (ch == 2) nu = stage::wrap(nu);
             const double S = P[tri(ch, ch)] + r2[ch];
-            const bool skip = !obs_finite(zz[ch]) || !(S > 0.0 && obs_finite(S)) || (gate > 0.0 && nu * nu > gate * gate * S);
+            const bool skip = !stage::finite(zz[ch]) || !(S > 0.0 && stage::finite(S)) || (gate > 0.0 && nu * nu > gate * gate * S);
             if (skip) {
                 flags |= 1 << ch;
                 ++nskip;
@@ -180,16 +164,16 @@ __global__ __launch_bounds__(256) void kmpc_observe_kernel(int B, double *__rest
                 nu_out[ch] = nu / sqrt(S);
             }
         }
-        xh[2] = obs_wrap(xh[2]);
+        xh[2] = stage::wrap(xh[2]);
         xh[3] = xh[3] < 0.0 ? 0.0 : xh[3];
         count = count + 1.0;
         skipped = skipped + (double)nskip;
         // ---- containment: a record with a non-finite word does not survive the call
-        bool ok = obs_finite(count) && obs_finite(skipped);
+        bool ok = stage::finite(count) && stage::finite(skipped);
 #pragma unroll
-        for (int a = 0; a < NS; ++a) ok = ok && obs_finite(xh[a]);
+        for (int a = 0; a < NS; ++a) ok = ok && stage::finite(xh[a]);
 #pragma unroll
-        for (int m = 0; m < NP; ++m) ok = ok && obs_finite(P[m]);
+        for (int m = 0; m < NP; ++m) ok = ok && stage::finite(P[m]);
         if (!ok) {
             fresh_out = true;
             flags |= KMPC_EST_FLAG_RESET;
@@ -211,7 +195,7 @@ __global__ __launch_bounds__(256) void kmpc_observe_kernel(int B, double *__rest
     rp[KMPC_OBS_COUNT] = count; rp[KMPC_OBS_SKIPPED] = skipped;
     rp[37] = 0.0; rp[38] = 0.0; rp[39] = 0.0;
     double *eo = est_out + 4 * (size_t)i;
-    const double psi_out = obs_wrap(xh[2] + obs_clip(xh[4], psi_cap));
+    const double psi_out = stage::wrap(xh[2] + stage::clip(xh[4], psi_cap));
     const bool z_out = fresh_out || init;
     eo[0] = z_out ? zz[0] : xh[0];
     eo[1] = z_out ? zz[1] : xh[1];
@@ -238,8 +222,8 @@ __global__ __launch_bounds__(256) void kmpc_cmd_offset_kernel(int B, const doubl
     if (latch && latch[i]) return;
     const double *rp = rec + KMPC_OBS_WORDS * (size_t)i;
     const double dd = rp[KMPC_OBS_DDELTA], da = rp[KMPC_OBS_DA], count = rp[KMPC_OBS_COUNT];
-    if (count == 0.0 || !obs_finite(dd) || !obs_finite(da)) return;
-    const double ca = obs_clip(da, acc_cap), cd = obs_clip(dd, df_cap);
+    if (count == 0.0 || !stage::finite(dd) || !stage::finite(da)) return;
+    const double ca = stage::clip(da, acc_cap), cd = stage::clip(dd, df_cap);
     double *cp = cmd + 2 * (size_t)i;
     if (ca != 0.0) cp[0] = cp[0] - ca;
     if (cd != 0.0) cp[1] = cp[1] - cd;

@@ -10,6 +10,7 @@
 
 #include "../../include/kmpc.h"   // KMPC_PLANT_*, KMPC_SENSOR_*: the row layouts
 #include "kmpc_dispatch.h"
+#include "kmpc_stage.h"
 
 #pragma clang fp contract(off)
 
@@ -70,59 +71,116 @@ __device__ __forceinline__ void sim_sincos_poly(double x, double *s, double *c)
     *c = ((q + 1) & 2) ? -cc : cc;
 }
 
+// a road row's constants of a call (sim_substep<true> only): KMPC_ROAD_*; lim = mu x the static axle load
+struct sim_road { double a_long, a_lat, df_offset, acc_gain, lim_f, lim_r; };
+
+// the plant's state: X, Y, psi, vx, vy, wz and the two lagged actuators, as a row of `state` [B,8] holds it
+struct sim_state { double X, Y, psi, vx, vy, wz, acc, df; };
+
+// grip bookkeeping of a call (sim_substep<true> only)
+struct sim_grip {
+    int sat_f, sat_r;          // clipped sub-steps
+    double peak_f, peak_r;     // largest |C_alpha alpha| [N]
+};
+
+// ONE Euler sub-step of 1 ms (vehicle_simulator.py:75-113) towards the targets (acc_des, df_des): the body of all four plant kernels.
+// The state comes in BY VALUE and the new state goes out through `n` (the grip bookkeeping likewise, g -> gn), and each word of `n` is written where
+// it is computed: a kernel's own state variables then never have their address taken, so they are promoted to registers before inlining exactly as
+// when the body stood in the kernel, and the velocities are not sunk behind the wrap's branch.  With the state passed by reference the four kernels
+// computed the same bits on another schedule, 1 - 3 % slower at one wave per SIMD (profiles/stage_refactor_ab.txt).
+// ROAD adds what include/kmpc.h lists for kmpc_sim_advance_road, each in a statement of its own after the expression it extends: the tyre model
+// reads dfe = df + DF_OFFSET, vx's derivative acce = ACC_GAIN * acc, each axle's force is clipped at its limit (stage::clip: inside the limit the
+// force keeps its own bits, a NaN passes) and counted, and the two specific forces are added after the sums they join -- so a neutral row
+// (inf, inf, 0, 0, 0, 1) leaves the state of sim_substep<false> bit for bit.  The polynomials' ranges are statements about the state, not about the
+// parameters, so one wave-uniform test picks between them and the library for every plant.
+template <bool ROAD>
+__device__ __forceinline__ void sim_substep(const sim_state z, sim_state &n, double acc_des, double df_des, double lf, double lr, double inv_m,
+                                            double inv_Iz, double C_alpha_f, double C_alpha_r, double k_acc, double k_df, const sim_road rd, const sim_grip g,
+                                            sim_grip &gn)
+{
+    const double X = z.X, Y = z.Y, psi = z.psi, vx = z.vx, vy = z.vy, wz = z.wz, acc = z.acc, df = z.df;
+    const double deltaT = 0.01 / 10.0;                              // dt_model / disc_steps, :24,:69
+    const double pi = 3.141592653589793;
+    const bool moving = fabs(vx) > 1e-6;                            // :75
+    const double yf = vy + lf * wz, yr = vy - lf * wz;              // :76, :77 (lf where lr is expected -- as in the reference)
+    const double rvx = sim_rcp(vx);
+    const double tf = yf * rvx, tr = yr * rvx;
+    double dfe = df, acce = acc;
+    if constexpr (ROAD) {
+        dfe = df + rd.df_offset;                                     // the tyre angle the tyre model reads
+        acce = rd.acc_gain * acc;                                    // the acceleration that acts
+    }
+    // polynomial ranges: x > 0 and |y / x| <= 1/8 for the slip angles (a caller-written state may carry vx < 0: atan2's own quadrant logic),
+    // |d_f| <= 0.6, |psi| <= 4
+    const bool in_range = (!moving || (vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) && fabs(dfe) <= 0.6 && fabs(psi) <= 4.0;
+    double af = sim_atan_poly(tf), ar = sim_atan_poly(tr), cd = sim_cos_poly(dfe * dfe), sp, cp;
+    sim_sincos_poly(psi, &sp, &cp);
+    if (__any(!in_range)) {   // wave-uniform: some lane is outside a polynomial's range -> the library calls (per lane, where needed)
+        if (moving && !(vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) { af = atan2(yf, vx); ar = atan2(yr, vx); }
+        if (!(fabs(dfe) <= 0.6)) cd = cos(dfe);
+        if (!(fabs(psi) <= 4.0)) sincos(psi, &sp, &cp);
+    }
+    const double alpha_f = moving ? dfe - af : 0.0;                 // :76
+    const double alpha_r = moving ? -ar : 0.0;                      // :77
+    double Fyf = C_alpha_f * alpha_f, Fyr = C_alpha_r * alpha_r;    // :80-81: what the linear tyre asks for
+    if constexpr (ROAD) {
+        const double Ff = Fyf, Fr = Fyr;
+        Fyf = stage::clip(Ff, rd.lim_f);
+        Fyr = stage::clip(Fr, rd.lim_r);
+        gn.sat_f = g.sat_f + ((Ff > rd.lim_f || Ff < -rd.lim_f) ? 1 : 0);
+        gn.sat_r = g.sat_r + ((Fr > rd.lim_r || Fr < -rd.lim_r) ? 1 : 0);
+        gn.peak_f = fabs(Ff) > g.peak_f ? fabs(Ff) : g.peak_f;
+        gn.peak_r = fabs(Fr) > g.peak_r ? fabs(Fr) : g.peak_r;
+    }
+    // :84 reads `acc - 1/m*Fyf*np.sin(self.df) + self.wz*self.vy` with m = 1840 an int: the reference is Python 2 (print statements,
+    // no `from __future__ import division`), so 1/m is INTEGER division = 0 and the lateral-force drag term vanishes (:88 uses 1.0/m)
+    double vx_s = vx + deltaT * (acce + wz * vy);
+    if constexpr (ROAD) vx_s = vx_s + deltaT * rd.a_long;
+    const double vx_n = fmax(0.0, vx_s);
+    const bool fwd = vx_n > 1e-6;                                   // :87
+    double vy_c = vy + deltaT * (inv_m * (Fyf * cd + Fyr) - wz * vx);                    // :88
+    if constexpr (ROAD) vy_c = vy_c + deltaT * rd.a_lat;
+    const double wz_c = wz + deltaT * (inv_Iz * (lf * Fyf * cd - lr * Fyr));             // :89
+    const double vy_n = fwd ? vy_c : 0.0, wz_n = fwd ? wz_c : 0.0;                         // :91-92
+    const double psi_n = psi + deltaT * wz;                         // :94
+    const double X_n = X + deltaT * (vx * cp - vy * sp);            // :95
+    const double Y_n = Y + deltaT * (vx * sp + vy * cp);            // :96
+    n.X = X_n; n.Y = Y_n;
+    n.vx = vx_n; n.vy = vy_n; n.wz = wz_n;
+    const double a = psi_n + pi, p2 = 2.0 * pi;                     // :101  python's float % : result has the divisor's sign
+    double md = a;
+    const bool wrap = !(a >= 0.0 && a < p2);                        // (a % p2 == a exactly while a is inside [0, p2))
+    if (__any(wrap)) {
+        if (wrap) {
+            md = fmod(a, p2);
+            if (md < 0.0) md += p2;
+        }
+    }
+    n.psi = md - pi;
+    n.acc = k_acc * (acc_des - acc) * deltaT + acc;                 // :112
+    n.df = k_df * (df_des - df) * deltaT + df;                    // :113
+}
+
+// without a road row
+__device__ __forceinline__ void sim_substep(const sim_state z, sim_state &n, double acc_des, double df_des, double lf, double lr, double inv_m,
+                                            double inv_Iz, double C_alpha_f, double C_alpha_r, double k_acc, double k_df)
+{
+    sim_grip gn;
+    sim_substep<false>(z, n, acc_des, df_des, lf, lr, inv_m, inv_Iz, C_alpha_f, C_alpha_r, k_acc, k_df, sim_road{}, sim_grip{}, gn);
+}
+
+// the reference's plant: its constants, one command per call, the 10 n_updates sub-steps in one loop
 __global__ __launch_bounds__(256) void kmpc_sim_kernel(int B, double *__restrict__ state, const double *__restrict__ cmd, int n_updates)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
-    const double lf = 1.152, lr = 1.693, m = 1840.0, Iz = 3477.0;   // vehicle_simulator.py:61-65
-    const double C_alpha_f = 4.0703e4, C_alpha_r = 6.4495e4;        // :66-67
-    const double deltaT = 0.01 / 10.0;                              // dt_model / disc_steps, :24,:69
-    const double pi = 3.141592653589793;
     double *s = state + 8 * (size_t)i;
     double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
     const double acc_des = cmd[2 * (size_t)i], df_des = cmd[2 * (size_t)i + 1];
-    for (int it = 0; it < n_updates * 10; ++it) {
-        const bool moving = fabs(vx) > 1e-6;                        // :75
-        const double yf = vy + lf * wz, yr = vy - lf * wz;          // :76, :77 (lf where lr is expected -- as in the reference)
-        const double rvx = sim_rcp(vx);
-        const double tf = yf * rvx, tr = yr * rvx;
-        // polynomial ranges: x > 0 and |y / x| <= 1/8 for the slip angles (a caller-written state may carry vx < 0: atan2's own quadrant logic),
-        // |d_f| <= 0.6, |psi| <= 4
-        const bool in_range = (!moving || (vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) && fabs(df) <= 0.6 && fabs(psi) <= 4.0;
-        double af = sim_atan_poly(tf), ar = sim_atan_poly(tr), cd = sim_cos_poly(df * df), sp, cp;
-        sim_sincos_poly(psi, &sp, &cp);
-        if (__any(!in_range)) {   // wave-uniform: some lane is outside a polynomial's range -> the library calls (per lane, where needed)
-            if (moving && !(vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) { af = atan2(yf, vx); ar = atan2(yr, vx); }
-            if (!(fabs(df) <= 0.6)) cd = cos(df);
-            if (!(fabs(psi) <= 4.0)) sincos(psi, &sp, &cp);
-        }
-        const double alpha_f = moving ? df - af : 0.0;              // :76
-        const double alpha_r = moving ? -ar : 0.0;                  // :77
-        const double Fyf = C_alpha_f * alpha_f, Fyr = C_alpha_r * alpha_r;  // :80-81
-        // :84 reads `acc - 1/m*Fyf*np.sin(self.df) + self.wz*self.vy` with m = 1840 an int: the reference is Python 2 (print statements,
-        // no `from __future__ import division`), so 1/m is INTEGER division = 0 and the lateral-force drag term vanishes (:88 uses 1.0/m)
-        const double vx_n = fmax(0.0, vx + deltaT * (acc + wz * vy));
-        const bool fwd = vx_n > 1e-6;                               // :87
-        const double vy_c = vy + deltaT * (1.0 / m * (Fyf * cd + Fyr) - wz * vx);               // :88
-        const double wz_c = wz + deltaT * (1.0 / Iz * (lf * Fyf * cd - lr * Fyr));              // :89
-        const double vy_n = fwd ? vy_c : 0.0, wz_n = fwd ? wz_c : 0.0;                          // :91-92
-        const double psi_n = psi + deltaT * wz;                     // :94
-        const double X_n = X + deltaT * (vx * cp - vy * sp);        // :95
-        const double Y_n = Y + deltaT * (vx * sp + vy * cp);        // :96
-        X = X_n; Y = Y_n;
-        const double a = psi_n + pi, p2 = 2.0 * pi;                 // :101  python's float % : result has the divisor's sign
-        double md = a;
-        const bool wrap = !(a >= 0.0 && a < p2);                    // (a % p2 == a exactly while a is inside [0, p2))
-        if (__any(wrap)) {
-            if (wrap) {
-                md = fmod(a, p2);
-                if (md < 0.0) md += p2;
-            }
-        }
-        psi = md - pi;
-        vx = vx_n; vy = vy_n; wz = wz_n;
-        acc = 5.0 * (acc_des - acc) * deltaT + acc;                 // :112
-        df = 5.0 * (df_des - df) * deltaT + df;                     // :113
+    for (int it = 0; it < n_updates * 10; ++it) {   // vehicle_simulator.py:61-67, :112-113: the reference's constants (the two quotients are folded)
+        sim_state n;
+        sim_substep(sim_state{X, Y, psi, vx, vy, wz, acc, df}, n, acc_des, df_des, 1.152, 1.693, 1.0 / 1840.0, 1.0 / 3477.0, 4.0703e4, 6.4495e4, 5.0, 5.0);
+        X = n.X; Y = n.Y; psi = n.psi; vx = n.vx; vy = n.vy; wz = n.wz; acc = n.acc; df = n.df;
     }
     s[0] = X; s[1] = Y; s[2] = psi; s[3] = vx; s[4] = vy; s[5] = wz; s[6] = acc; s[7] = df;
 }
@@ -133,13 +191,10 @@ hipError_t kmpc_launch_sim(int B, double *state, const double *cmd, int n_update
     return hipGetLastError();
 }
 
-// A plant per vehicle (kmpc_sim_advance_plant): kmpc_sim_kernel's sub-step, operation for operation, with the eight literals read from the
-// vehicle's row `plant` [B,8] (KMPC_PLANT_*) and kept in registers across all sub-steps -- 64 B more read per vehicle and call.  The polynomials'
-// ranges are statements about the state, not about the parameters, so the same wave-uniform test picks between them and the library.  1 / m and
-// 1 / Iz are divided once (correctly rounded, as the compiler folds 1.0 / 1840.0 above) and multiplied as the source does: a row holding
-// kmpc_plant_default's values gives kmpc_sim_kernel's results bit for bit.
-// Command delay: the first d = clamp(cmd_delay[i], 0, n_updates) updates (10 sub-steps each) run towards cmd_held[i], the rest towards cmd[i];
-// the target is a select per update, so lanes with different delays stay in one loop.  cmd[i] is then written to cmd_held[i].
+// A plant per vehicle (kmpc_sim_advance_plant): the eight constants come from the vehicle's row `plant` [B,8] (KMPC_PLANT_*) -- 64 B more read per
+// vehicle and call; a row holding kmpc_plant_default's values gives kmpc_sim_kernel's results bit for bit.
+// Command delay: the first d = clamp(cmd_delay[i], 0, n_updates) updates (10 sub-steps each) run towards cmd_held[i], the rest towards cmd[i]; the
+// target is a select per update, so lanes with different delays stay in one loop.  cmd[i] is then written to cmd_held[i].
 __global__ __launch_bounds__(256) void kmpc_sim_plant_kernel(int B, double *__restrict__ state, const double *__restrict__ cmd,
                                                              const double *__restrict__ plant, const int32_t *__restrict__ cmd_delay,
                                                              double *__restrict__ cmd_held, int n_updates)
@@ -150,9 +205,7 @@ __global__ __launch_bounds__(256) void kmpc_sim_plant_kernel(int B, double *__re
     const double lf = pr[KMPC_PLANT_LF], lr = pr[KMPC_PLANT_LR], m = pr[KMPC_PLANT_M], Iz = pr[KMPC_PLANT_IZ];
     const double C_alpha_f = pr[KMPC_PLANT_C_ALPHA_F], C_alpha_r = pr[KMPC_PLANT_C_ALPHA_R];
     const double k_acc = pr[KMPC_PLANT_K_ACC], k_df = pr[KMPC_PLANT_K_DF];
-    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;
-    const double deltaT = 0.01 / 10.0;
-    const double pi = 3.141592653589793;
+    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;   // divided once (correctly rounded, as the compiler folds 1.0 / 1840.0), multiplied as the source does
     double *s = state + 8 * (size_t)i;
     double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
     const double acc_new = cmd[2 * (size_t)i], df_new = cmd[2 * (size_t)i + 1];
@@ -166,43 +219,9 @@ __global__ __launch_bounds__(256) void kmpc_sim_plant_kernel(int B, double *__re
         const double acc_des = up < d ? acc_old : acc_new, df_des = up < d ? df_old : df_new;   // the target changes between updates only
 #pragma unroll 1
         for (int it = 0; it < 10; ++it) {
-            const bool moving = fabs(vx) > 1e-6;
-            const double yf = vy + lf * wz, yr = vy - lf * wz;          // lf where lr is expected -- as in the reference
-            const double rvx = sim_rcp(vx);
-            const double tf = yf * rvx, tr = yr * rvx;
-            const bool in_range = (!moving || (vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) && fabs(df) <= 0.6 && fabs(psi) <= 4.0;
-            double af = sim_atan_poly(tf), ar = sim_atan_poly(tr), cd = sim_cos_poly(df * df), sp, cp;
-            sim_sincos_poly(psi, &sp, &cp);
-            if (__any(!in_range)) {
-                if (moving && !(vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) { af = atan2(yf, vx); ar = atan2(yr, vx); }
-                if (!(fabs(df) <= 0.6)) cd = cos(df);
-                if (!(fabs(psi) <= 4.0)) sincos(psi, &sp, &cp);
-            }
-            const double alpha_f = moving ? df - af : 0.0;
-            const double alpha_r = moving ? -ar : 0.0;
-            const double Fyf = C_alpha_f * alpha_f, Fyr = C_alpha_r * alpha_r;
-            const double vx_n = fmax(0.0, vx + deltaT * (acc + wz * vy));   // no Fyf * sin(df) / m term -- as in the reference
-            const bool fwd = vx_n > 1e-6;
-            const double vy_c = vy + deltaT * (inv_m * (Fyf * cd + Fyr) - wz * vx);
-            const double wz_c = wz + deltaT * (inv_Iz * (lf * Fyf * cd - lr * Fyr));
-            const double vy_n = fwd ? vy_c : 0.0, wz_n = fwd ? wz_c : 0.0;
-            const double psi_n = psi + deltaT * wz;
-            const double X_n = X + deltaT * (vx * cp - vy * sp);
-            const double Y_n = Y + deltaT * (vx * sp + vy * cp);
-            X = X_n; Y = Y_n;
-            const double a = psi_n + pi, p2 = 2.0 * pi;
-            double md = a;
-            const bool wrap = !(a >= 0.0 && a < p2);
-            if (__any(wrap)) {
-                if (wrap) {
-                    md = fmod(a, p2);
-                    if (md < 0.0) md += p2;
-                }
-            }
-            psi = md - pi;
-            vx = vx_n; vy = vy_n; wz = wz_n;
-            acc = k_acc * (acc_des - acc) * deltaT + acc;
-            df = k_df * (df_des - df) * deltaT + df;
+            sim_state n;
+            sim_substep(sim_state{X, Y, psi, vx, vy, wz, acc, df}, n, acc_des, df_des, lf, lr, inv_m, inv_Iz, C_alpha_f, C_alpha_r, k_acc, k_df);
+            X = n.X; Y = n.Y; psi = n.psi; vx = n.vx; vy = n.vy; wz = n.wz; acc = n.acc; df = n.df;
         }
     }
     s[0] = X; s[1] = Y; s[2] = psi; s[3] = vx; s[4] = vy; s[5] = wz; s[6] = acc; s[7] = df;
@@ -231,17 +250,12 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
 }
 
-__global__ __launch_bounds__(256) void kmpc_sense_kernel(int B, const double *__restrict__ state, const double *__restrict__ sensor, uint64_t seed,
-                                                         uint64_t period, uint64_t id_base, double *__restrict__ est)
+// what both measurement kernels do once the truth t = x, y, psi, vx is fetched and the four Philox words w are drawn: bias, noise, the plant's wrap
+// (:101; a heading in range passes unchanged) and the steering report's speed floor
+__device__ __forceinline__ void sim_measure(const double t[4], const double *__restrict__ sr, const uint32_t w[4], double *__restrict__ o)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B) return;
-    const uint64_t gid = id_base + (uint64_t)i;
-    uint32_t w[4];
-    philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)period, (uint32_t)(period >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    const double *sr = sensor + KMPC_SENSOR_WORDS * (size_t)i, *st = state + 8 * (size_t)i;
     double e[4];
-    for (int c = 0; c < 4; ++c) e[c] = st[c] + sr[KMPC_SENSOR_BIAS_X + c];
+    for (int c = 0; c < 4; ++c) e[c] = t[c] + sr[KMPC_SENSOR_BIAS_X + c];
     for (int h = 0; h < 2; ++h) {
         const double sg0 = sr[KMPC_SENSOR_SIGMA_X + 2 * h], sg1 = sr[KMPC_SENSOR_SIGMA_X + 2 * h + 1];
         if (sg0 != 0.0 || sg1 != 0.0) {
@@ -251,15 +265,23 @@ __global__ __launch_bounds__(256) void kmpc_sense_kernel(int B, const double *__
             if (sg1 != 0.0) e[2 * h + 1] = e[2 * h + 1] + sg1 * (r * sin(a));
         }
     }
-    const double pi = 3.141592653589793, p2 = 2.0 * pi;
-    if (!(e[2] >= -pi && e[2] < pi)) {   // the plant's wrap (:101), only where there is something to wrap: a heading in range passes unchanged
-        double md = fmod(e[2] + pi, p2);
-        if (md < 0.0) md += p2;
-        e[2] = md - pi;
-    }
+    e[2] = stage::wrap(e[2]);
     e[3] = fmax(0.0, e[3]);              // the steering report's speed is not negative
-    double *o = est + 4 * (size_t)i;
     o[0] = e[0]; o[1] = e[1]; o[2] = e[2]; o[3] = e[3];
+}
+
+__global__ __launch_bounds__(256) void kmpc_sense_kernel(int B, const double *__restrict__ state, const double *__restrict__ sensor, uint64_t seed,
+                                                         uint64_t period, uint64_t id_base, double *__restrict__ est)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const uint64_t gid = id_base + (uint64_t)i;
+    uint32_t w[4];
+    philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)period, (uint32_t)(period >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    const double *st = state + 8 * (size_t)i;
+    double t[4];
+    for (int c = 0; c < 4; ++c) t[c] = st[c];
+    sim_measure(t, sensor + KMPC_SENSOR_WORDS * (size_t)i, w, est + 4 * (size_t)i);
 }
 
 hipError_t kmpc_launch_sense(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base, double *est,
@@ -291,12 +313,41 @@ hipError_t kmpc_launch_command(int B, const double *u0, const int32_t *stop, uin
     return hipGetLastError();
 }
 
-// A command queue (kmpc_sim_advance_queue): kmpc_sim_plant_kernel with the one held command replaced by a ring of the last `depth` periods' commands,
-// cmd_queue [depth,B,2] (slot j mod depth holds period j; consecutive lanes read consecutive 16 B), so that a command may take effect several
-// control periods late.  With d = clamp(cmd_delay, 0, (depth - 1) n) = q n + r the update `up` of period p runs towards the command of period
-// p - q - (up < r): only two commands are in play per call, fetched before the loop -- the loop is kmpc_sim_plant_kernel's with its two targets
-// substituted, and the sub-step below is a COPY of that kernel's, operation for operation (the two existing kernels are not touched: a shared body
-// would have to be shown not to move their instruction streams, a copy cannot).  A period before the first (j < 0) commands (0, 0).
+// A command queue (kmpc_sim_advance_queue): the one held command replaced by a ring of the last `depth` periods' commands, cmd_queue [depth,B,2]
+// (slot j mod depth holds period j; consecutive lanes read consecutive 16 B), so that a command may take effect several control periods late.
+// With d = clamp(cmd_delay, 0, (depth - 1) n) = q n + r the update `up` of period p runs towards the command of period p - q - (up < r): only two
+// commands are in play per call.  sim_ring_commands logs this period's command, fetches the two -- period p - q (the later) and p - q - 1 (the
+// earlier, needed only when r > 0; with q == depth - 1, r is 0 and its slot is this period's); a period before the first commands (0, 0) -- and
+// returns r.
+__device__ __forceinline__ int sim_ring_commands(double *cmd_queue, int depth, int B, int i, long long period, int n_updates,
+                                                 const int32_t *__restrict__ cmd_delay, double acc_now, double df_now, double *acc_new,
+                                                 double *df_new, double *acc_old, double *df_old)
+{
+    const size_t slot_words = 2 * (size_t)B;
+    {
+        double *own = cmd_queue + (size_t)(period % depth) * slot_words + 2 * (size_t)i;
+        own[0] = acc_now; own[1] = df_now;
+    }
+    int d = cmd_delay ? cmd_delay[i] : 0;
+    const long long dmax = (long long)(depth - 1) * n_updates;   // n_updates >= 1 here (the host returns before a launch otherwise)
+    d = d < 0 ? 0 : ((long long)d > dmax ? (int)dmax : d);
+    const int q = d / n_updates, r = d % n_updates;
+    *acc_new = acc_now; *df_new = df_now; *acc_old = 0.0; *df_old = 0.0;
+    const long long jn = period - q, jo = jn - 1;
+    if (q > 0) {
+        *acc_new = 0.0; *df_new = 0.0;
+        if (jn >= 0) {
+            const double *e = cmd_queue + (size_t)(jn % depth) * slot_words + 2 * (size_t)i;
+            *acc_new = e[0]; *df_new = e[1];
+        }
+    }
+    if (r > 0 && jo >= 0) {
+        const double *e = cmd_queue + (size_t)(jo % depth) * slot_words + 2 * (size_t)i;
+        *acc_old = e[0]; *df_old = e[1];
+    }
+    return r;
+}
+
 __global__ __launch_bounds__(256) void kmpc_sim_queue_kernel(int B, double *__restrict__ state, const double *__restrict__ cmd,
                                                              const double *__restrict__ plant, const int32_t *__restrict__ cmd_delay,
                                                              double *cmd_queue, int depth, long long period, int n_updates)
@@ -307,76 +358,19 @@ __global__ __launch_bounds__(256) void kmpc_sim_queue_kernel(int B, double *__re
     const double lf = pr[KMPC_PLANT_LF], lr = pr[KMPC_PLANT_LR], m = pr[KMPC_PLANT_M], Iz = pr[KMPC_PLANT_IZ];
     const double C_alpha_f = pr[KMPC_PLANT_C_ALPHA_F], C_alpha_r = pr[KMPC_PLANT_C_ALPHA_R];
     const double k_acc = pr[KMPC_PLANT_K_ACC], k_df = pr[KMPC_PLANT_K_DF];
-    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;
-    const double deltaT = 0.01 / 10.0;
-    const double pi = 3.141592653589793;
+    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;   // divided once (correctly rounded, as the compiler folds 1.0 / 1840.0), multiplied as the source does
     double *s = state + 8 * (size_t)i;
     double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
-    const double acc_now = cmd[2 * (size_t)i], df_now = cmd[2 * (size_t)i + 1];
-    const size_t slot_words = 2 * (size_t)B;
-    {
-        double *own = cmd_queue + (size_t)(period % depth) * slot_words + 2 * (size_t)i;
-        own[0] = acc_now; own[1] = df_now;
-    }
-    int d = cmd_delay ? cmd_delay[i] : 0;
-    const long long dmax = (long long)(depth - 1) * n_updates;   // n_updates >= 1 here (the host returns before a launch otherwise)
-    d = d < 0 ? 0 : ((long long)d > dmax ? (int)dmax : d);
-    const int q = d / n_updates, r = d % n_updates;
-    // period p - q (the later of the two) and p - q - 1 (the earlier, needed only when r > 0; with q == depth - 1, r is 0 and its slot is this period's)
-    double acc_new = acc_now, df_new = df_now, acc_old = 0.0, df_old = 0.0;
-    const long long jn = period - q, jo = jn - 1;
-    if (q > 0) {
-        acc_new = 0.0; df_new = 0.0;
-        if (jn >= 0) {
-            const double *e = cmd_queue + (size_t)(jn % depth) * slot_words + 2 * (size_t)i;
-            acc_new = e[0]; df_new = e[1];
-        }
-    }
-    if (r > 0 && jo >= 0) {
-        const double *e = cmd_queue + (size_t)(jo % depth) * slot_words + 2 * (size_t)i;
-        acc_old = e[0]; df_old = e[1];
-    }
+    double acc_new, df_new, acc_old, df_old;
+    const int r = sim_ring_commands(cmd_queue, depth, B, i, period, n_updates, cmd_delay, cmd[2 * (size_t)i], cmd[2 * (size_t)i + 1], &acc_new, &df_new,
+                                    &acc_old, &df_old);
     for (int up = 0; up < n_updates; ++up) {
         const double acc_des = up < r ? acc_old : acc_new, df_des = up < r ? df_old : df_new;   // the target changes between updates only
 #pragma unroll 1
         for (int it = 0; it < 10; ++it) {
-            const bool moving = fabs(vx) > 1e-6;
-            const double yf = vy + lf * wz, yr = vy - lf * wz;          // lf where lr is expected -- as in the reference
-            const double rvx = sim_rcp(vx);
-            const double tf = yf * rvx, tr = yr * rvx;
-            const bool in_range = (!moving || (vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) && fabs(df) <= 0.6 && fabs(psi) <= 4.0;
-            double af = sim_atan_poly(tf), ar = sim_atan_poly(tr), cd = sim_cos_poly(df * df), sp, cp;
-            sim_sincos_poly(psi, &sp, &cp);
-            if (__any(!in_range)) {
-                if (moving && !(vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) { af = atan2(yf, vx); ar = atan2(yr, vx); }
-                if (!(fabs(df) <= 0.6)) cd = cos(df);
-                if (!(fabs(psi) <= 4.0)) sincos(psi, &sp, &cp);
-            }
-            const double alpha_f = moving ? df - af : 0.0;
-            const double alpha_r = moving ? -ar : 0.0;
-            const double Fyf = C_alpha_f * alpha_f, Fyr = C_alpha_r * alpha_r;
-            const double vx_n = fmax(0.0, vx + deltaT * (acc + wz * vy));   // no Fyf * sin(df) / m term -- as in the reference
-            const bool fwd = vx_n > 1e-6;
-            const double vy_c = vy + deltaT * (inv_m * (Fyf * cd + Fyr) - wz * vx);
-            const double wz_c = wz + deltaT * (inv_Iz * (lf * Fyf * cd - lr * Fyr));
-            const double vy_n = fwd ? vy_c : 0.0, wz_n = fwd ? wz_c : 0.0;
-            const double psi_n = psi + deltaT * wz;
-            const double X_n = X + deltaT * (vx * cp - vy * sp);
-            const double Y_n = Y + deltaT * (vx * sp + vy * cp);
-            X = X_n; Y = Y_n;
-            const double a = psi_n + pi, p2 = 2.0 * pi;
-            double md = a;
-            const bool wrap = !(a >= 0.0 && a < p2);
-            if (__any(wrap)) {
-                if (wrap) {
-                    md = fmod(a, p2);
-                    if (md < 0.0) md += p2;
-                }
-            }
-            psi = md - pi;
-            vx = vx_n; vy = vy_n; wz = wz_n;
-            acc = k_acc * (acc_des - acc) * deltaT + acc;
-            df = k_df * (df_des - df) * deltaT + df;
+            sim_state n;
+            sim_substep(sim_state{X, Y, psi, vx, vy, wz, acc, df}, n, acc_des, df_des, lf, lr, inv_m, inv_Iz, C_alpha_f, C_alpha_r, k_acc, k_df);
+            X = n.X; Y = n.Y; psi = n.psi; vx = n.vx; vy = n.vy; wz = n.wz; acc = n.acc; df = n.df;
         }
     }
     s[0] = X; s[1] = Y; s[2] = psi; s[3] = vx; s[4] = vy; s[5] = wz; s[6] = acc; s[7] = df;
@@ -390,11 +384,8 @@ hipError_t kmpc_launch_sim_queue(int B, double *state, const double *cmd, const 
     return hipGetLastError();
 }
 
-// Grip and road (kmpc_sim_advance_road): kmpc_sim_queue_kernel with a road row per vehicle, `road` [B,8] (KMPC_ROAD_*), kept in registers like the plant
-// row -- 64 B more read per vehicle and call.  The sub-step is a COPY of the queue kernel's, operation for operation, with the changes include/kmpc.h
-// lists: the tyre model reads dfe = df + DF_OFFSET, vx's derivative acce = ACC_GAIN * acc, each axle's force is clipped at mu times its static load
-// (compare-and-select: inside the limit the force keeps its own bits, a NaN passes), and the two specific forces are added in statements of their own
-// after the parent's expressions, so a neutral row (inf, inf, 0, 0, 0, 1) leaves the queue kernel's state bit for bit.
+// Grip and road (kmpc_sim_advance_road): the queue kernel with a road row per vehicle, `road` [B,8] (KMPC_ROAD_*), kept in registers like the plant
+// row -- 64 B more read per vehicle and call -- and sim_substep<true>.
 // Grip bookkeeping: per axle the number of clipped sub-steps and the largest |C_alpha alpha| of the call stay in registers (4 VGPRs + 2 counters);
 // the utilisation is that maximum divided by the limit ONCE after the loop (a correctly rounded division by one positive number is monotone: the
 // quotient of the maximum is the maximum of the quotients, bit for bit), so the sub-step carries no division.  road_stat [B,4] is read and
@@ -410,98 +401,35 @@ __global__ __launch_bounds__(256) void kmpc_sim_road_kernel(int B, double *__res
     const double lf = pr[KMPC_PLANT_LF], lr = pr[KMPC_PLANT_LR], m = pr[KMPC_PLANT_M], Iz = pr[KMPC_PLANT_IZ];
     const double C_alpha_f = pr[KMPC_PLANT_C_ALPHA_F], C_alpha_r = pr[KMPC_PLANT_C_ALPHA_R];
     const double k_acc = pr[KMPC_PLANT_K_ACC], k_df = pr[KMPC_PLANT_K_DF];
-    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;
+    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;   // divided once (correctly rounded, as the compiler folds 1.0 / 1840.0), multiplied as the source does
     const double *rr = road + KMPC_ROAD_WORDS * (size_t)i;
-    const double a_long = rr[KMPC_ROAD_A_LONG], a_lat = rr[KMPC_ROAD_A_LAT], df_offset = rr[KMPC_ROAD_DF_OFFSET], acc_gain = rr[KMPC_ROAD_ACC_GAIN];
-    const double lim_f = rr[KMPC_ROAD_MU_F] * (m * 9.81 * lr / (lf + lr));   // mu x the static axle loads, divided once per call
-    const double lim_r = rr[KMPC_ROAD_MU_R] * (m * 9.81 * lf / (lf + lr));
-    const double deltaT = 0.01 / 10.0;
-    const double pi = 3.141592653589793;
-    double *s = state + 8 * (size_t)i;
-    double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
-    const double acc_now = cmd[2 * (size_t)i], df_now = cmd[2 * (size_t)i + 1];
-    const size_t slot_words = 2 * (size_t)B;
-    {
-        double *own = cmd_queue + (size_t)(period % depth) * slot_words + 2 * (size_t)i;
-        own[0] = acc_now; own[1] = df_now;
-    }
-    int d = cmd_delay ? cmd_delay[i] : 0;
-    const long long dmax = (long long)(depth - 1) * n_updates;   // n_updates >= 1 here (the host returns before a launch otherwise)
-    d = d < 0 ? 0 : ((long long)d > dmax ? (int)dmax : d);
-    const int q = d / n_updates, r = d % n_updates;
-    double acc_new = acc_now, df_new = df_now, acc_old = 0.0, df_old = 0.0;
-    const long long jn = period - q, jo = jn - 1;
-    if (q > 0) {
-        acc_new = 0.0; df_new = 0.0;
-        if (jn >= 0) {
-            const double *e = cmd_queue + (size_t)(jn % depth) * slot_words + 2 * (size_t)i;
-            acc_new = e[0]; df_new = e[1];
-        }
-    }
-    if (r > 0 && jo >= 0) {
-        const double *e = cmd_queue + (size_t)(jo % depth) * slot_words + 2 * (size_t)i;
-        acc_old = e[0]; df_old = e[1];
-    }
+    const sim_road rd{rr[KMPC_ROAD_A_LONG], rr[KMPC_ROAD_A_LAT], rr[KMPC_ROAD_DF_OFFSET], rr[KMPC_ROAD_ACC_GAIN],
+                      rr[KMPC_ROAD_MU_F] * (m * 9.81 * lr / (lf + lr)),    // mu x the static axle loads, divided once per call
+                      rr[KMPC_ROAD_MU_R] * (m * 9.81 * lf / (lf + lr))};
     int sat_f = 0, sat_r = 0;           // clipped sub-steps of this call
     double peak_f = 0.0, peak_r = 0.0;  // largest |C_alpha alpha| of this call [N]
+    double *s = state + 8 * (size_t)i;
+    double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
+    double acc_new, df_new, acc_old, df_old;
+    const int r = sim_ring_commands(cmd_queue, depth, B, i, period, n_updates, cmd_delay, cmd[2 * (size_t)i], cmd[2 * (size_t)i + 1], &acc_new, &df_new,
+                                    &acc_old, &df_old);
     for (int up = 0; up < n_updates; ++up) {
         const double acc_des = up < r ? acc_old : acc_new, df_des = up < r ? df_old : df_new;   // the target changes between updates only
 #pragma unroll 1
         for (int it = 0; it < 10; ++it) {
-            const bool moving = fabs(vx) > 1e-6;
-            const double yf = vy + lf * wz, yr = vy - lf * wz;          // lf where lr is expected -- as in the reference
-            const double rvx = sim_rcp(vx);
-            const double tf = yf * rvx, tr = yr * rvx;
-            const double dfe = df + df_offset;                          // the tyre angle the tyre model reads
-            const double acce = acc_gain * acc;                         // the acceleration that acts
-            const bool in_range = (!moving || (vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) && fabs(dfe) <= 0.6 && fabs(psi) <= 4.0;
-            double af = sim_atan_poly(tf), ar = sim_atan_poly(tr), cd = sim_cos_poly(dfe * dfe), sp, cp;
-            sim_sincos_poly(psi, &sp, &cp);
-            if (__any(!in_range)) {
-                if (moving && !(vx > 0.0 && fabs(tf) <= 0.125 && fabs(tr) <= 0.125)) { af = atan2(yf, vx); ar = atan2(yr, vx); }
-                if (!(fabs(dfe) <= 0.6)) cd = cos(dfe);
-                if (!(fabs(psi) <= 4.0)) sincos(psi, &sp, &cp);
-            }
-            const double alpha_f = moving ? dfe - af : 0.0;
-            const double alpha_r = moving ? -ar : 0.0;
-            const double Ff = C_alpha_f * alpha_f, Fr = C_alpha_r * alpha_r;   // what the linear tyre asks for
-            const double Fyf = Ff > lim_f ? lim_f : (Ff < -lim_f ? -lim_f : Ff);
-            const double Fyr = Fr > lim_r ? lim_r : (Fr < -lim_r ? -lim_r : Fr);
-            sat_f += (Ff > lim_f || Ff < -lim_f) ? 1 : 0;
-            sat_r += (Fr > lim_r || Fr < -lim_r) ? 1 : 0;
-            peak_f = fabs(Ff) > peak_f ? fabs(Ff) : peak_f;
-            peak_r = fabs(Fr) > peak_r ? fabs(Fr) : peak_r;
-            const double vx0 = vx + deltaT * (acce + wz * vy);          // no Fyf * sin(df) / m term -- as in the reference
-            const double vx_n = fmax(0.0, vx0 + deltaT * a_long);
-            const bool fwd = vx_n > 1e-6;
-            const double vy0 = vy + deltaT * (inv_m * (Fyf * cd + Fyr) - wz * vx);
-            const double vy_c = vy0 + deltaT * a_lat;
-            const double wz_c = wz + deltaT * (inv_Iz * (lf * Fyf * cd - lr * Fyr));
-            const double vy_n = fwd ? vy_c : 0.0, wz_n = fwd ? wz_c : 0.0;
-            const double psi_n = psi + deltaT * wz;
-            const double X_n = X + deltaT * (vx * cp - vy * sp);
-            const double Y_n = Y + deltaT * (vx * sp + vy * cp);
-            X = X_n; Y = Y_n;
-            const double a = psi_n + pi, p2 = 2.0 * pi;
-            double md = a;
-            const bool wrap = !(a >= 0.0 && a < p2);
-            if (__any(wrap)) {
-                if (wrap) {
-                    md = fmod(a, p2);
-                    if (md < 0.0) md += p2;
-                }
-            }
-            psi = md - pi;
-            vx = vx_n; vy = vy_n; wz = wz_n;
-            acc = k_acc * (acc_des - acc) * deltaT + acc;
-            df = k_df * (df_des - df) * deltaT + df;
+            sim_state n;
+            sim_grip gn;
+            sim_substep<true>(sim_state{X, Y, psi, vx, vy, wz, acc, df}, n, acc_des, df_des, lf, lr, inv_m, inv_Iz, C_alpha_f, C_alpha_r, k_acc, k_df, rd,
+                              sim_grip{sat_f, sat_r, peak_f, peak_r}, gn);
+            X = n.X; Y = n.Y; psi = n.psi; vx = n.vx; vy = n.vy; wz = n.wz; acc = n.acc; df = n.df;
+            sat_f = gn.sat_f; sat_r = gn.sat_r; peak_f = gn.peak_f; peak_r = gn.peak_r;
         }
     }
     s[0] = X; s[1] = Y; s[2] = psi; s[3] = vx; s[4] = vy; s[5] = wz; s[6] = acc; s[7] = df;
     if (road_stat) {
         double *rs = road_stat + KMPC_ROAD_STAT_WORDS * (size_t)i;
         const double c_f = rs[KMPC_ROAD_STAT_SAT_F], c_r = rs[KMPC_ROAD_STAT_SAT_R], u_f = rs[KMPC_ROAD_STAT_UTIL_F], u_r = rs[KMPC_ROAD_STAT_UTIL_R];
-        const double n_f = peak_f / lim_f, n_r = peak_r / lim_r;   // an infinite limit: 0 by the division itself
+        const double n_f = peak_f / rd.lim_f, n_r = peak_r / rd.lim_r;   // an infinite limit: 0 by the division itself
         rs[KMPC_ROAD_STAT_SAT_F] = c_f + (double)sat_f; rs[KMPC_ROAD_STAT_SAT_R] = c_r + (double)sat_r;
         rs[KMPC_ROAD_STAT_UTIL_F] = n_f > u_f ? n_f : u_f; rs[KMPC_ROAD_STAT_UTIL_R] = n_r > u_r ? n_r : u_r;
     }
@@ -518,7 +446,7 @@ hipError_t kmpc_launch_sim_road(int B, double *state, const double *cmd, const d
 // Stale fixes (kmpc_sense_delayed_batch): kmpc_sense_kernel measuring the truth of period - L instead of this period's.  This period's x, y, psi, vx go
 // into slot period mod depth of truth_ring [depth,B,4] (consecutive lanes write consecutive 32 B) and the measured truth comes out of slot
 // (period - L) mod depth, L = clamp(meas_delay, 0, min(depth - 1, period)); bias and noise are this period's (counter = (vehicle id, period)): noise
-// belongs to the moment of emission.  The arithmetic after the fetch is kmpc_sense_kernel's, operation for operation (a copy: that kernel stays).
+// belongs to the moment of emission.
 __global__ __launch_bounds__(256) void kmpc_sense_delayed_kernel(int B, const double *__restrict__ state, const double *__restrict__ sensor, uint64_t seed,
                                                                  uint64_t period, uint64_t id_base, const int32_t *__restrict__ meas_delay,
                                                                  double *truth_ring, int depth, double *__restrict__ est)
@@ -528,7 +456,7 @@ __global__ __launch_bounds__(256) void kmpc_sense_delayed_kernel(int B, const do
     const uint64_t gid = id_base + (uint64_t)i;
     uint32_t w[4];
     philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)period, (uint32_t)(period >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    const double *sr = sensor + KMPC_SENSOR_WORDS * (size_t)i, *st = state + 8 * (size_t)i;
+    const double *st = state + 8 * (size_t)i;
     const size_t slot_words = 4 * (size_t)B;
     double t[4];
     for (int c = 0; c < 4; ++c) t[c] = st[c];
@@ -543,26 +471,7 @@ __global__ __launch_bounds__(256) void kmpc_sense_delayed_kernel(int B, const do
         const double *old = truth_ring + (size_t)((period - L) % (uint64_t)depth) * slot_words + 4 * (size_t)i;
         for (int c = 0; c < 4; ++c) t[c] = old[c];
     }
-    double e[4];
-    for (int c = 0; c < 4; ++c) e[c] = t[c] + sr[KMPC_SENSOR_BIAS_X + c];
-    for (int h = 0; h < 2; ++h) {
-        const double sg0 = sr[KMPC_SENSOR_SIGMA_X + 2 * h], sg1 = sr[KMPC_SENSOR_SIGMA_X + 2 * h + 1];
-        if (sg0 != 0.0 || sg1 != 0.0) {
-            const double u0 = ((double)w[2 * h] + 0.5) * 0x1p-32, u1 = ((double)w[2 * h + 1] + 0.5) * 0x1p-32;
-            const double r = sqrt(-2.0 * log(u0)), a = 6.283185307179586 * u1;
-            if (sg0 != 0.0) e[2 * h] = e[2 * h] + sg0 * (r * cos(a));
-            if (sg1 != 0.0) e[2 * h + 1] = e[2 * h + 1] + sg1 * (r * sin(a));
-        }
-    }
-    const double pi = 3.141592653589793, p2 = 2.0 * pi;
-    if (!(e[2] >= -pi && e[2] < pi)) {
-        double md = fmod(e[2] + pi, p2);
-        if (md < 0.0) md += p2;
-        e[2] = md - pi;
-    }
-    e[3] = fmax(0.0, e[3]);
-    double *o = est + 4 * (size_t)i;
-    o[0] = e[0]; o[1] = e[1]; o[2] = e[2]; o[3] = e[3];
+    sim_measure(t, sensor + KMPC_SENSOR_WORDS * (size_t)i, w, est + 4 * (size_t)i);
 }
 
 hipError_t kmpc_launch_sense_delayed(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base,
