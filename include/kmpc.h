@@ -469,6 +469,114 @@ int32_t kmpc_sim_advance_road(int32_t device, int32_t B, void *state, const void
                               const int32_t *cmd_delay, void *cmd_queue, int32_t depth, int64_t period, int32_t n_updates, void *road_stat,
                               void *stream);
 
+/* ---- low-level controller (L0 actuation) and a pedal-driven plant ---------------------------------------------------------------------------
+ * On the reference's vehicle MPC_cmd never acts as an acceleration and a tyre angle: the 50 Hz node src/LowLevelController.cpp (with PidControl.h
+ * and LowPass.h; SURVEY.md section 2, component 11) turns it into a throttle fraction, a brake torque and a steering-wheel angle.  One TICK is one
+ * recvSteeringReport (:205-226) followed by one controlCallback (:111-198) with sys_enable_ true, for one vehicle, in fp64, no product and sum
+ * contracted, with the parameter row `llc` [B,8] fp64 DEVICE, row of vehicle b: */
+enum {
+    KMPC_LLC_KP = 0,              /* proportional gain of the throttle loop (:49: 0.8) */
+    KMPC_LLC_KI = 1,              /* integral gain (:50: 0.4) */
+    KMPC_LLC_ACCEL_MAX = 2,       /* the command is clamped to [-DECEL_MAX, ACCEL_MAX] (:71-72, :123-128: 1.0, 1.0) [m/s^2] */
+    KMPC_LLC_DECEL_MAX = 3,
+    KMPC_LLC_STEER_RATIO = 4,     /* steering wheel angle per tyre angle as the CONTROLLER believes it (:66: 14.8) */
+    KMPC_LLC_MASS = 5,            /* the mass the brake law multiplies by (.h:116 BASE_VEHICLE_MASS = 1847.78 at fuel level 0, :118) [kg] */
+    KMPC_LLC_BRAKE_DEADBAND = 6,  /* no brake unless the clamped command is below minus this (.h:114: 0.1) [m/s^2] */
+    KMPC_LLC_WHEEL_RADIUS = 7,    /* the radius the brake law multiplies by (.h:115: 0.33) [m] */
+    KMPC_LLC_WORDS = 8
+};
+/* and the record `llc_rec` [B,16] fp64 DEVICE in/out, 128 bytes per vehicle; all zeros is the reference's freshly constructed node: */
+enum {
+    KMPC_LLCREC_INT = 0,          /* PidControl::int_val_ */
+    KMPC_LLCREC_LPF = 1,          /* lpf_accel_'s last_val_: the low-passed measured acceleration [m/s^2] */
+    KMPC_LLCREC_READY = 2,        /* lpf_accel_'s ready_ (0 or 1) */
+    KMPC_LLCREC_V_LAST = 3,       /* actual_.linear.x: the speed of the previous report [m/s] */
+    KMPC_LLCREC_TH_CMD = 4,       /* last published throttle fraction, 0 ... 1 */
+    KMPC_LLCREC_BR_CMD = 5,       /* last published brake torque [N m] */
+    KMPC_LLCREC_WHEEL_CMD = 6,    /* last published steering-wheel angle [rad] */
+    KMPC_LLCREC_ACC_CMD = 7,      /* the clamped acceleration command ac of the last tick (req_accel) */
+    KMPC_LLCREC_TH = 8,           /* the plant's throttle actuator state (kmpc_sim_advance_drive only) */
+    KMPC_LLCREC_BR = 9,           /* the plant's brake actuator state [N m] (kmpc_sim_advance_drive only) */
+    KMPC_LLCREC_TICKS = 10,       /* ticks so far */
+    KMPC_LLCREC_N_TH_SAT = 11,    /* ticks whose PI output exceeded 1 */
+    KMPC_LLCREC_N_DEADBAND = 12,  /* ticks with -BRAKE_DEADBAND <= ac < 0: neither pedal, the car coasts */
+    KMPC_LLCREC_N_BRAKE = 13,     /* ticks with ac < -BRAKE_DEADBAND */
+    KMPC_LLCREC_SUM_ERR2 = 14,    /* sum over ticks of (ac - LPF)^2 */
+    KMPC_LLCREC_MAX_ERR = 15,     /* largest |ac - LPF| */
+    KMPC_LLCREC_WORDS = 16
+};
+/* A tick with the report's speed v and the command (acc_des, df_des), every line one rounding per operation, left to right:
+ *   report (:207-219, LowPass.h:53-61)
+ *       raw = 50.0 * (v - V_LAST)
+ *       LPF = READY != 0 ? a * raw + b * LPF : raw;   READY = 1;   V_LAST = v
+ *         with a = 1 / (0.5 / 0.02 + 1) and b = 0.5 / 0.02 / (0.5 / 0.02 + 1)          (LowPass::setParams(0.5, 0.02), LowPass.h:48-51, :47)
+ *   clamp (:123-128)
+ *       ac = acc_des > ACCEL_MAX ? ACCEL_MAX : (acc_des < -DECEL_MAX ? -DECEL_MAX : acc_des)
+ *       e  = ac - LPF                                                                   (:145, :148)
+ *   throttle, ac >= 0 (:147-148; PidControl::step(e, 0.02), PidControl.h:63-79, gains (KP, KI, 0), range (0, 1), :55-56)
+ *       integral = INT + e * 0.02;   y = KP * e + KI * INT                              (the OLD integrator)
+ *       y > 1: y = 1, N_TH_SAT += 1;   else y < 0: y = 0;   else INT = integral          (conditional integration, PidControl.h:70-76)
+ *       TH_CMD = y
+ *     The derivative term kd * (e - last_error) / 0.02 is dropped: kd = 0 (:55), the term is +-0 and changes no comparison and no non-zero y.
+ *   throttle, ac < 0 (:149-152):   INT = 0, TH_CMD = 0;   N_DEADBAND += 1 when ac >= -BRAKE_DEADBAND
+ *   brake (:156-160):              BR_CMD = ac < -BRAKE_DEADBAND ? -ac * MASS * WHEEL_RADIUS : 0   [N m];   N_BRAKE += 1 when it brakes
+ *   steering wheel (:164, :175-177): w = df_des * STEER_RATIO;  fabs(w) > 8.2: w = w > 0 ? 8.2 : -8.2;   WHEEL_CMD = w
+ *   bookkeeping:  ACC_CMD = ac, TICKS += 1, SUM_ERR2 += e * e, MAX_ERR = fabs(e) > MAX_ERR ? fabs(e) : MAX_ERR
+ * Not modelled: the 0.2 s command timeout (:113-116; the loops publish every period), the fuel low-pass (:46, :118: MASS is the row's word),
+ * pedals_enable_ / steer_enable_ (:181-188: both on), sys_enable_ false.
+ * Pinned against the reference: PidControl and LowPass are header-only; their recorded outputs are tests/golden/lowlevel_classes.npz, which the
+ * numpy restatement and the kernel reproduce bit for bit.  The callback that composes them needs ROS to compile and is restated by reading.
+ *
+ * kmpc_llc_step_batch: the node itself for B vehicles, one tick each.
+ *   cmd [B,2] fp64 DEVICE: accel_cmd, steer_angle_cmd          speed: DEVICE fp64, vehicle b's at speed + b * speed_stride doubles
+ *                                                              (the plant's state + 3 with a stride of 8)
+ *   llc [B,8], llc_rec [B,16] as above (TH, BR are left alone)  pedals_out [B,4] or NULL: TH_CMD, BR_CMD, WHEEL_CMD, ac
+ * One thread per vehicle; no lane reads another's row: a non-finite word poisons its own vehicle alone.  Argument checks before any device
+ * call: B < 0, speed_stride < 1, and with B > 0 a NULL cmd, speed, llc or llc_rec return KMPC_ERR_ARG (text in kmpc_last_error(NULL)); B == 0
+ * succeeds without a launch.  Asynchronous on `stream`. */
+int32_t kmpc_llc_default(double *row8);   /* HOST: 0.8, 0.4, 1.0, 1.0, 14.8, 1847.78, 0.1, 0.33 (:49-72, .h:113-118); KMPC_ERR_ARG for NULL */
+int32_t kmpc_llc_step_batch(int32_t device, int32_t B, const void *cmd, const void *speed, int32_t speed_stride, const void *llc, void *llc_rec,
+                            void *pedals_out, void *stream);
+
+/* kmpc_sim_advance_drive: kmpc_sim_advance_road with the controller in the loop and a powertrain that turns pedals into force.
+ *   state, cmd, plant, road, cmd_delay, cmd_queue, depth, period, n_updates, road_stat   exactly as in kmpc_sim_advance_road, with its clamping
+ *   llc [B,8], llc_rec [B,16] as above                 drive [B,8] fp64 DEVICE, row of vehicle b: */
+enum {
+    KMPC_DRIVE_F_PEAK = 0,        /* largest traction force [N] */
+    KMPC_DRIVE_P_MAX = 1,         /* largest traction power [W] */
+    KMPC_DRIVE_K_TH = 2,          /* gain of the throttle actuator's lag [1/s] */
+    KMPC_DRIVE_K_BR = 3,          /* gain of the brake actuator's lag [1/s] */
+    KMPC_DRIVE_C_ROLL = 4,        /* rolling resistance [m/s^2] */
+    KMPC_DRIVE_C_DRAG = 5,        /* air resistance per unit mass [1/m]: C_DRAG vx^2 */
+    KMPC_DRIVE_STEER_RATIO = 6,   /* the TRUE steering ratio (KMPC_LLC_STEER_RATIO is the controller's belief) */
+    KMPC_DRIVE_WHEEL_RADIUS = 7,  /* the TRUE wheel radius [m] */
+    KMPC_DRIVE_WORDS = 8
+};
+/* kmpc_drive_default writes 6000, 120e3, 5, 5, 0.15, 4e-4, 14.8, 0.33.  These are this project's choice: the reference has no powertrain model
+ * (its simulator's first-order lag acc += 5 (acc_des - acc) dt delivers every commanded acceleration exactly).  With them the linearised PI loop
+ * has a phase margin of about 70 degrees (crossover near 3.7 rad/s against lags of 0.2 s and 0.5 s).
+ * Per absolute update tau = period * n_updates + up (the caller counts periods from 0 and keeps n_updates, as for the queue):
+ *   tau even (50 Hz against the 100 Hz updates): one tick, before the update's sub-steps, on v = the state's vx as it is then and the command in
+ *       force for that update -- the queue's selection, so cmd_delay is the MPC -> L0 transport delay.  It sets the targets held until the next
+ *       tick, TH_CMD, BR_CMD and df_eff = WHEEL_CMD / drive.STEER_RATIO (a call that begins on an odd tau takes df_eff from the record).
+ *   once per update:  Fmax = min(F_PEAK, P_MAX / max(vx, 1.0)), by compare-and-select (vx > 1 ? vx : 1;  q < F_PEAK ? q : F_PEAK)
+ *   each 1 ms sub-step: kmpc_sim_advance_road's sub-step, unchanged, towards the tyre angle df_eff, with the state's word 6 as the acceleration
+ *       that acts (ACC_GAIN, A_LONG and the floor vx >= 0 act on it as there); then, with vx_n the new speed and deltaT = 0.001,
+ *           TH = K_TH * (TH_CMD - TH) * deltaT + TH          BR = K_BR * (BR_CMD - BR) * deltaT + BR
+ *           acc_n = 1/m * (TH * Fmax - BR * 1/r) - (vx_n > 1e-6 ? C_ROLL + C_DRAG * vx_n * vx_n : 0)          (the NEW TH, BR)
+ *       replaces the acceleration lag; 1/m is the PLANT's (KMPC_PLANT_M), 1/r = 1 / drive.WHEEL_RADIUS divided once per call; KMPC_PLANT_K_ACC is
+ *       not read.  State word 6 is thus the powertrain's net longitudinal acceleration: what state_est.a and estimator_input="actuator" read.
+ *       A braked vehicle stops at vx = 0 and stays there.
+ * The record is read once before and written once after the loop; TH and BR are its words 8 and 9.  A fresh record (all zeros) differentiates its
+ * first report against V_LAST = 0, as the reference does from rest: a loop that starts at speed sets V_LAST first.
+ * A row cannot be checked from the host: a non-finite word or a zero radius poisons its own vehicle alone (Python: vehicle_sim.check_drive_rows,
+ * check_llc_rows).  Argument checks as kmpc_sim_advance_road's, before any device call, and with B > 0 a NULL drive, llc or llc_rec returns
+ * KMPC_ERR_ARG (text in kmpc_last_error(NULL)); B == 0 or n_updates == 0 succeeds without a launch.  Asynchronous on `stream`. */
+int32_t kmpc_drive_default(double *row8);   /* HOST: 6000, 120e3, 5, 5, 0.15, 4e-4, 14.8, 0.33; KMPC_ERR_ARG for NULL */
+int32_t kmpc_sim_advance_drive(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const void *road, const void *drive,
+                               const void *llc, void *llc_rec, const int32_t *cmd_delay, void *cmd_queue, int32_t depth, int64_t period,
+                               int32_t n_updates, void *road_stat, void *stream);
+
 /* ---- measurement stage: what the controller sees of the plant ------------------------------------------------------------------------------
  * The reference's vehicle builds state_est from a GPS fix, an IMU yaw and the steering report's speed (scripts/state_publisher.py); its simulator
  * publishes the truth (vehicle_simulator.py:40-48).  kmpc_sense_batch puts additive Gaussian noise and a bias on the four channels the MPC reads.

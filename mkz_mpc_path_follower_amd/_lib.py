@@ -39,7 +39,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_plant_default", "kmpc_sim_advance_plant", "kmpc_sense_batch", "kmpc_estimate_batch",
            "kmpc_sim_advance_queue", "kmpc_sense_delayed_batch", "kmpc_cmd_in_force_batch", "kmpc_predict_ahead_batch",
            "kmpc_road_default", "kmpc_sim_advance_road", "kmpc_observe_batch", "kmpc_cmd_offset_batch",
-           "kmpc_predict_ahead_dist_batch"]
+           "kmpc_predict_ahead_dist_batch",
+           "kmpc_llc_default", "kmpc_llc_step_batch", "kmpc_drive_default", "kmpc_sim_advance_drive"]
 
 _lib = None
 
@@ -97,6 +98,10 @@ def load():
     L.kmpc_sim_advance_queue.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, C.c_int64, i32, vp]
     L.kmpc_road_default.argtypes = [dp]
     L.kmpc_sim_advance_road.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, C.c_int64, i32, vp, vp]
+    L.kmpc_llc_default.argtypes = [dp]
+    L.kmpc_drive_default.argtypes = [dp]
+    L.kmpc_llc_step_batch.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.kmpc_sim_advance_drive.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.c_int64, i32, vp, vp]
     L.kmpc_sense_delayed_batch.argtypes = [i32, i32, vp, vp, C.c_uint64, C.c_int64, C.c_int64, vp, vp, i32, vp, vp]
     L.kmpc_cmd_in_force_batch.argtypes = [i32, i32, vp, i32, C.c_int64, i32, vp, vp, i32, i32, vp, vp]
     L.kmpc_predict_ahead_batch.argtypes = [i32, i32, vp, vp, i32, C.c_int64, i32, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp]

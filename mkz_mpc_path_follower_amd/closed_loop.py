@@ -50,6 +50,11 @@ compensator's ASSUMED delays and its log of sent commands); waypoints, fit and s
 logs the command.  `estimator_input="history"` feeds the filter `compensator.filter_input(k)`, the logged command in force over the period the filter
 steps across (refused without a compensator).  Scoring, the history's `state` and the plant stay on the truth; nothing synchronises.  The
 compensator's n_updates must be the loop's plant_updates (checked every period).  Without a compensator the loops take exactly the path they took.
+
+L0 actuation: the reference's low-level controller and a pedal-driven powertrain belong to the simulator (VehicleSimulator(drive=, llc=):
+kmpc_sim_advance_drive runs the controller's 50 Hz tick inside the plant call).  The loops only call `sim._update_vehicle_model`; `sim.state[:, 6]`
+is then the powertrain's net acceleration, which `estimator_input="actuator"` reads as delivered, while `estimator_input="command"` lets an
+observer see the difference between what was commanded and what the pedals delivered.
 """
 import ctypes as C
 import time

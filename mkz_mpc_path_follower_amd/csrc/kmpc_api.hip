@@ -787,6 +787,59 @@ extern "C" int32_t kmpc_sim_advance_road(int32_t device, int32_t B, void *state,
     return KMPC_OK;
 }
 
+// ---- low-level controller and pedal-driven plant (kmpc_drive.hip) ----------------------------------------------------
+// the reference node's constants (LowLevelController.cpp:49-72, .h:113-118; the mass at fuel level 0, as before the first fuel report)
+extern "C" int32_t kmpc_llc_default(double *row8)
+{
+    if (!row8) return fail(nullptr, KMPC_ERR_ARG, "kmpc_llc_default: null row");
+    row8[KMPC_LLC_KP] = 0.8; row8[KMPC_LLC_KI] = 0.4; row8[KMPC_LLC_ACCEL_MAX] = 1.0; row8[KMPC_LLC_DECEL_MAX] = 1.0;
+    row8[KMPC_LLC_STEER_RATIO] = 14.8; row8[KMPC_LLC_MASS] = 1847.78; row8[KMPC_LLC_BRAKE_DEADBAND] = 0.1; row8[KMPC_LLC_WHEEL_RADIUS] = 0.33;
+    return KMPC_OK;
+}
+
+// the powertrain's constants: this project's choice (the reference has no powertrain model)
+extern "C" int32_t kmpc_drive_default(double *row8)
+{
+    if (!row8) return fail(nullptr, KMPC_ERR_ARG, "kmpc_drive_default: null row");
+    row8[KMPC_DRIVE_F_PEAK] = 6000.0; row8[KMPC_DRIVE_P_MAX] = 120e3; row8[KMPC_DRIVE_K_TH] = 5.0; row8[KMPC_DRIVE_K_BR] = 5.0;
+    row8[KMPC_DRIVE_C_ROLL] = 0.15; row8[KMPC_DRIVE_C_DRAG] = 4e-4; row8[KMPC_DRIVE_STEER_RATIO] = 14.8; row8[KMPC_DRIVE_WHEEL_RADIUS] = 0.33;
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_llc_step_batch(int32_t device, int32_t B, const void *cmd, const void *speed, int32_t speed_stride, const void *llc,
+                                       void *llc_rec, void *pedals_out, void *stream)
+{
+    if (B < 0 || speed_stride < 1 || (B > 0 && (!cmd || !speed || !llc || !llc_rec)))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_llc_step_batch: bad argument (B=%d, speed_stride=%d, at least 1; cmd, speed, llc and llc_rec are required)", B,
+                    speed_stride);
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_llc_step_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_llc_step(B, (const double *)cmd, (const double *)speed, speed_stride, (const double *)llc, (double *)llc_rec,
+                                              (double *)pedals_out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_llc_step_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_sim_advance_drive(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const void *road,
+                                          const void *drive, const void *llc, void *llc_rec, const int32_t *cmd_delay, void *cmd_queue, int32_t depth,
+                                          int64_t period, int32_t n_updates, void *road_stat, void *stream)
+{
+    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: bad argument (B=%d, n_updates=%d)", B, n_updates);
+    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: null plant rows");
+    if (B > 0 && !road) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: null road rows");
+    if (B > 0 && (!drive || !llc || !llc_rec)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: null drive rows, llc rows or llc_rec");
+    if (depth < 2 || period < 0 || !cmd_queue)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: bad queue (depth=%d, at least 2; period=%lld, at least 0; cmd_queue %s)", depth,
+                    (long long)period, cmd_queue ? "given" : "NULL");
+    if (B == 0 || n_updates == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_drive: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_sim_drive(B, (double *)state, (const double *)cmd, (const double *)plant, (const double *)road,
+                                               (const double *)drive, (const double *)llc, (double *)llc_rec, cmd_delay, (double *)cmd_queue, depth,
+                                               (long long)period, n_updates, (double *)road_stat, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_drive: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 extern "C" int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period,
                                             int64_t id_base, const int32_t *meas_delay, void *truth_ring, int32_t depth, void *est, void *stream)
 {

@@ -102,6 +102,12 @@ hipError_t kmpc_launch_sense_delayed(int B, const double *state, const double *s
                                      const int32_t *meas_delay, double *truth_ring, int depth, double *est, hipStream_t st);
 hipError_t kmpc_launch_sim_road(int B, double *state, const double *cmd, const double *plant, const double *road, const int32_t *cmd_delay,
                                 double *cmd_queue, int depth, long long period, int n_updates, double *road_stat, hipStream_t st);
+// low-level controller and pedal-driven plant (kmpc_drive.hip)
+hipError_t kmpc_launch_llc_step(int B, const double *cmd, const double *speed, int speed_stride, const double *llc_rows, double *llc_rec,
+                                double *pedals_out, hipStream_t st);
+hipError_t kmpc_launch_sim_drive(int B, double *state, const double *cmd, const double *plant, const double *road, const double *drive,
+                                 const double *llc_rows, double *llc_rec, const int32_t *cmd_delay, double *cmd_queue, int depth, long long period,
+                                 int n_updates, double *road_stat, hipStream_t st);
 // delay compensation (kmpc_latency.hip)
 hipError_t kmpc_launch_cmd_in_force(int B, const double *hist, int depth, long long period, int n, const int32_t *cmd_delay, const int32_t *meas_delay,
                                     int max_cmd_delay, int max_meas_delay, double *u_out, hipStream_t st);

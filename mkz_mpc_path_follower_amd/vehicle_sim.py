@@ -21,6 +21,11 @@ observer's record (kmpc_predict_ahead_dist_batch).
 Grip and road: `VehicleSimulator(road=road_params(B, mu=0.5, a_lat=1.5, ...))` gives every vehicle a road row -- friction limits per axle, specific
 forces of grade and bank, a steering offset, an acceleration gain (kmpc_sim_advance_road) -- and counts, per vehicle and axle, the sub-steps in
 which the tyre force was clipped (`road_stat`, `road_summary()`).  The neutral row computes what the command-queue plant computes, bit for bit.
+
+L0 actuation: `LowLevelController` is the reference's 50 Hz node src/LowLevelController.cpp for B vehicles (kmpc_llc_step_batch: clamp, throttle PI on
+a low-passed differentiated speed, brake torque below a deadband, steering-wheel angle), and `VehicleSimulator(drive=drive_params(B, ...), llc=)`
+puts it inside the plant, in front of a powertrain that turns pedals into force (kmpc_sim_advance_drive): the command then no longer acts as an
+acceleration.  `llc.summary()` downloads the controller's counters.  Without `drive=` every code path is the one that ran before.
 """
 import ctypes as C
 
@@ -39,6 +44,10 @@ ESTIMATOR_FIELDS = ("x", "y", "psi", "v", "pxx", "pxy", "pxpsi", "pxv", "pyy", "
 ESTIMATOR_PARAM_FIELDS = ("q_x", "q_y", "q_psi", "q_v", "r_x", "r_y", "r_psi", "r_v")   # KMPC_ESTPAR_*
 OBSERVER_FIELDS = ("x", "y", "psi", "v", "dpsi", "ddelta", "da")   # KMPC_OBS_* words 0 ... 6; 7 ... 34 the covariance, 35 count, 36 skipped
 OBSERVER_PARAM_FIELDS = ("q_x", "q_y", "q_psi", "q_v", "q_dpsi", "q_ddelta", "q_da", "r_x", "r_y", "r_psi", "r_v", "p0_dpsi", "p0_ddelta", "p0_da")   # KMPC_OBSPAR_*
+LLC_FIELDS = ("kp", "ki", "accel_max", "decel_max", "steer_ratio", "mass", "brake_deadband", "wheel_radius")   # KMPC_LLC_*
+DRIVE_FIELDS = ("f_peak", "p_max", "k_th", "k_br", "c_roll", "c_drag", "steer_ratio", "wheel_radius")   # KMPC_DRIVE_*
+LLC_RECORD_FIELDS = ("int", "lpf", "ready", "v_last", "th_cmd", "br_cmd", "wheel_cmd", "acc_cmd", "th", "br", "ticks", "n_th_sat", "n_deadband",
+                     "n_brake", "sum_err2", "max_err")   # KMPC_LLCREC_*
 EST_SKIP_X, EST_SKIP_Y, EST_SKIP_PSI, EST_SKIP_V, EST_INIT, EST_RESET = 1, 2, 4, 8, 16, 32   # KMPC_EST_FLAG_*
 
 
@@ -134,10 +143,143 @@ def road_params(B, device=0, **overrides):
     return torch.as_tensor(check_road_rows(rows)).to(_device(device))
 
 
+def _rows_with(name, fields, default, B, overrides):
+    """the default row tiled B times with each override a scalar or one value per vehicle -> [B,8] host rows"""
+    rows = np.tile(default, (int(B), 1))
+    for k, v in overrides.items():
+        if k not in fields:
+            raise ValueError("%s: unknown parameter %r (one of %s)" % (name, k, ", ".join(fields)))
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
+            raise ValueError("%s: %s is a scalar or one value per vehicle [%d], got %s" % (name, k, B, v.shape))
+        rows[:, fields.index(k)] = v
+    return rows
+
+
+def llc_default():
+    """the reference node's constants (LowLevelController.cpp:49-72, .h:113-118) as a numpy row [8], from kmpc_llc_default"""
+    row = np.zeros(8)
+    _lib.check(_lib.load().kmpc_llc_default(row.ctypes.data_as(C.POINTER(C.c_double))))
+    return row
+
+
+def check_llc_rows(rows):
+    """[B,8] host rows -> ValueError unless all are finite, accel_max, decel_max, steer_ratio, mass, wheel_radius > 0 and kp, ki, brake_deadband
+    >= 0 (the kernel cannot refuse a row: a bad one poisons that vehicle)"""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 8:
+        raise ValueError("llc rows: [B,8] (%s), got %s" % (", ".join(LLC_FIELDS), rows.shape))
+    if not np.isfinite(rows).all():
+        raise ValueError("llc rows: non-finite value in vehicle(s) %s" % np.flatnonzero(~np.isfinite(rows).all(1))[:8].tolist())
+    pos = rows[:, [2, 3, 4, 5, 7]]
+    if not (pos > 0.0).all():
+        raise ValueError("llc rows: accel_max, decel_max, steer_ratio, mass, wheel_radius must be > 0 (vehicle(s) %s)" % np.flatnonzero(~(pos > 0.0).all(1))[:8].tolist())
+    nonneg = rows[:, [0, 1, 6]]
+    if not (nonneg >= 0.0).all():
+        raise ValueError("llc rows: kp, ki, brake_deadband must be >= 0 (vehicle(s) %s)" % np.flatnonzero(~(nonneg >= 0.0).all(1))[:8].tolist())
+    return rows
+
+
+def llc_params(B, device=0, **overrides):
+    """[B,8] float64 controller rows on `device`: the reference's constants, with each override (`kp=`, `mass=`, `brake_deadband=`, ... : LLC_FIELDS)
+    a scalar or one value per vehicle.  Validated on the host (check_llc_rows) before anything reaches the device."""
+    return torch.as_tensor(check_llc_rows(_rows_with("llc_params", LLC_FIELDS, llc_default(), B, overrides))).to(_device(device))
+
+
+def drive_default():
+    """the powertrain's default row (6000 N, 120 kW, lags 5 1/s, 0.15 m/s^2, 4e-4 1/m, 14.8, 0.33 m) as a numpy row [8], from kmpc_drive_default"""
+    row = np.zeros(8)
+    _lib.check(_lib.load().kmpc_drive_default(row.ctypes.data_as(C.POINTER(C.c_double))))
+    return row
+
+
+def check_drive_rows(rows):
+    """[B,8] host rows -> ValueError unless all are finite, f_peak, p_max, steer_ratio, wheel_radius > 0 and k_th, k_br, c_roll, c_drag >= 0 (the
+    kernel cannot refuse a row: a bad one poisons that vehicle)"""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 8:
+        raise ValueError("drive rows: [B,8] (%s), got %s" % (", ".join(DRIVE_FIELDS), rows.shape))
+    if not np.isfinite(rows).all():
+        raise ValueError("drive rows: non-finite value in vehicle(s) %s" % np.flatnonzero(~np.isfinite(rows).all(1))[:8].tolist())
+    pos = rows[:, [0, 1, 6, 7]]
+    if not (pos > 0.0).all():
+        raise ValueError("drive rows: f_peak, p_max, steer_ratio, wheel_radius must be > 0 (vehicle(s) %s)" % np.flatnonzero(~(pos > 0.0).all(1))[:8].tolist())
+    if not (rows[:, 2:6] >= 0.0).all():
+        raise ValueError("drive rows: k_th, k_br, c_roll, c_drag must be >= 0 (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 2:6] >= 0.0).all(1))[:8].tolist())
+    return rows
+
+
+def drive_params(B, device=0, **overrides):
+    """[B,8] float64 powertrain rows on `device`: the default row, with each override (`f_peak=`, `c_drag=`, `steer_ratio=`, ... : DRIVE_FIELDS) a
+    scalar or one value per vehicle.  Validated on the host (check_drive_rows) before anything reaches the device."""
+    return torch.as_tensor(check_drive_rows(_rows_with("drive_params", DRIVE_FIELDS, drive_default(), B, overrides))).to(_device(device))
+
+
+class LowLevelController:
+    """The reference's 50 Hz low-level controller (src/LowLevelController.cpp) for B vehicles: one step() is one tick -- a speed report, then the
+    control callback -- of every vehicle (kmpc_llc_step_batch; include/kmpc.h states the arithmetic).  Keyword arguments are LLC_FIELDS overrides,
+    a scalar or one value per vehicle.  `params` [B,8] and `rec` [B,16] (LLC_RECORD_FIELDS; all zeros = the freshly constructed node) are plain
+    device tensors the caller may edit between calls.  `v0`: the speed the vehicles already have (reset(v0)): a fresh record differentiates the
+    first report against 0, as the reference does from rest, so a loop that starts at speed must say so.
+    VehicleSimulator(drive=, llc=this) runs the same tick inside the plant; step() is the stage alone, for a caller with a plant of its own."""
+
+    def __init__(self, B, device=0, v0=None, **overrides):
+        self._lib = _lib.load()
+        self.B = int(B)
+        rows = check_llc_rows(_rows_with("LowLevelController", LLC_FIELDS, llc_default(), self.B, overrides))
+        if v0 is not None:
+            v0 = np.asarray(v0, dtype=np.float64)
+            if v0.shape not in ((), (self.B,)) or not np.isfinite(v0).all():
+                raise ValueError("LowLevelController: v0 is a finite scalar or one speed per vehicle [%d]" % self.B)
+        self.device = _device(device)
+        self.params = torch.as_tensor(rows).to(self.device)
+        self.rec = torch.zeros((self.B, 16), dtype=torch.float64, device=self.device)
+        self.reset(v0)
+
+    def reset(self, v=None):
+        """every record fresh; V_LAST = v (a scalar or [B]) when given"""
+        self.rec.zero_()
+        if v is not None:
+            self.rec[:, 3] = torch.as_tensor(v, dtype=torch.float64, device=self.device)
+
+    def _own(self):
+        for t, w in ((self.params, 8), (self.rec, 16)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+                raise ValueError("params [B,8] and rec [B,16] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
+
+    def step(self, cmd, speed, out=None):
+        """cmd [B,2] (accel, steer); speed [B]: a contiguous tensor or a column view such as sim.state[:, 3] (no copy is made)
+        -> pedals [B,4]: throttle fraction, brake torque [N m], steering-wheel angle [rad], the clamped acceleration command"""
+        self._own()
+        ped = out if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
+        for t, w in ((cmd, 2), (ped, 4)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+                raise ValueError("cmd [B,2] and out [B,4] must be contiguous float64 tensors on %s" % self.device)
+        if not (isinstance(speed, torch.Tensor) and speed.dtype == torch.float64 and tuple(speed.shape) == (self.B,) and speed.device == self.device
+                and (self.B <= 1 or speed.stride(0) >= 1)):
+            raise ValueError("speed: float64 [B] on %s, rows a fixed distance >= 1 apart (a [B] buffer or sim.state[:, 3])" % self.device)
+        stride = speed.stride(0) if self.B > 1 else 1
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_llc_step_batch(self.device.index, self.B, C.c_void_p(cmd.data_ptr()), C.c_void_p(speed.data_ptr()), int(stride),
+                                                 C.c_void_p(self.params.data_ptr()), C.c_void_p(self.rec.data_ptr()), C.c_void_p(ped.data_ptr()), stream))
+        return ped
+
+    def summary(self):
+        """the record so far, one download -> dict of numpy arrays [B]: every LLC_RECORD_FIELDS word (the counters as int64) and rms_err, the root
+        mean square of ac - LPF over the ticks"""
+        r = self.rec.detach().cpu().numpy()
+        out = {k: r[:, i].copy() for i, k in enumerate(LLC_RECORD_FIELDS)}
+        for k in ("ticks", "n_th_sat", "n_deadband", "n_brake"):
+            out[k] = out[k].astype(np.int64)
+        with np.errstate(all="ignore"):
+            out["rms_err"] = np.sqrt(out["sum_err2"] / np.maximum(out["ticks"], 1))
+        return out
+
+
 class VehicleSimulator:
     dt_model = 0.01  # :24
 
-    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None, cmd_queue_depth=None, road=None):
+    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None, cmd_queue_depth=None, road=None, drive=None, llc=None):
         """plant: [B,8] rows (plant_params) -- a plant per vehicle; cmd_delay: a scalar or one per vehicle, model updates of 10 ms by which a new
         command takes effect late (clamped to one call's n_updates; the command in force until then is `cmd_held`, 0 at the start).  Giving
         either runs kmpc_sim_advance_plant (the other defaults to the reference's constants / no delay); `plant`, `cmd_delay` (int32 [B]) and
@@ -148,7 +290,23 @@ class VehicleSimulator:
         road: [B,8] rows (road_params) -- grip limits, grade, bank, steering offset and acceleration gain per vehicle (kmpc_sim_advance_road).  It
         implies the queue path (cmd_queue_depth defaults to 2, which equals the held-command plant call after call) and allocates `road_stat` [B,4];
         `road` and `road_stat` are plain device tensors the caller may edit between steps (a wet patch: write `road` between periods), and
-        road_summary() downloads the grip bookkeeping."""
+        road_summary() downloads the grip bookkeeping.
+        drive: [B,8] rows (drive_params) -- a powertrain per vehicle behind a LowLevelController `llc` (default: LowLevelController(B) with the
+        reference's constants, its V_LAST at 0): the command passes through the controller's 50 Hz tick and acts as throttle and brake
+        (kmpc_sim_advance_drive).  It implies the road and queue path (road defaults to the neutral rows); `drive`, `llc.params` and `llc.rec` are
+        plain device tensors the caller may edit between steps.  A run that starts at speed calls llc.reset(v) first."""
+        drive_rows = None
+        if llc is not None and drive is None:
+            raise ValueError("llc= belongs to drive=: the controller acts on the plant only through the powertrain (drive_params)")
+        if drive is not None:   # checked before the GPU is touched
+            drive_rows = drive.detach().cpu().numpy() if isinstance(drive, torch.Tensor) else drive
+            if np.shape(drive_rows) != (int(B), 8):
+                raise ValueError("drive: [%d,8] rows (drive_params), got %s" % (int(B), np.shape(drive_rows)))
+            drive_rows = check_drive_rows(drive_rows)
+            if llc is not None and not (isinstance(llc, LowLevelController) and llc.B == int(B)):
+                raise ValueError("llc: a LowLevelController for %d vehicles" % int(B))
+            if road is None:
+                road = np.tile(road_default(), (int(B), 1))
         road_rows = None
         if road is not None:   # checked before the GPU is touched, like the depth
             road_rows = road.detach().cpu().numpy() if isinstance(road, torch.Tensor) else road
@@ -173,7 +331,7 @@ class VehicleSimulator:
         self.state[:, 1] = torch.as_tensor(Y0, dtype=torch.float64, device=self.device)
         self.state[:, 2] = torch.as_tensor(Psi0, dtype=torch.float64, device=self.device)
         self.cmd = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)  # acc_des, df_des (:21-22)
-        self.plant = self.cmd_delay = self.cmd_held = self.cmd_queue = self.road = self.road_stat = None
+        self.plant = self.cmd_delay = self.cmd_held = self.cmd_queue = self.road = self.road_stat = self.drive = self.llc = None
         self.period = 0
         if plant is not None or cmd_delay is not None or cmd_queue_depth is not None:
             if plant is None:
@@ -194,6 +352,11 @@ class VehicleSimulator:
             if road_rows is not None:
                 self.road = torch.as_tensor(road_rows).to(self.device).contiguous()
                 self.road_stat = torch.zeros((self.B, 4), dtype=torch.float64, device=self.device)
+            if drive_rows is not None:
+                self.drive = torch.as_tensor(drive_rows).to(self.device).contiguous()
+                self.llc = llc if llc is not None else LowLevelController(self.B, device=self.device)
+                if self.llc.device != self.device:
+                    raise ValueError("llc on %s, plant on %s" % (self.llc.device, self.device))
 
     # views named as in the reference
     X = property(lambda s: s.state[:, 0]); Y = property(lambda s: s.state[:, 1]); psi = property(lambda s: s.state[:, 2])
@@ -225,10 +388,22 @@ class VehicleSimulator:
                     if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous()
                             and t.device == self.device):
                         raise ValueError("road [B,8] / road_stat [B,4] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
-                rc = self._lib.kmpc_sim_advance_road(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
-                                                     C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.road.data_ptr()),
-                                                     C.c_void_p(self.cmd_delay.data_ptr()), C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth,
-                                                     int(self.period), int(n_updates), C.c_void_p(self.road_stat.data_ptr()), stream)
+                if self.drive is not None:
+                    if not (isinstance(self.drive, torch.Tensor) and self.drive.dtype == torch.float64 and tuple(self.drive.shape) == (self.B, 8)
+                            and self.drive.is_contiguous() and self.drive.device == self.device):
+                        raise ValueError("drive [B,8] must stay a contiguous float64 tensor on %s (write into it with copy_)" % self.device)
+                    self.llc._own()
+                    rc = self._lib.kmpc_sim_advance_drive(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
+                                                          C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.road.data_ptr()),
+                                                          C.c_void_p(self.drive.data_ptr()), C.c_void_p(self.llc.params.data_ptr()),
+                                                          C.c_void_p(self.llc.rec.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
+                                                          C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth, int(self.period), int(n_updates),
+                                                          C.c_void_p(self.road_stat.data_ptr()), stream)
+                else:
+                    rc = self._lib.kmpc_sim_advance_road(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
+                                                         C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.road.data_ptr()),
+                                                         C.c_void_p(self.cmd_delay.data_ptr()), C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth,
+                                                         int(self.period), int(n_updates), C.c_void_p(self.road_stat.data_ptr()), stream)
             else:
                 rc = self._lib.kmpc_sim_advance_queue(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
                                                       C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),

@@ -25,7 +25,13 @@ once with vehicle_sim.DisturbanceObserver (its defaults) in the loop: the existi
 0.35 s (command delay 10 / 10 / 25 updates, fix 0 / 1 / 1 periods old) x the observer's q_dist at 1 / 0.5 / 0.25 of its default, each cell three ways:
 Estimator + LatencyCompensator, DisturbanceObserver alone, and DisturbanceObserver + LatencyCompensator(disturbances=True).
 
+--actuation is the sweep of the L0 layer (-> profiles/robustness_sweep_actuation.txt): the pedal-driven plant behind vehicle_sim.LowLevelController
+(VehicleSimulator(drive=, llc=)), no noise, no delay, neutral road, on the three paths at 6 m/s: the controller's brake deadband (0, 0.1, 0.2) m/s^2
+x plant mass x (0.85, 1, 1.3) x F_PEAK (2500, 6000) N x error of the controller's steering ratio (0, +5 %, -5 %), each cell once as it is and once
+with vehicle_sim.DisturbanceObserver (its defaults, estimator_input="command": it compares what was commanded with what the speed did).
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
+       python tools/robustness_sweep.py --actuation [out.txt] [steps]
        python tools/robustness_sweep.py --observer [out.txt] [steps]
        python tools/robustness_sweep.py --observer-latency [out.txt] [steps]
        python tools/robustness_sweep.py --latency [out.txt] [steps]
@@ -387,8 +393,86 @@ def observer_latency_main():
             f.write("\n".join(LINES) + "\n")
 
 
+ACT_DEADBAND, ACT_MASS, ACT_FPEAK, ACT_RATIO, ACT_PER_CELL = (0.0, 0.1, 0.2), (0.85, 1.0, 1.3), (2500.0, 6000.0), (0.0, 0.05, -0.05), 12
+
+
+def actuation_main():
+    """two loops of 3 x 3 x 2 x 3 cells of 12 vehicles (the road sweep's first 12 starts, all at 6 m/s): without and with observer=.  The tracking
+    figures are those of the run's second half; the controller's counters cover the whole run."""
+    from mkz_mpc_path_follower_amd.vehicle_sim import LowLevelController, drive_params
+    argv = [a for a in sys.argv if a != "--actuation"]
+    steps = int(argv[2]) if len(argv) > 2 else 200
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    cells = list(itertools.product(range(3), range(3), range(2), range(3)))
+    B = len(cells) * ACT_PER_CELL
+    ix = np.array(cells)[np.repeat(np.arange(len(cells)), ACT_PER_CELL)]     # [B,4] grid indices: deadband, mass, F_PEAK, ratio error
+    rng = np.random.default_rng(0)
+    pid = np.tile(np.arange(ACT_PER_CELL) % 3, len(cells))
+    fleet = FleetRefTrajectory(paths, pid, traj_horizon=8, traj_dt=0.2)
+    frac = np.tile(rng.uniform(0.02, 0.45, ROAD_PER_CELL)[:ACT_PER_CELL], len(cells))
+    pose = np.empty((B, 3))
+    for b in range(B):
+        tr = fleet.trajectories[pid[b]]
+        i = int(frac[b] * len(tr))
+        pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+    d0 = plant_default()
+    res = {}
+    for with_observer in (False, True):
+        llc = LowLevelController(B, v0=VT, brake_deadband=np.array(ACT_DEADBAND)[ix[:, 0]], steer_ratio=14.8 * (1.0 + np.array(ACT_RATIO)[ix[:, 3]]))
+        sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2], plant=plant_params(B, m=d0[2] * np.array(ACT_MASS)[ix[:, 1]]),
+                               drive=drive_params(B, f_peak=np.array(ACT_FPEAK)[ix[:, 2]]), llc=llc)
+        sim.state[:, 3] = VT
+        kw = dict(observer=DisturbanceObserver(B), estimator_input="command") if with_observer else {}
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, **kw)
+        loop.run(steps // 2)
+        first = loop.score_summary()
+        loop.reset_score()
+        v_sum = torch.zeros(B, dtype=torch.float64, device=sim.device)
+        for _ in range(steps - steps // 2):
+            loop.run(1)
+            v_sum += sim.state[:, 3]
+        second, c = loop.score_summary(), llc.summary()
+        res[with_observer] = dict(rms2=second["rms_ect"], max=np.maximum(first["max_ect"], second["max_ect"]), nonopt=first["n_nonopt"] + second["n_nonopt"],
+                                  live=first["n_live"] + second["n_live"], v=(v_sum / (steps - steps // 2)).cpu().numpy(), ctl=c,
+                                  dist=loop.dist.cpu().numpy() if with_observer else None, finite=bool(torch.isfinite(sim.state).all().item()),
+                                  latched=int((second["latch_index"] >= 0).sum()))
+    say("%s: 2 x %d vehicles, %d periods of 0.1 s on three paths at %.0f m/s, pedal-driven plant behind the low-level controller, no noise, no delay, "
+        "neutral road; every state finite: %s / %s; latched vehicles: %d / %d; periods not Optimal per 1000: %.2f / %.2f (without / with the observer)"
+        % (torch.cuda.get_device_name(0), B, steps, VT, res[False]["finite"], res[True]["finite"], res[False]["latched"], res[True]["latched"],
+           1000.0 * res[False]["nonopt"].sum() / max(1, res[False]["live"].sum()), 1000.0 * res[True]["nonopt"].sum() / max(1, res[True]["live"].sum())))
+    head = ("without | with DisturbanceObserver: median rms e_ct over the second half [m], largest |e_ct| [m], median of the mean speed over the second half "
+            "[m/s], share of ticks in the deadband / braking / throttle saturated [%], median rms(ac - a) [m/s^2]; then the median da-hat [m/s^2]")
+
+    def row(label, sel):
+        part = []
+        for w in (False, True):
+            r, c = res[w], res[w]["ctl"]
+            t = max(1, c["ticks"][sel].sum())
+            part.append("%6.3f %6.3f %6.3f %5.1f %5.1f %5.1f %6.3f" % (np.median(r["rms2"][sel]), r["max"][sel].max(), np.median(r["v"][sel]),
+                                                                       100.0 * c["n_deadband"][sel].sum() / t, 100.0 * c["n_brake"][sel].sum() / t,
+                                                                       100.0 * c["n_th_sat"][sel].sum() / t, np.median(c["rms_err"][sel])))
+        say("   %-34s %s | %s   %+.4f" % (label, part[0], part[1], np.median(res[True]["dist"][sel, 2])))
+    say("per factor level, over all other factors: " + head)
+    for f, (name, levels, fmt) in enumerate((("brake deadband [m/s^2]", ACT_DEADBAND, "%.1f"), ("plant mass x", ACT_MASS, "%.2f"), ("F_PEAK [N]", ACT_FPEAK, "%.0f"),
+                                             ("steering-ratio error", ACT_RATIO, "%+.2f"))):
+        for lv in range(len(levels)):
+            row("%s %s" % (name, fmt % levels[lv]), ix[:, f] == lv)
+    say("per cell without a ratio error (%d vehicles per line): " % ACT_PER_CELL + head)
+    for dbi, mi, fi in itertools.product(range(3), range(3), range(2)):
+        row("%.1f m/s^2, mass x %.2f, %4.0f N" % (ACT_DEADBAND[dbi], ACT_MASS[mi], ACT_FPEAK[fi]),
+            (ix[:, 0] == dbi) & (ix[:, 1] == mi) & (ix[:, 2] == fi) & (ix[:, 3] == 0))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 if __name__ == "__main__":
-    if "--observer-latency" in sys.argv[1:]:
+    if "--actuation" in sys.argv[1:]:
+        actuation_main()
+    elif "--observer-latency" in sys.argv[1:]:
         observer_latency_main()
     elif "--observer" in sys.argv[1:]:
         observer_main()
