@@ -342,6 +342,60 @@ int32_t kmpc_track_score_fleet(kmpc_pathset *ps, int32_t B, const double *state,
                                const uint8_t *stop_latch, double *err_out, int32_t *seg_out, int32_t *closest_out, double *score,
                                void *stream);
 
+/* ---- curvature- and grip-limited target speeds: a speed plan per vehicle --------------------------------------------------------------------
+ * The reference node drives every corner at one constant target_vel (scripts/mpc_cmd_pub.jl:58-62) and has no such stage; the defaults below are
+ * therefore this project's own.  Two calls: the curvature table of a set of paths, once per set and window, and the plan, once per period --
+ * "how fast may vehicle b be at its nearest sample i so that it can still brake, at A_BRAKE, to what every sample ahead allows":
+ * v^2 <= v_lim,j^2 + 2 a (s_j - s_i) for every j >= i of its own path, the backward braking pass of a speed profile as a min-reduction.
+ *
+ * kmpc_pathset_curvature: kappa_out [sum M] fp64 DEVICE, caller-owned, in the set's sample order (path p's samples at off_p .. off_p + M_p - 1).
+ * For sample i of its path, with indices inside THAT path only, s = cdist, psi the recorded heading and h = 0.5 * window:
+ *     ia = the smallest index with s[ia] >= s[i] - h        ib = the largest index with s[ib] <= s[i] + h        (binary searches; ia <= i <= ib)
+ *     den = s[ib] - s[ia]
+ *     kappa[i] = den > 0 ? fix_heading(psi[ib] - psi[ia]) / den : 0
+ * fix_heading as in the track score: the first of p, p + 2 pi, p - 2 pi of smallest magnitude.  Every operation is rounded once (no contraction);
+ * the table is bit-identical to the same expressions in numpy.  The heading difference, not a circle through three recorded positions: GPS jitter
+ * and near-stationary samples make the latter useless on recorded paths.  No read leaves the sample's own path.  cdist must be non-decreasing
+ * within a path (kmpc_pathset_create's own cumulative distance is).  window finite and > 0.
+ *
+ * kmpc_speed_plan_fleet, DEVICE pointers:
+ *   kappa   [sum M] fp64: the table above (or the caller's own, in the same order; finite)
+ *   state   fp64, row b at state + b * state_stride doubles, X and Y first; state_stride >= 2: the plant's [B,8], an estimate [B,4], a pose [B,3]
+ *   path_id [B] int32, v_cap [B] fp64 (the speed the vehicle would drive without a plan: finite, >= 0)
+ *   rows    [B,8] fp64, 64 bytes per vehicle, row of vehicle b: */
+enum {
+    KMPC_PLAN_A_LAT = 0,       /* lateral acceleration the plan allows in a corner [m/s^2]: > 0; +inf = no cornering limit */
+    KMPC_PLAN_A_BRAKE = 1,     /* deceleration the plan counts on ahead of a limit [m/s^2]: > 0 and finite */
+    KMPC_PLAN_V_FLOOR = 2,     /* the plan never asks for less than min(v_cap, V_FLOOR) [m/s]: >= 0 and finite */
+    KMPC_PLAN_END_STOP = 3,    /* non-zero: the path's last sample has limit 0 (brake to a stop at the end); 0: it has its cornering limit */
+                               /* words 4 ... 7 are read by nobody */
+    KMPC_PLAN_WORDS = 8
+};
+/* The default row is (2.0, 0.7, 1.0, 0, 0, 0, 0, 0): kmpc_speed_plan_default writes B of them to HOST memory.
+ * Arithmetic, per vehicle, i = the nearest sample with kmpc_waypoints_fleet's argmin (the same device function), M its path's sample count:
+ *     vcap2 = v_cap * v_cap
+ *     lim_j = min(vcap2, A_LAT / max(|kappa_j|, 1e-9));   if END_STOP != 0 and j == M - 1: lim_j = 0
+ *     c_j   = lim_j + (2 * A_BRAKE) * (s_j - s_i)          the product, then the sum, each rounded once
+ *     w     = min over j = i ... M - 1 of c_j,   jb = the lowest j that attains it
+ *     v_plan = (w == vcap2) ? v_cap : min(v_cap, max(V_FLOOR, sqrt(w)))
+ * The select on w == vcap2 makes an unlimited vehicle's output v_cap itself, bit for bit.  The kernel stops at the first 64-sample chunk whose
+ * first sample has (2 * A_BRAKE) * (s_j - s_i), in the same arithmetic, >= the minimum so far: s is non-decreasing and every limit is >= 0, so
+ * no later term can be smaller -- the result is that of the full pass.
+ * Outputs: v_plan_out [B] fp64; info_out [B,4] fp64 or NULL = (w, s_jb - s_i, kappa_jb, sqrt(lim_i)); closest_out [B] int32 or NULL = i, for a
+ * finite pose bit-identical to kmpc_waypoints_fleet's closest_out.
+ * Refused vehicles: a path_id outside [0, P); a non-finite X or Y; v_cap non-finite or < 0; a row word out of the range above or NaN; a
+ * non-finite w or info word (v_cap^2 overflowing with no cornering limit; a NaN table entry or sample among those the pass visits).  v_plan_out 0,
+ * info_out row 0, closest_out -1; no sample and no table entry is read for a bad path_id; no other vehicle's outputs change.  Every word written
+ * is finite.
+ * Argument checks come before any use of the handle and any device call: a NULL set, a window not finite or <= 0, a NULL kappa_out; B < 0,
+ * state_stride < 2, and with B > 0 a NULL kappa, state, path_id, v_cap, rows or v_plan_out return KMPC_ERR_ARG, text in kmpc_last_error(NULL),
+ * also on a machine without a GPU.  B = 0 succeeds without a launch.  Asynchronous on `stream`; nothing is kept of the arguments. */
+int32_t kmpc_pathset_curvature(kmpc_pathset *ps, double window, double *kappa_out, void *stream);
+int32_t kmpc_speed_plan_default(double *rows_host, int32_t B);   /* HOST: B default rows; KMPC_ERR_ARG for B < 0 or, with B > 0, NULL */
+int32_t kmpc_speed_plan_fleet(kmpc_pathset *ps, int32_t B, const double *kappa, const double *state, int32_t state_stride,
+                              const int32_t *path_id, const double *v_cap, const double *rows,
+                              double *v_plan_out, double *info_out, int32_t *closest_out, void *stream);
+
 /* ---- closed-loop simulator --------------------------------------------------------
  * Replaces, for B simulated vehicles at once, `n_updates` passes of VehicleSimulator._update_vehicle_model
  * (scripts/vehicle_simulator.py:58-107: dynamic bicycle, linear tyres, 10 Euler sub-steps of 1 ms per pass, heading

@@ -4,7 +4,7 @@ Drop-in for ONE path of govvijaycal/mkz_mpc_path_follower: the per-step nonlinea
 scripts/mpc_utils/MKZMPCPathFollower.jl as driven by scripts/mpc_cmd_pub.jl.  Importing the
 package does not touch the GPU; constructing a solver does, and fails loudly without one.
 """
-__all__ = ["BatchMPC", "KinematicMPC", "synthetic", "get_reference_frenet_batch", "ClosedLoopFrenet", "ClosedLoop", "FleetRefTrajectory"]
+__all__ = ["BatchMPC", "KinematicMPC", "synthetic", "get_reference_frenet_batch", "ClosedLoopFrenet", "ClosedLoop", "FleetRefTrajectory", "SpeedPlanner"]
 
 
 def __getattr__(name):
@@ -26,6 +26,9 @@ def __getattr__(name):
     if name == "FleetRefTrajectory":
         from .ref_traj import FleetRefTrajectory
         return FleetRefTrajectory
+    if name == "SpeedPlanner":
+        from .ref_traj import SpeedPlanner
+        return SpeedPlanner
     if name == "synthetic":
         from . import synthetic
         return synthetic

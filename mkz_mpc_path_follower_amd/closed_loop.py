@@ -51,6 +51,11 @@ logs the command.  `estimator_input="history"` feeds the filter `compensator.fil
 steps across (refused without a compensator).  Scoring, the history's `state` and the plant stay on the truth; nothing synchronises.  The
 compensator's n_updates must be the loop's plant_updates (checked every period).  Without a compensator the loops take exactly the path they took.
 
+Speed plan: `planner=ref_traj.SpeedPlanner(grt, ...)` (grt a FleetRefTrajectory, every vehicle in target-velocity mode) runs in front of the waypoint
+stage, on the state the controller reads (truth, est, est_filt or est_pred), with `v_target` as the cap: `loop.v_plan` [B] replaces `v_target` in BOTH
+the waypoint call (the spacing is how the XY model follows a speed at C_v = 0) and the solve of that period.  `v_target` and `des_speed` are not
+modified; stop latch, rate-limit anchor, command stage and scoring are untouched.  Without a planner nothing changes.
+
 L0 actuation: the reference's low-level controller and a pedal-driven powertrain belong to the simulator (VehicleSimulator(drive=, llc=):
 kmpc_sim_advance_drive runs the controller's 50 Hz tick inside the plant call).  The loops only call `sim._update_vehicle_model`; `sim.state[:, 6]`
 is then the powertrain's net acceleration, which `estimator_input="actuator"` reads as delivered, while `estimator_input="command"` lets an
@@ -90,7 +95,7 @@ class _ScoredLoop:
     _reference(st) -> (ref, stop, solve, extra): the reference built from the controller's state `st`, the helper's stop flags, the solve as a
     call without arguments -> the solver's output dict, and the entries the loop adds to step()'s dict."""
 
-    def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer):
+    def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer, planner=None, track_with_time=False):
         """what both loops own beside grt, sim, N, B, mpc and the target speeds: buffers, the stop latch, the library, and the stages"""
         dev = self.sim.device
         self.u_prev = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)       # (acc, d_f): update_current_input starts at 0
@@ -105,6 +110,7 @@ class _ScoredLoop:
         self.k = 0
         self._init_sensor(sensor)
         self._init_estimator(estimator, estimator_input, compensator, observer)
+        self._init_planner(planner, track_with_time)
         self._init_score()
 
     def _period(self, plant_updates, time_solve):
@@ -141,6 +147,27 @@ class _ScoredLoop:
         self.sim._update_vehicle_model(plant_updates)
         self.k += 1
         return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s, **extra)
+
+    def _init_planner(self, planner, track_with_time):
+        if planner is not None:
+            if track_with_time:
+                raise ValueError("planner= plans a speed along the arclength grid: track_with_time must stay False")
+            if getattr(planner, "fleet", None) is not self.grt:
+                raise ValueError("planner= must be a ref_traj.SpeedPlanner built on this loop's own waypoint helper (a FleetRefTrajectory)")
+            if planner.device != self.sim.device or planner.B != self.B:
+                raise ValueError("planner for %d vehicles on %s, plant with %d on %s" % (planner.B, planner.device, self.B, self.sim.device))
+            if self.grt.time_mode is not None and bool(self.grt.time_mode.any().item()):
+                raise ValueError("planner= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode")
+        self.planner = planner
+        self.v_plan = None     # [B] the planned speed of the last period (planner given): waypoint spacing and the solver's v_target
+
+    def _speed(self, st):
+        """the speed this period's waypoints and solve run at: v_target, or with a planner loop.v_plan, planned on the state the controller reads
+        with v_target as the cap (v_target itself is not modified)"""
+        if self.planner is None:
+            return self.v_target
+        self.v_plan = self.planner.plan(st, self.v_target, out=self.v_plan)
+        return self.v_plan
 
     def _init_sensor(self, sensor):
         if sensor is not None and (sensor.B != self.B or sensor.device != self.sim.device):
@@ -227,7 +254,8 @@ class _ScoredLoop:
         period's new state is scored with that period's status, iters, command and stop latch.  history=True also records, on the device,
         state [steps+1,B,8] (the state before the first period first), cmd [steps,B,2], status [steps,B], latch [steps,B] and, with a sensor, est [steps,B,4]
         (what was measured of state[j] in period j: what the controller saw, unless an estimator follows) and, with an estimator, est_filt [steps,B,4]
-        (what the controller saw then, unless a compensator follows; an observer's est_filt likewise, with dist [steps,B,3]) and, with a compensator, est_pred [steps,B,4] (what the controller saw then).
+        (what the controller saw then, unless a compensator follows; an observer's est_filt likewise, with dist [steps,B,3]) and, with a compensator, est_pred [steps,B,4] (what the controller saw then)
+        and, with a planner, v_plan [steps,B] (the speed period j's waypoints and solve ran at).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -248,6 +276,8 @@ class _ScoredLoop:
                 hist["dist"] = torch.empty((steps, self.B, 3), dtype=torch.float64, device=dev)
             if self.compensator is not None:
                 hist["est_pred"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
+            if self.planner is not None:
+                hist["v_plan"] = torch.empty((steps, self.B), dtype=torch.float64, device=dev)
             hist["state"][0].copy_(self.sim.state)
         if score and self.k == 0 and self._score_fresh:
             self._score_state(None, settle_tol)
@@ -267,6 +297,8 @@ class _ScoredLoop:
                     hist["dist"][j].copy_(self.dist)
                 if self.compensator is not None:
                     hist["est_pred"][j].copy_(self.est_pred)
+                if self.planner is not None:
+                    hist["v_plan"][j].copy_(self.v_plan)
         out = dict(score=self.score, last=o)
         if score and self.track is not None:
             out.update(self.track)
@@ -298,7 +330,8 @@ class ClosedLoop(_ScoredLoop):
     v_des.  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
-                 mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, observer=None, **options):
+                 mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, observer=None, planner=None,
+                 **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -314,7 +347,7 @@ class ClosedLoop(_ScoredLoop):
             raise ValueError("a FleetRefTrajectory owns the tracking modes (its time_mode): track_with_time must stay False")
         self.track_with_time = track_with_time
         self.des_speed, self.v_target = _target_speeds(target_vel, self.B, sim.device)  # mpc_cmd_pub.jl:58-62
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time)
 
     def step(self, plant_updates=10, time_solve=False):
         """time_solve=True brackets the solve with device synchronisations and returns its wall time (`solve_s`)"""
@@ -322,9 +355,10 @@ class ClosedLoop(_ScoredLoop):
 
     def _reference(self, st):
         pose = st[:, 0:3].contiguous()
-        ref, stop = self.grt.get_waypoints_batch(pose, None if self.track_with_time else self.v_target)
+        vt = self._speed(st)
+        ref, stop = self.grt.get_waypoints_batch(pose, None if self.track_with_time else vt)
         z0 = st[:, 0:4].contiguous()                                                # x, y, psi, v = vx  (state_est, :43-46 of the simulator)
-        return ref, stop, lambda: self.mpc.solve(z0, ref, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
+        return ref, stop, lambda: self.mpc.solve(z0, ref, vt, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
                                                  params=self.params), {}
 
 
@@ -339,7 +373,7 @@ class ClosedLoopFrenet(_ScoredLoop):
     (checked once, here).  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, estimator=None,
-                 estimator_input="actuator", compensator=None, observer=None, **options):
+                 estimator_input="actuator", compensator=None, observer=None, planner=None, **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -358,7 +392,7 @@ class ClosedLoopFrenet(_ScoredLoop):
         if grt.device != sim.device:
             raise ValueError("waypoint helper on %s, plant on %s: the loop runs on one device" % (grt.device, sim.device))
         self.des_speed, self.v_target = des_speed, v_target
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time)
 
     def step(self, plant_updates=10, time_solve=False):
         """as ClosedLoop.step; the returned dict also carries `k_poly` [B,4] and `fit_status` [B]"""
@@ -366,7 +400,8 @@ class ClosedLoopFrenet(_ScoredLoop):
 
     def _reference(self, st):
         pose = st[:, 0:3].contiguous()
-        ref, stop = self.grt.get_waypoints_batch(pose, self.v_target)
+        vt = self._speed(st)
+        ref, stop = self.grt.get_waypoints_batch(pose, vt)
         k_poly, _psi, z0, fit_status = get_reference_frenet_batch(pose, ref, st[:, 3].contiguous())
-        return ref, stop, lambda: self.mpc.solve_frenet(z0, k_poly, self.v_target, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
+        return ref, stop, lambda: self.mpc.solve_frenet(z0, k_poly, vt, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
                                                         params=self.params), dict(k_poly=k_poly, fit_status=fit_status)

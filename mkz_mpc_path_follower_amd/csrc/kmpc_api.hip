@@ -697,6 +697,48 @@ extern "C" int32_t kmpc_track_score_fleet(kmpc_pathset *ps, int32_t B, const dou
     return KMPC_OK;
 }
 
+// ---- curvature table and speed plan (kmpc_speed_plan.hip) ------------------------------------------------------------
+extern "C" int32_t kmpc_pathset_curvature(kmpc_pathset *ps, double window, double *kappa_out, void *stream)
+{
+    if (!ps) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_curvature: null path set");
+    if (!std::isfinite(window) || !(window > 0)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_curvature: window must be finite and > 0");
+    if (!kappa_out) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_curvature: null kappa_out");
+    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_pathset_curvature: hipSetDevice(%d) failed", ps->device);
+    const SPC k = {ps->P, ps->total, 0.5 * window, ps->d, ps->off, kappa_out};
+    const hipError_t e = kmpc_launch_curvature(k, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_pathset_curvature: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+// this project's own defaults (the reference has no such stage): the one place they exist
+extern "C" int32_t kmpc_speed_plan_default(double *rows_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_speed_plan_default: bad argument (B=%d)", B);
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        double *r = rows_host + KMPC_PLAN_WORDS * b;
+        for (int i = 0; i < KMPC_PLAN_WORDS; ++i) r[i] = 0.0;
+        r[KMPC_PLAN_A_LAT] = 2.0; r[KMPC_PLAN_A_BRAKE] = 0.7; r[KMPC_PLAN_V_FLOOR] = 1.0; r[KMPC_PLAN_END_STOP] = 0.0;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_speed_plan_fleet(kmpc_pathset *ps, int32_t B, const double *kappa, const double *state, int32_t state_stride,
+                                         const int32_t *path_id, const double *v_cap, const double *rows, double *v_plan_out, double *info_out,
+                                         int32_t *closest_out, void *stream)
+{
+    if (!ps) return fail(nullptr, KMPC_ERR_ARG, "kmpc_speed_plan_fleet: null path set");
+    if (B < 0 || state_stride < 2)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_speed_plan_fleet: bad B / state_stride (B=%d, state_stride=%d; state_stride >= 2)", B, state_stride);
+    if (B > 0 && (!kappa || !state || !path_id || !v_cap || !rows || !v_plan_out))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_speed_plan_fleet: null required buffer");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_speed_plan_fleet: hipSetDevice(%d) failed", ps->device);
+    const SPF w = {ps->P, B, ps->total, state_stride, ps->d, ps->off, kappa, state, path_id, v_cap, rows, v_plan_out, info_out, closest_out};
+    const hipError_t e = kmpc_launch_speed_plan_fleet(w, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_speed_plan_fleet: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 // ---- closed-loop simulator (kmpc_sim.hip) ------------------------------------------------------------------------
 extern "C" int32_t kmpc_sim_advance_batch(int32_t device, int32_t B, void *state, const void *cmd, int32_t n_updates, void *stream)
 {

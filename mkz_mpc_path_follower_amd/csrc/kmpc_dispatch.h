@@ -189,6 +189,30 @@ struct TSF {                   // a set of paths, a path per vehicle
 hipError_t kmpc_launch_track_score(const TSB &k, hipStream_t st);
 hipError_t kmpc_launch_track_score_fleet(const TSF &k, hipStream_t st);
 
+// curvature table of a set of paths and a speed plan per vehicle (kmpc_speed_plan.hip)
+struct SPC {
+    int P, total;              // paths; sum of the paths' sample counts = off[P]
+    double h;                  // half the arclength window
+    const double *d;           // t | X | Y | psi | s, each `total` doubles
+    const int32_t *off;        // [P+1]
+    double *kappa;             // [total]
+};
+struct SPF {
+    int P, B, total, stride;   // paths, vehicles, samples in all; doubles between two rows of `state` (>= 2)
+    const double *d;           // t | X | Y | psi | s, each `total` doubles
+    const int32_t *off;        // [P+1]
+    const double *kappa;       // [total] the table kmpc_launch_curvature wrote
+    const double *state;       // row b: X, Y first
+    const int32_t *path_id;    // [B]
+    const double *v_cap;       // [B]
+    const double *rows;        // [B,8] (layout: include/kmpc.h, KMPC_PLAN_*)
+    double *v_plan;            // [B]
+    double *info;              // [B,4] w, s_jb - s_i, kappa_jb, sqrt(lim_i), or null
+    int32_t *closest;          // [B] or null: index within the vehicle's own path, -1 if refused
+};
+hipError_t kmpc_launch_curvature(const SPC &k, hipStream_t st);
+hipError_t kmpc_launch_speed_plan_fleet(const SPF &w, hipStream_t st);
+
 // batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
 // scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)
 struct FR {

@@ -18,6 +18,7 @@
 #include "kmpc_common.h"
 #include "kmpc_dispatch.h"
 #include "kmpc_interp.h"   // np_interp
+#include "kmpc_nearest.h"  // nearest_sample
 
 // one recorded path as the body sees it: five arrays of M samples
 struct PathView {
@@ -32,19 +33,7 @@ DEV void waypoints_vehicle(const PathView &pv, const int use_vtarget, const int 
 {
     const double x = pose[3 * (size_t)b], y = pose[3 * (size_t)b + 1], yaw = pose[3 * (size_t)b + 2];
     // ---- closest recorded point: argmin (X-x)^2 + (Y-y)^2, first occurrence (np.argmin) ---------
-    double best = INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = lane; i < pv.M; i += 64) {
-        const double dx = __dsub_rn(pv.X[i], x), dy = __dsub_rn(pv.Y[i], y);
-        const double d = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
-        if (d < best) { best = d; bi = i; }
-    }
-    const double dmin = dpp_min(best);
-    const double cand = (best == dmin) ? (double)bi : 1e18;
-    int closest = (int)dpp_min(cand);
-    // a non-finite pose (NaN or +-inf from the GPS / plant) makes every distance NaN or +inf: no lane records an index.  np.argmin
-    // returns 0 then (first NaN / first of the equal minima), and so does this -- never an index outside the path arrays
-    closest = (unsigned)closest < (unsigned)pv.M ? closest : 0;
+    const int closest = nearest_sample(pv.X, pv.Y, pv.M, x, y, lane);   // kmpc_nearest.h: shared with the speed plan
     // ---- look-ahead grid ---------------------------------------------------------------------------
     const int k = lane;
     const bool act = k <= H;

@@ -253,3 +253,104 @@ class FleetRefTrajectory:
             raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, self.device))
         return _track_score(self._lib, self._lib.kmpc_track_score_fleet, self._h, self.device, B, pid, state, score, status, iters, cmd,
                             stop_latch, settle_tol, out)
+
+
+PLAN_WORDS = 8
+PLAN_FIELDS = ("a_lat", "a_brake", "v_floor", "end_stop")   # KMPC_PLAN_* words 0 ... 3 of include/kmpc.h, in row order (4 ... 7 are read by nobody)
+
+
+def speed_plan_default():
+    """the default plan row (2.0, 0.7, 1.0, 0, 0, 0, 0, 0) as a numpy row [8], from kmpc_speed_plan_default"""
+    row = np.zeros(PLAN_WORDS)
+    _lib.check(_lib.load().kmpc_speed_plan_default(row.ctypes.data_as(C.POINTER(C.c_double)), 1))
+    return row
+
+
+def check_speed_plan_rows(rows):
+    """[B,8] host rows -> ValueError unless a_lat > 0 (+inf: no cornering limit), a_brake > 0 and finite, v_floor >= 0 and finite and end_stop is
+    not NaN.  The kernel refuses such a vehicle (v_plan 0) on its own; this says so where the rows are written."""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != PLAN_WORDS:
+        raise ValueError("speed plan rows: [B,8] (%s, four unused words), got %s" % (", ".join(PLAN_FIELDS), rows.shape))
+    with np.errstate(invalid="ignore"):
+        ok = (rows[:, 0] > 0.0) & (rows[:, 1] > 0.0) & np.isfinite(rows[:, 1]) & (rows[:, 2] >= 0.0) & np.isfinite(rows[:, 2]) & ~np.isnan(rows[:, 3])
+    if not ok.all():
+        raise ValueError("speed plan rows: a_lat > 0 (+inf: no limit), a_brake > 0 and finite, v_floor >= 0 and finite, end_stop not NaN "
+                         "(vehicle(s) %s)" % np.flatnonzero(~ok)[:8].tolist())
+    return rows
+
+
+def speed_plan_params(B, device=0, **overrides):
+    """[B,8] float64 plan rows on `device`: the default row, with each override (`a_lat=`, `a_brake=`, `v_floor=`, `end_stop=`) a scalar or one
+    value per vehicle.  Validated on the host (check_speed_plan_rows) before anything reaches the device."""
+    rows = np.tile(speed_plan_default(), (int(B), 1))
+    for k, v in overrides.items():
+        if k not in PLAN_FIELDS:
+            raise ValueError("speed_plan_params: unknown parameter %r (one of %s)" % (k, ", ".join(PLAN_FIELDS)))
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
+            raise ValueError("speed_plan_params: %s is a scalar or one value per vehicle [%d], got %s" % (k, B, v.shape))
+        rows[:, PLAN_FIELDS.index(k)] = v
+    return torch.as_tensor(check_speed_plan_rows(rows)).to(torch.device("cuda", device) if isinstance(device, int) else torch.device(device))
+
+
+class SpeedPlanner:
+    """A curvature- and grip-limited target speed per vehicle of a FleetRefTrajectory (kmpc_pathset_curvature once, here; kmpc_speed_plan_fleet
+    per call of plan()).  A one-path fleet covers the single-path case.
+
+    kappa [sum M]: the curvature table of the fleet's paths at `window` m, a device tensor, in the order of fleet.trajectories.
+    rows [B,8] (speed_plan_params): a public device tensor, read by every plan() as it is -- edit it in place between steps, like fleet.path_id.
+    The vehicle's path is fleet.path_id[b] at the time of the call.  A vehicle the kernel refuses (include/kmpc.h) gets v_plan 0."""
+
+    def __init__(self, fleet, window=4.0, rows=None):
+        if not isinstance(fleet, FleetRefTrajectory):
+            raise ValueError("SpeedPlanner plans on a FleetRefTrajectory (a one-path fleet covers a single path); a %s is not one"
+                             % type(fleet).__name__)
+        window = float(window)
+        if not (math.isfinite(window) and window > 0.0):
+            raise ValueError("window: finite and > 0 [m], got %r" % (window,))
+        self.fleet, self.window, self.device = fleet, window, fleet.device
+        self.B = int(fleet.path_id.shape[0])
+        self._lib = fleet._lib
+        self.kappa = torch.empty((sum(len(tr) for tr in fleet.trajectories),), dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_pathset_curvature(fleet._h, window, C.c_void_p(self.kappa.data_ptr()), stream))
+        self.rows = speed_plan_params(self.B, self.device) if rows is None else rows
+        self._check_rows()
+        self.info = self.closest = None   # [B,4] (w, s_jb - s_i, kappa_jb, sqrt(lim_i)) and [B] of the last plan(want_info=True)
+
+    def _check_rows(self):
+        r = self.rows
+        if not (type(r) is torch.Tensor and r.dtype == torch.float64 and tuple(r.shape) == (self.B, PLAN_WORDS) and r.is_contiguous()
+                and r.device == self.device):
+            raise ValueError("rows must be a contiguous float64 tensor [%d,8] on %s (speed_plan_params; write into it in place)" % (self.B, self.device))
+
+    def plan(self, state, v_cap, out=None, want_info=False):
+        """state: device tensor [B,W], X and Y first (the plant's [B,8], an estimate [B,4], a pose [B,3]: no copy); v_cap [B] -> v_plan [B] (`out`
+        or a new tensor).  want_info=True also fills self.info [B,4] and self.closest [B].  Asynchronous on torch's current stream."""
+        dev, B = self.device, self.B
+        st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=dev)
+        if not (st.dtype == torch.float64 and st.device == dev and st.dim() == 2 and st.shape[1] >= 2 and (B == 0 or st.stride(1) == 1)
+                and st.stride(0) >= 2):
+            st = torch.as_tensor(st, dtype=torch.float64, device=dev).contiguous()
+        if st.dim() != 2 or st.shape[0] != B or st.shape[1] < 2:
+            raise ValueError("state: expected [%d,W] with X, Y in the first two columns, got %s" % (B, tuple(st.shape)))
+        vc = torch.as_tensor(v_cap, dtype=torch.float64, device=dev).contiguous()
+        if tuple(vc.shape) != (B,):
+            raise ValueError("v_cap: expected [%d], got %s" % (B, tuple(vc.shape)))
+        self._check_rows()
+        pid = self.fleet.path_id
+        if not (pid.dtype == torch.int32 and tuple(pid.shape) == (B,) and pid.is_contiguous() and pid.device == dev):
+            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
+        if out is None:
+            out = torch.empty((B,), dtype=torch.float64, device=dev)
+        elif not (type(out) is torch.Tensor and out.dtype == torch.float64 and tuple(out.shape) == (B,) and out.is_contiguous() and out.device == dev):
+            raise ValueError("out: expected a contiguous float64 tensor [%d] on %s" % (B, dev))
+        if want_info and self.info is None:
+            self.info = torch.empty((B, 4), dtype=torch.float64, device=dev)
+            self.closest = torch.empty((B,), dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(self._lib.kmpc_speed_plan_fleet(self.fleet._h, B, p(self.kappa), p(st), int(st.stride(0)) if B else 2, p(pid), p(vc), p(self.rows),
+                                                   p(out), p(self.info) if want_info else None, p(self.closest) if want_info else None, stream))
+        return out
