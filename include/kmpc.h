@@ -396,6 +396,57 @@ int32_t kmpc_speed_plan_fleet(kmpc_pathset *ps, int32_t B, const double *kappa, 
                               const int32_t *path_id, const double *v_cap, const double *rows,
                               double *v_plan_out, double *info_out, int32_t *closest_out, void *stream);
 
+/* ---- road profile per path sample: grip, bank, grade, speed limits ----------------------------------------------------------------------------
+ * The road row of kmpc_sim_advance_road and the plan row above describe the road as one row per vehicle for a whole run.  A road profile describes
+ * it per PLACE: a table with one row per recorded sample of a path set, in the set's sample order, like the curvature table.  Two consumers read
+ * it, each through its own call and each from a table of its own: the plant's table is the truth (kmpc_road_profile_fleet composes it into the road
+ * row the plant reads, once per period), the plan's table is the map (kmpc_speed_plan_fleet_profile).  A map that knows nothing is the neutral table.
+ *
+ * profile [sum M, 8] fp64 DEVICE, caller-owned, 64 bytes per sample, row of sample g = off_p + i (sample i of path p): */
+enum {
+    KMPC_PROFILE_MU_SCALE = 0, /* multiplies both friction coefficients / the plan's A_LAT at this sample: > 0 and finite; 1 = neutral */
+    KMPC_PROFILE_A_LONG = 1,   /* added to the road row's A_LONG at this sample [m/s^2] (grade): finite */
+    KMPC_PROFILE_A_LAT = 2,    /* added to the road row's A_LAT at this sample [m/s^2] (bank): finite */
+    KMPC_PROFILE_V_LIMIT = 3,  /* posted speed limit [m/s], read by the plan only: >= 0; +inf = none */
+                               /* words 4 ... 7 are read by nobody */
+    KMPC_PROFILE_WORDS = 8
+};
+/* The neutral row is (1, 0, 0, +inf, 0, 0, 0, 0): kmpc_road_profile_default writes n of them to HOST memory.  DF_OFFSET and ACC_GAIN belong to the
+ * vehicle, not to the road: the profile has no word for them.
+ *
+ * kmpc_road_profile_fleet, DEVICE pointers: profile as above; state, state_stride and path_id as kmpc_speed_plan_fleet's; road_base [B,8] fp64, the
+ * caller's road rows (KMPC_ROAD_*); road_out [B,8] fp64, the rows the plant reads; closest_out [B] int32 or NULL.
+ * Per vehicle, i = the nearest sample with kmpc_waypoints_fleet's argmin (the same device function) within its own path, r = the profile's row at
+ * off[path] + i, each operation rounded once:
+ *     road_out[MU_F]   = road_base[MU_F] * r[MU_SCALE]        road_out[MU_R]  = road_base[MU_R] * r[MU_SCALE]        (inf stays inf)
+ *     road_out[A_LONG] = road_base[A_LONG] + r[A_LONG]        road_out[A_LAT] = road_base[A_LAT] + r[A_LAT]
+ *     words 4 ... 7 of road_out = words 4 ... 7 of road_base, bit for bit
+ *     closest_out = i, for a finite pose bit-identical to kmpc_waypoints_fleet's closest_out
+ * The profile is piecewise constant by nearest sample: no interpolation.  With the neutral table road_out equals road_base as numbers; only a -0.0
+ * in A_LONG / A_LAT may come back as +0.0.
+ * Refused vehicles: a path_id outside [0, P) or a non-finite X or Y.  road_out row = road_base row bit for bit (the vehicle drives on its own base
+ * road), closest_out -1; no sample and no table entry is read for a bad path_id; no other vehicle's outputs change.
+ * The kernel cannot validate the table: a bad table word reaches the vehicles whose nearest sample holds it, and only those.  Validate on the host.
+ * road_out must not be road_base (the scaling would compound call after call): equal pointers return KMPC_ERR_ARG.
+ * Argument checks come before any device call: a NULL set, B < 0, state_stride < 2, and with B > 0 a NULL profile, state, path_id, road_base or
+ * road_out return KMPC_ERR_ARG, text in kmpc_last_error(NULL), also on a machine without a GPU.  B = 0 succeeds without a launch.  Asynchronous on
+ * `stream`; nothing is kept of the arguments.
+ *
+ * kmpc_speed_plan_fleet_profile: kmpc_speed_plan_fleet with a map.  Rows, refusals, outputs, the early exit and the select on w == vcap2 are that
+ * call's; only the limit of a sample differs, with profile_j the map's row of sample j of the vehicle's own path:
+ *     a_j   = A_LAT * profile_j[MU_SCALE]                                                          one rounding; inf stays inf
+ *     lim_j = min(vcap2, a_j / max(|kappa_j|, 1e-9), profile_j[V_LIMIT] * profile_j[V_LIMIT]);     each rounded once; END_STOP as above
+ * A NaN in MU_SCALE or V_LIMIT of a sample the pass visits refuses the vehicle, as a NaN kappa entry does.  A_LONG, A_LAT and words 4 ... 7 of the
+ * map are not read.  Every limit is still >= 0 for a valid table, so the early exit stays exact.  With the neutral table every output word is
+ * bit-identical to kmpc_speed_plan_fleet's (A_LAT * 1 and min(., inf) are exact).  Argument checks as kmpc_speed_plan_fleet's, and with B > 0 a
+ * NULL profile returns KMPC_ERR_ARG. */
+int32_t kmpc_road_profile_default(double *rows_host, int32_t n);   /* HOST: n neutral rows; KMPC_ERR_ARG for n < 0 or, with n > 0, NULL */
+int32_t kmpc_road_profile_fleet(kmpc_pathset *ps, int32_t B, const double *profile, const double *state, int32_t state_stride,
+                                const int32_t *path_id, const double *road_base, double *road_out, int32_t *closest_out, void *stream);
+int32_t kmpc_speed_plan_fleet_profile(kmpc_pathset *ps, int32_t B, const double *kappa, const double *profile, const double *state,
+                                      int32_t state_stride, const int32_t *path_id, const double *v_cap, const double *rows,
+                                      double *v_plan_out, double *info_out, int32_t *closest_out, void *stream);
+
 /* ---- closed-loop simulator --------------------------------------------------------
  * Replaces, for B simulated vehicles at once, `n_updates` passes of VehicleSimulator._update_vehicle_model
  * (scripts/vehicle_simulator.py:58-107: dynamic bicycle, linear tyres, 10 Euler sub-steps of 1 ms per pass, heading
@@ -510,8 +561,8 @@ enum {
  *     utilisation is not larger).  road_stat is read and written once per call, after the last sub-step.
  * The reference's two quirks stay: lf in the rear slip angle and no Fyf sin(df) / m term in vx.
  * Not modelled: a longitudinal grip limit and combined slip (the solver's a_max is 1 m/s^2, far inside mu g for any mu worth sweeping), load
- * transfer (the axle loads are the static ones), a limit that varies along the path, random gusts.  The rows are plain device memory: a caller
- * who wants a wet patch edits `road` between periods.
+ * transfer (the axle loads are the static ones), random gusts.  The rows are plain device memory.  A limit, a bank or a grade that varies
+ * along the path comes from a road profile (kmpc_road_profile_fleet, above): it composes this row once per period, on the device.
  * Contract: with the neutral row in every vehicle the call leaves the state that kmpc_sim_advance_queue leaves on the same arguments, bit for
  * bit, and road_stat untouched (count + 0, and 0 is not larger).  A row cannot be checked from the host: a non-finite word, a mu <= 0 or a NaN
  * anywhere poisons that vehicle's state or statistics alone -- one thread per vehicle, no lane reads another's row.  Validate rows where they

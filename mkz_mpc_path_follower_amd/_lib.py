@@ -41,7 +41,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_road_default", "kmpc_sim_advance_road", "kmpc_observe_batch", "kmpc_cmd_offset_batch",
            "kmpc_predict_ahead_dist_batch",
            "kmpc_llc_default", "kmpc_llc_step_batch", "kmpc_drive_default", "kmpc_sim_advance_drive",
-           "kmpc_pathset_curvature", "kmpc_speed_plan_default", "kmpc_speed_plan_fleet"]
+           "kmpc_pathset_curvature", "kmpc_speed_plan_default", "kmpc_speed_plan_fleet",
+           "kmpc_road_profile_default", "kmpc_road_profile_fleet", "kmpc_speed_plan_fleet_profile"]
 
 _lib = None
 
@@ -92,6 +93,9 @@ def load():
     L.kmpc_pathset_curvature.argtypes = [vp, C.c_double, vp, vp]
     L.kmpc_speed_plan_default.argtypes = [dp, i32]
     L.kmpc_speed_plan_fleet.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.kmpc_road_profile_default.argtypes = [dp, i32]
+    L.kmpc_road_profile_fleet.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.kmpc_speed_plan_fleet_profile.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.kmpc_sim_advance_batch.argtypes = [i32, i32, vp, vp, i32, vp]
     L.kmpc_plant_default.argtypes = [dp]
     L.kmpc_sim_advance_plant.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, vp]

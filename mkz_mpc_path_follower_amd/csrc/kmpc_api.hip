@@ -722,20 +722,68 @@ extern "C" int32_t kmpc_speed_plan_default(double *rows_host, int32_t B)
     return KMPC_OK;
 }
 
+// both plan entry points: `profile` is the map of kmpc_speed_plan_fleet_profile (required there), null for kmpc_speed_plan_fleet
+static int32_t speed_plan_fleet(const char *fn, bool with_profile, kmpc_pathset *ps, int32_t B, const double *kappa, const double *profile,
+                                const double *state, int32_t state_stride, const int32_t *path_id, const double *v_cap, const double *rows,
+                                double *v_plan_out, double *info_out, int32_t *closest_out, void *stream)
+{
+    if (!ps) return fail(nullptr, KMPC_ERR_ARG, "%s: null path set", fn);
+    if (B < 0 || state_stride < 2)
+        return fail(nullptr, KMPC_ERR_ARG, "%s: bad B / state_stride (B=%d, state_stride=%d; state_stride >= 2)", fn, B, state_stride);
+    if (B > 0 && (!kappa || (with_profile && !profile) || !state || !path_id || !v_cap || !rows || !v_plan_out))
+        return fail(nullptr, KMPC_ERR_ARG, "%s: null required buffer", fn);
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "%s: hipSetDevice(%d) failed", fn, ps->device);
+    const SPF w = {ps->P, B, ps->total, state_stride, ps->d, ps->off, kappa, with_profile ? profile : nullptr, state, path_id, v_cap, rows,
+                   v_plan_out, info_out, closest_out};
+    const hipError_t e = kmpc_launch_speed_plan_fleet(w, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 extern "C" int32_t kmpc_speed_plan_fleet(kmpc_pathset *ps, int32_t B, const double *kappa, const double *state, int32_t state_stride,
                                          const int32_t *path_id, const double *v_cap, const double *rows, double *v_plan_out, double *info_out,
                                          int32_t *closest_out, void *stream)
 {
-    if (!ps) return fail(nullptr, KMPC_ERR_ARG, "kmpc_speed_plan_fleet: null path set");
+    return speed_plan_fleet("kmpc_speed_plan_fleet", false, ps, B, kappa, nullptr, state, state_stride, path_id, v_cap, rows, v_plan_out, info_out,
+                            closest_out, stream);
+}
+
+extern "C" int32_t kmpc_speed_plan_fleet_profile(kmpc_pathset *ps, int32_t B, const double *kappa, const double *profile, const double *state,
+                                                 int32_t state_stride, const int32_t *path_id, const double *v_cap, const double *rows,
+                                                 double *v_plan_out, double *info_out, int32_t *closest_out, void *stream)
+{
+    return speed_plan_fleet("kmpc_speed_plan_fleet_profile", true, ps, B, kappa, profile, state, state_stride, path_id, v_cap, rows, v_plan_out,
+                            info_out, closest_out, stream);
+}
+
+// ---- road profile per path sample (kmpc_road_profile.hip) ----------------------------------------------------------------
+extern "C" int32_t kmpc_road_profile_default(double *rows_host, int32_t n)
+{
+    if (n < 0 || (n > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_road_profile_default: bad argument (n=%d)", n);
+    for (size_t g = 0; g < (size_t)n; ++g) {
+        double *r = rows_host + KMPC_PROFILE_WORDS * g;
+        for (int i = 0; i < KMPC_PROFILE_WORDS; ++i) r[i] = 0.0;
+        r[KMPC_PROFILE_MU_SCALE] = 1.0; r[KMPC_PROFILE_V_LIMIT] = INFINITY;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_road_profile_fleet(kmpc_pathset *ps, int32_t B, const double *profile, const double *state, int32_t state_stride,
+                                           const int32_t *path_id, const double *road_base, double *road_out, int32_t *closest_out, void *stream)
+{
+    if (!ps) return fail(nullptr, KMPC_ERR_ARG, "kmpc_road_profile_fleet: null path set");
     if (B < 0 || state_stride < 2)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_speed_plan_fleet: bad B / state_stride (B=%d, state_stride=%d; state_stride >= 2)", B, state_stride);
-    if (B > 0 && (!kappa || !state || !path_id || !v_cap || !rows || !v_plan_out))
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_speed_plan_fleet: null required buffer");
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_road_profile_fleet: bad B / state_stride (B=%d, state_stride=%d; state_stride >= 2)", B, state_stride);
+    if (B > 0 && (!profile || !state || !path_id || !road_base || !road_out))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_road_profile_fleet: null required buffer");
+    if (road_out && road_out == road_base)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_road_profile_fleet: road_out must not be road_base (the scaling would compound call after call)");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_speed_plan_fleet: hipSetDevice(%d) failed", ps->device);
-    const SPF w = {ps->P, B, ps->total, state_stride, ps->d, ps->off, kappa, state, path_id, v_cap, rows, v_plan_out, info_out, closest_out};
-    const hipError_t e = kmpc_launch_speed_plan_fleet(w, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_speed_plan_fleet: %s", hipGetErrorString(e));
+    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_road_profile_fleet: hipSetDevice(%d) failed", ps->device);
+    const RPF w = {ps->P, B, ps->total, state_stride, ps->d, ps->off, profile, state, path_id, road_base, road_out, closest_out};
+    const hipError_t e = kmpc_launch_road_profile_fleet(w, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_road_profile_fleet: %s", hipGetErrorString(e));
     return KMPC_OK;
 }
 

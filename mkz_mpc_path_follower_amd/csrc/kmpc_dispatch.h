@@ -202,6 +202,7 @@ struct SPF {
     const double *d;           // t | X | Y | psi | s, each `total` doubles
     const int32_t *off;        // [P+1]
     const double *kappa;       // [total] the table kmpc_launch_curvature wrote
+    const double *profile;     // [total,8] the map (layout: include/kmpc.h, KMPC_PROFILE_*), or null: the plan without one
     const double *state;       // row b: X, Y first
     const int32_t *path_id;    // [B]
     const double *v_cap;       // [B]
@@ -212,6 +213,20 @@ struct SPF {
 };
 hipError_t kmpc_launch_curvature(const SPC &k, hipStream_t st);
 hipError_t kmpc_launch_speed_plan_fleet(const SPF &w, hipStream_t st);
+
+// the road under each vehicle, from a profile of a set of paths (kmpc_road_profile.hip)
+struct RPF {
+    int P, B, total, stride;   // paths, vehicles, samples in all; doubles between two rows of `state` (>= 2)
+    const double *d;           // t | X | Y | psi | s, each `total` doubles
+    const int32_t *off;        // [P+1]
+    const double *profile;     // [total,8] (layout: include/kmpc.h, KMPC_PROFILE_*)
+    const double *state;       // row b: X, Y first
+    const int32_t *path_id;    // [B]
+    const double *road_base;   // [B,8] the caller's road rows (KMPC_ROAD_*)
+    double *road_out;          // [B,8] what the plant reads; never road_base
+    int32_t *closest;          // [B] or null: index within the vehicle's own path, -1 if refused
+};
+hipError_t kmpc_launch_road_profile_fleet(const RPF &w, hipStream_t st);
 
 // batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
 // scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)

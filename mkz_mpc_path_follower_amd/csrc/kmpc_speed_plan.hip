@@ -12,9 +12,11 @@
 // the waypoint kernel's argmin; then lanes take 64 consecutive samples per chunk from i on, keep their own minimum and lowest index, and the wave
 // reduces with dpp_min after every chunk so that the loop can stop -- exactly -- at the first chunk whose first sample's braking term alone is >=
 // the running minimum (s is non-decreasing and every limit is >= 0: no later term can be smaller, and an equal one loses to the lower index).
+// kmpc_speed_plan_fleet_kernel<true> is the plan with a map (kmpc_speed_plan_fleet_profile): the same body, with the limit of sample j read through the
+// road profile's row of that sample (MU_SCALE scales A_LAT, V_LIMIT^2 joins the minimum); <false> computes what it computed before the map existed.
 // Arithmetic is _rn intrinsics throughout: no product and sum share a rounding, and the outputs match the numpy restatement bit for bit (v_plan and
 // sqrt(lim_i) as far as the device's fp64 sqrt is correctly rounded).  Plain C++: vector stores, no inline assembly, no scratch.
-#include "../../include/kmpc.h"   // KMPC_PLAN_*: the row layout
+#include "../../include/kmpc.h"   // KMPC_PLAN_*, KMPC_PROFILE_*: the row layouts
 #include "kmpc_common.h"
 #include "kmpc_dispatch.h"
 #include "kmpc_nearest.h"
@@ -71,7 +73,17 @@ DEV double plan_limit(const double kap, const double a_lat, const double vcap2)
     return vcap2 < q ? vcap2 : q;
 }
 
-__global__ __launch_bounds__(64) void kmpc_speed_plan_fleet_kernel(SPF w)
+// the same with a map: a_j = A_LAT * MU_SCALE_j, lim_j = min(vcap2, a_j / max(|kappa_j|, 1e-9), V_LIMIT_j^2), each rounded once.  The second select
+// would swallow a NaN of the first (mu, kappa), so `nan` collects the NaNs of both operands: the caller ors it into saw_nan
+DEV double plan_limit_profile(const double kap, const double *prow, const double a_lat, const double vcap2, bool &nan)
+{
+    const double vl = prow[KMPC_PROFILE_V_LIMIT];
+    const double m = plan_limit(kap, __dmul_rn(a_lat, prow[KMPC_PROFILE_MU_SCALE]), vcap2), vl2 = __dmul_rn(vl, vl);
+    nan |= m != m || vl2 != vl2;
+    return m < vl2 ? m : vl2;
+}
+
+template <bool PROFILE> __global__ __launch_bounds__(64) void kmpc_speed_plan_fleet_kernel(SPF w)
 {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= w.B) return;
@@ -89,6 +101,8 @@ __global__ __launch_bounds__(64) void kmpc_speed_plan_fleet_kernel(SPF w)
     const size_t n = (size_t)w.total;
     const double *seg = w.d + o0;                                    // d = t | X | Y | psi | s
     const double *s = seg + 4 * n, *kappa = w.kappa + o0;            // indices 0 .. M-1 of the vehicle's own path
+    const double *prof = nullptr;                                    // the map's rows of the vehicle's own path
+    if constexpr (PROFILE) prof = w.profile + KMPC_PROFILE_WORDS * (size_t)o0;
     const int i = nearest_sample(seg + n, seg + 2 * n, M, x, y, lane);
     const double s_i = s[i], vcap2 = __dmul_rn(vcap, vcap), two_a = __dmul_rn(2.0, a_brake);
     const bool stop_at_end = end_stop != 0.0;
@@ -102,7 +116,9 @@ __global__ __launch_bounds__(64) void kmpc_speed_plan_fleet_kernel(SPF w)
         if (base != i && __dmul_rn(two_a, __dsub_rn(s[base], s_i)) >= wmin) break;
         const int j = base + lane;
         if (j < M) {
-            double lim = plan_limit(kappa[j], a_lat, vcap2);
+            double lim;
+            if constexpr (PROFILE) lim = plan_limit_profile(kappa[j], prof + KMPC_PROFILE_WORDS * (size_t)j, a_lat, vcap2, saw_nan);
+            else lim = plan_limit(kappa[j], a_lat, vcap2);
             if (stop_at_end && j == M - 1) lim = 0.0;
             const double c = __dadd_rn(lim, __dmul_rn(two_a, __dsub_rn(s[j], s_i)));
             saw_nan |= c != c;
@@ -114,7 +130,9 @@ __global__ __launch_bounds__(64) void kmpc_speed_plan_fleet_kernel(SPF w)
     int jb = (int)dpp_min(cand);
     jb = (jb >= i && jb < M) ? jb : i;                               // never an index outside the path arrays
     const bool any_nan = __builtin_amdgcn_ballot_w64(saw_nan) != 0;
-    double lim_i = plan_limit(kappa[i], a_lat, vcap2);
+    double lim_i;
+    if constexpr (PROFILE) lim_i = plan_limit_profile(kappa[i], prof + KMPC_PROFILE_WORDS * (size_t)i, a_lat, vcap2, saw_nan);   // sample i was visited: no new NaN
+    else lim_i = plan_limit(kappa[i], a_lat, vcap2);
     if (stop_at_end && i == M - 1) lim_i = 0.0;
     const double d_bind = __dsub_rn(s[jb], s_i), kappa_bind = kappa[jb], v_here = __dsqrt_rn(lim_i);
     // an unlimited vehicle's speed is v_cap itself, bit for bit, whatever the device's sqrt
@@ -143,5 +161,6 @@ hipError_t kmpc_launch_curvature(const SPC &k, hipStream_t st)
 
 hipError_t kmpc_launch_speed_plan_fleet(const SPF &w, hipStream_t st)
 {
-    return kmpc_launch(kmpc_speed_plan_fleet_kernel, dim3(w.B), dim3(64), 0, st, w);
+    return w.profile ? kmpc_launch(kmpc_speed_plan_fleet_kernel<true>, dim3(w.B), dim3(64), 0, st, w)
+                     : kmpc_launch(kmpc_speed_plan_fleet_kernel<false>, dim3(w.B), dim3(64), 0, st, w);
 }

@@ -300,9 +300,11 @@ class SpeedPlanner:
 
     kappa [sum M]: the curvature table of the fleet's paths at `window` m, a device tensor, in the order of fleet.trajectories.
     rows [B,8] (speed_plan_params): a public device tensor, read by every plan() as it is -- edit it in place between steps, like fleet.path_id.
-    The vehicle's path is fleet.path_id[b] at the time of the call.  A vehicle the kernel refuses (include/kmpc.h) gets v_plan 0."""
+    The vehicle's path is fleet.path_id[b] at the time of the call.  A vehicle the kernel refuses (include/kmpc.h) gets v_plan 0.
+    profile: a vehicle_sim.RoadProfile built on the same fleet -- the MAP: the plan scales A_LAT by the sample's MU_SCALE and honours its V_LIMIT
+    (kmpc_speed_plan_fleet_profile).  It is the planner's own table, not the plant's; without one plan() calls kmpc_speed_plan_fleet as before."""
 
-    def __init__(self, fleet, window=4.0, rows=None):
+    def __init__(self, fleet, window=4.0, rows=None, profile=None):
         if not isinstance(fleet, FleetRefTrajectory):
             raise ValueError("SpeedPlanner plans on a FleetRefTrajectory (a one-path fleet covers a single path); a %s is not one"
                              % type(fleet).__name__)
@@ -317,6 +319,11 @@ class SpeedPlanner:
         _lib.check(self._lib.kmpc_pathset_curvature(fleet._h, window, C.c_void_p(self.kappa.data_ptr()), stream))
         self.rows = speed_plan_params(self.B, self.device) if rows is None else rows
         self._check_rows()
+        if profile is not None:
+            from .vehicle_sim import RoadProfile
+            if not (isinstance(profile, RoadProfile) and profile.fleet is fleet):
+                raise ValueError("profile: a RoadProfile built on the planner's own fleet")
+        self.profile = profile
         self.info = self.closest = None   # [B,4] (w, s_jb - s_i, kappa_jb, sqrt(lim_i)) and [B] of the last plan(want_info=True)
 
     def _check_rows(self):
@@ -351,6 +358,11 @@ class SpeedPlanner:
             self.closest = torch.empty((B,), dtype=torch.int32, device=dev)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._lib.kmpc_speed_plan_fleet(self.fleet._h, B, p(self.kappa), p(st), int(st.stride(0)) if B else 2, p(pid), p(vc), p(self.rows),
-                                                   p(out), p(self.info) if want_info else None, p(self.closest) if want_info else None, stream))
+        tail = (p(st), int(st.stride(0)) if B else 2, p(pid), p(vc), p(self.rows), p(out), p(self.info) if want_info else None,
+                p(self.closest) if want_info else None, stream)
+        if self.profile is not None:
+            self.profile._own()
+            _lib.check(self._lib.kmpc_speed_plan_fleet_profile(self.fleet._h, B, p(self.kappa), p(self.profile.table), *tail))
+        else:
+            _lib.check(self._lib.kmpc_speed_plan_fleet(self.fleet._h, B, p(self.kappa), *tail))
         return out

@@ -21,6 +21,9 @@ observer's record (kmpc_predict_ahead_dist_batch).
 Grip and road: `VehicleSimulator(road=road_params(B, mu=0.5, a_lat=1.5, ...))` gives every vehicle a road row -- friction limits per axle, specific
 forces of grade and bank, a steering offset, an acceleration gain (kmpc_sim_advance_road) -- and counts, per vehicle and axle, the sub-steps in
 which the tyre force was clipped (`road_stat`, `road_summary()`).  The neutral row computes what the command-queue plant computes, bit for bit.
+`VehicleSimulator(road=, road_profile=RoadProfile(fleet, table))` makes the road a property of the place: a table with one row per recorded sample of
+the fleet's paths (grip scale, grade, bank; road_profile_table / road_profile_patch / check_road_profile) is composed with the caller's rows
+(`road_base`) into `road` at the top of every plant call (kmpc_road_profile_fleet), without a host round trip.
 
 L0 actuation: `LowLevelController` is the reference's 50 Hz node src/LowLevelController.cpp for B vehicles (kmpc_llc_step_batch: clamp, throttle PI on
 a low-passed differentiated speed, brake torque below a deadband, steering-wheel angle), and `VehicleSimulator(drive=drive_params(B, ...), llc=)`
@@ -141,6 +144,114 @@ def road_params(B, device=0, **overrides):
         for w in ((0, 1) if k == "mu" else (ROAD_FIELDS.index(k),)):
             rows[:, w] = v
     return torch.as_tensor(check_road_rows(rows)).to(_device(device))
+
+
+PROFILE_WORDS = 8
+PROFILE_FIELDS = ("mu_scale", "a_long", "a_lat", "v_limit")   # KMPC_PROFILE_* words 0 ... 3 of include/kmpc.h, in row order (4 ... 7 are read by nobody)
+
+
+def road_profile_default():
+    """the neutral profile row (1, 0, 0, inf, 0, 0, 0, 0) as a numpy row [8], from kmpc_road_profile_default"""
+    row = np.zeros(PROFILE_WORDS)
+    _lib.check(_lib.load().kmpc_road_profile_default(row.ctypes.data_as(C.POINTER(C.c_double)), 1))
+    return row
+
+
+def check_road_profile(table):
+    """[n,8] host rows -> ValueError unless no word is NaN, mu_scale > 0 and finite, a_long and a_lat finite, v_limit >= 0 (+inf: none) and every
+    other word finite (the kernels cannot refuse a row: a bad one reaches the vehicles whose nearest sample holds it)"""
+    table = np.asarray(table, dtype=np.float64)
+    if table.ndim != 2 or table.shape[1] != PROFILE_WORDS:
+        raise ValueError("road profile: [n,8] (%s, four unused words), got %s" % (", ".join(PROFILE_FIELDS), table.shape))
+    rows_of = lambda bad: np.flatnonzero(bad)[:8].tolist()
+    if np.isnan(table).any():
+        raise ValueError("road profile: NaN in sample(s) %s" % rows_of(np.isnan(table).any(1)))
+    if not ((table[:, 0] > 0.0) & np.isfinite(table[:, 0])).all():
+        raise ValueError("road profile: mu_scale must be > 0 and finite (sample(s) %s)" % rows_of(~((table[:, 0] > 0.0) & np.isfinite(table[:, 0]))))
+    for w in (1, 2):
+        if not np.isfinite(table[:, w]).all():
+            raise ValueError("road profile: %s must be finite (sample(s) %s)" % (PROFILE_FIELDS[w], rows_of(~np.isfinite(table[:, w]))))
+    if not (table[:, 3] >= 0.0).all():
+        raise ValueError("road profile: v_limit must be >= 0 (+inf: none) (sample(s) %s)" % rows_of(~(table[:, 3] >= 0.0)))
+    if not np.isfinite(table[:, 4:8]).all():
+        raise ValueError("road profile: only v_limit may be infinite (sample(s) %s)" % rows_of(~np.isfinite(table[:, 4:8]).all(1)))
+    return table
+
+
+def road_profile_table(fleet):
+    """a neutral profile of a FleetRefTrajectory's paths: numpy [sum M, 8], path p's samples at rows off_p ... off_p + M_p - 1, in the order of
+    fleet.trajectories (the curvature table's order)"""
+    return np.tile(road_profile_default(), (sum(len(tr) for tr in fleet.trajectories), 1))
+
+
+def road_profile_patch(table, fleet, path, s0, s1, **words):
+    """writes the words given (`mu_scale=`, `a_long=`, `a_lat=`, `v_limit=`) into the rows of the samples of path `path` whose cdist lies in
+    [s0, s1], in place -> the number of samples written.  Nothing else of the table is touched."""
+    for k in words:
+        if k not in PROFILE_FIELDS:
+            raise ValueError("road_profile_patch: unknown word %r (one of %s)" % (k, ", ".join(PROFILE_FIELDS)))
+    path = int(path)
+    if not 0 <= path < len(fleet.trajectories):
+        raise ValueError("road_profile_patch: path %d of %d" % (path, len(fleet.trajectories)))
+    total = sum(len(tr) for tr in fleet.trajectories)
+    if not (isinstance(table, np.ndarray) and table.dtype == np.float64 and table.shape == (total, PROFILE_WORDS)):
+        raise ValueError("road_profile_patch: a float64 numpy table [%d,8] (road_profile_table), got %s" % (total, getattr(table, "shape", type(table))))
+    off = sum(len(tr) for tr in fleet.trajectories[:path])
+    s = fleet.trajectories[path][:, 6]
+    idx = off + np.flatnonzero((s >= s0) & (s <= s1))
+    for k, v in words.items():
+        table[idx, PROFILE_FIELDS.index(k)] = float(v)
+    return len(idx)
+
+
+class RoadProfile:
+    """A road profile of a FleetRefTrajectory's paths on the device: one row per recorded sample (grip scale, grade, bank, speed limit; include/kmpc.h,
+    KMPC_PROFILE_*).  The same class serves as the truth (VehicleSimulator(road_profile=): the plant's road under each vehicle, once per period,
+    kmpc_road_profile_fleet) and as the map (SpeedPlanner(profile=): kmpc_speed_plan_fleet_profile); the two are separate objects with separate tables.
+
+    table [sum M, 8]: validated on the host (check_road_profile), then a public device tensor, read by every call as it is -- edit it in place with
+    copy_ between steps (the kernels cannot validate it: check_road_profile first)."""
+
+    def __init__(self, fleet, table=None):
+        from .ref_traj import FleetRefTrajectory
+        if not isinstance(fleet, FleetRefTrajectory):
+            raise ValueError("RoadProfile is built on a FleetRefTrajectory (a one-path fleet covers a single path); a %s is not one" % type(fleet).__name__)
+        self.fleet, self.device, self._lib = fleet, fleet.device, fleet._lib
+        self.B = int(fleet.path_id.shape[0])
+        self.total = sum(len(tr) for tr in fleet.trajectories)
+        rows = road_profile_table(fleet) if table is None else (table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table)
+        if np.shape(rows) != (self.total, PROFILE_WORDS):
+            raise ValueError("road profile: [%d,8] rows, one per sample of the fleet's paths (road_profile_table), got %s" % (self.total, np.shape(rows)))
+        self.table = torch.as_tensor(np.ascontiguousarray(check_road_profile(rows))).to(self.device).contiguous()
+        self.closest = None   # [B] of the last apply(want_closest=True)
+
+    def _own(self):
+        t = self.table
+        if not (type(t) is torch.Tensor and t.dtype == torch.float64 and tuple(t.shape) == (self.total, PROFILE_WORDS) and t.is_contiguous()
+                and t.device == self.device):
+            raise ValueError("table must stay a contiguous float64 tensor [%d,8] on %s (write into it with copy_)" % (self.total, self.device))
+
+    def apply(self, state, road_base, out, want_closest=False):
+        """state: device tensor [B,W], X and Y first (no copy); road_base [B,8], the caller's road rows; out [B,8], never road_base itself -> out: the
+        rows the plant reads this period.  want_closest=True also fills self.closest [B].  Asynchronous on torch's current stream."""
+        dev, B = self.device, self.B
+        self._own()
+        if not (type(state) is torch.Tensor and state.dtype == torch.float64 and state.device == dev and state.dim() == 2 and state.shape[0] == B
+                and state.shape[1] >= 2 and (B == 0 or state.stride(1) == 1) and state.stride(0) >= 2):
+            raise ValueError("state: a float64 tensor [%d,W] on %s with X, Y in the first two columns" % (B, dev))
+        for t, name in ((road_base, "road_base"), (out, "out")):
+            if not (type(t) is torch.Tensor and t.dtype == torch.float64 and tuple(t.shape) == (B, 8) and t.is_contiguous() and t.device == dev):
+                raise ValueError("%s: a contiguous float64 tensor [%d,8] on %s" % (name, B, dev))
+        pid = self.fleet.path_id
+        if not (pid.dtype == torch.int32 and tuple(pid.shape) == (B,) and pid.is_contiguous() and pid.device == dev):
+            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
+        if want_closest and self.closest is None:
+            self.closest = torch.empty((B,), dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(self._lib.kmpc_road_profile_fleet(self.fleet._h, B, p(self.table), p(state), int(state.stride(0)) if B else 2, p(pid), p(road_base),
+                                                     p(out), p(self.closest) if want_closest else None, stream))
+        return out
 
 
 def _rows_with(name, fields, default, B, overrides):
@@ -279,7 +390,8 @@ class LowLevelController:
 class VehicleSimulator:
     dt_model = 0.01  # :24
 
-    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None, cmd_queue_depth=None, road=None, drive=None, llc=None):
+    def __init__(self, B=1, X0=X0, Y0=Y0, Psi0=PSI0, device=0, plant=None, cmd_delay=None, cmd_queue_depth=None, road=None, drive=None, llc=None,
+                 road_profile=None):
         """plant: [B,8] rows (plant_params) -- a plant per vehicle; cmd_delay: a scalar or one per vehicle, model updates of 10 ms by which a new
         command takes effect late (clamped to one call's n_updates; the command in force until then is `cmd_held`, 0 at the start).  Giving
         either runs kmpc_sim_advance_plant (the other defaults to the reference's constants / no delay); `plant`, `cmd_delay` (int32 [B]) and
@@ -289,12 +401,21 @@ class VehicleSimulator:
         in `period` (slot period mod D holds that call's command); every call of a run must use the same n_updates.
         road: [B,8] rows (road_params) -- grip limits, grade, bank, steering offset and acceleration gain per vehicle (kmpc_sim_advance_road).  It
         implies the queue path (cmd_queue_depth defaults to 2, which equals the held-command plant call after call) and allocates `road_stat` [B,4];
-        `road` and `road_stat` are plain device tensors the caller may edit between steps (a wet patch: write `road` between periods), and
+        `road` and `road_stat` are plain device tensors the caller may edit between steps (a wet patch that belongs to a place: road_profile=), and
         road_summary() downloads the grip bookkeeping.
         drive: [B,8] rows (drive_params) -- a powertrain per vehicle behind a LowLevelController `llc` (default: LowLevelController(B) with the
         reference's constants, its V_LAST at 0): the command passes through the controller's 50 Hz tick and acts as throttle and brake
         (kmpc_sim_advance_drive).  It implies the road and queue path (road defaults to the neutral rows); `drive`, `llc.params` and `llc.rec` are
-        plain device tensors the caller may edit between steps.  A run that starts at speed calls llc.reset(v) first."""
+        plain device tensors the caller may edit between steps.  A run that starts at speed calls llc.reset(v) first.
+        road_profile: a RoadProfile for B vehicles on this device -- the road under each vehicle, per recorded sample of its path (the truth).  It
+        implies road= (neutral rows by default).  The caller's rows then live in `road_base`; `road` is what the plant reads, rewritten from
+        `road_base`, `state` and the profile's table at the top of every _update_vehicle_model call with n_updates > 0 (kmpc_road_profile_fleet: one
+        more launch per period, no host round trip).  Without road_profile= there is no `road_base` and no such launch."""
+        if road_profile is not None:   # checked before the GPU is touched
+            if not (isinstance(road_profile, RoadProfile) and road_profile.B == int(B)):
+                raise ValueError("road_profile: a RoadProfile for %d vehicles" % int(B))
+            if road is None:
+                road = np.tile(road_default(), (int(B), 1))
         drive_rows = None
         if llc is not None and drive is None:
             raise ValueError("llc= belongs to drive=: the controller acts on the plant only through the powertrain (drive_params)")
@@ -332,6 +453,7 @@ class VehicleSimulator:
         self.state[:, 2] = torch.as_tensor(Psi0, dtype=torch.float64, device=self.device)
         self.cmd = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)  # acc_des, df_des (:21-22)
         self.plant = self.cmd_delay = self.cmd_held = self.cmd_queue = self.road = self.road_stat = self.drive = self.llc = None
+        self.road_base = self.road_profile = None
         self.period = 0
         if plant is not None or cmd_delay is not None or cmd_queue_depth is not None:
             if plant is None:
@@ -352,6 +474,11 @@ class VehicleSimulator:
             if road_rows is not None:
                 self.road = torch.as_tensor(road_rows).to(self.device).contiguous()
                 self.road_stat = torch.zeros((self.B, 4), dtype=torch.float64, device=self.device)
+                if road_profile is not None:
+                    if road_profile.device != self.device:
+                        raise ValueError("road_profile on %s, plant on %s" % (road_profile.device, self.device))
+                    self.road_profile, self.road_base = road_profile, self.road
+                    self.road = self.road_base.clone()
             if drive_rows is not None:
                 self.drive = torch.as_tensor(drive_rows).to(self.device).contiguous()
                 self.llc = llc if llc is not None else LowLevelController(self.B, device=self.device)
@@ -388,6 +515,8 @@ class VehicleSimulator:
                     if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous()
                             and t.device == self.device):
                         raise ValueError("road [B,8] / road_stat [B,4] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
+                if self.road_profile is not None and int(n_updates) > 0:   # the road under each vehicle, from where it is now
+                    self.road_profile.apply(self.state, self.road_base, self.road)
                 if self.drive is not None:
                     if not (isinstance(self.drive, torch.Tensor) and self.drive.dtype == torch.float64 and tuple(self.drive.shape) == (self.B, 8)
                             and self.drive.is_contiguous() and self.drive.device == self.device):
