@@ -721,6 +721,78 @@ int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state, const voi
 int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period,
                                  int64_t id_base, const int32_t *meas_delay, void *truth_ring, int32_t depth, void *est, void *stream);
 
+/* ---- sensor faults: outages, outliers, held fixes ------------------------------------------------------------------------------------------
+ * scripts/state_publisher.py keeps the last GPS fix, IMU yaw and steering-report speed and republishes them at 100 Hz whether they are fresh or
+ * not (its time_valid check is commented out).  kmpc_sense_faults_batch is kmpc_sense_batch (kmpc_sense_delayed_batch with a ring) with three
+ * sources that can fall silent -- GPS -> x, y; IMU -> psi; SPD, the steering report -> v -- and GPS outliers.  One thread per vehicle, fp64.
+ *   state, sensor, seed, period, id_base   exactly as in kmpc_sense_batch
+ *   meas_delay, truth_ring, depth          both NULL (depth is then ignored), or exactly as in kmpc_sense_delayed_batch
+ *   faults [B,16] fp64 DEVICE, row of vehicle b: */
+enum {
+    KMPC_FAULT_P_LOSE_GPS = 0, KMPC_FAULT_P_LOSE_IMU = 1, KMPC_FAULT_P_LOSE_SPD = 2,         /* probability per period that a delivering source falls silent */
+    KMPC_FAULT_P_REGAIN_GPS = 3, KMPC_FAULT_P_REGAIN_IMU = 4, KMPC_FAULT_P_REGAIN_SPD = 5,   /* probability per period that a silent source delivers again */
+    KMPC_FAULT_WIN_FROM_GPS = 6, KMPC_FAULT_WIN_FROM_IMU = 7, KMPC_FAULT_WIN_FROM_SPD = 8,   /* first period of a scheduled silence */
+    KMPC_FAULT_WIN_LEN_GPS = 9, KMPC_FAULT_WIN_LEN_IMU = 10, KMPC_FAULT_WIN_LEN_SPD = 11,    /* its length in periods; 0 = none */
+    KMPC_FAULT_P_OUTLIER = 12,       /* probability that a delivered GPS fix is an outlier */
+    KMPC_FAULT_OUTLIER_SIGMA = 13,   /* standard deviation [m] of an outlier fix on x and y, in place of SIGMA_X, SIGMA_Y */
+    KMPC_FAULT_MAX_AGE = 14,         /* periods a source may be silent before the vehicle counts as blind; +inf = never */
+                                     /* word 15 is read by nobody */
+    KMPC_FAULT_WORDS = 16
+};
+/*   kmpc_sense_faults_default writes B neutral rows (0,0,0, 1,1,1, 0,0,0, 0,0,0, 0, 0, +inf, 0) to HOST memory.
+ *   fault_rec [B,16] fp64 DEVICE in/out, record of vehicle b; all zeros (hipMemset) = fresh; counters are fp64 words as in the score record: */
+enum {
+    KMPC_FAULTREC_HELD_X = 0, KMPC_FAULTREC_HELD_Y = 1, KMPC_FAULTREC_HELD_PSI = 2, KMPC_FAULTREC_HELD_V = 3,   /* the last delivered value of each channel */
+    KMPC_FAULTREC_COUNT = 4,         /* calls so far; 0 = fresh */
+    KMPC_FAULTREC_CHAIN = 5,         /* 0 ... 7: bit s = source s silent by the random chain (s = 0 GPS, 1 IMU, 2 SPD) */
+    KMPC_FAULTREC_AGE_GPS = 6, KMPC_FAULTREC_AGE_IMU = 7, KMPC_FAULTREC_AGE_SPD = 8,   /* periods since the source last delivered, 0 = this period */
+    KMPC_FAULTREC_N_SILENT_GPS = 9, KMPC_FAULTREC_N_SILENT_IMU = 10, KMPC_FAULTREC_N_SILENT_SPD = 11,   /* silent periods so far */
+    KMPC_FAULTREC_LONGEST_GPS = 12, KMPC_FAULTREC_LONGEST_IMU = 13, KMPC_FAULTREC_LONGEST_SPD = 14,     /* the longest silence so far [periods] */
+    KMPC_FAULTREC_N_OUTLIER = 15,
+    KMPC_FAULTREC_WORDS = 16
+};
+enum {   /* flags_out bits */
+    KMPC_FAULT_FLAG_SILENT_GPS = 1, KMPC_FAULT_FLAG_SILENT_IMU = 2, KMPC_FAULT_FLAG_SILENT_SPD = 4,   /* bit s: source s silent in this period */
+    KMPC_FAULT_FLAG_OUTLIER = 8,     /* the delivered GPS fix is an outlier */
+    KMPC_FAULT_FLAG_BLIND = 16,      /* a source has been silent for more than MAX_AGE periods */
+    KMPC_FAULT_FLAG_FRESH = 32,      /* the record was fresh */
+    KMPC_FAULT_FLAG_RESET = 64       /* the record was unusable and taken as fresh (FRESH is set too) */
+};
+/*   z_out [B,4] fp64 DEVICE out: the measured value, a quiet NaN in the channels of a silent source -- what kmpc_estimate_batch and
+ *                                kmpc_observe_batch read (a non-finite channel is a dropout: the filter coasts)
+ *   held_out [B,4] fp64 DEVICE out: the measured value, the record's HELD_c in the channels of a silent source -- what state_publisher.py publishes
+ *   flags_out [B] int32 DEVICE out or NULL          blind_out [B] uint8 DEVICE out or NULL: 1 when any AGE_s > MAX_AGE after this call's update
+ * Per vehicle b, with gid = id_base + b and p = period:
+ *   DRAWS  the noise draw is kmpc_sense_batch's.  The fault draw is a second Philox4x32-10 call with the same key and the counter
+ *     (gid lo, gid hi, p lo, p hi ^ 0x80000000) -- periods are below 2^63, so no measurement draw has that bit -- words w0..w3,
+ *     u_i = (w_i + 0.5) * 2^-32; u0, u1, u2 drive the chains of GPS, IMU, SPD and u3 decides the outlier.
+ *   RESET  a record whose COUNT is non-finite or negative, or whose CHAIN is not one of 0 ... 7, is taken as fresh (RESET | FRESH).
+ *   FRESH RECORD (COUNT == 0, or reset): its other words are not read and count as zero.  Every source delivers, there is no outlier and
+ *     CHAIN = 0, whatever the row says: the publisher itself waits until every source has reported once, and a fresh filter then initialises
+ *     from a complete z.
+ *   OTHERWISE, per source s with was_silent_s = bit s of CHAIN:
+ *     chain_s = was_silent_s ? !(u_s < P_REGAIN_s) : (u_s < P_LOSE_s)
+ *     sched_s = WIN_LEN_s > 0 && p >= WIN_FROM_s && p < WIN_FROM_s + WIN_LEN_s        (p converted to fp64, the sum rounded once)
+ *     silent_s = chain_s || sched_s;  only chain_s is stored, so a schedule does not disturb the chain
+ *     outlier = !silent_GPS && u3 < P_OUTLIER
+ *     A NaN word compares false: a NaN probability or window does nothing.
+ *   MEASUREMENT  m = kmpc_sense_batch's est of this period's truth -- with a ring, kmpc_sense_delayed_batch's of the truth of period - L, its
+ *     ring write included -- under the vehicle's sensor row with SIGMA_X and SIGMA_Y replaced by OUTLIER_SIGMA when `outlier`.  Noise and silence
+ *     belong to the moment of emission, period p.  z_out_c = silent ? NaN : m_c;  held_out_c = silent ? HELD_c : m_c  (c's source).
+ *   RECORD  HELD_c = held_out_c;  AGE_s = silent_s ? AGE_s + 1 : 0;  N_SILENT_s += silent_s;  LONGEST_s = AGE_s > LONGEST_s ? AGE_s : LONGEST_s;
+ *     N_OUTLIER += outlier;  COUNT += 1;  CHAIN = sum of chain_s << s.  blind = any AGE_s > MAX_AGE (a NaN MAX_AGE: never).
+ *   CONTAINMENT  no lane reads another vehicle's row or record: a bad row, a poisoned record or a non-finite truth affects that vehicle alone.
+ * With the neutral row z_out and held_out are kmpc_sense_batch's est (kmpc_sense_delayed_batch's with a ring) bit for bit, call after call, and
+ * the flags show at most FRESH.  A vehicle's whole fault history is a function of (seed, gid, its row, the periods called): not of B, the launch
+ * geometry or the shard.  Row contents cannot be checked from the host (Python: vehicle_sim.check_fault_rows).
+ * Argument checks before any device call: B, period or id_base < 0; with B > 0 a NULL state, sensor, faults, fault_rec, z_out or held_out; one
+ * of meas_delay and truth_ring without the other; depth < 1 with a ring: KMPC_ERR_ARG (text in kmpc_last_error(NULL)).  B == 0 succeeds without
+ * a launch.  Asynchronous on `stream`. */
+int32_t kmpc_sense_faults_default(double *rows_host, int32_t B);   /* HOST; KMPC_ERR_ARG for B < 0 or, with B > 0, NULL rows */
+int32_t kmpc_sense_faults_batch(int32_t device, int32_t B, const void *state, const void *sensor, const void *faults, uint64_t seed,
+                                int64_t period, int64_t id_base, const int32_t *meas_delay, void *truth_ring, int32_t depth, void *fault_rec,
+                                void *z_out, void *held_out, int32_t *flags_out, uint8_t *blind_out, void *stream);
+
 /* ---- delay compensation: the controller's side -------------------------------------------------------------------------------------------
  * The controller keeps a log of the commands it sent and its own ASSUMED delays -- buffers of its own, not the plant's or the sensor's, so that
  * a run can have a delay mismatch.

@@ -56,6 +56,12 @@ stage, on the state the controller reads (truth, est, est_filt or est_pred), wit
 the waypoint call (the spacing is how the XY model follows a speed at C_v = 0) and the solve of that period.  `v_target` and `des_speed` are not
 modified; stop latch, rate-limit anchor, command stage and scoring are untouched.  Without a planner nothing changes.
 
+Sensor faults: with `sensor=SensorModel(..., faults=fault_params(...))` a source can fall silent.  A filter (estimator= or observer=) is then fed
+`sensor.z`, NaN in a silent source's channels, and coasts; without a filter the controller reads the held state, the last delivered value of every
+channel -- the reference's publisher -- and `loop.est` stays what that publisher would have published.  `blind_stop=True` ORs `sensor.blind` (a
+source silent for longer than the row's max_age) into the waypoint helper's stop flags ahead of the command stage, so a blind vehicle latches and
+brakes like one at the end of its path.  Loops without faults= run the code they ran before.
+
 L0 actuation: the reference's low-level controller and a pedal-driven powertrain belong to the simulator (VehicleSimulator(drive=, llc=):
 kmpc_sim_advance_drive runs the controller's 50 Hz tick inside the plant call).  The loops only call `sim._update_vehicle_model`; `sim.state[:, 6]`
 is then the powertrain's net acceleration, which `estimator_input="actuator"` reads as delivered, while `estimator_input="command"` lets an
@@ -95,7 +101,7 @@ class _ScoredLoop:
     _reference(st) -> (ref, stop, solve, extra): the reference built from the controller's state `st`, the helper's stop flags, the solve as a
     call without arguments -> the solver's output dict, and the entries the loop adds to step()'s dict."""
 
-    def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer, planner=None, track_with_time=False):
+    def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer, planner=None, track_with_time=False, blind_stop=False):
         """what both loops own beside grt, sim, N, B, mpc and the target speeds: buffers, the stop latch, the library, and the stages"""
         dev = self.sim.device
         self.u_prev = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)       # (acc, d_f): update_current_input starts at 0
@@ -108,7 +114,7 @@ class _ScoredLoop:
         self.have_warm = False
         self.out = None
         self.k = 0
-        self._init_sensor(sensor)
+        self._init_sensor(sensor, blind_stop)
         self._init_estimator(estimator, estimator_input, compensator, observer)
         self._init_planner(planner, track_with_time)
         self._init_score()
@@ -118,10 +124,12 @@ class _ScoredLoop:
         log -> plant"""
         st = self.sim.state if self.sensor is None else self._sense()
         if self.estimator is not None or self.observer is not None:
-            st = self._filter(st)
+            st = self._filter(self.sensor.z if self.faulty else st)   # a faulty sensor's z: NaN where a source is silent, the filter coasts
         if self.compensator is not None:
             st = self._predict(st, plant_updates)
         ref, stop, solve, extra = self._reference(st)
+        if self.blind_stop:   # blind for longer than MAX_AGE: latch and brake like a vehicle at the end of its path (on the device, no synchronisation)
+            stop = torch.bitwise_or(stop, self.sensor.blind.to(stop.dtype))
         if time_solve:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -169,10 +177,14 @@ class _ScoredLoop:
         self.v_plan = self.planner.plan(st, self.v_target, out=self.v_plan)
         return self.v_plan
 
-    def _init_sensor(self, sensor):
+    def _init_sensor(self, sensor, blind_stop=False):
         if sensor is not None and (sensor.B != self.B or sensor.device != self.sim.device):
             raise ValueError("sensor for %d vehicles on %s, plant with %d on %s" % (sensor.B, sensor.device, self.B, self.sim.device))
         self.sensor = sensor
+        self.faulty = sensor is not None and getattr(sensor, "faults", None) is not None   # SensorModel(faults=): z, flags, blind beside the held state
+        if blind_stop and not self.faulty:
+            raise ValueError("blind_stop=True reads the sensor's blind flags: give sensor=SensorModel(..., faults=...)")
+        self.blind_stop = bool(blind_stop)
         self.est = None   # [B,4] x, y, psi, v as sensed in the last period (sensor given)
 
     def _init_estimator(self, estimator, estimator_input, compensator=None, observer=None):
@@ -255,7 +267,8 @@ class _ScoredLoop:
         state [steps+1,B,8] (the state before the first period first), cmd [steps,B,2], status [steps,B], latch [steps,B] and, with a sensor, est [steps,B,4]
         (what was measured of state[j] in period j: what the controller saw, unless an estimator follows) and, with an estimator, est_filt [steps,B,4]
         (what the controller saw then, unless a compensator follows; an observer's est_filt likewise, with dist [steps,B,3]) and, with a compensator, est_pred [steps,B,4] (what the controller saw then)
-        and, with a planner, v_plan [steps,B] (the speed period j's waypoints and solve ran at).
+        and, with a planner, v_plan [steps,B] (the speed period j's waypoints and solve ran at) and, with a faulty sensor (SensorModel(faults=)),
+        z [steps,B,4] (NaN where a source was silent: what a filter read; est is then the held state) and fault_flags [steps,B] int32.
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -270,6 +283,9 @@ class _ScoredLoop:
                         latch=torch.empty((steps, self.B), dtype=torch.bool, device=dev))
             if self.sensor is not None:
                 hist["est"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
+            if self.faulty:
+                hist["z"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
+                hist["fault_flags"] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
             if self.estimator is not None or self.observer is not None:
                 hist["est_filt"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
             if self.observer is not None:
@@ -291,6 +307,8 @@ class _ScoredLoop:
                 hist["latch"][j].copy_(self.command_stop); hist["state"][j + 1].copy_(self.sim.state)
                 if self.sensor is not None:
                     hist["est"][j].copy_(self.est)
+                if self.faulty:
+                    hist["z"][j].copy_(self.sensor.z); hist["fault_flags"][j].copy_(self.sensor.flags)
                 if self.estimator is not None or self.observer is not None:
                     hist["est_filt"][j].copy_(self.est_filt)
                 if self.observer is not None:
@@ -331,7 +349,7 @@ class ClosedLoop(_ScoredLoop):
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
                  mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, observer=None, planner=None,
-                 **options):
+                 blind_stop=False, **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -347,7 +365,7 @@ class ClosedLoop(_ScoredLoop):
             raise ValueError("a FleetRefTrajectory owns the tracking modes (its time_mode): track_with_time must stay False")
         self.track_with_time = track_with_time
         self.des_speed, self.v_target = _target_speeds(target_vel, self.B, sim.device)  # mpc_cmd_pub.jl:58-62
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop)
 
     def step(self, plant_updates=10, time_solve=False):
         """time_solve=True brackets the solve with device synchronisations and returns its wall time (`solve_s`)"""
@@ -373,7 +391,7 @@ class ClosedLoopFrenet(_ScoredLoop):
     (checked once, here).  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, estimator=None,
-                 estimator_input="actuator", compensator=None, observer=None, planner=None, **options):
+                 estimator_input="actuator", compensator=None, observer=None, planner=None, blind_stop=False, **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -392,7 +410,7 @@ class ClosedLoopFrenet(_ScoredLoop):
         if grt.device != sim.device:
             raise ValueError("waypoint helper on %s, plant on %s: the loop runs on one device" % (grt.device, sim.device))
         self.des_speed, self.v_target = des_speed, v_target
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop)
 
     def step(self, plant_updates=10, time_solve=False):
         """as ClosedLoop.step; the returned dict also carries `k_poly` [B,4] and `fit_status` [B]"""

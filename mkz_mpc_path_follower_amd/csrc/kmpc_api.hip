@@ -945,6 +945,40 @@ extern "C" int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const voi
     return KMPC_OK;
 }
 
+// ---- measurement stage with sensor faults (kmpc_sense_faults.hip) ------------------------------------------------------
+// the neutral fault row: no source is ever lost, a lost one returns at once, no window, no outlier, never blind
+extern "C" int32_t kmpc_sense_faults_default(double *rows_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_faults_default: bad argument (B=%d, rows %s)", B, rows_host ? "given" : "NULL");
+    for (int32_t b = 0; b < B; ++b) {
+        double *r = rows_host + KMPC_FAULT_WORDS * (size_t)b;
+        for (int w = 0; w < KMPC_FAULT_WORDS; ++w) r[w] = 0.0;
+        r[KMPC_FAULT_P_REGAIN_GPS] = 1.0; r[KMPC_FAULT_P_REGAIN_IMU] = 1.0; r[KMPC_FAULT_P_REGAIN_SPD] = 1.0;
+        r[KMPC_FAULT_MAX_AGE] = INFINITY;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_sense_faults_batch(int32_t device, int32_t B, const void *state, const void *sensor, const void *faults, uint64_t seed,
+                                           int64_t period, int64_t id_base, const int32_t *meas_delay, void *truth_ring, int32_t depth,
+                                           void *fault_rec, void *z_out, void *held_out, int32_t *flags_out, uint8_t *blind_out, void *stream)
+{
+    if (B < 0 || period < 0 || id_base < 0 || (B > 0 && (!state || !sensor || !faults || !fault_rec || !z_out || !held_out)))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_faults_batch: bad argument (B=%d, period=%lld, id_base=%lld; state, sensor, faults, fault_rec, "
+                    "z_out and held_out are required)", B, (long long)period, (long long)id_base);
+    if ((meas_delay != nullptr) != (truth_ring != nullptr))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_faults_batch: meas_delay and truth_ring go together (meas_delay %s, truth_ring %s)",
+                    meas_delay ? "given" : "NULL", truth_ring ? "given" : "NULL");
+    if (meas_delay && depth < 1) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_faults_batch: bad ring (depth=%d, at least 1)", depth);
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_faults_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_sense_faults(B, (const double *)state, (const double *)sensor, (const double *)faults, seed, (uint64_t)period,
+                                                  (uint64_t)id_base, meas_delay, (double *)truth_ring, depth, (double *)fault_rec, (double *)z_out,
+                                                  (double *)held_out, flags_out, blind_out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_faults_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 // ---- delay compensation (kmpc_latency.hip) ---------------------------------------------------------------------------
 static int32_t latency_args(const char *fn, int32_t B, const void *cmd_hist, int32_t depth, int64_t period, int32_t n_updates, const int32_t *cmd_delay,
                             const int32_t *meas_delay, int32_t max_cmd_delay, int32_t max_meas_delay)

@@ -102,6 +102,10 @@ hipError_t kmpc_launch_sense_delayed(int B, const double *state, const double *s
                                      const int32_t *meas_delay, double *truth_ring, int depth, double *est, hipStream_t st);
 hipError_t kmpc_launch_sim_road(int B, double *state, const double *cmd, const double *plant, const double *road, const int32_t *cmd_delay,
                                 double *cmd_queue, int depth, long long period, int n_updates, double *road_stat, hipStream_t st);
+// measurement stage with sensor faults (kmpc_sense_faults.hip); meas_delay and truth_ring both NULL: no ring
+hipError_t kmpc_launch_sense_faults(int B, const double *state, const double *sensor, const double *faults, uint64_t seed, uint64_t period,
+                                    uint64_t id_base, const int32_t *meas_delay, double *truth_ring, int depth, double *fault_rec, double *z_out,
+                                    double *held_out, int32_t *flags_out, uint8_t *blind_out, hipStream_t st);
 // low-level controller and pedal-driven plant (kmpc_drive.hip)
 hipError_t kmpc_launch_llc_step(int B, const double *cmd, const double *speed, int speed_stride, const double *llc_rows, double *llc_rec,
                                 double *pedals_out, hipStream_t st);

@@ -146,6 +146,66 @@ def road_params(B, device=0, **overrides):
     return torch.as_tensor(check_road_rows(rows)).to(_device(device))
 
 
+FAULT_WORDS = 16
+FAULT_FIELDS = ("p_lose_gps", "p_lose_imu", "p_lose_spd", "p_regain_gps", "p_regain_imu", "p_regain_spd", "win_from_gps", "win_from_imu", "win_from_spd",
+                "win_len_gps", "win_len_imu", "win_len_spd", "p_outlier", "outlier_sigma", "max_age")   # KMPC_FAULT_* words 0 ... 14 (15 is read by nobody)
+FAULT_RECORD_FIELDS = ("held_x", "held_y", "held_psi", "held_v", "count", "chain", "age_gps", "age_imu", "age_spd", "n_silent_gps", "n_silent_imu",
+                       "n_silent_spd", "longest_gps", "longest_imu", "longest_spd", "n_outlier")   # KMPC_FAULTREC_*
+FAULT_SILENT_GPS, FAULT_SILENT_IMU, FAULT_SILENT_SPD, FAULT_OUTLIER, FAULT_BLIND, FAULT_FRESH, FAULT_RESET = 1, 2, 4, 8, 16, 32, 64   # KMPC_FAULT_FLAG_*
+
+
+def fault_default():
+    """the neutral fault row (0,0,0, 1,1,1, 0,0,0, 0,0,0, 0, 0, inf, 0) as a numpy row [16], from kmpc_sense_faults_default"""
+    row = np.zeros(FAULT_WORDS)
+    _lib.check(_lib.load().kmpc_sense_faults_default(row.ctypes.data_as(C.POINTER(C.c_double)), 1))
+    return row
+
+
+def check_fault_rows(rows):
+    """[B,16] host rows -> ValueError unless no word is NaN, the seven probabilities lie in [0, 1], the windows' starts and lengths are non-negative
+    whole numbers, outlier_sigma is finite and >= 0, and max_age >= 0 (+inf: never blind) (the kernel cannot refuse a row)"""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != FAULT_WORDS:
+        raise ValueError("fault rows: [B,16] (%s, one unused word), got %s" % (", ".join(FAULT_FIELDS), rows.shape))
+    rows_of = lambda bad: np.flatnonzero(bad)[:8].tolist()
+    if np.isnan(rows).any():
+        raise ValueError("fault rows: NaN in vehicle(s) %s" % rows_of(np.isnan(rows).any(1)))
+    prob = rows[:, [0, 1, 2, 3, 4, 5, 12]]
+    if not ((prob >= 0.0) & (prob <= 1.0)).all():
+        raise ValueError("fault rows: p_lose_*, p_regain_* and p_outlier are probabilities in [0, 1] (vehicle(s) %s)"
+                         % rows_of(~((prob >= 0.0) & (prob <= 1.0)).all(1)))
+    win = rows[:, 6:12]
+    ok = np.isfinite(win) & (win >= 0.0)
+    ok &= np.where(ok, win, 0.0) == np.floor(np.where(ok, win, 0.0))
+    if not ok.all():
+        raise ValueError("fault rows: win_from_* and win_len_* are non-negative whole numbers of periods (vehicle(s) %s)" % rows_of(~ok.all(1)))
+    if not (np.isfinite(rows[:, 13]) & (rows[:, 13] >= 0.0)).all():
+        raise ValueError("fault rows: outlier_sigma must be finite and >= 0 (vehicle(s) %s)" % rows_of(~(np.isfinite(rows[:, 13]) & (rows[:, 13] >= 0.0))))
+    if not (rows[:, 14] >= 0.0).all():
+        raise ValueError("fault rows: max_age must be >= 0 (+inf: never blind) (vehicle(s) %s)" % rows_of(~(rows[:, 14] >= 0.0)))
+    if not np.isfinite(rows[:, 15]).all():
+        raise ValueError("fault rows: word 15 must be finite (vehicle(s) %s)" % rows_of(~np.isfinite(rows[:, 15])))
+    return rows
+
+
+def fault_params(B, device=0, **overrides):
+    """[B,16] float64 fault rows on `device`: the neutral row, with each override (FAULT_FIELDS; also `p_lose=`, `p_regain=`, `win_from=`, `win_len=`
+    for all three sources) a scalar or one value per vehicle.  Validated on the host (check_fault_rows) before anything reaches the device."""
+    rows = np.tile(fault_default(), (int(B), 1))
+    groups = {"p_lose": 0, "p_regain": 3, "win_from": 6, "win_len": 9}
+    for k, v in overrides.items():
+        if k not in groups and k not in FAULT_FIELDS:
+            raise ValueError("fault_params: unknown parameter %r (%s or one of %s)" % (k, ", ".join(groups), ", ".join(FAULT_FIELDS)))
+        if k in groups and any((k + s) in overrides for s in ("_gps", "_imu", "_spd")):
+            raise ValueError("fault_params: %s= sets all three sources; give the per-source words instead of combining them with it" % k)
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
+            raise ValueError("fault_params: %s is a scalar or one value per vehicle [%d], got %s" % (k, B, v.shape))
+        for w in (range(groups[k], groups[k] + 3) if k in groups else (FAULT_FIELDS.index(k),)):
+            rows[:, w] = v
+    return torch.as_tensor(check_fault_rows(rows)).to(_device(device))
+
+
 PROFILE_WORDS = 8
 PROFILE_FIELDS = ("mu_scale", "a_long", "a_lat", "v_limit")   # KMPC_PROFILE_* words 0 ... 3 of include/kmpc.h, in row order (4 ... 7 are read by nobody)
 
@@ -572,9 +632,15 @@ class SensorModel:
     `meas_delay` (an integer or one per vehicle, whole control periods, 0 ... depth - 1): the fix is that old when it is read
     (kmpc_sense_delayed_batch: the truth of period - meas_delay with this period's noise; period 0's state until the ring is filled); `depth`
     (default: the largest meas_delay + 1) sizes `truth_ring` [depth,B,4].  `meas_delay` [B] int32 is then a plain device tensor too, and sense()
-    must be called once per period with consecutive periods from 0.  Without meas_delay the stage is what it was."""
+    must be called once per period with consecutive periods from 0.  Without meas_delay the stage is what it was.
+    `faults` [B,16] (FAULT_FIELDS: fault_params) gives every vehicle a fault row -- outages of the GPS, the IMU and the steering report by a random
+    chain or a scheduled window, GPS outliers, a blind-time limit (kmpc_sense_faults_batch, with the ring when meas_delay is set).  sense() still
+    returns the held state, what state_publisher.py would publish (a silent source's channels keep their last delivered value), and fills
+    `z` [B,4] (NaN in a silent source's channels: what a filter reads), `flags` [B] int32 (FAULT_* bits), `blind` [B] uint8 and
+    `fault_record` [B,16] (FAULT_RECORD_FIELDS; all zeros = fresh), all plain device tensors; `faults` is one too.  Without faults= the class
+    calls what it called before."""
 
-    def __init__(self, B, sigma=0.0, bias=0.0, seed=0, id_base=0, device=0, meas_delay=None, depth=None):
+    def __init__(self, B, sigma=0.0, bias=0.0, seed=0, id_base=0, device=0, meas_delay=None, depth=None, faults=None):
         self._lib = _lib.load()
         self.B, self.seed, self.id_base = int(B), int(seed), int(id_base)
         if not (0 <= self.seed < 2 ** 64 and 0 <= self.id_base and self.id_base + self.B < 2 ** 63):
@@ -602,6 +668,54 @@ class SensorModel:
             self.depth = int(depth)
             self.meas_delay = d.to(self.device)
             self.truth_ring = torch.zeros((self.depth, self.B, 4), dtype=torch.float64, device=self.device)
+        self.faults = self.z = self.flags = self.blind = self.fault_record = None
+        if faults is not None:
+            rows = faults.detach().cpu().numpy() if isinstance(faults, torch.Tensor) else faults
+            rows = check_fault_rows(rows)
+            if rows.shape[0] != self.B:
+                raise ValueError("SensorModel: faults is [%d,16], got %s" % (self.B, rows.shape))
+            self.faults = torch.as_tensor(rows).to(self.device).contiguous()
+            self.z = torch.zeros((self.B, 4), dtype=torch.float64, device=self.device)
+            self.flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+            self.blind = torch.zeros((self.B,), dtype=torch.uint8, device=self.device)
+            self.fault_record = torch.zeros((self.B, FAULT_WORDS), dtype=torch.float64, device=self.device)
+
+    def reset_faults(self):
+        """every fault record fresh: the next sense() delivers every source"""
+        if self.faults is None:
+            raise ValueError("SensorModel.reset_faults: this sensor was built without faults=")
+        self.fault_record.zero_()
+        self.flags.zero_()
+        self.blind.zero_()
+
+    def fault_summary(self):
+        """the fault records so far, one download -> dict of numpy arrays [B] named by FAULT_RECORD_FIELDS (the counters as int64); None without
+        faults="""
+        if self.faults is None:
+            return None
+        rec = self.fault_record.detach().cpu().numpy()
+        out = {k: rec[:, i].copy() for i, k in enumerate(FAULT_RECORD_FIELDS)}
+        for k in FAULT_RECORD_FIELDS[4:]:
+            out[k] = out[k].astype(np.int64)
+        return out
+
+    def _sense_faults(self, state, period, est, stream):
+        own = ((self.faults, (self.B, FAULT_WORDS), torch.float64), (self.fault_record, (self.B, FAULT_WORDS), torch.float64),
+               (self.z, (self.B, 4), torch.float64), (self.flags, (self.B,), torch.int32), (self.blind, (self.B,), torch.uint8))
+        if self.meas_delay is not None:
+            own += ((self.meas_delay, (self.B,), torch.int32), (self.truth_ring, (self.depth, self.B, 4), torch.float64))
+        for t, shape, dt in own:
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+                raise ValueError("faults / fault_record [B,16] and z [B,4] float64, flags [B] int32, blind [B] uint8, meas_delay [B] int32 and "
+                                 "truth_ring [depth,B,4] float64 must stay contiguous tensors on %s" % self.device)
+        ring = self.meas_delay is not None
+        _lib.check(self._lib.kmpc_sense_faults_batch(self.device.index, self.B, C.c_void_p(state.data_ptr()), C.c_void_p(self.params.data_ptr()),
+                                                     C.c_void_p(self.faults.data_ptr()), self.seed, int(period), self.id_base,
+                                                     C.c_void_p(self.meas_delay.data_ptr()) if ring else None,
+                                                     C.c_void_p(self.truth_ring.data_ptr()) if ring else None, self.depth if ring else 0,
+                                                     C.c_void_p(self.fault_record.data_ptr()), C.c_void_p(self.z.data_ptr()), C.c_void_p(est.data_ptr()),
+                                                     C.c_void_p(self.flags.data_ptr()), C.c_void_p(self.blind.data_ptr()), stream))
+        return est
 
     def sense(self, state, period, out=None):
         """state [B,8] (the plant's) -> est [B,4] = x, y, psi (wrapped to [-pi, pi)), v (>= 0) as measured in control period `period`"""
@@ -610,6 +724,8 @@ class SensorModel:
             if not (t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
                 raise ValueError("state [B,8], params [B,8] and est [B,4] must be contiguous float64 tensors on %s" % self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.faults is not None:
+            return self._sense_faults(state, period, est, stream)
         if self.meas_delay is not None:
             for t, shape, dt in ((self.meas_delay, (self.B,), torch.int32), (self.truth_ring, (self.depth, self.B, 4), torch.float64)):
                 if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):

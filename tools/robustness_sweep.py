@@ -40,7 +40,14 @@ table), planner= with map = truth (rows a_lat = 0.6 g, a_brake 0.7, v_floor 1.0)
 1.5 m/s^2 on alternating 100 m stretches (through the profile) against the same bank held constant (through road=), at 6 m/s without a grip limit,
 each without and with vehicle_sim.DisturbanceObserver.
 
+--outage is the sweep of sensor faults (-> profiles/robustness_sweep_outage.txt): SensorModel(faults=vehicle_sim.fault_params(...)), nominal plant,
+no delay, the road sweep's 48 starts at 6 m/s: GPS window length (0, 10, 30, 100) periods, its start drawn per vehicle, x IMU bias (0, 0.02) rad, each
+cell once on the held fix (no filter: what scripts/state_publisher.py publishes) and once with estimator= (fed z: it dead-reckons on heading and
+speed); one outlier row (P_OUTLIER 0.05, OUTLIER_SIGMA 3 m on a GPS of sigma 0.1 m; the estimator with gate 0 against gate 4); one blind_stop row
+(MAX_AGE 30: a vehicle blind for longer latches and brakes).
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
+       python tools/robustness_sweep.py --outage [out.txt] [steps]
        python tools/robustness_sweep.py --road-profile [out.txt] [steps]
        python tools/robustness_sweep.py --speed-plan [out.txt] [steps]
        python tools/robustness_sweep.py --actuation [out.txt] [steps]
@@ -668,8 +675,97 @@ def actuation_main():
             f.write("\n".join(LINES) + "\n")
 
 
+OUT_LEN, OUT_BIAS, OUT_PER_CELL = (0, 10, 30, 100), (0.0, 0.02), 48
+
+
+def outage_main():
+    """loops of the road sweep's 48 starts at 6 m/s, nominal plant, no delay, 200 periods, SensorModel(faults=):
+    the grid, two loops of 4 x 2 cells (GPS window length x IMU bias, the window's start drawn per vehicle in periods 10 ... 39, no noise): the held
+    fix (no filter: the reference's publisher) and estimator=; the outlier row, two loops of 48 (GPS sigma 0.1 m, P_OUTLIER 0.05, OUTLIER_SIGMA 3 m):
+    the estimator with gate 0 and with gate 4; the blind_stop row, one loop of 3 x 48 (windows 10 / 30 / 100, MAX_AGE 30, estimator=, blind_stop)."""
+    from mkz_mpc_path_follower_amd.vehicle_sim import fault_params
+    argv = [a for a in sys.argv if a != "--outage"]
+    steps = int(argv[2]) if len(argv) > 2 else 200
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    rng = np.random.default_rng(0)
+    frac48 = rng.uniform(0.02, 0.45, ROAD_PER_CELL)          # the road sweep's starts
+    from48 = rng.integers(10, 40, OUT_PER_CELL).astype(float)
+
+    def run(ncells, faults, sigma=0.0, bias=0.0, estimator=False, gate=0.0, blind_stop=False):
+        B = ncells * OUT_PER_CELL
+        pid = np.tile(np.arange(OUT_PER_CELL) % 3, ncells)
+        fleet = FleetRefTrajectory(paths, pid, traj_horizon=8, traj_dt=0.2)
+        frac = np.tile(frac48, ncells)
+        pose = np.empty((B, 3))
+        for b in range(B):
+            tr = fleet.trajectories[pid[b]]
+            i = int(frac[b] * len(tr))
+            pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+        sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2])
+        sim.state[:, 3] = VT
+        sensor = SensorModel(B, sigma=sigma, bias=bias, seed=2024, faults=faults(B))
+        kw = dict(estimator=Estimator.from_sensor(sensor, gate=gate)) if estimator else {}
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, sensor=sensor, blind_stop=blind_stop, **kw)
+        loop.run(steps)
+        s = loop.score_summary()
+        s["finite"] = bool(torch.isfinite(sim.state).all().item())
+        s["resets"] = int((loop.estimator.flags & 32).sum().item()) if estimator else 0
+        s["skipped"] = int(loop.estimator.record[:, 15].sum().item()) if estimator else 0
+        return s, sensor.fault_summary()
+
+    def cols(s, c, sel):
+        return (np.median(s["max_ect"][sel]), s["max_ect"][sel].max(), 1000.0 * s["n_nonopt"][sel].sum() / max(1, s["n_live"][sel].sum()),
+                int((s["latch_index"][sel] >= 0).sum()), int(c["n_silent_gps"][sel].sum()), int(c["longest_gps"][sel].max()), int(c["n_outlier"][sel].sum()))
+    fmt = "%7.3f %8.3f %7.2f %3d %6d %4d %5d"
+    cells = list(itertools.product(range(len(OUT_LEN)), range(len(OUT_BIAS))))
+    ix = np.array(cells)[np.repeat(np.arange(len(cells)), OUT_PER_CELL)]       # [B,2] grid indices: window length, IMU bias
+    bias = np.zeros((len(ix), 4))
+    bias[:, 2] = np.array(OUT_BIAS)[ix[:, 1]]
+    grid_rows = lambda B: fault_params(B, win_from_gps=np.tile(from48, len(cells)), win_len_gps=np.array(OUT_LEN, dtype=float)[ix[:, 0]])
+    held = run(len(cells), grid_rows, bias=bias)
+    filt = run(len(cells), grid_rows, bias=bias, estimator=True)
+    say("%s: %d periods of 0.1 s at %.0f m/s on three paths, nominal plant, no delay; every state finite: %s / %s (held fix / estimator=); filter resets: %d"
+        % (torch.cuda.get_device_name(0), steps, VT, held[0]["finite"], filt[0]["finite"], filt[0]["resets"]))
+    head = ("median over vehicles of the largest |e_ct| [m], largest |e_ct| [m], periods not Optimal per 1000, latched vehicles, GPS-silent vehicle-periods, "
+            "longest GPS silence [periods], outlier fixes")
+    say("GPS window length x IMU bias, no noise, the window's start drawn per vehicle in periods 10 ... 39 (%d vehicles per line), held fix | estimator=: "
+        % OUT_PER_CELL + head)
+    for c, (w, b) in enumerate(cells):
+        sel = (ix[:, 0] == w) & (ix[:, 1] == b)
+        say(("   window %3d periods, IMU bias %.2f rad   " + fmt + "  | " + fmt) % ((OUT_LEN[w], OUT_BIAS[b]) + cols(held[0], held[1], sel) + cols(filt[0], filt[1], sel)))
+    sig = (0.1, 0.1, 0.0, 0.0)
+    out_rows = lambda B: fault_params(B, p_outlier=0.05, outlier_sigma=3.0)
+    g0 = run(1, out_rows, sigma=sig, estimator=True, gate=0.0)
+    g4 = run(1, out_rows, sigma=sig, estimator=True, gate=4.0)
+    every = np.ones(OUT_PER_CELL, bool)
+    say("outlier row: GPS sigma 0.1 m, P_OUTLIER 0.05, OUTLIER_SIGMA 3 m, no window, estimator= with gate 0 | gate 4 (%d vehicles): " % OUT_PER_CELL + head
+        + "; then the channel measurements the filter skipped")
+    say(("   P_OUTLIER 0.05                          " + fmt + "  | " + fmt + "   %d | %d") % (cols(g0[0], g0[1], every) + cols(g4[0], g4[1], every)
+                                                                                              + (g0[0]["skipped"], g4[0]["skipped"])))
+    bl = (10, 30, 100)
+    bix = np.repeat(np.arange(3), OUT_PER_CELL)
+    blind = run(3, lambda B: fault_params(B, win_from_gps=np.tile(from48, 3), win_len_gps=np.array(bl, dtype=float)[bix], max_age=30.0), estimator=True,
+                blind_stop=True)
+    say("blind_stop row: MAX_AGE 30, estimator=, blind_stop=True, no noise, no bias (%d vehicles per line): " % OUT_PER_CELL + head
+        + "; then the earliest and latest latch period")
+    for k, w in enumerate(bl):
+        sel = bix == k
+        li = blind[0]["latch_index"][sel]
+        li = li[li >= 0]
+        say(("   window %3d periods                       " + fmt + "   %s") % ((w,) + cols(blind[0], blind[1], sel)
+                                                                                + (("%d ... %d" % (li.min(), li.max())) if len(li) else "-",)))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 if __name__ == "__main__":
-    if "--actuation" in sys.argv[1:]:
+    if "--outage" in sys.argv[1:]:
+        outage_main()
+    elif "--actuation" in sys.argv[1:]:
         actuation_main()
     elif "--observer-latency" in sys.argv[1:]:
         observer_latency_main()
