@@ -561,8 +561,9 @@ enum {
  *     utilisation is not larger).  road_stat is read and written once per call, after the last sub-step.
  * The reference's two quirks stay: lf in the rear slip angle and no Fyf sin(df) / m term in vx.
  * Not modelled: a longitudinal grip limit and combined slip (the solver's a_max is 1 m/s^2, far inside mu g for any mu worth sweeping), load
- * transfer (the axle loads are the static ones), random gusts.  The rows are plain device memory.  A limit, a bank or a grade that varies
- * along the path comes from a road profile (kmpc_road_profile_fleet, above): it composes this row once per period, on the device.
+ * transfer (the axle loads are the static ones).  The rows are plain device memory.  A limit, a bank or a grade that varies
+ * along the path comes from a road profile (kmpc_road_profile_fleet, above): it composes this row once per period, on the device.  Random gusts
+ * and a wandering steering offset come from the Gauss-Markov stage (kmpc_wander_batch, below), which composes A_LONG, A_LAT and DF_OFFSET.
  * Contract: with the neutral row in every vehicle the call leaves the state that kmpc_sim_advance_queue leaves on the same arguments, bit for
  * bit, and road_stat untouched (count + 0, and 0 is not larger).  A row cannot be checked from the host: a non-finite word, a mu <= 0 or a NaN
  * anywhere poisons that vehicle's state or statistics alone -- one thread per vehicle, no lane reads another's row.  Validate rows where they
@@ -792,6 +793,72 @@ int32_t kmpc_sense_faults_default(double *rows_host, int32_t B);   /* HOST; KMPC
 int32_t kmpc_sense_faults_batch(int32_t device, int32_t B, const void *state, const void *sensor, const void *faults, uint64_t seed,
                                 int64_t period, int64_t id_base, const int32_t *meas_delay, void *truth_ring, int32_t depth, void *fault_rec,
                                 void *z_out, void *held_out, int32_t *flags_out, uint8_t *blind_out, void *stream);
+
+/* ---- coloured noise and gusts: a Gauss-Markov stage ("wander") ----------------------------------------------------------------------------
+ * kmpc_sense_batch's noise is white and a road row is a constant.  kmpc_wander_batch keeps eight first-order Gauss-Markov processes per vehicle
+ * -- a GPS error that wanders, a gust, a gyro's random walk -- advances them once per control period and composes them into the rows the
+ * measurement and plant kernels already read: a sensor row's biases and a road row's A_LONG, A_LAT and DF_OFFSET.  Those kernels do not change.
+ * One thread per vehicle, fp64.  The channels: */
+enum {
+    KMPC_WANDER_CH_X = 0, KMPC_WANDER_CH_Y = 1, KMPC_WANDER_CH_PSI = 2, KMPC_WANDER_CH_V = 3,   /* measurement error on x, y, psi, v [m, m, rad, m/s] */
+    KMPC_WANDER_CH_A_LONG = 4,      /* added to the road row's A_LONG [m/s^2] */
+    KMPC_WANDER_CH_A_LAT = 5,       /* added to the road row's A_LAT [m/s^2]: a lateral gust */
+    KMPC_WANDER_CH_DF_OFFSET = 6,   /* added to the road row's DF_OFFSET [rad] */
+    KMPC_WANDER_CH_FREE = 7,        /* advanced like the others, composed into nothing: the caller's */
+    KMPC_WANDER_CHANNELS = 8
+};
+/*   wander [B,24] fp64 DEVICE, row of vehicle b: three groups of eight words, one word per channel c (word = group + c): */
+enum {
+    KMPC_WANDER_S0 = 0,             /* words 0 ... 7: standard deviation of the first value, >= 0 */
+    KMPC_WANDER_A = 8,              /* words 8 ... 15: carry-over per period, in [0, 1] */
+    KMPC_WANDER_Q = 16,             /* words 16 ... 23: standard deviation of the innovation per period, >= 0 */
+    KMPC_WANDER_WORDS = 24
+};
+/*   kmpc_wander_default writes B neutral rows to HOST memory: all 24 words 0 (A = 0 too), every channel off.
+ *   wander_rec [B,16] fp64 DEVICE in/out, record of vehicle b; all zeros (hipMemset) = fresh: */
+enum {
+    KMPC_WANDERREC_X = 0,           /* words 0 ... 7: X_c, the current value of channel c.  This is the stage's output: there is no separate x_out */
+    KMPC_WANDERREC_COUNT = 8,       /* calls so far; 0 = fresh */
+                                    /* words 9 ... 15 are written back as read, whatever the record's state */
+    KMPC_WANDERREC_WORDS = 16
+};
+/*   seed, period, id_base        as in kmpc_sense_batch; period < 2^62
+ *   sensor_base, sensor_out      both NULL, or [B,8] fp64 DEVICE sensor rows (KMPC_SENSOR_*): the caller's rows and the rows the sense kernels read
+ *   road_base, road_out          both NULL, or [B,8] fp64 DEVICE road rows (KMPC_ROAD_*): the caller's rows and the rows the plant (or
+ *                                kmpc_road_profile_fleet, as its road_base) reads
+ * Per vehicle b, with gid = id_base + b and p = period; no product and sum are contracted, every operation is rounded once:
+ *   DRAWS  two Philox4x32-10 calls with kmpc_sense_batch's key.  Call j (0 or 1) has the counter
+ *     (gid lo, gid hi, p lo, p hi ^ (j == 0 ? 0x40000000 : 0xC0000000)).  With p < 2^62 the top two bits of p hi are clear, so the four domains --
+ *     00 the measurement draw, 10 the fault draw, 01 and 11 these -- never share a counter.  Uniforms and Box-Muller exactly as in
+ *     kmpc_sense_batch: u_i = (w_i + 0.5) * 2^-32;  n_(4j) = sqrt(-2 ln u0) cos(t), n_(4j+1) = sqrt(-2 ln u0) sin(t), t = 6.283185307179586 * u1;
+ *     n_(4j+2), n_(4j+3) likewise from (u2, u3).  Call j thus gives the normals of channels 4j ... 4j+3.
+ *   OFF  a channel with S0_c == 0 && Q_c == 0 is off: its X_c is written +0.0, its composed word is the base word bit for bit (no add), and it
+ *     need not draw (a call none of whose four channels is on is skipped).  Every other channel is active (a NaN S0 or Q compares false: active).
+ *   RESET  a record whose COUNT is non-finite or negative is taken as fresh.
+ *   FRESH RECORD (COUNT == 0, or reset):  X_c = S0_c * n_c;  COUNT = 1.  The record's X words are not read.
+ *   OTHERWISE  X_c = A_c * X_c + Q_c * n_c  (product, product, sum);  COUNT = COUNT + 1.
+ *   COMPOSITION (each pair that is given)
+ *     sensor_out words 0 ... 3 (the sigmas) = sensor_base's, bit for bit;  sensor_out[BIAS_X + c] = sensor_base[BIAS_X + c] + X_c for an active
+ *     channel c = 0 ... 3, sensor_base's bits for one that is off.
+ *     road_out[A_LONG] = road_base[A_LONG] + X_4, road_out[A_LAT] = road_base[A_LAT] + X_5, road_out[DF_OFFSET] = road_base[DF_OFFSET] + X_6 where
+ *     the channel is active, road_base's bits where it is off;  road_out words 0, 1, 5, 6, 7 = road_base's, bit for bit.
+ *     out == base is refused: the sum would compound call after call (kmpc_road_profile_fleet's rule).
+ * Properties:
+ *   - With the neutral row in every vehicle both outputs equal their bases bit for bit and every X is +0.0.
+ *   - A vehicle's whole history is a function of (seed, gid, its row, the periods called): not of B, the launch geometry or the shard.
+ *   - A = 1, Q = 0 keeps the first draw for ever: 1 * X + 0 * n is exact, except that a -0.0 becomes +0.0 in the second call.
+ *   - Q = S0 * sqrt(1 - A^2) makes the process stationary with standard deviation S0 and correlation A^k at lag k: A = exp(-dt / tau) for a
+ *     correlation time tau.  S0 = 0, A = 1, Q > 0 is a random walk.  A = 0 is white noise.
+ *   - The kernel cannot validate a row (Python: vehicle_sim.check_wander_rows): a non-finite word poisons that vehicle's X and composed words
+ *     alone.  No lane reads another vehicle's words.
+ *   - The noise belongs to the moment of emission: a delayed or faulty sense reads this period's composed bias, as it reads this period's
+ *     normals.  A value is held for one control period, like the road profile's.
+ * Argument checks before any device call (they answer on a machine without a GPU): B, period or id_base < 0, period >= 2^62; with B > 0 a NULL
+ * wander or wander_rec; one of a pair without the other; out == base: KMPC_ERR_ARG (text in kmpc_last_error(NULL)).  B == 0 succeeds without a
+ * launch.  Asynchronous on `stream`. */
+int32_t kmpc_wander_default(double *rows_host, int32_t B);   /* HOST: B rows of 24 zeros; KMPC_ERR_ARG for B < 0 or, with B > 0, NULL rows */
+int32_t kmpc_wander_batch(int32_t device, int32_t B, const void *wander, void *wander_rec, uint64_t seed, int64_t period, int64_t id_base,
+                          const void *sensor_base, void *sensor_out, const void *road_base, void *road_out, void *stream);
 
 /* ---- delay compensation: the controller's side -------------------------------------------------------------------------------------------
  * The controller keeps a log of the commands it sent and its own ASSUMED delays -- buffers of its own, not the plant's or the sensor's, so that

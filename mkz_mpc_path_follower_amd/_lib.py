@@ -43,7 +43,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_llc_default", "kmpc_llc_step_batch", "kmpc_drive_default", "kmpc_sim_advance_drive",
            "kmpc_pathset_curvature", "kmpc_speed_plan_default", "kmpc_speed_plan_fleet",
            "kmpc_road_profile_default", "kmpc_road_profile_fleet", "kmpc_speed_plan_fleet_profile",
-           "kmpc_sense_faults_default", "kmpc_sense_faults_batch"]
+           "kmpc_sense_faults_default", "kmpc_sense_faults_batch",
+           "kmpc_wander_default", "kmpc_wander_batch"]
 
 _lib = None
 
@@ -114,6 +115,8 @@ def load():
     L.kmpc_sense_delayed_batch.argtypes = [i32, i32, vp, vp, C.c_uint64, C.c_int64, C.c_int64, vp, vp, i32, vp, vp]
     L.kmpc_sense_faults_default.argtypes = [dp, i32]
     L.kmpc_sense_faults_batch.argtypes = [i32, i32, vp, vp, vp, C.c_uint64, C.c_int64, C.c_int64, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.kmpc_wander_default.argtypes = [dp, i32]
+    L.kmpc_wander_batch.argtypes = [i32, i32, vp, vp, C.c_uint64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
     L.kmpc_cmd_in_force_batch.argtypes = [i32, i32, vp, i32, C.c_int64, i32, vp, vp, i32, i32, vp, vp]
     L.kmpc_predict_ahead_batch.argtypes = [i32, i32, vp, vp, i32, C.c_int64, i32, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp]
     L.kmpc_predict_ahead_dist_batch.argtypes = [i32, i32, vp, vp, vp, i32, C.c_int64, i32, vp, vp, i32, i32] + [C.c_double] * 3 + [vp, vp]

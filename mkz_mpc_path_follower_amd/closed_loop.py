@@ -66,6 +66,13 @@ L0 actuation: the reference's low-level controller and a pedal-driven powertrain
 kmpc_sim_advance_drive runs the controller's 50 Hz tick inside the plant call).  The loops only call `sim._update_vehicle_model`; `sim.state[:, 6]`
 is then the powertrain's net acceleration, which `estimator_input="actuator"` reads as delivered, while `estimator_input="command"` lets an
 observer see the difference between what was commanded and what the pedals delivered.
+
+Coloured noise and gusts: `wander=vehicle_sim.Wander(B, wander_params(...))` runs first in every period (kmpc_wander_batch, one launch): eight
+Gauss-Markov processes per vehicle are advanced to period `loop.k` and added to the sensor's biases and the road's a_long, a_lat, df_offset.  With a
+sensor the caller's sensor rows move to `sensor.params_base` and `sensor.params` -- what the sense kernels read -- is rewritten every period; with a
+road the caller's rows are `sim.road_base` and the stage writes `sim.road` (in front of a road profile: base -> wander -> profile -> `sim.road`).
+Active measurement channels without sensor=, or active road channels without a simulator built with road=, are refused at construction.
+`run(history=True)` adds `wander` [steps,B,8].  Without wander= there is no launch and no tensor more.
 """
 import ctypes as C
 import time
@@ -77,6 +84,7 @@ from . import _lib
 from .kinematic_mpc_frenet import get_reference_frenet_batch
 from .ref_traj import SCORE_FIELDS, FleetRefTrajectory, fresh_score
 from .solver import BatchMPC
+from .vehicle_sim import Wander
 
 FRENET_WEIGHTS = (0.0, 9.0, 10.0, 0.5, 100.0, 1000.0, 0.0, 0.0)   # MKZMPCPathFollowerFrenet.jl:51-59 in update_cost's 8-slot layout (no x slot)
 
@@ -101,7 +109,8 @@ class _ScoredLoop:
     _reference(st) -> (ref, stop, solve, extra): the reference built from the controller's state `st`, the helper's stop flags, the solve as a
     call without arguments -> the solver's output dict, and the entries the loop adds to step()'s dict."""
 
-    def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer, planner=None, track_with_time=False, blind_stop=False):
+    def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer, planner=None, track_with_time=False, blind_stop=False,
+                   wander=None):
         """what both loops own beside grt, sim, N, B, mpc and the target speeds: buffers, the stop latch, the library, and the stages"""
         dev = self.sim.device
         self.u_prev = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)       # (acc, d_f): update_current_input starts at 0
@@ -115,13 +124,16 @@ class _ScoredLoop:
         self.out = None
         self.k = 0
         self._init_sensor(sensor, blind_stop)
+        self._init_wander(wander)
         self._init_estimator(estimator, estimator_input, compensator, observer)
         self._init_planner(planner, track_with_time)
         self._init_score()
 
     def _period(self, plant_updates, time_solve):
-        """one control period -> step()'s dict: sense -> filter -> predict -> reference and solve (the loop's own) -> command stage -> offset ->
-        log -> plant"""
+        """one control period -> step()'s dict: wander -> sense -> filter -> predict -> reference and solve (the loop's own) -> command stage ->
+        offset -> log -> plant"""
+        if self.wander is not None:   # this period's coloured errors and gusts, into the rows the sense and the plant call below read
+            self.wander.step(self.k, *self._wander_rows)
         st = self.sim.state if self.sensor is None else self._sense()
         if self.estimator is not None or self.observer is not None:
             st = self._filter(self.sensor.z if self.faulty else st)   # a faulty sensor's z: NaN where a source is silent, the filter coasts
@@ -186,6 +198,27 @@ class _ScoredLoop:
             raise ValueError("blind_stop=True reads the sensor's blind flags: give sensor=SensorModel(..., faults=...)")
         self.blind_stop = bool(blind_stop)
         self.est = None   # [B,4] x, y, psi, v as sensed in the last period (sensor given)
+
+    def _init_wander(self, wander):
+        """wander=: the Gauss-Markov stage in front of the sense.  The sensor pair is composed whenever the loop has a sensor, the road pair whenever
+        the simulator has a road; a channel that is on without its consumer is refused here, on the host rows the stage was built from."""
+        self.wander, self._wander_rows = wander, None
+        if wander is None:
+            return
+        if not (isinstance(wander, Wander) and wander.B == self.B and wander.device == self.sim.device):
+            raise ValueError("wander= is a vehicle_sim.Wander for %d vehicles on %s" % (self.B, self.sim.device))
+        if wander.sensor_active and self.sensor is None:
+            raise ValueError("wander= has active measurement channels (x, y, psi, v): give sensor=SensorModel(...), whose biases they are added to")
+        if wander.road_active and self.sim.road is None:
+            raise ValueError("wander= has active road channels (a_long, a_lat, df_offset): build the simulator with road= (road_params)")
+        sensor_pair = road_pair = (None, None)
+        if self.sensor is not None:
+            if self.sensor.params_base is None:
+                self.sensor.params_base, self.sensor.params = self.sensor.params, self.sensor.params.clone()
+            sensor_pair = (self.sensor.params_base, self.sensor.params)
+        if self.sim.road is not None:
+            road_pair = self.sim.wander_road_buffers()
+        self._wander_rows = sensor_pair + road_pair
 
     def _init_estimator(self, estimator, estimator_input, compensator=None, observer=None):
         if observer is not None:
@@ -268,7 +301,8 @@ class _ScoredLoop:
         (what was measured of state[j] in period j: what the controller saw, unless an estimator follows) and, with an estimator, est_filt [steps,B,4]
         (what the controller saw then, unless a compensator follows; an observer's est_filt likewise, with dist [steps,B,3]) and, with a compensator, est_pred [steps,B,4] (what the controller saw then)
         and, with a planner, v_plan [steps,B] (the speed period j's waypoints and solve ran at) and, with a faulty sensor (SensorModel(faults=)),
-        z [steps,B,4] (NaN where a source was silent: what a filter read; est is then the held state) and fault_flags [steps,B] int32.
+        z [steps,B,4] (NaN where a source was silent: what a filter read; est is then the held state) and fault_flags [steps,B] int32 and, with
+        wander=, wander [steps,B,8] (the processes' values in period j: what was added to the biases and the road words then).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -294,6 +328,8 @@ class _ScoredLoop:
                 hist["est_pred"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
             if self.planner is not None:
                 hist["v_plan"] = torch.empty((steps, self.B), dtype=torch.float64, device=dev)
+            if self.wander is not None:
+                hist["wander"] = torch.empty((steps, self.B, 8), dtype=torch.float64, device=dev)
             hist["state"][0].copy_(self.sim.state)
         if score and self.k == 0 and self._score_fresh:
             self._score_state(None, settle_tol)
@@ -317,6 +353,8 @@ class _ScoredLoop:
                     hist["est_pred"][j].copy_(self.est_pred)
                 if self.planner is not None:
                     hist["v_plan"][j].copy_(self.v_plan)
+                if self.wander is not None:
+                    hist["wander"][j].copy_(self.wander.x)
         out = dict(score=self.score, last=o)
         if score and self.track is not None:
             out.update(self.track)
@@ -349,7 +387,7 @@ class ClosedLoop(_ScoredLoop):
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
                  mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, observer=None, planner=None,
-                 blind_stop=False, **options):
+                 blind_stop=False, wander=None, **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -365,7 +403,7 @@ class ClosedLoop(_ScoredLoop):
             raise ValueError("a FleetRefTrajectory owns the tracking modes (its time_mode): track_with_time must stay False")
         self.track_with_time = track_with_time
         self.des_speed, self.v_target = _target_speeds(target_vel, self.B, sim.device)  # mpc_cmd_pub.jl:58-62
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander)
 
     def step(self, plant_updates=10, time_solve=False):
         """time_solve=True brackets the solve with device synchronisations and returns its wall time (`solve_s`)"""
@@ -391,7 +429,7 @@ class ClosedLoopFrenet(_ScoredLoop):
     (checked once, here).  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, estimator=None,
-                 estimator_input="actuator", compensator=None, observer=None, planner=None, blind_stop=False, **options):
+                 estimator_input="actuator", compensator=None, observer=None, planner=None, blind_stop=False, wander=None, **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -410,7 +448,7 @@ class ClosedLoopFrenet(_ScoredLoop):
         if grt.device != sim.device:
             raise ValueError("waypoint helper on %s, plant on %s: the loop runs on one device" % (grt.device, sim.device))
         self.des_speed, self.v_target = des_speed, v_target
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander)
 
     def step(self, plant_updates=10, time_solve=False):
         """as ClosedLoop.step; the returned dict also carries `k_poly` [B,4] and `fit_status` [B]"""

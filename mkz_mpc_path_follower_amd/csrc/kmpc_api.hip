@@ -979,6 +979,35 @@ extern "C" int32_t kmpc_sense_faults_batch(int32_t device, int32_t B, const void
     return KMPC_OK;
 }
 
+// ---- Gauss-Markov stage (kmpc_wander.hip) ----------------------------------------------------------------------------
+// the neutral row: 24 zeros, every channel off
+extern "C" int32_t kmpc_wander_default(double *rows_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_default: bad argument (B=%d, rows %s)", B, rows_host ? "given" : "NULL");
+    for (size_t w = 0; w < KMPC_WANDER_WORDS * (size_t)B; ++w) rows_host[w] = 0.0;
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_wander_batch(int32_t device, int32_t B, const void *wander, void *wander_rec, uint64_t seed, int64_t period, int64_t id_base,
+                                     const void *sensor_base, void *sensor_out, const void *road_base, void *road_out, void *stream)
+{
+    if (B < 0 || period < 0 || id_base < 0 || period >= ((int64_t)1 << 62) || (B > 0 && (!wander || !wander_rec)))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_batch: bad argument (B=%d, period=%lld, below 2^62; id_base=%lld; wander %s, wander_rec %s)", B,
+                    (long long)period, (long long)id_base, wander ? "given" : "NULL", wander_rec ? "given" : "NULL");
+    if ((sensor_base != nullptr) != (sensor_out != nullptr) || (road_base != nullptr) != (road_out != nullptr))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_batch: a base and its out go together (sensor_base %s, sensor_out %s, road_base %s, road_out %s)",
+                    sensor_base ? "given" : "NULL", sensor_out ? "given" : "NULL", road_base ? "given" : "NULL", road_out ? "given" : "NULL");
+    if ((sensor_out && sensor_out == sensor_base) || (road_out && road_out == road_base))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_batch: an out must not be its base (the sum would compound call after call)");
+    if (B == 0) return KMPC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_wander_batch: hipSetDevice(%d) failed", device);
+    const hipError_t e = kmpc_launch_wander(B, (const double *)wander, (double *)wander_rec, seed, (uint64_t)period, (uint64_t)id_base,
+                                            (const double *)sensor_base, (double *)sensor_out, (const double *)road_base, (double *)road_out,
+                                            (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_wander_batch: %s", hipGetErrorString(e));
+    return KMPC_OK;
+}
+
 // ---- delay compensation (kmpc_latency.hip) ---------------------------------------------------------------------------
 static int32_t latency_args(const char *fn, int32_t B, const void *cmd_hist, int32_t depth, int64_t period, int32_t n_updates, const int32_t *cmd_delay,
                             const int32_t *meas_delay, int32_t max_cmd_delay, int32_t max_meas_delay)

@@ -106,6 +106,9 @@ hipError_t kmpc_launch_sim_road(int B, double *state, const double *cmd, const d
 hipError_t kmpc_launch_sense_faults(int B, const double *state, const double *sensor, const double *faults, uint64_t seed, uint64_t period,
                                     uint64_t id_base, const int32_t *meas_delay, double *truth_ring, int depth, double *fault_rec, double *z_out,
                                     double *held_out, int32_t *flags_out, uint8_t *blind_out, hipStream_t st);
+// Gauss-Markov stage (kmpc_wander.hip); each pair (base, out) both NULL or both given
+hipError_t kmpc_launch_wander(int B, const double *wander, double *wander_rec, uint64_t seed, uint64_t period, uint64_t id_base,
+                              const double *sensor_base, double *sensor_out, const double *road_base, double *road_out, hipStream_t st);
 // low-level controller and pedal-driven plant (kmpc_drive.hip)
 hipError_t kmpc_launch_llc_step(int B, const double *cmd, const double *speed, int speed_stride, const double *llc_rows, double *llc_rec,
                                 double *pedals_out, hipStream_t st);

@@ -23,6 +23,15 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
 }
 
+// two Philox words -> two normals, the operations of sim_measure's pair below (kmpc_wander.hip; sim_measure keeps its own text)
+__device__ __forceinline__ void box_muller(uint32_t w0, uint32_t w1, double *n0, double *n1)
+{
+    const double u0 = ((double)w0 + 0.5) * 0x1p-32, u1 = ((double)w1 + 0.5) * 0x1p-32;
+    const double r = sqrt(-2.0 * log(u0)), a = 6.283185307179586 * u1;
+    *n0 = r * cos(a);
+    *n1 = r * sin(a);
+}
+
 // what the measurement kernels do once the truth t = x, y, psi, vx is fetched and the four Philox words w are drawn: bias, noise, the plant's wrap
 // (:101; a heading in range passes unchanged) and the steering report's speed floor
 __device__ __forceinline__ void sim_measure(const double t[4], const double *__restrict__ sr, const uint32_t w[4], double *__restrict__ o)

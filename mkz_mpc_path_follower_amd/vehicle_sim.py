@@ -29,6 +29,10 @@ L0 actuation: `LowLevelController` is the reference's 50 Hz node src/LowLevelCon
 a low-passed differentiated speed, brake torque below a deadband, steering-wheel angle), and `VehicleSimulator(drive=drive_params(B, ...), llc=)`
 puts it inside the plant, in front of a powertrain that turns pedals into force (kmpc_sim_advance_drive): the command then no longer acts as an
 acceleration.  `llc.summary()` downloads the controller's counters.  Without `drive=` every code path is the one that ran before.
+
+Coloured noise and gusts: `Wander(B, wander_params(B, sigma=..., tau=..., walk=...))` keeps eight Gauss-Markov processes per vehicle and, once per
+period, adds them to a sensor row's biases and a road row's a_long, a_lat, df_offset (kmpc_wander_batch), on the device.  The closed loops take it
+as `wander=`; the sense and plant kernels read the composed rows as they read the caller's before.
 """
 import ctypes as C
 
@@ -206,8 +210,129 @@ def fault_params(B, device=0, **overrides):
     return torch.as_tensor(check_fault_rows(rows)).to(_device(device))
 
 
+WANDER_CHANNELS, WANDER_WORDS, WANDER_RECORD_WORDS = 8, 24, 16
+WANDER_CHANNEL_NAMES = ("x", "y", "psi", "v", "a_long", "a_lat", "df_offset", "free")   # KMPC_WANDER_CH_*
+WANDER_FIELDS = tuple(g + "_" + c for g in ("s0", "a", "q") for c in WANDER_CHANNEL_NAMES)   # KMPC_WANDER_S0 / _A / _Q + channel: words 0 ... 23
+WANDER_RECORD_FIELDS = tuple("x_" + c for c in WANDER_CHANNEL_NAMES) + ("count",)   # KMPC_WANDERREC_* words 0 ... 8 (9 ... 15 are written back as read)
+
+
+def wander_default():
+    """the neutral wander row (24 zeros: every channel off) as a numpy row [24], from kmpc_wander_default"""
+    row = np.ones(WANDER_WORDS)
+    _lib.check(_lib.load().kmpc_wander_default(row.ctypes.data_as(C.POINTER(C.c_double)), 1))
+    return row
+
+
+def check_wander_rows(rows):
+    """[B,24] host rows -> ValueError unless every word is finite, S0 >= 0, Q >= 0 and A in [0, 1] (the kernel cannot refuse a row: a bad one
+    poisons that vehicle's processes)"""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != WANDER_WORDS:
+        raise ValueError("wander rows: [B,24] (S0, A, Q of the channels %s), got %s" % (", ".join(WANDER_CHANNEL_NAMES), rows.shape))
+    rows_of = lambda bad: np.flatnonzero(bad)[:8].tolist()
+    if not np.isfinite(rows).all():
+        raise ValueError("wander rows: non-finite value in vehicle(s) %s" % rows_of(~np.isfinite(rows).all(1)))
+    s0, a, q = rows[:, 0:8], rows[:, 8:16], rows[:, 16:24]
+    if not ((s0 >= 0.0) & (q >= 0.0)).all():
+        raise ValueError("wander rows: the standard deviations S0 and Q must be >= 0 (vehicle(s) %s)" % rows_of(~((s0 >= 0.0) & (q >= 0.0)).all(1)))
+    if not ((a >= 0.0) & (a <= 1.0)).all():
+        raise ValueError("wander rows: the carry-over A lies in [0, 1] (vehicle(s) %s)" % rows_of(~((a >= 0.0) & (a <= 1.0)).all(1)))
+    return rows
+
+
+def wander_rows(B, dt=0.1, sigma=0.0, tau=0.0, walk=0.0):
+    """[B,24] host rows from physical parameters, each of `sigma`, `tau`, `walk` a scalar, 8 values (one per channel: WANDER_CHANNEL_NAMES) or [B,8].
+    A stationary channel has the standard deviation `sigma` and the correlation time `tau` [s]: S0 = sigma, A = exp(-dt / tau) -- tau = inf gives
+    A = 1, Q = 0, a random constant; tau = 0 gives A = 0, white noise -- and Q = sigma * sqrt(1 - A * A).  A channel with a `walk` rate r > 0
+    [unit / sqrt(s)] is a random walk from 0: S0 = 0, A = 1, Q = r * sqrt(dt); its sigma must be 0.  sigma = 0 and walk = 0: the channel is off.
+    `dt` is the control period [s].  Validated (check_wander_rows)."""
+    B = int(B)
+    if not (np.isfinite(dt) and dt > 0.0):
+        raise ValueError("wander_rows: dt is the control period, finite and > 0, got %r" % (dt,))
+    par = {}
+    for name, v in (("sigma", sigma), ("tau", tau), ("walk", walk)):
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape not in ((), (WANDER_CHANNELS,), (B, WANDER_CHANNELS)):
+            raise ValueError("wander_rows: %s is a scalar, 8 values (one per channel) or [%d,8], got %s" % (name, B, v.shape))
+        if np.isnan(v).any() or (v < 0.0).any() or (name != "tau" and np.isinf(v).any()):
+            raise ValueError("wander_rows: %s must be >= 0%s" % (name, "" if name == "tau" else " and finite"))
+        par[name] = np.broadcast_to(v, (B, WANDER_CHANNELS))
+    sg, tau, wk = par["sigma"], par["tau"], par["walk"]
+    if ((wk > 0.0) & (sg > 0.0)).any():
+        raise ValueError("wander_rows: a channel is stationary (sigma, tau) or a random walk (walk), not both")
+    with np.errstate(divide="ignore"):
+        a = np.where(tau == 0.0, 0.0, np.exp(-dt / np.where(tau == 0.0, 1.0, tau)))
+    rows = np.zeros((B, WANDER_WORDS))
+    rows[:, 0:8] = np.where(wk > 0.0, 0.0, sg)
+    rows[:, 8:16] = np.where(wk > 0.0, 1.0, a)
+    rows[:, 16:24] = np.where(wk > 0.0, wk * np.sqrt(dt), sg * np.sqrt(1.0 - a * a))
+    return check_wander_rows(rows)
+
+
+def wander_params(B, device=0, dt=0.1, sigma=0.0, tau=0.0, walk=0.0):
+    """wander_rows(B, dt, sigma, tau, walk) as a float64 tensor [B,24] on `device`"""
+    return torch.as_tensor(wander_rows(B, dt=dt, sigma=sigma, tau=tau, walk=walk)).to(_device(device))
+
+
+class Wander:
+    """The Gauss-Markov stage: eight first-order processes per vehicle -- errors on the measured x, y, psi, v that wander, gusts on the road row's
+    a_long, a_lat and df_offset, and one free channel -- advanced once per control period and composed into the rows the sense and plant kernels
+    read (kmpc_wander_batch; include/kmpc.h states the arithmetic).  `rows` [B,24] (WANDER_FIELDS: wander_params / wander_rows) are validated on the
+    host.  `params` [B,24] and `rec` [B,16] (WANDER_RECORD_FIELDS; all zeros = fresh) are plain device tensors the caller may edit between calls;
+    `x` is a view of rec[:, 0:8], the current values: the stage's output.  Vehicle b's history depends only on (seed, id_base + b, its row, the
+    periods called): a shard passes its first vehicle's index as id_base.  `sensor_active` / `road_active`: whether any of the channels 0 ... 3 /
+    4 ... 6 is on in any of the rows given here (what the closed loops check their sensor= and road= against)."""
+
+    def __init__(self, B, rows, seed=0, id_base=0, device=0):
+        self._lib = _lib.load()
+        self.B, self.seed, self.id_base = int(B), int(seed), int(id_base)
+        if not (0 <= self.seed < 2 ** 64 and 0 <= self.id_base and self.id_base + self.B < 2 ** 63):
+            raise ValueError("Wander: seed in [0, 2^64), id_base >= 0")
+        rows = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else rows
+        rows = check_wander_rows(rows)
+        if rows.shape[0] != self.B:
+            raise ValueError("Wander: rows is [%d,24], got %s" % (self.B, rows.shape))
+        on = (rows[:, 0:8] != 0.0) | (rows[:, 16:24] != 0.0)
+        self.sensor_active, self.road_active = bool(on[:, 0:4].any()), bool(on[:, 4:7].any())
+        self.device = _device(device)
+        self.params = torch.as_tensor(np.ascontiguousarray(rows)).to(self.device)
+        self.rec = torch.zeros((self.B, WANDER_RECORD_WORDS), dtype=torch.float64, device=self.device)
+
+    x = property(lambda s: s.rec[:, 0:WANDER_CHANNELS])
+
+    def reset(self):
+        """every record fresh: the next step() draws first values again"""
+        self.rec.zero_()
+
+    def step(self, period, sensor_base=None, sensor_out=None, road_base=None, road_out=None):
+        """advances every process to control period `period` (0 <= period < 2^62) and composes: sensor_out [B,8] = sensor_base with x[:, 0:4] added
+        to the biases, road_out [B,8] = road_base with x[:, 4:7] added to a_long, a_lat, df_offset (each pair both None or both given; an out is
+        never its base) -> x [B,8], the view of `rec`.  Asynchronous on torch's current stream."""
+        own = ((self.params, WANDER_WORDS, "params"), (self.rec, WANDER_RECORD_WORDS, "rec"))
+        for t, w, name in own + tuple((t, 8, name) for t, name in ((sensor_base, "sensor_base"), (sensor_out, "sensor_out"), (road_base, "road_base"),
+                                                                   (road_out, "road_out")) if t is not None):
+            if not (type(t) is torch.Tensor and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+                raise ValueError("%s: a contiguous float64 tensor [%d,%d] on %s" % (name, self.B, w, self.device))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if self.device.type != "cuda":
+            raise RuntimeError("Wander.step runs on an MI355X; no CPU fallback (device %s)" % self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.kmpc_wander_batch(self.device.index, self.B, p(self.params), p(self.rec), self.seed, int(period), self.id_base,
+                                               p(sensor_base), p(sensor_out), p(road_base), p(road_out), stream))
+        return self.x
+
+    def summary(self):
+        """the records so far, one download -> dict of numpy arrays: x [B,8] (the current values), count [B] int64 and one [B] array per channel
+        named by WANDER_RECORD_FIELDS"""
+        rec = self.rec.detach().cpu().numpy()
+        out = {k: rec[:, i].copy() for i, k in enumerate(WANDER_RECORD_FIELDS)}
+        out["count"] = out["count"].astype(np.int64)
+        out["x"] = rec[:, 0:WANDER_CHANNELS].copy()
+        return out
+
+
 PROFILE_WORDS = 8
-PROFILE_FIELDS = ("mu_scale", "a_long", "a_lat", "v_limit")   # KMPC_PROFILE_* words 0 ... 3 of include/kmpc.h, in row order (4 ... 7 are read by nobody)
+PROFILE_FIELDS =("mu_scale", "a_long", "a_lat", "v_limit")   # KMPC_PROFILE_* words 0 ... 3 of include/kmpc.h, in row order (4 ... 7 are read by nobody)
 
 
 def road_profile_default():
@@ -514,6 +639,7 @@ class VehicleSimulator:
         self.cmd = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)  # acc_des, df_des (:21-22)
         self.plant = self.cmd_delay = self.cmd_held = self.cmd_queue = self.road = self.road_stat = self.drive = self.llc = None
         self.road_base = self.road_profile = None
+        self.road_mid = None   # [B,8] with a Wander in front of a road profile: what the profile reads in road_base's place (wander_road_buffers)
         self.period = 0
         if plant is not None or cmd_delay is not None or cmd_queue_depth is not None:
             if plant is None:
@@ -576,7 +702,7 @@ class VehicleSimulator:
                             and t.device == self.device):
                         raise ValueError("road [B,8] / road_stat [B,4] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
                 if self.road_profile is not None and int(n_updates) > 0:   # the road under each vehicle, from where it is now
-                    self.road_profile.apply(self.state, self.road_base, self.road)
+                    self.road_profile.apply(self.state, self.road_base if self.road_mid is None else self.road_mid, self.road)
                 if self.drive is not None:
                     if not (isinstance(self.drive, torch.Tensor) and self.drive.dtype == torch.float64 and tuple(self.drive.shape) == (self.B, 8)
                             and self.drive.is_contiguous() and self.drive.device == self.device):
@@ -609,6 +735,20 @@ class VehicleSimulator:
                                                   C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
                                                   C.c_void_p(self.cmd_held.data_ptr()), int(n_updates), stream)
         _lib.check(rc)
+
+    def wander_road_buffers(self):
+        """where a Wander composes the road: -> (base, out), the caller's rows and the rows the stage writes.  Without a road profile the caller's
+        rows move to `road_base` and `road` (what the plant reads) is the stage's output; with one the stage acts first, base -> wander ->
+        `road_mid` -> profile -> `road`, so each affected word is (base + x) + the profile's word.  ValueError without road=."""
+        if self.road is None:
+            raise ValueError("a wander with road channels needs a simulator with road= (road_params)")
+        if self.road_profile is not None:
+            if self.road_mid is None:
+                self.road_mid = self.road_base.clone()
+            return self.road_base, self.road_mid
+        if self.road_base is None:
+            self.road_base, self.road = self.road, self.road.clone()
+        return self.road_base, self.road
 
     def road_summary(self):
         """the grip bookkeeping so far, one download -> dict of numpy arrays [B]: sat_f, sat_r (sub-steps in which the front / rear force was
@@ -655,6 +795,7 @@ class SensorModel:
             raise ValueError("SensorModel: sigma and bias must be finite, sigma >= 0")
         self.device = _device(device)
         self.params = torch.as_tensor(rows).to(self.device)
+        self.params_base = None   # [B,8] in a loop with wander=: the caller's rows; `params` is then rewritten from them every period
         self.meas_delay = self.truth_ring = self.depth = None
         if meas_delay is None and depth is not None:
             raise ValueError("SensorModel: depth belongs to meas_delay")

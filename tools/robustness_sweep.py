@@ -46,7 +46,13 @@ cell once on the held fix (no filter: what scripts/state_publisher.py publishes)
 speed); one outlier row (P_OUTLIER 0.05, OUTLIER_SIGMA 3 m on a GPS of sigma 0.1 m; the estimator with gate 0 against gate 4); one blind_stop row
 (MAX_AGE 30: a vehicle blind for longer latches and brakes).
 
+--wander is the sweep of coloured noise and gusts (-> profiles/robustness_sweep_wander.txt): wander=vehicle_sim.Wander, nominal plant, no delay, the
+road sweep's 48 starts at 6 m/s: a GPS error of sigma (0.1, 0.2, 0.5) m as white noise against the same sigma coloured with tau (2, 10, 30) s, each without
+and with estimator=; a lateral gust of sigma (0.5, 1.0) m/s^2 and tau (0.5, 2, 10) s without observer=, with it at its default q_dist and at 4 x; a
+heading random walk (0, 0.003, 0.01) rad/sqrt(s) on top of GPS outages of 30 and 100 periods with estimator=.
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
+       python tools/robustness_sweep.py --wander [out.txt] [steps]
        python tools/robustness_sweep.py --outage [out.txt] [steps]
        python tools/robustness_sweep.py --road-profile [out.txt] [steps]
        python tools/robustness_sweep.py --speed-plan [out.txt] [steps]
@@ -762,8 +768,120 @@ def outage_main():
             f.write("\n".join(LINES) + "\n")
 
 
+WAN_SIGMA, WAN_TAU = (0.1, 0.2, 0.5), (0.0, 2.0, 10.0, 30.0)             # GPS error [m]; its correlation time [s], 0 = white (the sensor's own noise)
+WAN_GUST, WAN_GUST_TAU, WAN_QSCALE = (0.5, 1.0), (0.5, 2.0, 10.0), (None, 1.0, 4.0)   # lateral gust [m/s^2], its tau [s]; no observer, q_dist x 1, x 4
+WAN_WALK, WAN_WINDOW = (0.0, 0.003, 0.01), (30, 100)                      # heading walk [rad / sqrt(s)]; GPS window [periods]
+
+
+def wander_main():
+    """loops of the road sweep's 48 starts at 6 m/s, nominal plant, no delay, with wander=vehicle_sim.Wander (seed 2024):
+    coloured GPS error, two loops of 3 x 4 cells (sigma x tau; tau = 0 is the sensor's white noise, the others the wander's channels x, y with a
+    noiseless sensor), without and with estimator= (r = sigma in every cell: what a user who knows the error's size but not its colour sets);
+    gusts, three loops of 2 x 3 cells (a_lat channel, sigma x tau) on a road without a grip limit: no observer, observer= at its default q_dist, at 4 x;
+    heading walk, one loop of 2 x 3 cells (GPS window x walk rate on the psi channel), estimator=, the window's start drawn per vehicle as in --outage."""
+    from mkz_mpc_path_follower_amd.vehicle_sim import Wander, fault_params, wander_params
+    argv = [a for a in sys.argv if a != "--wander"]
+    steps = int(argv[2]) if len(argv) > 2 else 300
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    rng = np.random.default_rng(0)
+    frac48 = rng.uniform(0.02, 0.45, ROAD_PER_CELL)          # the road sweep's starts
+    from48 = rng.integers(10, 40, ROAD_PER_CELL).astype(float)
+
+    def run(ncells, sigma8, tau8, walk8=0.0, sensor_sigma=0.0, est_r=None, q_scale=None, road=False, faults=None):
+        """one loop of ncells x 48 vehicles -> score summary with `finite`, `latched`, and (sensor given) the rms position error of est / est_filt"""
+        B = ncells * ROAD_PER_CELL
+        pid = np.tile(np.arange(ROAD_PER_CELL) % 3, ncells)
+        fleet = FleetRefTrajectory(paths, pid, traj_horizon=8, traj_dt=0.2)
+        frac = np.tile(frac48, ncells)
+        pose = np.empty((B, 3))
+        for b in range(B):
+            tr = fleet.trajectories[pid[b]]
+            i = int(frac[b] * len(tr))
+            pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+        sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2], road=road_params(B) if road else None)
+        sim.state[:, 3] = VT
+        kw = dict(wander=Wander(B, wander_params(B, sigma=sigma8, tau=tau8, walk=walk8), seed=2024))
+        if not road:
+            kw["sensor"] = SensorModel(B, sigma=sensor_sigma, seed=2024, faults=None if faults is None else faults(B))
+        if est_r is not None:
+            kw["estimator"] = Estimator(B, r=est_r)
+        if q_scale is not None:
+            kw["observer"] = DisturbanceObserver(B, q_dist=tuple(q_scale * q for q in (0.002, 0.002, 0.02)))
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=VT, **kw)
+        hist = loop.run(steps, history=not road)
+        s = loop.score_summary()
+        s["finite"] = bool(torch.isfinite(sim.state).all().item())
+        s["latched"] = int((s["latch_index"] >= 0).sum())
+        if not road and faults is None:
+            truth = hist["state"][:steps, :, 0:2]
+            s["e_raw"] = ((hist["est"][:, :, 0:2] - truth) ** 2).sum(2).mean(0).sqrt().cpu().numpy()
+            if est_r is not None:
+                s["e_filt"] = ((hist["est_filt"][:, :, 0:2] - truth) ** 2).sum(2).mean(0).sqrt().cpu().numpy()
+        return s
+
+    say("%s: %d periods of 0.1 s at %.0f m/s on three paths, nominal plant, no delay, %d vehicles per cell (the road sweep's starts), wander seed 2024"
+        % (torch.cuda.get_device_name(0), steps, VT, ROAD_PER_CELL))
+    # ---- coloured GPS error
+    cells = list(itertools.product(range(len(WAN_SIGMA)), range(len(WAN_TAU))))
+    ix = np.array(cells)[np.repeat(np.arange(len(cells)), ROAD_PER_CELL)]
+    sg, tau = np.array(WAN_SIGMA)[ix[:, 0]], np.array(WAN_TAU)[ix[:, 1]]
+    white = tau == 0.0
+    sigma8, tau8, ssig = np.zeros((len(ix), 8)), np.zeros((len(ix), 8)), np.zeros((len(ix), 4))
+    sigma8[:, 0] = sigma8[:, 1] = np.where(white, 0.0, sg)
+    tau8[:, 0] = tau8[:, 1] = tau
+    ssig[:, 0] = ssig[:, 1] = np.where(white, sg, 0.0)
+    r = np.tile([1e-3, 1e-3, 1e-4, 1e-3], (len(ix), 1))
+    r[:, 0] = r[:, 1] = sg
+    raw = run(len(cells), sigma8, tau8, sensor_sigma=ssig)
+    flt = run(len(cells), sigma8, tau8, sensor_sigma=ssig, est_r=r)
+    say("coloured GPS error on x and y, without | with estimator= (r = sigma): every state finite %s / %s, latched vehicles %d / %d" %
+        (raw["finite"], flt["finite"], raw["latched"], flt["latched"]))
+    say("   per cell: median rms e_ct [m] without | with, their ratio; median rms position error of what the controller saw against the truth [m] without | with, their ratio")
+    for c, (a, t) in enumerate(cells):
+        sel = (ix[:, 0] == a) & (ix[:, 1] == t)
+        e0, e1 = np.median(raw["rms_ect"][sel]), np.median(flt["rms_ect"][sel])
+        p0, p1 = np.median(raw["e_raw"][sel]), np.median(flt["e_filt"][sel])
+        say("   sigma %.1f m, %-10s   %6.3f | %6.3f  x %4.2f     %6.3f | %6.3f  x %4.2f" %
+            (WAN_SIGMA[a], "white" if WAN_TAU[t] == 0.0 else "tau %g s" % WAN_TAU[t], e0, e1, e1 / e0, p0, p1, p1 / p0))
+    # ---- gusts
+    cells = list(itertools.product(range(len(WAN_GUST)), range(len(WAN_GUST_TAU))))
+    ix = np.array(cells)[np.repeat(np.arange(len(cells)), ROAD_PER_CELL)]
+    sigma8, tau8 = np.zeros((len(ix), 8)), np.zeros((len(ix), 8))
+    sigma8[:, 5], tau8[:, 5] = np.array(WAN_GUST)[ix[:, 0]], np.array(WAN_GUST_TAU)[ix[:, 1]]
+    res = [run(len(cells), sigma8, tau8, q_scale=q, road=True) for q in WAN_QSCALE]
+    say("lateral gust (a_lat channel), no grip limit, the truth fed to the controller: no observer | observer= at the default q_dist | at 4 x: every state "
+        "finite %s, latched vehicles %s" % (" / ".join(str(x["finite"]) for x in res), " / ".join(str(x["latched"]) for x in res)))
+    say("   per cell: median rms e_ct [m] three ways, then the largest |e_ct| [m] three ways")
+    for c, (a, t) in enumerate(cells):
+        sel = (ix[:, 0] == a) & (ix[:, 1] == t)
+        say("   sigma %.1f m/s^2, tau %4.1f s   %6.3f | %6.3f | %6.3f     %6.3f | %6.3f | %6.3f" %
+            ((WAN_GUST[a], WAN_GUST_TAU[t]) + tuple(np.median(x["rms_ect"][sel]) for x in res) + tuple(x["max_ect"][sel].max() for x in res)))
+    # ---- heading random walk on top of a GPS outage
+    cells = list(itertools.product(range(len(WAN_WINDOW)), range(len(WAN_WALK))))
+    ix = np.array(cells)[np.repeat(np.arange(len(cells)), ROAD_PER_CELL)]
+    walk8 = np.zeros((len(ix), 8))
+    walk8[:, 2] = np.array(WAN_WALK)[ix[:, 1]]
+    rows = lambda B: fault_params(B, win_from_gps=np.tile(from48, len(cells)), win_len_gps=np.array(WAN_WINDOW, dtype=float)[ix[:, 0]])
+    out = run(len(cells), 0.0, 0.0, walk8=walk8, est_r=(0.2, 0.2, 0.02, 0.1), faults=rows)
+    say("heading random walk (psi channel) on top of a GPS outage, estimator= (its default r), no other noise: every state finite %s, latched vehicles %d"
+        % (out["finite"], out["latched"]))
+    say("   per cell: median over vehicles of the largest |e_ct| [m], largest |e_ct| [m], median rms e_ct [m]")
+    for c, (w, k) in enumerate(cells):
+        sel = (ix[:, 0] == w) & (ix[:, 1] == k)
+        say("   window %3d periods, walk %.3f rad/sqrt(s)   %7.3f %8.3f %7.3f" %
+            (WAN_WINDOW[w], WAN_WALK[k], np.median(out["max_ect"][sel]), out["max_ect"][sel].max(), np.median(out["rms_ect"][sel])))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 if __name__ == "__main__":
-    if "--outage" in sys.argv[1:]:
+    if "--wander" in sys.argv[1:]:
+        wander_main()
+    elif "--outage" in sys.argv[1:]:
         outage_main()
     elif "--actuation" in sys.argv[1:]:
         actuation_main()
