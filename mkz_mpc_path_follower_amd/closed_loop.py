@@ -74,13 +74,13 @@ road the caller's rows are `sim.road_base` and the stage writes `sim.road` (in f
 Active measurement channels without sensor=, or active road channels without a simulator built with road=, are refused at construction.
 `run(history=True)` adds `wander` [steps,B,8].  Without wander= there is no launch and no tensor more.
 """
-import ctypes as C
 import time
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._stage import is_buffer, ptr, stream
 from .kinematic_mpc_frenet import get_reference_frenet_batch
 from .ref_traj import SCORE_FIELDS, FleetRefTrajectory, fresh_score
 from .solver import BatchMPC
@@ -111,8 +111,11 @@ class _ScoredLoop:
 
     def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer, planner=None, track_with_time=False, blind_stop=False,
                    wander=None):
-        """what both loops own beside grt, sim, N, B, mpc and the target speeds: buffers, the stop latch, the library, and the stages"""
+        """what both loops own beside grt, sim, N, B, mpc and the target speeds: buffers, the stop latch, the library, and the stages; and the one
+        check of the helper against the plant that both word alike (a loop's own refusals, worded for that loop, come before this call)"""
         dev = self.sim.device
+        if self.grt.device != dev:
+            raise ValueError("waypoint helper on %s, plant on %s: the loop runs on one device" % (self.grt.device, dev))
         self.u_prev = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)       # (acc, d_f): update_current_input starts at 0
         self.warm_U = torch.zeros((self.B, self.N, 2), dtype=torch.float64, device=dev)
         self.command_stop = torch.zeros((self.B,), dtype=torch.bool, device=dev)   # the stop latch (one byte per vehicle: kmpc_command_batch's uint8)
@@ -155,11 +158,9 @@ class _ScoredLoop:
         # into the plant's command buffer
         cmd = self.sim.cmd
         u0 = self.out["u0"]
-        assert u0.dtype == torch.float64 and u0.is_contiguous() and u0.device == cmd.device and u0.shape == (self.B, 2)
-        stream = C.c_void_p(torch.cuda.current_stream(cmd.device).cuda_stream)
-        _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, C.c_void_p(u0.data_ptr()), C.c_void_p(stop.data_ptr()),
-                                                C.c_void_p(self.command_stop.data_ptr()), C.c_void_p(self.u_prev.data_ptr()),
-                                                C.c_void_p(cmd.data_ptr()), stream))
+        assert is_buffer(u0, torch.float64, (self.B, 2), cmd.device)
+        _lib.check(self._lib.kmpc_command_batch(cmd.device.index, self.B, ptr(u0), ptr(stop), ptr(self.command_stop), ptr(self.u_prev), ptr(cmd),
+                                                stream(cmd.device)))
         if self.observer is not None:
             self.observer.offset(cmd, self.command_stop)
         if self.compensator is not None:
@@ -168,14 +169,18 @@ class _ScoredLoop:
         self.k += 1
         return dict(ref=ref, cmd=cmd, status=self.out["status"], iters=self.out["iters"], cost=self.out["cost"], solve_s=solve_s, **extra)
 
+    def _same_fleet(self, name, stage):
+        """a stage built for another fleet size or on another device than the plant's is refused, every stage in the same words"""
+        if stage.B != self.B or stage.device != self.sim.device:
+            raise ValueError("%s for %d vehicles on %s, plant with %d on %s" % (name, stage.B, stage.device, self.B, self.sim.device))
+
     def _init_planner(self, planner, track_with_time):
         if planner is not None:
             if track_with_time:
                 raise ValueError("planner= plans a speed along the arclength grid: track_with_time must stay False")
             if getattr(planner, "fleet", None) is not self.grt:
                 raise ValueError("planner= must be a ref_traj.SpeedPlanner built on this loop's own waypoint helper (a FleetRefTrajectory)")
-            if planner.device != self.sim.device or planner.B != self.B:
-                raise ValueError("planner for %d vehicles on %s, plant with %d on %s" % (planner.B, planner.device, self.B, self.sim.device))
+            self._same_fleet("planner", planner)
             if self.grt.time_mode is not None and bool(self.grt.time_mode.any().item()):
                 raise ValueError("planner= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode")
         self.planner = planner
@@ -190,8 +195,8 @@ class _ScoredLoop:
         return self.v_plan
 
     def _init_sensor(self, sensor, blind_stop=False):
-        if sensor is not None and (sensor.B != self.B or sensor.device != self.sim.device):
-            raise ValueError("sensor for %d vehicles on %s, plant with %d on %s" % (sensor.B, sensor.device, self.B, self.sim.device))
+        if sensor is not None:
+            self._same_fleet("sensor", sensor)
         self.sensor = sensor
         self.faulty = sensor is not None and getattr(sensor, "faults", None) is not None   # SensorModel(faults=): z, flags, blind beside the held state
         if blind_stop and not self.faulty:
@@ -227,8 +232,7 @@ class _ScoredLoop:
             if compensator is not None and not getattr(compensator, "disturbances", False):
                 raise ValueError("observer= with compensator= needs LatencyCompensator(..., disturbances=True): the prediction ahead must run on "
                                  "the observer's model")
-            if observer.B != self.B or observer.device != self.sim.device:
-                raise ValueError("observer for %d vehicles on %s, plant with %d on %s" % (observer.B, observer.device, self.B, self.sim.device))
+            self._same_fleet("observer", observer)
             if compensator is not None:
                 compensator.check_observer(observer)
         elif compensator is not None and getattr(compensator, "disturbances", False):
@@ -239,13 +243,13 @@ class _ScoredLoop:
             raise ValueError("estimator_input: 'actuator', 'command' or 'history', got %r" % (estimator_input,))
         if estimator_input == "history" and compensator is None:
             raise ValueError("estimator_input='history' reads the compensator's command log: give compensator=")
-        if compensator is not None and (compensator.B != self.B or compensator.device != self.sim.device):
-            raise ValueError("compensator for %d vehicles on %s, plant with %d on %s" % (compensator.B, compensator.device, self.B, self.sim.device))
+        if compensator is not None:
+            self._same_fleet("compensator", compensator)
         self.compensator = compensator
         self.est_pred = None   # [B,4] the state predicted ahead to where this period's command acts (compensator given)
         self._u_hist = None
-        if estimator is not None and (estimator.B != self.B or estimator.device != self.sim.device):
-            raise ValueError("estimator for %d vehicles on %s, plant with %d on %s" % (estimator.B, estimator.device, self.B, self.sim.device))
+        if estimator is not None:
+            self._same_fleet("estimator", estimator)
         self.estimator, self.estimator_input = estimator, estimator_input
         self.est_filt = None   # [B,4] the filtered x, y, psi, v of the last period (estimator given)
 
@@ -293,6 +297,20 @@ class _ScoredLoop:
         self.track = self.grt.track_score_batch(self.sim.state, score=self.score, settle_tol=settle_tol, out=self.track, **side)
         self._score_fresh = False
 
+    def _optional_history(self):
+        """what run(history=True) records beside state, cmd, status and latch, for the stages this loop has: (key, trailing shape, dtype, source), in
+        the order the keys appear in run()'s dict; source() is the tensor a period leaves behind"""
+        f64 = torch.float64
+        rows = ((self.sensor is not None, "est", (4,), f64, lambda: self.est),
+                (self.faulty, "z", (4,), f64, lambda: self.sensor.z),
+                (self.faulty, "fault_flags", (), torch.int32, lambda: self.sensor.flags),
+                (self.estimator is not None or self.observer is not None, "est_filt", (4,), f64, lambda: self.est_filt),
+                (self.observer is not None, "dist", (3,), f64, lambda: self.dist),
+                (self.compensator is not None, "est_pred", (4,), f64, lambda: self.est_pred),
+                (self.planner is not None, "v_plan", (), f64, lambda: self.v_plan),
+                (self.wander is not None, "wander", (8,), f64, lambda: self.wander.x))
+        return [row[1:] for row in rows if row[0]]
+
     def run(self, steps, score=True, settle_tol=0.5, history=False, plant_updates=10):
         """`steps` control periods back to back: no host synchronisation and no device -> host copy in here.
         score=True: the initial state is scored geometry-only when the loop has not stepped (k == 0) and its record is fresh; then every
@@ -311,25 +329,13 @@ class _ScoredLoop:
         dev = self.sim.device
         hist = None
         if history:
+            optional = self._optional_history()
             hist = dict(state=torch.empty((steps + 1, self.B, 8), dtype=torch.float64, device=dev),
                         cmd=torch.empty((steps, self.B, 2), dtype=torch.float64, device=dev),
                         status=torch.empty((steps, self.B), dtype=torch.int32, device=dev),
                         latch=torch.empty((steps, self.B), dtype=torch.bool, device=dev))
-            if self.sensor is not None:
-                hist["est"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
-            if self.faulty:
-                hist["z"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
-                hist["fault_flags"] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
-            if self.estimator is not None or self.observer is not None:
-                hist["est_filt"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
-            if self.observer is not None:
-                hist["dist"] = torch.empty((steps, self.B, 3), dtype=torch.float64, device=dev)
-            if self.compensator is not None:
-                hist["est_pred"] = torch.empty((steps, self.B, 4), dtype=torch.float64, device=dev)
-            if self.planner is not None:
-                hist["v_plan"] = torch.empty((steps, self.B), dtype=torch.float64, device=dev)
-            if self.wander is not None:
-                hist["wander"] = torch.empty((steps, self.B, 8), dtype=torch.float64, device=dev)
+            for key, shape, dt, _ in optional:
+                hist[key] = torch.empty((steps, self.B) + shape, dtype=dt, device=dev)
             hist["state"][0].copy_(self.sim.state)
         if score and self.k == 0 and self._score_fresh:
             self._score_state(None, settle_tol)
@@ -341,20 +347,8 @@ class _ScoredLoop:
             if history:
                 hist["cmd"][j].copy_(o["cmd"]); hist["status"][j].copy_(o["status"])
                 hist["latch"][j].copy_(self.command_stop); hist["state"][j + 1].copy_(self.sim.state)
-                if self.sensor is not None:
-                    hist["est"][j].copy_(self.est)
-                if self.faulty:
-                    hist["z"][j].copy_(self.sensor.z); hist["fault_flags"][j].copy_(self.sensor.flags)
-                if self.estimator is not None or self.observer is not None:
-                    hist["est_filt"][j].copy_(self.est_filt)
-                if self.observer is not None:
-                    hist["dist"][j].copy_(self.dist)
-                if self.compensator is not None:
-                    hist["est_pred"][j].copy_(self.est_pred)
-                if self.planner is not None:
-                    hist["v_plan"][j].copy_(self.v_plan)
-                if self.wander is not None:
-                    hist["wander"][j].copy_(self.wander.x)
+                for key, _, _, source in optional:
+                    hist[key][j].copy_(source())
         out = dict(score=self.score, last=o)
         if score and self.track is not None:
             out.update(self.track)
@@ -397,8 +391,6 @@ class ClosedLoop(_ScoredLoop):
         if self.mpc.dtype != torch.float64 or self.mpc.N != self.N or self.mpc.device != sim.device or sim.device.index is None:
             raise ValueError("ClosedLoop needs a float64 BatchMPC with horizon %d on %s (got %s, N=%d, %s)"
                              % (self.N, sim.device, self.mpc.dtype, self.mpc.N, self.mpc.device))
-        if grt.device != sim.device:
-            raise ValueError("waypoint helper on %s, plant on %s: the loop runs on one device" % (grt.device, sim.device))
         if track_with_time and isinstance(grt, FleetRefTrajectory):
             raise ValueError("a FleetRefTrajectory owns the tracking modes (its time_mode): track_with_time must stay False")
         self.track_with_time = track_with_time
@@ -445,8 +437,6 @@ class ClosedLoopFrenet(_ScoredLoop):
                 or self.mpc.cfg.model != 1):
             raise ValueError("ClosedLoopFrenet needs a float64 model=1 BatchMPC with horizon %d on %s (got %s, model=%d, N=%d, %s)"
                              % (self.N, sim.device, self.mpc.dtype, self.mpc.cfg.model, self.mpc.N, self.mpc.device))
-        if grt.device != sim.device:
-            raise ValueError("waypoint helper on %s, plant on %s: the loop runs on one device" % (grt.device, sim.device))
         self.des_speed, self.v_target = des_speed, v_target
         self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander)
 

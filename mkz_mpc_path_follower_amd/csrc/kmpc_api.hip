@@ -645,6 +645,41 @@ extern "C" int32_t kmpc_waypoints_fleet(kmpc_pathset *ps, int32_t B, int32_t hor
 
 extern "C" const char *kmpc_pathset_last_error(kmpc_pathset *ps) { return ps ? ps->err.c_str() : g_create_err.c_str(); }
 
+// ---- what the device-indexed and path-handle entry points below share --------------------------------------------------
+// Every one of them checks its arguments first (each check answers before the first HIP call), returns KMPC_OK where there is nothing to do, and
+// ends in on_device(): select the device, launch, and turn a hipError_t into the entry point's own text.
+template <typename Launch>
+static int32_t on_device(const char *fn, int device, Launch launch)
+{
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "%s: hipSetDevice(%d) failed", fn, device);
+    const hipError_t e = launch();
+    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return KMPC_OK;
+}
+
+static bool pos(double a) { return a > 0.0 && a <= 1.7976931348623157e308; }       // finite and > 0
+static bool nonneg(double a) { return a >= 0.0 && a <= 1.7976931348623157e308; }   // finite and >= 0
+
+// the plant calls' common arguments, in the order their refusals are documented: B / n_updates / state / cmd, then the plant rows, then the road rows
+// (where the entry point has them).  The drive rows and the queue follow in the callers, and only then "B == 0 or n_updates == 0: nothing to do".
+static int32_t sim_args(const char *fn, int32_t B, int32_t n_updates, const void *state, const void *cmd, const void *plant, const void *road,
+                        bool need_road)
+{
+    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "%s: bad argument (B=%d, n_updates=%d)", fn, B, n_updates);
+    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "%s: null plant rows", fn);
+    if (need_road && B > 0 && !road) return fail(nullptr, KMPC_ERR_ARG, "%s: null road rows", fn);
+    return KMPC_OK;
+}
+
+// the command ring of the queue, road and drive plants: checked whatever B is
+static int32_t queue_args(const char *fn, int32_t depth, int64_t period, const void *cmd_queue)
+{
+    if (depth < 2 || period < 0 || !cmd_queue)
+        return fail(nullptr, KMPC_ERR_ARG, "%s: bad queue (depth=%d, at least 2; period=%lld, at least 0; cmd_queue %s)", fn, depth, (long long)period,
+                    cmd_queue ? "given" : "NULL");
+    return KMPC_OK;
+}
+
 // ---- tracking errors and the running score record (kmpc_track_score.hip) ----------------------------------------------
 extern "C" int32_t kmpc_track_score_init(double *score_host, int32_t B)
 {
@@ -672,13 +707,10 @@ extern "C" int32_t kmpc_track_score_batch(kmpc_path *p, int32_t B, const double 
 {
     const int rc = track_score_args("kmpc_track_score_batch", p, B, state, state_stride, nullptr, false, settle_tol, status, iters, cmd, stop_latch);
     if (rc != KMPC_OK) return rc < 0 ? rc : KMPC_OK;
-    if (hipSetDevice(p->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_track_score_batch: hipSetDevice(%d) failed", p->device);
     TSB k;
     k.w = {B, state_stride, settle_tol, state, status, iters, cmd, stop_latch, err_out, seg_out, closest_out, score};
     k.M = p->M; k.X = p->d + p->M; k.Y = p->d + 2 * (size_t)p->M; k.psi = p->d + 3 * (size_t)p->M; k.s = p->d + 4 * (size_t)p->M;
-    const hipError_t e = kmpc_launch_track_score(k, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_track_score_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_track_score_batch", p->device, [&] { return kmpc_launch_track_score(k, (hipStream_t)stream); });
 }
 
 extern "C" int32_t kmpc_track_score_fleet(kmpc_pathset *ps, int32_t B, const double *state, int32_t state_stride, const int32_t *path_id,
@@ -688,13 +720,10 @@ extern "C" int32_t kmpc_track_score_fleet(kmpc_pathset *ps, int32_t B, const dou
 {
     const int rc = track_score_args("kmpc_track_score_fleet", ps, B, state, state_stride, path_id, true, settle_tol, status, iters, cmd, stop_latch);
     if (rc != KMPC_OK) return rc < 0 ? rc : KMPC_OK;
-    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_track_score_fleet: hipSetDevice(%d) failed", ps->device);
     TSF k;
     k.w = {B, state_stride, settle_tol, state, status, iters, cmd, stop_latch, err_out, seg_out, closest_out, score};
     k.P = ps->P; k.total = ps->total; k.d = ps->d; k.off = ps->off; k.path_id = path_id;
-    const hipError_t e = kmpc_launch_track_score_fleet(k, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_track_score_fleet: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_track_score_fleet", ps->device, [&] { return kmpc_launch_track_score_fleet(k, (hipStream_t)stream); });
 }
 
 // ---- curvature table and speed plan (kmpc_speed_plan.hip) ------------------------------------------------------------
@@ -703,11 +732,8 @@ extern "C" int32_t kmpc_pathset_curvature(kmpc_pathset *ps, double window, doubl
     if (!ps) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_curvature: null path set");
     if (!std::isfinite(window) || !(window > 0)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_curvature: window must be finite and > 0");
     if (!kappa_out) return fail(nullptr, KMPC_ERR_ARG, "kmpc_pathset_curvature: null kappa_out");
-    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_pathset_curvature: hipSetDevice(%d) failed", ps->device);
     const SPC k = {ps->P, ps->total, 0.5 * window, ps->d, ps->off, kappa_out};
-    const hipError_t e = kmpc_launch_curvature(k, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_pathset_curvature: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_pathset_curvature", ps->device, [&] { return kmpc_launch_curvature(k, (hipStream_t)stream); });
 }
 
 // this project's own defaults (the reference has no such stage): the one place they exist
@@ -733,12 +759,9 @@ static int32_t speed_plan_fleet(const char *fn, bool with_profile, kmpc_pathset 
     if (B > 0 && (!kappa || (with_profile && !profile) || !state || !path_id || !v_cap || !rows || !v_plan_out))
         return fail(nullptr, KMPC_ERR_ARG, "%s: null required buffer", fn);
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "%s: hipSetDevice(%d) failed", fn, ps->device);
     const SPF w = {ps->P, B, ps->total, state_stride, ps->d, ps->off, kappa, with_profile ? profile : nullptr, state, path_id, v_cap, rows,
                    v_plan_out, info_out, closest_out};
-    const hipError_t e = kmpc_launch_speed_plan_fleet(w, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device(fn, ps->device, [&] { return kmpc_launch_speed_plan_fleet(w, (hipStream_t)stream); });
 }
 
 extern "C" int32_t kmpc_speed_plan_fleet(kmpc_pathset *ps, int32_t B, const double *kappa, const double *state, int32_t state_stride,
@@ -780,11 +803,8 @@ extern "C" int32_t kmpc_road_profile_fleet(kmpc_pathset *ps, int32_t B, const do
     if (road_out && road_out == road_base)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_road_profile_fleet: road_out must not be road_base (the scaling would compound call after call)");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(ps->device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_road_profile_fleet: hipSetDevice(%d) failed", ps->device);
     const RPF w = {ps->P, B, ps->total, state_stride, ps->d, ps->off, profile, state, path_id, road_base, road_out, closest_out};
-    const hipError_t e = kmpc_launch_road_profile_fleet(w, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_road_profile_fleet: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_road_profile_fleet", ps->device, [&] { return kmpc_launch_road_profile_fleet(w, (hipStream_t)stream); });
 }
 
 // ---- closed-loop simulator (kmpc_sim.hip) ------------------------------------------------------------------------
@@ -792,10 +812,7 @@ extern "C" int32_t kmpc_sim_advance_batch(int32_t device, int32_t B, void *state
 {
     if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_batch: bad argument (B=%d, n_updates=%d)", B, n_updates);
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_sim(B, (double *)state, (const double *)cmd, n_updates, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_sim_advance_batch", device, [&] { return kmpc_launch_sim(B, (double *)state, (const double *)cmd, n_updates, (hipStream_t)stream); });
 }
 
 // the reference's plant constants (vehicle_simulator.py:61-67, :112-113): the one place they exist for the per-vehicle plant
@@ -810,15 +827,13 @@ extern "C" int32_t kmpc_plant_default(double *row8)
 extern "C" int32_t kmpc_sim_advance_plant(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay,
                                           void *cmd_held, int32_t n_updates, void *stream)
 {
-    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_plant: bad argument (B=%d, n_updates=%d)", B, n_updates);
-    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_plant: null plant rows");
+    int32_t rc = sim_args("kmpc_sim_advance_plant", B, n_updates, state, cmd, plant, nullptr, false);
+    if (rc != KMPC_OK) return rc;
     if (B > 0 && cmd_delay && !cmd_held) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_plant: cmd_delay needs cmd_held");
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_plant: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_sim_plant(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_held, n_updates,
-                                               (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_plant: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_sim_advance_plant", device, [&] {
+        return kmpc_launch_sim_plant(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_held, n_updates, (hipStream_t)stream);
+    });
 }
 
 extern "C" int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period, int64_t id_base,
@@ -827,27 +842,22 @@ extern "C" int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state
     if (B < 0 || period < 0 || id_base < 0 || (B > 0 && (!state || !sensor || !est)))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_batch: bad argument (B=%d, period=%lld, id_base=%lld)", B, (long long)period, (long long)id_base);
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_sense(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, (double *)est,
-                                           (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_sense_batch", device, [&] {
+        return kmpc_launch_sense(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, (double *)est, (hipStream_t)stream);
+    });
 }
 
 extern "C" int32_t kmpc_sim_advance_queue(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay,
                                           void *cmd_queue, int32_t depth, int64_t period, int32_t n_updates, void *stream)
 {
-    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_queue: bad argument (B=%d, n_updates=%d)", B, n_updates);
-    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_queue: null plant rows");
-    if (depth < 2 || period < 0 || !cmd_queue)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_queue: bad queue (depth=%d, at least 2; period=%lld, at least 0; cmd_queue %s)", depth,
-                    (long long)period, cmd_queue ? "given" : "NULL");
+    int32_t rc = sim_args("kmpc_sim_advance_queue", B, n_updates, state, cmd, plant, nullptr, false);
+    if (rc != KMPC_OK) return rc;
+    if ((rc = queue_args("kmpc_sim_advance_queue", depth, period, cmd_queue)) != KMPC_OK) return rc;
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_queue: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_sim_queue(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_queue, depth,
-                                               (long long)period, n_updates, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_queue: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_sim_advance_queue", device, [&] {
+        return kmpc_launch_sim_queue(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_queue, depth, (long long)period,
+                                     n_updates, (hipStream_t)stream);
+    });
 }
 
 // the neutral road row: no grip limit, a flat and level road, no steering offset, the acceleration as commanded
@@ -863,18 +873,14 @@ extern "C" int32_t kmpc_sim_advance_road(int32_t device, int32_t B, void *state,
                                          const int32_t *cmd_delay, void *cmd_queue, int32_t depth, int64_t period, int32_t n_updates, void *road_stat,
                                          void *stream)
 {
-    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_road: bad argument (B=%d, n_updates=%d)", B, n_updates);
-    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_road: null plant rows");
-    if (B > 0 && !road) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_road: null road rows");
-    if (depth < 2 || period < 0 || !cmd_queue)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_road: bad queue (depth=%d, at least 2; period=%lld, at least 0; cmd_queue %s)", depth,
-                    (long long)period, cmd_queue ? "given" : "NULL");
+    int32_t rc = sim_args("kmpc_sim_advance_road", B, n_updates, state, cmd, plant, road, true);
+    if (rc != KMPC_OK) return rc;
+    if ((rc = queue_args("kmpc_sim_advance_road", depth, period, cmd_queue)) != KMPC_OK) return rc;
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_road: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_sim_road(B, (double *)state, (const double *)cmd, (const double *)plant, (const double *)road, cmd_delay,
-                                              (double *)cmd_queue, depth, (long long)period, n_updates, (double *)road_stat, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_road: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_sim_advance_road", device, [&] {
+        return kmpc_launch_sim_road(B, (double *)state, (const double *)cmd, (const double *)plant, (const double *)road, cmd_delay, (double *)cmd_queue, depth,
+                                    (long long)period, n_updates, (double *)road_stat, (hipStream_t)stream);
+    });
 }
 
 // ---- low-level controller and pedal-driven plant (kmpc_drive.hip) ----------------------------------------------------
@@ -903,31 +909,26 @@ extern "C" int32_t kmpc_llc_step_batch(int32_t device, int32_t B, const void *cm
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_llc_step_batch: bad argument (B=%d, speed_stride=%d, at least 1; cmd, speed, llc and llc_rec are required)", B,
                     speed_stride);
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_llc_step_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_llc_step(B, (const double *)cmd, (const double *)speed, speed_stride, (const double *)llc, (double *)llc_rec,
-                                              (double *)pedals_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_llc_step_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_llc_step_batch", device, [&] {
+        return kmpc_launch_llc_step(B, (const double *)cmd, (const double *)speed, speed_stride, (const double *)llc, (double *)llc_rec, (double *)pedals_out,
+                                    (hipStream_t)stream);
+    });
 }
 
 extern "C" int32_t kmpc_sim_advance_drive(int32_t device, int32_t B, void *state, const void *cmd, const void *plant, const void *road,
                                           const void *drive, const void *llc, void *llc_rec, const int32_t *cmd_delay, void *cmd_queue, int32_t depth,
                                           int64_t period, int32_t n_updates, void *road_stat, void *stream)
 {
-    if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: bad argument (B=%d, n_updates=%d)", B, n_updates);
-    if (B > 0 && !plant) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: null plant rows");
-    if (B > 0 && !road) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: null road rows");
+    int32_t rc = sim_args("kmpc_sim_advance_drive", B, n_updates, state, cmd, plant, road, true);
+    if (rc != KMPC_OK) return rc;
     if (B > 0 && (!drive || !llc || !llc_rec)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: null drive rows, llc rows or llc_rec");
-    if (depth < 2 || period < 0 || !cmd_queue)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: bad queue (depth=%d, at least 2; period=%lld, at least 0; cmd_queue %s)", depth,
-                    (long long)period, cmd_queue ? "given" : "NULL");
+    if ((rc = queue_args("kmpc_sim_advance_drive", depth, period, cmd_queue)) != KMPC_OK) return rc;
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_drive: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_sim_drive(B, (double *)state, (const double *)cmd, (const double *)plant, (const double *)road,
-                                               (const double *)drive, (const double *)llc, (double *)llc_rec, cmd_delay, (double *)cmd_queue, depth,
-                                               (long long)period, n_updates, (double *)road_stat, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sim_advance_drive: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_sim_advance_drive", device, [&] {
+        return kmpc_launch_sim_drive(B, (double *)state, (const double *)cmd, (const double *)plant, (const double *)road, (const double *)drive,
+                                     (const double *)llc, (double *)llc_rec, cmd_delay, (double *)cmd_queue, depth, (long long)period, n_updates, (double *)road_stat,
+                                     (hipStream_t)stream);
+    });
 }
 
 extern "C" int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period,
@@ -938,11 +939,10 @@ extern "C" int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const voi
     if (depth < 1 || (B > 0 && (!meas_delay || !truth_ring)))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_delayed_batch: bad ring (depth=%d, at least 1; meas_delay and truth_ring are required)", depth);
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_delayed_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_sense_delayed(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, meas_delay,
-                                                   (double *)truth_ring, depth, (double *)est, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_delayed_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_sense_delayed_batch", device, [&] {
+        return kmpc_launch_sense_delayed(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, meas_delay,
+                                         (double *)truth_ring, depth, (double *)est, (hipStream_t)stream);
+    });
 }
 
 // ---- measurement stage with sensor faults (kmpc_sense_faults.hip) ------------------------------------------------------
@@ -971,12 +971,11 @@ extern "C" int32_t kmpc_sense_faults_batch(int32_t device, int32_t B, const void
                     meas_delay ? "given" : "NULL", truth_ring ? "given" : "NULL");
     if (meas_delay && depth < 1) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_faults_batch: bad ring (depth=%d, at least 1)", depth);
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_faults_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_sense_faults(B, (const double *)state, (const double *)sensor, (const double *)faults, seed, (uint64_t)period,
-                                                  (uint64_t)id_base, meas_delay, (double *)truth_ring, depth, (double *)fault_rec, (double *)z_out,
-                                                  (double *)held_out, flags_out, blind_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_sense_faults_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_sense_faults_batch", device, [&] {
+        return kmpc_launch_sense_faults(B, (const double *)state, (const double *)sensor, (const double *)faults, seed, (uint64_t)period, (uint64_t)id_base,
+                                        meas_delay, (double *)truth_ring, depth, (double *)fault_rec, (double *)z_out, (double *)held_out, flags_out, blind_out,
+                                        (hipStream_t)stream);
+    });
 }
 
 // ---- Gauss-Markov stage (kmpc_wander.hip) ----------------------------------------------------------------------------
@@ -1000,12 +999,10 @@ extern "C" int32_t kmpc_wander_batch(int32_t device, int32_t B, const void *wand
     if ((sensor_out && sensor_out == sensor_base) || (road_out && road_out == road_base))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_batch: an out must not be its base (the sum would compound call after call)");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_wander_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_wander(B, (const double *)wander, (double *)wander_rec, seed, (uint64_t)period, (uint64_t)id_base,
-                                            (const double *)sensor_base, (double *)sensor_out, (const double *)road_base, (double *)road_out,
-                                            (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_wander_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_wander_batch", device, [&] {
+        return kmpc_launch_wander(B, (const double *)wander, (double *)wander_rec, seed, (uint64_t)period, (uint64_t)id_base, (const double *)sensor_base,
+                                  (double *)sensor_out, (const double *)road_base, (double *)road_out, (hipStream_t)stream);
+    });
 }
 
 // ---- delay compensation (kmpc_latency.hip) ---------------------------------------------------------------------------
@@ -1031,11 +1028,10 @@ extern "C" int32_t kmpc_cmd_in_force_batch(int32_t device, int32_t B, const void
     if (rc != KMPC_OK) return rc;
     if (B > 0 && !u_out) return fail(nullptr, KMPC_ERR_ARG, "kmpc_cmd_in_force_batch: null u_out");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_cmd_in_force_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_cmd_in_force(B, (const double *)cmd_hist, depth, (long long)period, n_updates, cmd_delay, meas_delay, max_cmd_delay,
-                                                  max_meas_delay, (double *)u_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_cmd_in_force_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_cmd_in_force_batch", device, [&] {
+        return kmpc_launch_cmd_in_force(B, (const double *)cmd_hist, depth, (long long)period, n_updates, cmd_delay, meas_delay, max_cmd_delay, max_meas_delay,
+                                        (double *)u_out, (hipStream_t)stream);
+    });
 }
 
 extern "C" int32_t kmpc_predict_ahead_batch(int32_t device, int32_t B, const void *z, const void *cmd_hist, int32_t depth, int64_t period,
@@ -1044,15 +1040,13 @@ extern "C" int32_t kmpc_predict_ahead_batch(int32_t device, int32_t B, const voi
 {
     const int32_t rc = latency_args("kmpc_predict_ahead_batch", B, cmd_hist, depth, period, n_updates, cmd_delay, meas_delay, max_cmd_delay, max_meas_delay);
     if (rc != KMPC_OK) return rc;
-    const auto pos = [](double a) { return a > 0.0 && a <= 1.7976931348623157e308; };   // finite and > 0
     if (!pos(L_a) || !pos(L_b)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_predict_ahead_batch: L_a=%g, L_b=%g must be finite and > 0", L_a, L_b);
     if (B > 0 && (!z || !z_out)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_predict_ahead_batch: null z or z_out");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_predict_ahead_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_predict_ahead(B, (const double *)z, (const double *)cmd_hist, depth, (long long)period, n_updates, cmd_delay, meas_delay,
-                                                   max_cmd_delay, max_meas_delay, L_a, L_b, (double *)z_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_predict_ahead_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_predict_ahead_batch", device, [&] {
+        return kmpc_launch_predict_ahead(B, (const double *)z, (const double *)cmd_hist, depth, (long long)period, n_updates, cmd_delay, meas_delay, max_cmd_delay,
+                                         max_meas_delay, L_a, L_b, (double *)z_out, (hipStream_t)stream);
+    });
 }
 
 // ---- state estimator (kmpc_estimator.hip) --------------------------------------------------------------------------
@@ -1060,17 +1054,15 @@ extern "C" int32_t kmpc_estimate_batch(int32_t device, int32_t B, void *rec, con
                                        double dt, double L_a, double L_b, double gate, void *est_out, void *innov_out, int32_t *flags_out,
                                        void *stream)
 {
-    const auto pos = [](double a) { return a > 0.0 && a <= 1.7976931348623157e308; };   // finite and > 0
     if (B < 0 || u_stride < 2 || !pos(dt) || !pos(L_a) || !pos(L_b) || !(gate == 0.0 || pos(gate)))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_estimate_batch: bad argument (B=%d, u_stride=%d, dt=%g, L_a=%g, L_b=%g, gate=%g)", B, u_stride, dt, L_a,
                     L_b, gate);
     if (B > 0 && (!rec || !z || !u || !params || !est_out)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_estimate_batch: null required buffer");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_estimate_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_estimate(B, (double *)rec, (const double *)z, (const double *)u, u_stride, (const double *)params, dt, L_a, L_b,
-                                              gate, (double *)est_out, (double *)innov_out, flags_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_estimate_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_estimate_batch", device, [&] {
+        return kmpc_launch_estimate(B, (double *)rec, (const double *)z, (const double *)u, u_stride, (const double *)params, dt, L_a, L_b, gate, (double *)est_out,
+                                    (double *)innov_out, flags_out, (hipStream_t)stream);
+    });
 }
 
 // ---- disturbance observer and command offset (kmpc_observer.hip) ---------------------------------------------------
@@ -1078,33 +1070,27 @@ extern "C" int32_t kmpc_observe_batch(int32_t device, int32_t B, void *rec, cons
                                       double dt, double L_a, double L_b, double gate, double v_min, double psi_cap, void *est_out, void *dist_out,
                                       void *innov_out, int32_t *flags_out, void *stream)
 {
-    const auto pos = [](double a) { return a > 0.0 && a <= 1.7976931348623157e308; };   // finite and > 0
-    const auto nonneg = [](double a) { return a >= 0.0 && a <= 1.7976931348623157e308; };   // finite and >= 0
     if (B < 0 || u_stride < 2 || !pos(dt) || !pos(L_a) || !pos(L_b) || !nonneg(gate) || !nonneg(v_min) || !nonneg(psi_cap))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_observe_batch: bad argument (B=%d, u_stride=%d, dt=%g, L_a=%g, L_b=%g, gate=%g, v_min=%g, psi_cap=%g)", B,
                     u_stride, dt, L_a, L_b, gate, v_min, psi_cap);
     if (B > 0 && (!rec || !z || !u || !params || !est_out)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_observe_batch: null required buffer");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_observe_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_observe(B, (double *)rec, (const double *)z, (const double *)u, u_stride, (const double *)params, dt, L_a, L_b,
-                                             gate, v_min, psi_cap, (double *)est_out, (double *)dist_out, (double *)innov_out, flags_out,
-                                             (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_observe_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_observe_batch", device, [&] {
+        return kmpc_launch_observe(B, (double *)rec, (const double *)z, (const double *)u, u_stride, (const double *)params, dt, L_a, L_b, gate, v_min, psi_cap,
+                                   (double *)est_out, (double *)dist_out, (double *)innov_out, flags_out, (hipStream_t)stream);
+    });
 }
 
 extern "C" int32_t kmpc_cmd_offset_batch(int32_t device, int32_t B, const void *rec, const uint8_t *stop_latch, double acc_cap, double df_cap,
                                          void *cmd, void *stream)
 {
-    const auto nonneg = [](double a) { return a >= 0.0 && a <= 1.7976931348623157e308; };   // finite and >= 0
     if (B < 0 || !nonneg(acc_cap) || !nonneg(df_cap))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_cmd_offset_batch: bad argument (B=%d, acc_cap=%g, df_cap=%g)", B, acc_cap, df_cap);
     if (B > 0 && (!rec || !cmd)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_cmd_offset_batch: null required buffer");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_cmd_offset_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_cmd_offset(B, (const double *)rec, stop_latch, acc_cap, df_cap, (double *)cmd, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_cmd_offset_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_cmd_offset_batch", device, [&] {
+        return kmpc_launch_cmd_offset(B, (const double *)rec, stop_latch, acc_cap, df_cap, (double *)cmd, (hipStream_t)stream);
+    });
 }
 
 // ---- prediction ahead under estimated disturbances (kmpc_predict_dist.hip) -------------------------------------------
@@ -1116,29 +1102,24 @@ extern "C" int32_t kmpc_predict_ahead_dist_batch(int32_t device, int32_t B, cons
     const int32_t rc = latency_args("kmpc_predict_ahead_dist_batch", B, cmd_hist, depth, period, n_updates, cmd_delay, meas_delay, max_cmd_delay,
                                     max_meas_delay);
     if (rc != KMPC_OK) return rc;
-    const auto pos = [](double a) { return a > 0.0 && a <= 1.7976931348623157e308; };   // finite and > 0
-    const auto nonneg = [](double a) { return a >= 0.0 && a <= 1.7976931348623157e308; };   // finite and >= 0
     if (!pos(L_a) || !pos(L_b) || !nonneg(psi_cap))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_predict_ahead_dist_batch: L_a=%g, L_b=%g must be finite and > 0, psi_cap=%g finite and >= 0", L_a, L_b,
                     psi_cap);
     if (B > 0 && (!rec || !est || !z_out)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_predict_ahead_dist_batch: null rec, est or z_out");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_predict_ahead_dist_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_predict_ahead_dist(B, (const double *)rec, (const double *)est, (const double *)cmd_hist, depth, (long long)period,
-                                                        n_updates, cmd_delay, meas_delay, max_cmd_delay, max_meas_delay, L_a, L_b, psi_cap,
-                                                        (double *)z_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_predict_ahead_dist_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_predict_ahead_dist_batch", device, [&] {
+        return kmpc_launch_predict_ahead_dist(B, (const double *)rec, (const double *)est, (const double *)cmd_hist, depth, (long long)period, n_updates, cmd_delay,
+                                              meas_delay, max_cmd_delay, max_meas_delay, L_a, L_b, psi_cap, (double *)z_out, (hipStream_t)stream);
+    });
 }
 
 extern "C" int32_t kmpc_command_batch(int32_t device, int32_t B, const void *u0, const int32_t *stop, uint8_t *stop_latch, void *u_prev, void *cmd, void *stream)
 {
     if (B < 0 || (B > 0 && (!u0 || !stop || !stop_latch || !u_prev || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_command_batch: bad argument (B=%d)", B);
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_command_batch: hipSetDevice(%d) failed", device);
-    const hipError_t e = kmpc_launch_command(B, (const double *)u0, stop, stop_latch, (double *)u_prev, (double *)cmd, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_command_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_command_batch", device, [&] {
+        return kmpc_launch_command(B, (const double *)u0, stop, stop_latch, (double *)u_prev, (double *)cmd, (hipStream_t)stream);
+    });
 }
 
 // ---- Frenet reference from waypoints (kmpc_frenet_ref.hip) ----------------------------------------------------------
@@ -1149,10 +1130,7 @@ extern "C" int32_t kmpc_frenet_reference_batch(int32_t device, int32_t B, int32_
     if (B > 0 && (!pose || !ref || !k_poly || !psi_start || !fit_status)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_frenet_reference_batch: null required buffer");
     if (z0 && !v) return fail(nullptr, KMPC_ERR_ARG, "kmpc_frenet_reference_batch: z0 needs v");
     if (B == 0) return KMPC_OK;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_frenet_reference_batch: hipSetDevice(%d) failed", device);
     FR f;
     f.B = B; f.H = horizon; f.pose = pose; f.ref = ref; f.v = v; f.k_poly = k_poly; f.psi = psi_start; f.z0 = z0; f.status = fit_status;
-    const hipError_t e = kmpc_launch_frenet_ref(f, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, KMPC_ERR_HIP, "kmpc_frenet_reference_batch: %s", hipGetErrorString(e));
-    return KMPC_OK;
+    return on_device("kmpc_frenet_reference_batch", device, [&] { return kmpc_launch_frenet_ref(f, (hipStream_t)stream); });
 }

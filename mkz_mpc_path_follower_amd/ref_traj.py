@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._stage import default_row, device_of, host_rows, is_buffer, ptr, rows_of, stream, table_rows
 
 LAT0, LON0, YAW0 = 37.917929, -122.331798, 0.0  # launch/path_follow.launch:19-21
 
@@ -72,7 +73,7 @@ def _track_score(lib, entry, handle, device, B_fixed, path_id, state, score, sta
     def buf(t, shape, dtypes, name):
         if t is None:
             return None
-        if not (type(t) is torch.Tensor and t.dtype in dtypes and tuple(t.shape) == shape and t.is_contiguous() and t.device == device):
+        if not is_buffer(t, dtypes, shape, device):
             raise ValueError("%s: expected a contiguous %s tensor %s on %s" % (name, dtypes[0], shape, device))
         return t
     status, iters = buf(status, (B,), (torch.int32,), "status"), buf(iters, (B,), (torch.int32,), "iters")
@@ -83,10 +84,8 @@ def _track_score(lib, entry, handle, device, B_fixed, path_id, state, score, sta
     for k, shape, dt in (("err", (B, 4), torch.float64), ("seg", (B,), torch.int32), ("closest", (B,), torch.int32)):
         if buf(o.get(k), shape, (dt,), k) is None:
             o[k] = torch.empty(shape, dtype=dt, device=device)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    args = (handle, B, p(st), int(st.stride(0)) if B else 3) + (() if path_id is None else (p(path_id),)) + \
-        (float(settle_tol), p(status), p(iters), p(cmd), p(stop_latch), p(o["err"]), p(o["seg"]), p(o["closest"]), p(score), stream)
+    args = (handle, B, ptr(st), int(st.stride(0)) if B else 3) + (() if path_id is None else (ptr(path_id),)) + \
+        (float(settle_tol), ptr(status), ptr(iters), ptr(cmd), ptr(stop_latch), ptr(o["err"]), ptr(o["seg"]), ptr(o["closest"]), ptr(score), stream(device))
     _lib.check(entry(*args))
     return o
 
@@ -140,10 +139,8 @@ class GPSRefTrajectory:
         ref = torch.empty((B, self.traj_horizon + 1, 3), dtype=torch.float64, device=self.device)
         stop = torch.empty((B,), dtype=torch.int32, device=self.device)
         closest = torch.empty((B,), dtype=torch.int32, device=self.device) if want_closest else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.kmpc_waypoints_batch(self._h, B, self.traj_horizon, self.traj_dt, p(pose), p(vt), p(ref), p(stop),
-                                            p(closest), stream)
+        rc = self._lib.kmpc_waypoints_batch(self._h, B, self.traj_horizon, self.traj_dt, ptr(pose), ptr(vt), ptr(ref), ptr(stop), ptr(closest),
+                                            stream(self.device))
         if rc != 0:
             raise _lib.KmpcError(self._lib.kmpc_path_last_error(self._h).decode())
         return (ref, stop, closest) if want_closest else (ref, stop)
@@ -228,18 +225,16 @@ class FleetRefTrajectory:
         if tm is not None:
             if vt is None:
                 raise ValueError("a fleet with per-vehicle modes needs v_target (it is not read for the vehicles in time mode)")
-            if not (tm.dtype == torch.uint8 and tuple(tm.shape) == (B,) and tm.is_contiguous() and tm.device == self.device):
+            if not is_buffer(tm, torch.uint8, (B,), self.device):
                 raise ValueError("time_mode must stay a contiguous uint8 tensor [%d] on %s (write into it in place)" % (B, self.device))
         pid = self.path_id   # a plain attribute: what reaches the kernel is a raw pointer
-        if not (pid.dtype == torch.int32 and tuple(pid.shape) == (B,) and pid.is_contiguous() and pid.device == self.device):
+        if not is_buffer(pid, torch.int32, (B,), self.device):
             raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, self.device))
         ref = torch.empty((B, self.traj_horizon + 1, 3), dtype=torch.float64, device=self.device)
         stop = torch.empty((B,), dtype=torch.int32, device=self.device)
         closest = torch.empty((B,), dtype=torch.int32, device=self.device) if want_closest else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.kmpc_waypoints_fleet(self._h, B, self.traj_horizon, self.traj_dt, p(pose), p(pid), p(tm), p(vt), p(ref), p(stop),
-                                            p(closest), stream)
+        rc = self._lib.kmpc_waypoints_fleet(self._h, B, self.traj_horizon, self.traj_dt, ptr(pose), ptr(pid), ptr(tm), ptr(vt), ptr(ref), ptr(stop),
+                                            ptr(closest), stream(self.device))
         if rc != 0:
             raise _lib.KmpcError(self._lib.kmpc_pathset_last_error(self._h).decode())
         return (ref, stop, closest) if want_closest else (ref, stop)
@@ -249,7 +244,7 @@ class FleetRefTrajectory:
         path_id is outside the set, or whose X, Y or psi is not finite, is refused: err row 0, seg = closest = -1, only its refused count moves."""
         pid = self.path_id
         B = pid.shape[0]
-        if not (pid.dtype == torch.int32 and pid.dim() == 1 and pid.is_contiguous() and pid.device == self.device):
+        if not is_buffer(pid, torch.int32, (B,), self.device):
             raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, self.device))
         return _track_score(self._lib, self._lib.kmpc_track_score_fleet, self._h, self.device, B, pid, state, score, status, iters, cmd,
                             stop_latch, settle_tol, out)
@@ -261,37 +256,27 @@ PLAN_FIELDS = ("a_lat", "a_brake", "v_floor", "end_stop")   # KMPC_PLAN_* words 
 
 def speed_plan_default():
     """the default plan row (2.0, 0.7, 1.0, 0, 0, 0, 0, 0) as a numpy row [8], from kmpc_speed_plan_default"""
-    row = np.zeros(PLAN_WORDS)
-    _lib.check(_lib.load().kmpc_speed_plan_default(row.ctypes.data_as(C.POINTER(C.c_double)), 1))
-    return row
+    return default_row("kmpc_speed_plan_default", PLAN_WORDS)
 
 
 def check_speed_plan_rows(rows):
     """[B,8] host rows -> ValueError unless a_lat > 0 (+inf: no cornering limit), a_brake > 0 and finite, v_floor >= 0 and finite and end_stop is
     not NaN.  The kernel refuses such a vehicle (v_plan 0) on its own; this says so where the rows are written."""
-    rows = np.asarray(rows, dtype=np.float64)
+    rows = host_rows(rows)
     if rows.ndim != 2 or rows.shape[1] != PLAN_WORDS:
         raise ValueError("speed plan rows: [B,8] (%s, four unused words), got %s" % (", ".join(PLAN_FIELDS), rows.shape))
     with np.errstate(invalid="ignore"):
         ok = (rows[:, 0] > 0.0) & (rows[:, 1] > 0.0) & np.isfinite(rows[:, 1]) & (rows[:, 2] >= 0.0) & np.isfinite(rows[:, 2]) & ~np.isnan(rows[:, 3])
     if not ok.all():
         raise ValueError("speed plan rows: a_lat > 0 (+inf: no limit), a_brake > 0 and finite, v_floor >= 0 and finite, end_stop not NaN "
-                         "(vehicle(s) %s)" % np.flatnonzero(~ok)[:8].tolist())
+                         "(vehicle(s) %s)" % rows_of(~ok))
     return rows
 
 
 def speed_plan_params(B, device=0, **overrides):
     """[B,8] float64 plan rows on `device`: the default row, with each override (`a_lat=`, `a_brake=`, `v_floor=`, `end_stop=`) a scalar or one
     value per vehicle.  Validated on the host (check_speed_plan_rows) before anything reaches the device."""
-    rows = np.tile(speed_plan_default(), (int(B), 1))
-    for k, v in overrides.items():
-        if k not in PLAN_FIELDS:
-            raise ValueError("speed_plan_params: unknown parameter %r (one of %s)" % (k, ", ".join(PLAN_FIELDS)))
-        v = np.asarray(v, dtype=np.float64)
-        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
-            raise ValueError("speed_plan_params: %s is a scalar or one value per vehicle [%d], got %s" % (k, B, v.shape))
-        rows[:, PLAN_FIELDS.index(k)] = v
-    return torch.as_tensor(check_speed_plan_rows(rows)).to(torch.device("cuda", device) if isinstance(device, int) else torch.device(device))
+    return torch.as_tensor(check_speed_plan_rows(table_rows("speed_plan_params", PLAN_FIELDS, speed_plan_default(), B, overrides))).to(device_of(device))
 
 
 class SpeedPlanner:
@@ -315,8 +300,7 @@ class SpeedPlanner:
         self.B = int(fleet.path_id.shape[0])
         self._lib = fleet._lib
         self.kappa = torch.empty((sum(len(tr) for tr in fleet.trajectories),), dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_pathset_curvature(fleet._h, window, C.c_void_p(self.kappa.data_ptr()), stream))
+        _lib.check(self._lib.kmpc_pathset_curvature(fleet._h, window, ptr(self.kappa), stream(self.device)))
         self.rows = speed_plan_params(self.B, self.device) if rows is None else rows
         self._check_rows()
         if profile is not None:
@@ -327,9 +311,7 @@ class SpeedPlanner:
         self.info = self.closest = None   # [B,4] (w, s_jb - s_i, kappa_jb, sqrt(lim_i)) and [B] of the last plan(want_info=True)
 
     def _check_rows(self):
-        r = self.rows
-        if not (type(r) is torch.Tensor and r.dtype == torch.float64 and tuple(r.shape) == (self.B, PLAN_WORDS) and r.is_contiguous()
-                and r.device == self.device):
+        if not is_buffer(self.rows, torch.float64, (self.B, PLAN_WORDS), self.device):
             raise ValueError("rows must be a contiguous float64 tensor [%d,8] on %s (speed_plan_params; write into it in place)" % (self.B, self.device))
 
     def plan(self, state, v_cap, out=None, want_info=False):
@@ -347,22 +329,20 @@ class SpeedPlanner:
             raise ValueError("v_cap: expected [%d], got %s" % (B, tuple(vc.shape)))
         self._check_rows()
         pid = self.fleet.path_id
-        if not (pid.dtype == torch.int32 and tuple(pid.shape) == (B,) and pid.is_contiguous() and pid.device == dev):
+        if not is_buffer(pid, torch.int32, (B,), dev):
             raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
         if out is None:
             out = torch.empty((B,), dtype=torch.float64, device=dev)
-        elif not (type(out) is torch.Tensor and out.dtype == torch.float64 and tuple(out.shape) == (B,) and out.is_contiguous() and out.device == dev):
+        elif not is_buffer(out, torch.float64, (B,), dev):
             raise ValueError("out: expected a contiguous float64 tensor [%d] on %s" % (B, dev))
         if want_info and self.info is None:
             self.info = torch.empty((B, 4), dtype=torch.float64, device=dev)
             self.closest = torch.empty((B,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        tail = (p(st), int(st.stride(0)) if B else 2, p(pid), p(vc), p(self.rows), p(out), p(self.info) if want_info else None,
-                p(self.closest) if want_info else None, stream)
+        tail = (ptr(st), int(st.stride(0)) if B else 2, ptr(pid), ptr(vc), ptr(self.rows), ptr(out), ptr(self.info) if want_info else None,
+                ptr(self.closest) if want_info else None, stream(dev))
         if self.profile is not None:
             self.profile._own()
-            _lib.check(self._lib.kmpc_speed_plan_fleet_profile(self.fleet._h, B, p(self.kappa), p(self.profile.table), *tail))
+            _lib.check(self._lib.kmpc_speed_plan_fleet_profile(self.fleet._h, B, ptr(self.kappa), ptr(self.profile.table), *tail))
         else:
-            _lib.check(self._lib.kmpc_speed_plan_fleet(self.fleet._h, B, p(self.kappa), *tail))
+            _lib.check(self._lib.kmpc_speed_plan_fleet(self.fleet._h, B, ptr(self.kappa), *tail))
         return out

@@ -34,12 +34,11 @@ Coloured noise and gusts: `Wander(B, wander_params(B, sigma=..., tau=..., walk=.
 period, adds them to a sensor row's biases and a road row's a_long, a_lat, df_offset (kmpc_wander_batch), on the device.  The closed loops take it
 as `wander=`; the sense and plant kernels read the composed rows as they read the caller's before.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._stage import default_row, device_of, fill_blocks, host_rows, is_buffer, ptr, rows_of, stream, table_rows
 from .messages import StateEst
 
 X0, Y0, PSI0 = -300.0, -450.0, 1.0  # vehicle_simulator.py:28-30 (rosparam defaults)
@@ -58,10 +57,6 @@ LLC_RECORD_FIELDS = ("int", "lpf", "ready", "v_last", "th_cmd", "br_cmd", "wheel
 EST_SKIP_X, EST_SKIP_Y, EST_SKIP_PSI, EST_SKIP_V, EST_INIT, EST_RESET = 1, 2, 4, 8, 16, 32   # KMPC_EST_FLAG_*
 
 
-def _device(device):
-    return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-
-
 def _int_per_vehicle(name, v, B, lo, hi=None):
     """a scalar or one integer per vehicle within [lo, hi] -> int32 [B] on the host (ValueError otherwise)"""
     d = torch.as_tensor(v).detach().cpu()
@@ -75,79 +70,58 @@ def _int_per_vehicle(name, v, B, lo, hi=None):
 
 def plant_default():
     """the reference's constants (vehicle_simulator.py:61-67, :112-113) as a numpy row [8], from kmpc_plant_default: they live in the library"""
-    row = np.zeros(8)
-    _lib.check(_lib.load().kmpc_plant_default(row.ctypes.data_as(C.POINTER(C.c_double))))
-    return row
+    return default_row("kmpc_plant_default", 8)
 
 
 def check_plant_rows(rows):
     """[B,8] host rows -> ValueError unless all are finite, lf, lr, m, Iz, C_alpha_f, C_alpha_r > 0 and the lag gains >= 0 (the kernel cannot
     refuse a row: a bad m or Iz poisons that vehicle's state)"""
-    rows = np.asarray(rows, dtype=np.float64)
+    rows = host_rows(rows)
     if rows.ndim != 2 or rows.shape[1] != 8:
         raise ValueError("plant rows: [B,8] (%s), got %s" % (", ".join(PLANT_FIELDS), rows.shape))
     if not np.isfinite(rows).all():
-        raise ValueError("plant rows: non-finite value in vehicle(s) %s" % np.flatnonzero(~np.isfinite(rows).all(1))[:8].tolist())
+        raise ValueError("plant rows: non-finite value in vehicle(s) %s" % rows_of(~np.isfinite(rows).all(1)))
     if not (rows[:, 0:6] > 0.0).all():
-        raise ValueError("plant rows: lf, lr, m, Iz, C_alpha_f, C_alpha_r must be > 0 (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 0:6] > 0.0).all(1))[:8].tolist())
+        raise ValueError("plant rows: lf, lr, m, Iz, C_alpha_f, C_alpha_r must be > 0 (vehicle(s) %s)" % rows_of(~(rows[:, 0:6] > 0.0).all(1)))
     if not (rows[:, 6:8] >= 0.0).all():
-        raise ValueError("plant rows: the lag gains k_acc, k_df must be >= 0 (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 6:8] >= 0.0).all(1))[:8].tolist())
+        raise ValueError("plant rows: the lag gains k_acc, k_df must be >= 0 (vehicle(s) %s)" % rows_of(~(rows[:, 6:8] >= 0.0).all(1)))
     return rows
 
 
 def plant_params(B, device=0, **overrides):
     """[B,8] float64 plant rows on `device`: the reference's constants, with each override (`m=`, `C_alpha_f=`, ... : PLANT_FIELDS) a scalar or
     one value per vehicle.  Validated on the host (check_plant_rows) before anything reaches the device."""
-    rows = np.tile(plant_default(), (int(B), 1))
-    for k, v in overrides.items():
-        if k not in PLANT_FIELDS:
-            raise ValueError("plant_params: unknown parameter %r (one of %s)" % (k, ", ".join(PLANT_FIELDS)))
-        v = np.asarray(v, dtype=np.float64)
-        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
-            raise ValueError("plant_params: %s is a scalar or one value per vehicle [%d], got %s" % (k, B, v.shape))
-        rows[:, PLANT_FIELDS.index(k)] = v
-    return torch.as_tensor(check_plant_rows(rows)).to(_device(device))
+    return torch.as_tensor(check_plant_rows(table_rows("plant_params", PLANT_FIELDS, plant_default(), B, overrides))).to(device_of(device))
 
 
 def road_default():
     """the neutral road row (inf, inf, 0, 0, 0, 1, 0, 0) as a numpy row [8], from kmpc_road_default"""
-    row = np.zeros(8)
-    _lib.check(_lib.load().kmpc_road_default(row.ctypes.data_as(C.POINTER(C.c_double))))
-    return row
+    return default_row("kmpc_road_default", 8)
 
 
 def check_road_rows(rows):
     """[B,8] host rows -> ValueError unless no word is NaN, mu_f, mu_r > 0 (+inf: no limit), every other word is finite and acc_gain > 0 (the
     kernel cannot refuse a row: a bad one poisons that vehicle)"""
-    rows = np.asarray(rows, dtype=np.float64)
+    rows = host_rows(rows)
     if rows.ndim != 2 or rows.shape[1] != 8:
         raise ValueError("road rows: [B,8] (%s, two unused words), got %s" % (", ".join(ROAD_FIELDS), rows.shape))
     if np.isnan(rows).any():
-        raise ValueError("road rows: NaN in vehicle(s) %s" % np.flatnonzero(np.isnan(rows).any(1))[:8].tolist())
+        raise ValueError("road rows: NaN in vehicle(s) %s" % rows_of(np.isnan(rows).any(1)))
     if not (rows[:, 0:2] > 0.0).all():
-        raise ValueError("road rows: mu_f, mu_r must be > 0 (+inf: no limit) (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 0:2] > 0.0).all(1))[:8].tolist())
+        raise ValueError("road rows: mu_f, mu_r must be > 0 (+inf: no limit) (vehicle(s) %s)" % rows_of(~(rows[:, 0:2] > 0.0).all(1)))
     if not np.isfinite(rows[:, 2:8]).all():
-        raise ValueError("road rows: only mu_f, mu_r may be infinite (vehicle(s) %s)" % np.flatnonzero(~np.isfinite(rows[:, 2:8]).all(1))[:8].tolist())
+        raise ValueError("road rows: only mu_f, mu_r may be infinite (vehicle(s) %s)" % rows_of(~np.isfinite(rows[:, 2:8]).all(1)))
     if not (rows[:, 5] > 0.0).all():
-        raise ValueError("road rows: acc_gain must be > 0 (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 5] > 0.0))[:8].tolist())
+        raise ValueError("road rows: acc_gain must be > 0 (vehicle(s) %s)" % rows_of(~(rows[:, 5] > 0.0)))
     return rows
 
 
 def road_params(B, device=0, **overrides):
     """[B,8] float64 road rows on `device`: the neutral row, with each override (`mu=` for both axles, `mu_f=`, `mu_r=`, `a_long=`, `a_lat=`,
     `df_offset=`, `acc_gain=`) a scalar or one value per vehicle.  Validated on the host (check_road_rows) before anything reaches the device."""
-    rows = np.tile(road_default(), (int(B), 1))
-    for k, v in overrides.items():
-        if k != "mu" and k not in ROAD_FIELDS:
-            raise ValueError("road_params: unknown parameter %r (mu or one of %s)" % (k, ", ".join(ROAD_FIELDS)))
-        if k == "mu" and ("mu_f" in overrides or "mu_r" in overrides):
-            raise ValueError("road_params: mu= sets both axles; give mu_f= and mu_r= instead of combining them with it")
-        v = np.asarray(v, dtype=np.float64)
-        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
-            raise ValueError("road_params: %s is a scalar or one value per vehicle [%d], got %s" % (k, B, v.shape))
-        for w in ((0, 1) if k == "mu" else (ROAD_FIELDS.index(k),)):
-            rows[:, w] = v
-    return torch.as_tensor(check_road_rows(rows)).to(_device(device))
+    rows = table_rows("road_params", ROAD_FIELDS, road_default(), B, overrides, groups={"mu": (0, 1)},
+                      conflict="%s= sets both axles; give mu_f= and mu_r= instead of combining them with it")
+    return torch.as_tensor(check_road_rows(rows)).to(device_of(device))
 
 
 FAULT_WORDS = 16
@@ -160,18 +134,15 @@ FAULT_SILENT_GPS, FAULT_SILENT_IMU, FAULT_SILENT_SPD, FAULT_OUTLIER, FAULT_BLIND
 
 def fault_default():
     """the neutral fault row (0,0,0, 1,1,1, 0,0,0, 0,0,0, 0, 0, inf, 0) as a numpy row [16], from kmpc_sense_faults_default"""
-    row = np.zeros(FAULT_WORDS)
-    _lib.check(_lib.load().kmpc_sense_faults_default(row.ctypes.data_as(C.POINTER(C.c_double)), 1))
-    return row
+    return default_row("kmpc_sense_faults_default", FAULT_WORDS)
 
 
 def check_fault_rows(rows):
     """[B,16] host rows -> ValueError unless no word is NaN, the seven probabilities lie in [0, 1], the windows' starts and lengths are non-negative
     whole numbers, outlier_sigma is finite and >= 0, and max_age >= 0 (+inf: never blind) (the kernel cannot refuse a row)"""
-    rows = np.asarray(rows, dtype=np.float64)
+    rows = host_rows(rows)
     if rows.ndim != 2 or rows.shape[1] != FAULT_WORDS:
         raise ValueError("fault rows: [B,16] (%s, one unused word), got %s" % (", ".join(FAULT_FIELDS), rows.shape))
-    rows_of = lambda bad: np.flatnonzero(bad)[:8].tolist()
     if np.isnan(rows).any():
         raise ValueError("fault rows: NaN in vehicle(s) %s" % rows_of(np.isnan(rows).any(1)))
     prob = rows[:, [0, 1, 2, 3, 4, 5, 12]]
@@ -195,19 +166,10 @@ def check_fault_rows(rows):
 def fault_params(B, device=0, **overrides):
     """[B,16] float64 fault rows on `device`: the neutral row, with each override (FAULT_FIELDS; also `p_lose=`, `p_regain=`, `win_from=`, `win_len=`
     for all three sources) a scalar or one value per vehicle.  Validated on the host (check_fault_rows) before anything reaches the device."""
-    rows = np.tile(fault_default(), (int(B), 1))
-    groups = {"p_lose": 0, "p_regain": 3, "win_from": 6, "win_len": 9}
-    for k, v in overrides.items():
-        if k not in groups and k not in FAULT_FIELDS:
-            raise ValueError("fault_params: unknown parameter %r (%s or one of %s)" % (k, ", ".join(groups), ", ".join(FAULT_FIELDS)))
-        if k in groups and any((k + s) in overrides for s in ("_gps", "_imu", "_spd")):
-            raise ValueError("fault_params: %s= sets all three sources; give the per-source words instead of combining them with it" % k)
-        v = np.asarray(v, dtype=np.float64)
-        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
-            raise ValueError("fault_params: %s is a scalar or one value per vehicle [%d], got %s" % (k, B, v.shape))
-        for w in (range(groups[k], groups[k] + 3) if k in groups else (FAULT_FIELDS.index(k),)):
-            rows[:, w] = v
-    return torch.as_tensor(check_fault_rows(rows)).to(_device(device))
+    groups = {"p_lose": (0, 1, 2), "p_regain": (3, 4, 5), "win_from": (6, 7, 8), "win_len": (9, 10, 11)}   # the words of the gps, imu, spd sources
+    rows = table_rows("fault_params", FAULT_FIELDS, fault_default(), B, overrides, groups=groups,
+                      conflict="%s= sets all three sources; give the per-source words instead of combining them with it")
+    return torch.as_tensor(check_fault_rows(rows)).to(device_of(device))
 
 
 WANDER_CHANNELS, WANDER_WORDS, WANDER_RECORD_WORDS = 8, 24, 16
@@ -218,18 +180,15 @@ WANDER_RECORD_FIELDS = tuple("x_" + c for c in WANDER_CHANNEL_NAMES) + ("count",
 
 def wander_default():
     """the neutral wander row (24 zeros: every channel off) as a numpy row [24], from kmpc_wander_default"""
-    row = np.ones(WANDER_WORDS)
-    _lib.check(_lib.load().kmpc_wander_default(row.ctypes.data_as(C.POINTER(C.c_double)), 1))
-    return row
+    return default_row("kmpc_wander_default", WANDER_WORDS)
 
 
 def check_wander_rows(rows):
     """[B,24] host rows -> ValueError unless every word is finite, S0 >= 0, Q >= 0 and A in [0, 1] (the kernel cannot refuse a row: a bad one
     poisons that vehicle's processes)"""
-    rows = np.asarray(rows, dtype=np.float64)
+    rows = host_rows(rows)
     if rows.ndim != 2 or rows.shape[1] != WANDER_WORDS:
         raise ValueError("wander rows: [B,24] (S0, A, Q of the channels %s), got %s" % (", ".join(WANDER_CHANNEL_NAMES), rows.shape))
-    rows_of = lambda bad: np.flatnonzero(bad)[:8].tolist()
     if not np.isfinite(rows).all():
         raise ValueError("wander rows: non-finite value in vehicle(s) %s" % rows_of(~np.isfinite(rows).all(1)))
     s0, a, q = rows[:, 0:8], rows[:, 8:16], rows[:, 16:24]
@@ -271,7 +230,7 @@ def wander_rows(B, dt=0.1, sigma=0.0, tau=0.0, walk=0.0):
 
 def wander_params(B, device=0, dt=0.1, sigma=0.0, tau=0.0, walk=0.0):
     """wander_rows(B, dt, sigma, tau, walk) as a float64 tensor [B,24] on `device`"""
-    return torch.as_tensor(wander_rows(B, dt=dt, sigma=sigma, tau=tau, walk=walk)).to(_device(device))
+    return torch.as_tensor(wander_rows(B, dt=dt, sigma=sigma, tau=tau, walk=walk)).to(device_of(device))
 
 
 class Wander:
@@ -288,13 +247,12 @@ class Wander:
         self.B, self.seed, self.id_base = int(B), int(seed), int(id_base)
         if not (0 <= self.seed < 2 ** 64 and 0 <= self.id_base and self.id_base + self.B < 2 ** 63):
             raise ValueError("Wander: seed in [0, 2^64), id_base >= 0")
-        rows = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else rows
         rows = check_wander_rows(rows)
         if rows.shape[0] != self.B:
             raise ValueError("Wander: rows is [%d,24], got %s" % (self.B, rows.shape))
         on = (rows[:, 0:8] != 0.0) | (rows[:, 16:24] != 0.0)
         self.sensor_active, self.road_active = bool(on[:, 0:4].any()), bool(on[:, 4:7].any())
-        self.device = _device(device)
+        self.device = device_of(device)
         self.params = torch.as_tensor(np.ascontiguousarray(rows)).to(self.device)
         self.rec = torch.zeros((self.B, WANDER_RECORD_WORDS), dtype=torch.float64, device=self.device)
 
@@ -311,14 +269,12 @@ class Wander:
         own = ((self.params, WANDER_WORDS, "params"), (self.rec, WANDER_RECORD_WORDS, "rec"))
         for t, w, name in own + tuple((t, 8, name) for t, name in ((sensor_base, "sensor_base"), (sensor_out, "sensor_out"), (road_base, "road_base"),
                                                                    (road_out, "road_out")) if t is not None):
-            if not (type(t) is torch.Tensor and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, torch.float64, (self.B, w), self.device):
                 raise ValueError("%s: a contiguous float64 tensor [%d,%d] on %s" % (name, self.B, w, self.device))
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         if self.device.type != "cuda":
             raise RuntimeError("Wander.step runs on an MI355X; no CPU fallback (device %s)" % self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_wander_batch(self.device.index, self.B, p(self.params), p(self.rec), self.seed, int(period), self.id_base,
-                                               p(sensor_base), p(sensor_out), p(road_base), p(road_out), stream))
+        _lib.check(self._lib.kmpc_wander_batch(self.device.index, self.B, ptr(self.params), ptr(self.rec), self.seed, int(period), self.id_base,
+                                               ptr(sensor_base), ptr(sensor_out), ptr(road_base), ptr(road_out), stream(self.device)))
         return self.x
 
     def summary(self):
@@ -337,18 +293,15 @@ PROFILE_FIELDS =("mu_scale", "a_long", "a_lat", "v_limit")   # KMPC_PROFILE_* wo
 
 def road_profile_default():
     """the neutral profile row (1, 0, 0, inf, 0, 0, 0, 0) as a numpy row [8], from kmpc_road_profile_default"""
-    row = np.zeros(PROFILE_WORDS)
-    _lib.check(_lib.load().kmpc_road_profile_default(row.ctypes.data_as(C.POINTER(C.c_double)), 1))
-    return row
+    return default_row("kmpc_road_profile_default", PROFILE_WORDS)
 
 
 def check_road_profile(table):
     """[n,8] host rows -> ValueError unless no word is NaN, mu_scale > 0 and finite, a_long and a_lat finite, v_limit >= 0 (+inf: none) and every
     other word finite (the kernels cannot refuse a row: a bad one reaches the vehicles whose nearest sample holds it)"""
-    table = np.asarray(table, dtype=np.float64)
+    table = host_rows(table)
     if table.ndim != 2 or table.shape[1] != PROFILE_WORDS:
         raise ValueError("road profile: [n,8] (%s, four unused words), got %s" % (", ".join(PROFILE_FIELDS), table.shape))
-    rows_of = lambda bad: np.flatnonzero(bad)[:8].tolist()
     if np.isnan(table).any():
         raise ValueError("road profile: NaN in sample(s) %s" % rows_of(np.isnan(table).any(1)))
     if not ((table[:, 0] > 0.0) & np.isfinite(table[:, 0])).all():
@@ -404,16 +357,14 @@ class RoadProfile:
         self.fleet, self.device, self._lib = fleet, fleet.device, fleet._lib
         self.B = int(fleet.path_id.shape[0])
         self.total = sum(len(tr) for tr in fleet.trajectories)
-        rows = road_profile_table(fleet) if table is None else (table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table)
+        rows = road_profile_table(fleet) if table is None else host_rows(table)
         if np.shape(rows) != (self.total, PROFILE_WORDS):
             raise ValueError("road profile: [%d,8] rows, one per sample of the fleet's paths (road_profile_table), got %s" % (self.total, np.shape(rows)))
         self.table = torch.as_tensor(np.ascontiguousarray(check_road_profile(rows))).to(self.device).contiguous()
         self.closest = None   # [B] of the last apply(want_closest=True)
 
     def _own(self):
-        t = self.table
-        if not (type(t) is torch.Tensor and t.dtype == torch.float64 and tuple(t.shape) == (self.total, PROFILE_WORDS) and t.is_contiguous()
-                and t.device == self.device):
+        if not is_buffer(self.table, torch.float64, (self.total, PROFILE_WORDS), self.device):
             raise ValueError("table must stay a contiguous float64 tensor [%d,8] on %s (write into it with copy_)" % (self.total, self.device))
 
     def apply(self, state, road_base, out, want_closest=False):
@@ -421,94 +372,75 @@ class RoadProfile:
         rows the plant reads this period.  want_closest=True also fills self.closest [B].  Asynchronous on torch's current stream."""
         dev, B = self.device, self.B
         self._own()
-        if not (type(state) is torch.Tensor and state.dtype == torch.float64 and state.device == dev and state.dim() == 2 and state.shape[0] == B
+        if not (isinstance(state, torch.Tensor) and state.dtype == torch.float64 and state.device == dev and state.dim() == 2 and state.shape[0] == B
                 and state.shape[1] >= 2 and (B == 0 or state.stride(1) == 1) and state.stride(0) >= 2):
             raise ValueError("state: a float64 tensor [%d,W] on %s with X, Y in the first two columns" % (B, dev))
         for t, name in ((road_base, "road_base"), (out, "out")):
-            if not (type(t) is torch.Tensor and t.dtype == torch.float64 and tuple(t.shape) == (B, 8) and t.is_contiguous() and t.device == dev):
+            if not is_buffer(t, torch.float64, (B, 8), dev):
                 raise ValueError("%s: a contiguous float64 tensor [%d,8] on %s" % (name, B, dev))
         pid = self.fleet.path_id
-        if not (pid.dtype == torch.int32 and tuple(pid.shape) == (B,) and pid.is_contiguous() and pid.device == dev):
+        if not is_buffer(pid, torch.int32, (B,), dev):
             raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
         if want_closest and self.closest is None:
             self.closest = torch.empty((B,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._lib.kmpc_road_profile_fleet(self.fleet._h, B, p(self.table), p(state), int(state.stride(0)) if B else 2, p(pid), p(road_base),
-                                                     p(out), p(self.closest) if want_closest else None, stream))
+        _lib.check(self._lib.kmpc_road_profile_fleet(self.fleet._h, B, ptr(self.table), ptr(state), int(state.stride(0)) if B else 2, ptr(pid),
+                                                     ptr(road_base), ptr(out), ptr(self.closest) if want_closest else None, stream(dev)))
         return out
-
-
-def _rows_with(name, fields, default, B, overrides):
-    """the default row tiled B times with each override a scalar or one value per vehicle -> [B,8] host rows"""
-    rows = np.tile(default, (int(B), 1))
-    for k, v in overrides.items():
-        if k not in fields:
-            raise ValueError("%s: unknown parameter %r (one of %s)" % (name, k, ", ".join(fields)))
-        v = np.asarray(v, dtype=np.float64)
-        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != int(B)):
-            raise ValueError("%s: %s is a scalar or one value per vehicle [%d], got %s" % (name, k, B, v.shape))
-        rows[:, fields.index(k)] = v
-    return rows
 
 
 def llc_default():
     """the reference node's constants (LowLevelController.cpp:49-72, .h:113-118) as a numpy row [8], from kmpc_llc_default"""
-    row = np.zeros(8)
-    _lib.check(_lib.load().kmpc_llc_default(row.ctypes.data_as(C.POINTER(C.c_double))))
-    return row
+    return default_row("kmpc_llc_default", 8)
 
 
 def check_llc_rows(rows):
     """[B,8] host rows -> ValueError unless all are finite, accel_max, decel_max, steer_ratio, mass, wheel_radius > 0 and kp, ki, brake_deadband
     >= 0 (the kernel cannot refuse a row: a bad one poisons that vehicle)"""
-    rows = np.asarray(rows, dtype=np.float64)
+    rows = host_rows(rows)
     if rows.ndim != 2 or rows.shape[1] != 8:
         raise ValueError("llc rows: [B,8] (%s), got %s" % (", ".join(LLC_FIELDS), rows.shape))
     if not np.isfinite(rows).all():
-        raise ValueError("llc rows: non-finite value in vehicle(s) %s" % np.flatnonzero(~np.isfinite(rows).all(1))[:8].tolist())
+        raise ValueError("llc rows: non-finite value in vehicle(s) %s" % rows_of(~np.isfinite(rows).all(1)))
     pos = rows[:, [2, 3, 4, 5, 7]]
     if not (pos > 0.0).all():
-        raise ValueError("llc rows: accel_max, decel_max, steer_ratio, mass, wheel_radius must be > 0 (vehicle(s) %s)" % np.flatnonzero(~(pos > 0.0).all(1))[:8].tolist())
+        raise ValueError("llc rows: accel_max, decel_max, steer_ratio, mass, wheel_radius must be > 0 (vehicle(s) %s)" % rows_of(~(pos > 0.0).all(1)))
     nonneg = rows[:, [0, 1, 6]]
     if not (nonneg >= 0.0).all():
-        raise ValueError("llc rows: kp, ki, brake_deadband must be >= 0 (vehicle(s) %s)" % np.flatnonzero(~(nonneg >= 0.0).all(1))[:8].tolist())
+        raise ValueError("llc rows: kp, ki, brake_deadband must be >= 0 (vehicle(s) %s)" % rows_of(~(nonneg >= 0.0).all(1)))
     return rows
 
 
 def llc_params(B, device=0, **overrides):
     """[B,8] float64 controller rows on `device`: the reference's constants, with each override (`kp=`, `mass=`, `brake_deadband=`, ... : LLC_FIELDS)
     a scalar or one value per vehicle.  Validated on the host (check_llc_rows) before anything reaches the device."""
-    return torch.as_tensor(check_llc_rows(_rows_with("llc_params", LLC_FIELDS, llc_default(), B, overrides))).to(_device(device))
+    return torch.as_tensor(check_llc_rows(table_rows("llc_params", LLC_FIELDS, llc_default(), B, overrides))).to(device_of(device))
 
 
 def drive_default():
     """the powertrain's default row (6000 N, 120 kW, lags 5 1/s, 0.15 m/s^2, 4e-4 1/m, 14.8, 0.33 m) as a numpy row [8], from kmpc_drive_default"""
-    row = np.zeros(8)
-    _lib.check(_lib.load().kmpc_drive_default(row.ctypes.data_as(C.POINTER(C.c_double))))
-    return row
+    return default_row("kmpc_drive_default", 8)
 
 
 def check_drive_rows(rows):
     """[B,8] host rows -> ValueError unless all are finite, f_peak, p_max, steer_ratio, wheel_radius > 0 and k_th, k_br, c_roll, c_drag >= 0 (the
     kernel cannot refuse a row: a bad one poisons that vehicle)"""
-    rows = np.asarray(rows, dtype=np.float64)
+    rows = host_rows(rows)
     if rows.ndim != 2 or rows.shape[1] != 8:
         raise ValueError("drive rows: [B,8] (%s), got %s" % (", ".join(DRIVE_FIELDS), rows.shape))
     if not np.isfinite(rows).all():
-        raise ValueError("drive rows: non-finite value in vehicle(s) %s" % np.flatnonzero(~np.isfinite(rows).all(1))[:8].tolist())
+        raise ValueError("drive rows: non-finite value in vehicle(s) %s" % rows_of(~np.isfinite(rows).all(1)))
     pos = rows[:, [0, 1, 6, 7]]
     if not (pos > 0.0).all():
-        raise ValueError("drive rows: f_peak, p_max, steer_ratio, wheel_radius must be > 0 (vehicle(s) %s)" % np.flatnonzero(~(pos > 0.0).all(1))[:8].tolist())
+        raise ValueError("drive rows: f_peak, p_max, steer_ratio, wheel_radius must be > 0 (vehicle(s) %s)" % rows_of(~(pos > 0.0).all(1)))
     if not (rows[:, 2:6] >= 0.0).all():
-        raise ValueError("drive rows: k_th, k_br, c_roll, c_drag must be >= 0 (vehicle(s) %s)" % np.flatnonzero(~(rows[:, 2:6] >= 0.0).all(1))[:8].tolist())
+        raise ValueError("drive rows: k_th, k_br, c_roll, c_drag must be >= 0 (vehicle(s) %s)" % rows_of(~(rows[:, 2:6] >= 0.0).all(1)))
     return rows
 
 
 def drive_params(B, device=0, **overrides):
     """[B,8] float64 powertrain rows on `device`: the default row, with each override (`f_peak=`, `c_drag=`, `steer_ratio=`, ... : DRIVE_FIELDS) a
     scalar or one value per vehicle.  Validated on the host (check_drive_rows) before anything reaches the device."""
-    return torch.as_tensor(check_drive_rows(_rows_with("drive_params", DRIVE_FIELDS, drive_default(), B, overrides))).to(_device(device))
+    return torch.as_tensor(check_drive_rows(table_rows("drive_params", DRIVE_FIELDS, drive_default(), B, overrides))).to(device_of(device))
 
 
 class LowLevelController:
@@ -522,12 +454,12 @@ class LowLevelController:
     def __init__(self, B, device=0, v0=None, **overrides):
         self._lib = _lib.load()
         self.B = int(B)
-        rows = check_llc_rows(_rows_with("LowLevelController", LLC_FIELDS, llc_default(), self.B, overrides))
+        rows = check_llc_rows(table_rows("LowLevelController", LLC_FIELDS, llc_default(), self.B, overrides))
         if v0 is not None:
             v0 = np.asarray(v0, dtype=np.float64)
             if v0.shape not in ((), (self.B,)) or not np.isfinite(v0).all():
                 raise ValueError("LowLevelController: v0 is a finite scalar or one speed per vehicle [%d]" % self.B)
-        self.device = _device(device)
+        self.device = device_of(device)
         self.params = torch.as_tensor(rows).to(self.device)
         self.rec = torch.zeros((self.B, 16), dtype=torch.float64, device=self.device)
         self.reset(v0)
@@ -540,7 +472,7 @@ class LowLevelController:
 
     def _own(self):
         for t, w in ((self.params, 8), (self.rec, 16)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, torch.float64, (self.B, w), self.device):
                 raise ValueError("params [B,8] and rec [B,16] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
 
     def step(self, cmd, speed, out=None):
@@ -549,15 +481,14 @@ class LowLevelController:
         self._own()
         ped = out if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
         for t, w in ((cmd, 2), (ped, 4)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, torch.float64, (self.B, w), self.device):
                 raise ValueError("cmd [B,2] and out [B,4] must be contiguous float64 tensors on %s" % self.device)
         if not (isinstance(speed, torch.Tensor) and speed.dtype == torch.float64 and tuple(speed.shape) == (self.B,) and speed.device == self.device
                 and (self.B <= 1 or speed.stride(0) >= 1)):
             raise ValueError("speed: float64 [B] on %s, rows a fixed distance >= 1 apart (a [B] buffer or sim.state[:, 3])" % self.device)
         stride = speed.stride(0) if self.B > 1 else 1
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_llc_step_batch(self.device.index, self.B, C.c_void_p(cmd.data_ptr()), C.c_void_p(speed.data_ptr()), int(stride),
-                                                 C.c_void_p(self.params.data_ptr()), C.c_void_p(self.rec.data_ptr()), C.c_void_p(ped.data_ptr()), stream))
+        _lib.check(self._lib.kmpc_llc_step_batch(self.device.index, self.B, ptr(cmd), ptr(speed), int(stride), ptr(self.params), ptr(self.rec), ptr(ped),
+                                                 stream(self.device)))
         return ped
 
     def summary(self):
@@ -605,7 +536,7 @@ class VehicleSimulator:
         if llc is not None and drive is None:
             raise ValueError("llc= belongs to drive=: the controller acts on the plant only through the powertrain (drive_params)")
         if drive is not None:   # checked before the GPU is touched
-            drive_rows = drive.detach().cpu().numpy() if isinstance(drive, torch.Tensor) else drive
+            drive_rows = host_rows(drive)
             if np.shape(drive_rows) != (int(B), 8):
                 raise ValueError("drive: [%d,8] rows (drive_params), got %s" % (int(B), np.shape(drive_rows)))
             drive_rows = check_drive_rows(drive_rows)
@@ -615,7 +546,7 @@ class VehicleSimulator:
                 road = np.tile(road_default(), (int(B), 1))
         road_rows = None
         if road is not None:   # checked before the GPU is touched, like the depth
-            road_rows = road.detach().cpu().numpy() if isinstance(road, torch.Tensor) else road
+            road_rows = host_rows(road)
             if np.shape(road_rows) != (int(B), 8):
                 raise ValueError("road: [%d,8] rows (road_params), got %s" % (int(B), np.shape(road_rows)))
             road_rows = check_road_rows(road_rows)
@@ -645,7 +576,7 @@ class VehicleSimulator:
             if plant is None:
                 self.plant = plant_params(self.B, self.device)
             else:
-                rows = plant.detach().cpu().numpy() if isinstance(plant, torch.Tensor) else plant
+                rows = host_rows(plant)
                 if np.shape(rows) != (self.B, 8):
                     raise ValueError("plant: [%d,8] rows (plant_params), got %s" % (self.B, np.shape(rows)))
                 self.plant = torch.as_tensor(check_plant_rows(rows)).to(self.device).contiguous()
@@ -683,57 +614,44 @@ class VehicleSimulator:
 
     def _update_vehicle_model(self, n_updates=1):
         """n_updates passes of :58-107 (each 10 Euler sub-steps of 1 ms + the actuator lag :109-113)"""
+        dev, B = self.device, self.B
         for t, w in ((self.state, 8), (self.cmd, 2)):  # `state` and `cmd` are plain attributes: what reaches the kernel is a raw pointer
-            if not (t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
-                raise ValueError("state [B,8] / cmd [B,2] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            if not is_buffer(t, torch.float64, (B, w), dev):
+                raise ValueError("state [B,8] / cmd [B,2] must stay contiguous float64 tensors on %s (write into them with copy_)" % dev)
+        head = (dev.index, B, ptr(self.state), ptr(self.cmd))   # what every plant call begins with
         if self.plant is None:
-            rc = self._lib.kmpc_sim_advance_batch(self.device.index, self.B, C.c_void_p(self.state.data_ptr()),
-                                                  C.c_void_p(self.cmd.data_ptr()), int(n_updates), stream)
+            rc = self._lib.kmpc_sim_advance_batch(*head, int(n_updates), stream(dev))
         elif self.cmd_queue_depth is not None:
-            for t, shape, dt in ((self.plant, (self.B, 8), torch.float64), (self.cmd_delay, (self.B,), torch.int32),
-                                 (self.cmd_queue, (self.cmd_queue_depth, self.B, 2), torch.float64)):
-                if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+            for t, shape, dt in ((self.plant, (B, 8), torch.float64), (self.cmd_delay, (B,), torch.int32),
+                                 (self.cmd_queue, (self.cmd_queue_depth, B, 2), torch.float64)):
+                if not is_buffer(t, dt, shape, dev):
                     raise ValueError("plant [B,8] / cmd_queue [D,B,2] float64 and cmd_delay [B] int32 must stay contiguous tensors on %s "
-                                     "(write into them with copy_)" % self.device)
+                                     "(write into them with copy_)" % dev)
+            queue = (ptr(self.cmd_delay), ptr(self.cmd_queue), self.cmd_queue_depth, int(self.period), int(n_updates))   # ... and the ring, in every queue call
             if self.road is not None:
                 for t, w in ((self.road, 8), (self.road_stat, 4)):
-                    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous()
-                            and t.device == self.device):
-                        raise ValueError("road [B,8] / road_stat [B,4] must stay contiguous float64 tensors on %s (write into them with copy_)" % self.device)
+                    if not is_buffer(t, torch.float64, (B, w), dev):
+                        raise ValueError("road [B,8] / road_stat [B,4] must stay contiguous float64 tensors on %s (write into them with copy_)" % dev)
                 if self.road_profile is not None and int(n_updates) > 0:   # the road under each vehicle, from where it is now
                     self.road_profile.apply(self.state, self.road_base if self.road_mid is None else self.road_mid, self.road)
                 if self.drive is not None:
-                    if not (isinstance(self.drive, torch.Tensor) and self.drive.dtype == torch.float64 and tuple(self.drive.shape) == (self.B, 8)
-                            and self.drive.is_contiguous() and self.drive.device == self.device):
-                        raise ValueError("drive [B,8] must stay a contiguous float64 tensor on %s (write into it with copy_)" % self.device)
+                    if not is_buffer(self.drive, torch.float64, (B, 8), dev):
+                        raise ValueError("drive [B,8] must stay a contiguous float64 tensor on %s (write into it with copy_)" % dev)
                     self.llc._own()
-                    rc = self._lib.kmpc_sim_advance_drive(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
-                                                          C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.road.data_ptr()),
-                                                          C.c_void_p(self.drive.data_ptr()), C.c_void_p(self.llc.params.data_ptr()),
-                                                          C.c_void_p(self.llc.rec.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
-                                                          C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth, int(self.period), int(n_updates),
-                                                          C.c_void_p(self.road_stat.data_ptr()), stream)
+                    rc = self._lib.kmpc_sim_advance_drive(*head, ptr(self.plant), ptr(self.road), ptr(self.drive), ptr(self.llc.params), ptr(self.llc.rec),
+                                                          *queue, ptr(self.road_stat), stream(dev))
                 else:
-                    rc = self._lib.kmpc_sim_advance_road(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
-                                                         C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.road.data_ptr()),
-                                                         C.c_void_p(self.cmd_delay.data_ptr()), C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth,
-                                                         int(self.period), int(n_updates), C.c_void_p(self.road_stat.data_ptr()), stream)
+                    rc = self._lib.kmpc_sim_advance_road(*head, ptr(self.plant), ptr(self.road), *queue, ptr(self.road_stat), stream(dev))
             else:
-                rc = self._lib.kmpc_sim_advance_queue(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
-                                                      C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
-                                                      C.c_void_p(self.cmd_queue.data_ptr()), self.cmd_queue_depth, int(self.period), int(n_updates),
-                                                      stream)
+                rc = self._lib.kmpc_sim_advance_queue(*head, ptr(self.plant), *queue, stream(dev))
             if rc == 0 and int(n_updates) > 0:
                 self.period += 1
         else:
-            for t, shape, dt in ((self.plant, (self.B, 8), torch.float64), (self.cmd_delay, (self.B,), torch.int32), (self.cmd_held, (self.B, 2), torch.float64)):
-                if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+            for t, shape, dt in ((self.plant, (B, 8), torch.float64), (self.cmd_delay, (B,), torch.int32), (self.cmd_held, (B, 2), torch.float64)):
+                if not is_buffer(t, dt, shape, dev):
                     raise ValueError("plant [B,8] / cmd_held [B,2] float64 and cmd_delay [B] int32 must stay contiguous tensors on %s "
-                                     "(write into them with copy_)" % self.device)
-            rc = self._lib.kmpc_sim_advance_plant(self.device.index, self.B, C.c_void_p(self.state.data_ptr()), C.c_void_p(self.cmd.data_ptr()),
-                                                  C.c_void_p(self.plant.data_ptr()), C.c_void_p(self.cmd_delay.data_ptr()),
-                                                  C.c_void_p(self.cmd_held.data_ptr()), int(n_updates), stream)
+                                     "(write into them with copy_)" % dev)
+            rc = self._lib.kmpc_sim_advance_plant(*head, ptr(self.plant), ptr(self.cmd_delay), ptr(self.cmd_held), int(n_updates), stream(dev))
         _lib.check(rc)
 
     def wander_road_buffers(self):
@@ -785,15 +703,10 @@ class SensorModel:
         self.B, self.seed, self.id_base = int(B), int(seed), int(id_base)
         if not (0 <= self.seed < 2 ** 64 and 0 <= self.id_base and self.id_base + self.B < 2 ** 63):
             raise ValueError("SensorModel: seed in [0, 2^64), id_base >= 0")
-        rows = np.zeros((self.B, 8))
-        for name, v, c0 in (("sigma", sigma, 0), ("bias", bias, 4)):
-            v = np.asarray(v, dtype=np.float64)
-            if v.shape not in ((), (4,), (self.B, 4)):
-                raise ValueError("SensorModel: %s is a scalar, four values (x, y, psi, v) or [%d,4], got %s" % (name, self.B, v.shape))
-            rows[:, c0:c0 + 4] = v
+        rows = fill_blocks("SensorModel", np.zeros((self.B, 8)), (("sigma", sigma, 0, 4), ("bias", bias, 4, 4)), "four values (x, y, psi, v)")
         if not np.isfinite(rows).all() or not (rows[:, 0:4] >= 0.0).all():
             raise ValueError("SensorModel: sigma and bias must be finite, sigma >= 0")
-        self.device = _device(device)
+        self.device = device_of(device)
         self.params = torch.as_tensor(rows).to(self.device)
         self.params_base = None   # [B,8] in a loop with wander=: the caller's rows; `params` is then rewritten from them every period
         self.meas_delay = self.truth_ring = self.depth = None
@@ -811,8 +724,7 @@ class SensorModel:
             self.truth_ring = torch.zeros((self.depth, self.B, 4), dtype=torch.float64, device=self.device)
         self.faults = self.z = self.flags = self.blind = self.fault_record = None
         if faults is not None:
-            rows = faults.detach().cpu().numpy() if isinstance(faults, torch.Tensor) else faults
-            rows = check_fault_rows(rows)
+            rows = check_fault_rows(faults)
             if rows.shape[0] != self.B:
                 raise ValueError("SensorModel: faults is [%d,16], got %s" % (self.B, rows.shape))
             self.faults = torch.as_tensor(rows).to(self.device).contiguous()
@@ -840,44 +752,58 @@ class SensorModel:
             out[k] = out[k].astype(np.int64)
         return out
 
-    def _sense_faults(self, state, period, est, stream):
+    def _sense_faults(self, state, period, est):
         own = ((self.faults, (self.B, FAULT_WORDS), torch.float64), (self.fault_record, (self.B, FAULT_WORDS), torch.float64),
                (self.z, (self.B, 4), torch.float64), (self.flags, (self.B,), torch.int32), (self.blind, (self.B,), torch.uint8))
         if self.meas_delay is not None:
             own += ((self.meas_delay, (self.B,), torch.int32), (self.truth_ring, (self.depth, self.B, 4), torch.float64))
         for t, shape, dt in own:
-            if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, dt, shape, self.device):
                 raise ValueError("faults / fault_record [B,16] and z [B,4] float64, flags [B] int32, blind [B] uint8, meas_delay [B] int32 and "
                                  "truth_ring [depth,B,4] float64 must stay contiguous tensors on %s" % self.device)
-        ring = self.meas_delay is not None
-        _lib.check(self._lib.kmpc_sense_faults_batch(self.device.index, self.B, C.c_void_p(state.data_ptr()), C.c_void_p(self.params.data_ptr()),
-                                                     C.c_void_p(self.faults.data_ptr()), self.seed, int(period), self.id_base,
-                                                     C.c_void_p(self.meas_delay.data_ptr()) if ring else None,
-                                                     C.c_void_p(self.truth_ring.data_ptr()) if ring else None, self.depth if ring else 0,
-                                                     C.c_void_p(self.fault_record.data_ptr()), C.c_void_p(self.z.data_ptr()), C.c_void_p(est.data_ptr()),
-                                                     C.c_void_p(self.flags.data_ptr()), C.c_void_p(self.blind.data_ptr()), stream))
+        ring = (self.meas_delay, self.truth_ring, self.depth) if self.meas_delay is not None else (None, None, 0)
+        _lib.check(self._lib.kmpc_sense_faults_batch(self.device.index, self.B, ptr(state), ptr(self.params), ptr(self.faults), self.seed, int(period),
+                                                     self.id_base, ptr(ring[0]), ptr(ring[1]), ring[2], ptr(self.fault_record), ptr(self.z), ptr(est),
+                                                     ptr(self.flags), ptr(self.blind), stream(self.device)))
         return est
 
     def sense(self, state, period, out=None):
         """state [B,8] (the plant's) -> est [B,4] = x, y, psi (wrapped to [-pi, pi)), v (>= 0) as measured in control period `period`"""
         est = out if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
         for t, w in ((state, 8), (self.params, 8), (est, 4)):
-            if not (t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, torch.float64, (self.B, w), self.device):
                 raise ValueError("state [B,8], params [B,8] and est [B,4] must be contiguous float64 tensors on %s" % self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         if self.faults is not None:
-            return self._sense_faults(state, period, est, stream)
+            return self._sense_faults(state, period, est)
         if self.meas_delay is not None:
             for t, shape, dt in ((self.meas_delay, (self.B,), torch.int32), (self.truth_ring, (self.depth, self.B, 4), torch.float64)):
-                if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+                if not is_buffer(t, dt, shape, self.device):
                     raise ValueError("meas_delay [B] int32 and truth_ring [depth,B,4] float64 must stay contiguous tensors on %s" % self.device)
-            _lib.check(self._lib.kmpc_sense_delayed_batch(self.device.index, self.B, C.c_void_p(state.data_ptr()), C.c_void_p(self.params.data_ptr()),
-                                                          self.seed, int(period), self.id_base, C.c_void_p(self.meas_delay.data_ptr()),
-                                                          C.c_void_p(self.truth_ring.data_ptr()), self.depth, C.c_void_p(est.data_ptr()), stream))
+            _lib.check(self._lib.kmpc_sense_delayed_batch(self.device.index, self.B, ptr(state), ptr(self.params), self.seed, int(period), self.id_base,
+                                                          ptr(self.meas_delay), ptr(self.truth_ring), self.depth, ptr(est), stream(self.device)))
             return est
-        _lib.check(self._lib.kmpc_sense_batch(self.device.index, self.B, C.c_void_p(state.data_ptr()), C.c_void_p(self.params.data_ptr()),
-                                              self.seed, int(period), self.id_base, C.c_void_p(est.data_ptr()), stream))
+        _lib.check(self._lib.kmpc_sense_batch(self.device.index, self.B, ptr(state), ptr(self.params), self.seed, int(period), self.id_base, ptr(est),
+                                              stream(self.device)))
         return est
+
+
+def _filter_scalars(name, gate, dt, L_a, L_b):
+    """the scalars the estimator and the observer share -> (gate, dt, L_a, L_b) as floats; ValueError unless gate >= 0, the others > 0, all finite"""
+    g, d, a, b = float(gate), float(dt), float(L_a), float(L_b)
+    if not (np.isfinite([g, d, a, b]).all() and g >= 0.0 and d > 0.0 and a > 0.0 and b > 0.0):
+        raise ValueError("%s: gate >= 0, dt > 0, L_a > 0, L_b > 0, all finite (got %r, %r, %r, %r)" % (name, gate, dt, L_a, L_b))
+    return g, d, a, b
+
+
+def _filter_input(flags, u, B, device):
+    """what Estimator.update and DisturbanceObserver.update check after their own buffers, in this order: the stage's `flags` [B] int32, then the
+    input `u` [B,2], which may be a column view (unit column stride, rows a fixed distance >= 2 apart) -> u's row stride as the kernel takes it"""
+    if not is_buffer(flags, torch.int32, (B,), device):
+        raise ValueError("flags must stay a contiguous int32 tensor [B] on %s" % device)
+    if not (isinstance(u, torch.Tensor) and u.dtype == torch.float64 and tuple(u.shape) == (B, 2) and u.device == device
+            and (B == 0 or (u.stride(1) == 1 and (B == 1 or u.stride(0) >= 2)))):
+        raise ValueError("u: float64 [B,2] on %s with unit column stride and rows >= 2 apart (a [B,2] buffer or sim.state[:, 6:8])" % device)
+    return int(u.stride(0)) if B > 1 else 2
 
 
 class Estimator:
@@ -892,18 +818,11 @@ class Estimator:
     def __init__(self, B, q=(0.02, 0.02, 0.01, 0.1), r=(0.2, 0.2, 0.02, 0.1), gate=0.0, dt=0.1, L_a=1.108, L_b=1.742, device=0):
         self._lib = _lib.load()
         self.B = int(B)
-        rows = np.zeros((self.B, 8))
-        for name, v, c0 in (("q", q, 0), ("r", r, 4)):
-            v = np.asarray(v, dtype=np.float64)
-            if v.shape not in ((), (4,), (self.B, 4)):
-                raise ValueError("Estimator: %s is a scalar, four values (x, y, psi, v) or [%d,4], got %s" % (name, self.B, v.shape))
-            rows[:, c0:c0 + 4] = v
+        rows = fill_blocks("Estimator", np.zeros((self.B, 8)), (("q", q, 0, 4), ("r", r, 4, 4)), "four values (x, y, psi, v)")
         if not np.isfinite(rows).all() or not (rows[:, 0:4] >= 0.0).all() or not (rows[:, 4:8] > 0.0).all():
             raise ValueError("Estimator: q and r must be finite, q >= 0, r > 0")
-        self.gate, self.dt, self.L_a, self.L_b = float(gate), float(dt), float(L_a), float(L_b)
-        if not (np.isfinite([self.gate, self.dt, self.L_a, self.L_b]).all() and self.gate >= 0.0 and self.dt > 0.0 and self.L_a > 0.0 and self.L_b > 0.0):
-            raise ValueError("Estimator: gate >= 0, dt > 0, L_a > 0, L_b > 0, all finite (got %r, %r, %r, %r)" % (gate, dt, L_a, L_b))
-        self.device = _device(device)
+        self.gate, self.dt, self.L_a, self.L_b = _filter_scalars("Estimator", gate, dt, L_a, L_b)
+        self.device = device_of(device)
         self.params = torch.as_tensor(rows).to(self.device)
         self.record = torch.zeros((self.B, 16), dtype=torch.float64, device=self.device)
         self.flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
@@ -930,19 +849,11 @@ class Estimator:
         column view such as sim.state[:, 6:8] (rows any fixed distance >= 2 apart: no copy is made) -> est [B,4], the filtered state"""
         est = out if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
         for t, w in ((z, 4), (self.params, 8), (self.record, 16), (est, 4), (self.innov, 4)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, torch.float64, (self.B, w), self.device):
                 raise ValueError("z [B,4], params [B,8], record [B,16], est [B,4] and innov [B,4] must be contiguous float64 tensors on %s" % self.device)
-        if not (self.flags.dtype == torch.int32 and tuple(self.flags.shape) == (self.B,) and self.flags.is_contiguous() and self.flags.device == self.device):
-            raise ValueError("flags must stay a contiguous int32 tensor [B] on %s" % self.device)
-        if not (isinstance(u, torch.Tensor) and u.dtype == torch.float64 and tuple(u.shape) == (self.B, 2) and u.device == self.device
-                and (self.B == 0 or (u.stride(1) == 1 and (self.B == 1 or u.stride(0) >= 2)))):
-            raise ValueError("u: float64 [B,2] on %s with unit column stride and rows >= 2 apart (a [B,2] buffer or sim.state[:, 6:8])" % self.device)
-        stride = u.stride(0) if self.B > 1 else 2
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_estimate_batch(self.device.index, self.B, C.c_void_p(self.record.data_ptr()), C.c_void_p(z.data_ptr()),
-                                                 C.c_void_p(u.data_ptr()), int(stride), C.c_void_p(self.params.data_ptr()), self.dt, self.L_a, self.L_b,
-                                                 self.gate, C.c_void_p(est.data_ptr()), C.c_void_p(self.innov.data_ptr()),
-                                                 C.c_void_p(self.flags.data_ptr()), stream))
+        stride = _filter_input(self.flags, u, self.B, self.device)
+        _lib.check(self._lib.kmpc_estimate_batch(self.device.index, self.B, ptr(self.record), ptr(z), ptr(u), stride, ptr(self.params), self.dt, self.L_a,
+                                                 self.L_b, self.gate, ptr(est), ptr(self.innov), ptr(self.flags), stream(self.device)))
         return est
 
 
@@ -963,22 +874,15 @@ class DisturbanceObserver:
                  v_min=1.0, psi_cap=0.2, acc_cap=0.5, df_cap=0.1, L_a=1.108, L_b=1.742, device=0):
         self._lib = _lib.load()
         self.B = int(B)
-        rows = np.zeros((self.B, 16))
-        for name, v, c0, w in (("q", q, 0, 4), ("q_dist", q_dist, 4, 3), ("r", r, 7, 4), ("p0", p0, 11, 3)):
-            v = np.asarray(v, dtype=np.float64)
-            if v.shape not in ((), (w,), (self.B, w)):
-                raise ValueError("DisturbanceObserver: %s is a scalar, %d values or [%d,%d], got %s" % (name, w, self.B, w, v.shape))
-            rows[:, c0:c0 + w] = v
+        rows = fill_blocks("DisturbanceObserver", np.zeros((self.B, 16)), (("q", q, 0, 4), ("q_dist", q_dist, 4, 3), ("r", r, 7, 4), ("p0", p0, 11, 3)))
         if not np.isfinite(rows).all() or not (rows[:, 0:7] >= 0.0).all() or not (rows[:, 7:11] > 0.0).all() or not (rows[:, 11:14] >= 0.0).all():
             raise ValueError("DisturbanceObserver: q, q_dist, r and p0 must be finite, q >= 0, q_dist >= 0, r > 0, p0 >= 0")
-        self.gate, self.dt, self.L_a, self.L_b = float(gate), float(dt), float(L_a), float(L_b)
+        self.gate, self.dt, self.L_a, self.L_b = _filter_scalars("DisturbanceObserver", gate, dt, L_a, L_b)
         self.v_min, self.psi_cap, self.acc_cap, self.df_cap = float(v_min), float(psi_cap), float(acc_cap), float(df_cap)
-        if not (np.isfinite([self.gate, self.dt, self.L_a, self.L_b]).all() and self.gate >= 0.0 and self.dt > 0.0 and self.L_a > 0.0 and self.L_b > 0.0):
-            raise ValueError("DisturbanceObserver: gate >= 0, dt > 0, L_a > 0, L_b > 0, all finite (got %r, %r, %r, %r)" % (gate, dt, L_a, L_b))
         caps = [self.v_min, self.psi_cap, self.acc_cap, self.df_cap]
         if not (np.isfinite(caps).all() and min(caps) >= 0.0):
             raise ValueError("DisturbanceObserver: v_min, psi_cap, acc_cap, df_cap >= 0, all finite (got %r, %r, %r, %r)" % (v_min, psi_cap, acc_cap, df_cap))
-        self.device = _device(device)
+        self.device = device_of(device)
         self.params = torch.as_tensor(rows).to(self.device)
         self.record = torch.zeros((self.B, 40), dtype=torch.float64, device=self.device)
         self.flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
@@ -994,7 +898,7 @@ class DisturbanceObserver:
 
     def _own(self):
         for t, w in ((self.params, 16), (self.record, 40)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, torch.float64, (self.B, w), self.device):
                 raise ValueError("params [B,16] and record [B,40] must stay contiguous float64 tensors on %s" % self.device)
 
     def update(self, z, u, out=None):
@@ -1003,34 +907,24 @@ class DisturbanceObserver:
         est = out if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
         self._own()
         for t, w in ((z, 4), (est, 4), (self.innov, 4), (self.dist, 3)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, torch.float64, (self.B, w), self.device):
                 raise ValueError("z [B,4], est [B,4], innov [B,4] and dist [B,3] must be contiguous float64 tensors on %s" % self.device)
-        if not (self.flags.dtype == torch.int32 and tuple(self.flags.shape) == (self.B,) and self.flags.is_contiguous() and self.flags.device == self.device):
-            raise ValueError("flags must stay a contiguous int32 tensor [B] on %s" % self.device)
-        if not (isinstance(u, torch.Tensor) and u.dtype == torch.float64 and tuple(u.shape) == (self.B, 2) and u.device == self.device
-                and (self.B == 0 or (u.stride(1) == 1 and (self.B == 1 or u.stride(0) >= 2)))):
-            raise ValueError("u: float64 [B,2] on %s with unit column stride and rows >= 2 apart (a [B,2] buffer or sim.state[:, 6:8])" % self.device)
-        stride = u.stride(0) if self.B > 1 else 2
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_observe_batch(self.device.index, self.B, C.c_void_p(self.record.data_ptr()), C.c_void_p(z.data_ptr()),
-                                                C.c_void_p(u.data_ptr()), int(stride), C.c_void_p(self.params.data_ptr()), self.dt, self.L_a, self.L_b,
-                                                self.gate, self.v_min, self.psi_cap, C.c_void_p(est.data_ptr()), C.c_void_p(self.dist.data_ptr()),
-                                                C.c_void_p(self.innov.data_ptr()), C.c_void_p(self.flags.data_ptr()), stream))
+        stride = _filter_input(self.flags, u, self.B, self.device)
+        _lib.check(self._lib.kmpc_observe_batch(self.device.index, self.B, ptr(self.record), ptr(z), ptr(u), stride, ptr(self.params), self.dt, self.L_a,
+                                                self.L_b, self.gate, self.v_min, self.psi_cap, ptr(est), ptr(self.dist), ptr(self.innov), ptr(self.flags),
+                                                stream(self.device)))
         return est
 
     def offset(self, cmd, stop_latch=None):
         """cmd [B,2] (accel, steer), in place: accel -= clip(da, acc_cap), steer -= clip(ddelta, df_cap); a vehicle whose `stop_latch` [B] (bool or
         uint8) is set, whose record is fresh or whose estimate is not finite keeps its command -> cmd"""
         self._own()
-        if not (isinstance(cmd, torch.Tensor) and cmd.dtype == torch.float64 and tuple(cmd.shape) == (self.B, 2) and cmd.is_contiguous() and cmd.device == self.device):
+        if not is_buffer(cmd, torch.float64, (self.B, 2), self.device):
             raise ValueError("cmd must be a contiguous float64 tensor [B,2] on %s" % self.device)
-        if stop_latch is not None and not (isinstance(stop_latch, torch.Tensor) and stop_latch.dtype in (torch.bool, torch.uint8)
-                                           and tuple(stop_latch.shape) == (self.B,) and stop_latch.is_contiguous() and stop_latch.device == self.device):
+        if stop_latch is not None and not is_buffer(stop_latch, (torch.bool, torch.uint8), (self.B,), self.device):
             raise ValueError("stop_latch must be a contiguous bool or uint8 tensor [B] on %s" % self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_cmd_offset_batch(self.device.index, self.B, C.c_void_p(self.record.data_ptr()),
-                                                   None if stop_latch is None else C.c_void_p(stop_latch.data_ptr()), self.acc_cap, self.df_cap,
-                                                   C.c_void_p(cmd.data_ptr()), stream))
+        _lib.check(self._lib.kmpc_cmd_offset_batch(self.device.index, self.B, ptr(self.record), ptr(stop_latch), self.acc_cap, self.df_cap, ptr(cmd),
+                                                   stream(self.device)))
         return cmd
 
 
@@ -1075,41 +969,39 @@ class LatencyCompensator:
         self.L_a, self.L_b = float(L_a), float(L_b)
         if not (np.isfinite([self.L_a, self.L_b]).all() and self.L_a > 0.0 and self.L_b > 0.0):
             raise ValueError("LatencyCompensator: L_a > 0, L_b > 0, finite (got %r, %r)" % (L_a, L_b))
-        self.device = _device(device)
+        self.device = device_of(device)
         self.cmd_delay, self.meas_delay = cd.to(self.device), md.to(self.device)
         self.cmd_hist = torch.zeros((self.depth, self.B, 2), dtype=torch.float64, device=self.device)
 
     def _check(self, period):
         for t, shape, dt in ((self.cmd_delay, (self.B,), torch.int32), (self.meas_delay, (self.B,), torch.int32),
                              (self.cmd_hist, (self.depth, self.B, 2), torch.float64)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device):
+            if not is_buffer(t, dt, shape, self.device):
                 raise ValueError("cmd_delay, meas_delay [B] int32 and cmd_hist [depth,B,2] float64 must stay contiguous tensors on %s" % self.device)
         if int(period) < 0:
             raise ValueError("period >= 0")
 
+    def _log(self, period):
+        """the command log and the assumed delays as the three kernels take them: cmd_hist, depth, period, n_updates, the delays and their bounds"""
+        return (ptr(self.cmd_hist), self.depth, int(period), self.n_updates, ptr(self.cmd_delay), ptr(self.meas_delay), int(self.max_cmd_delay),
+                int(self.max_meas_delay))
+
     def _buf(self, t, w, name):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (self.B, w) and t.is_contiguous() and t.device == self.device):
+        if not is_buffer(t, torch.float64, (self.B, w), self.device):
             raise ValueError("%s must be a contiguous float64 tensor [B,%d] on %s" % (name, w, self.device))
         return t
 
     def filter_input(self, period, out=None):
         self._check(period)
         u = self._buf(out, 2, "out") if out is not None else torch.empty((self.B, 2), dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_cmd_in_force_batch(self.device.index, self.B, C.c_void_p(self.cmd_hist.data_ptr()), self.depth, int(period),
-                                                     self.n_updates, C.c_void_p(self.cmd_delay.data_ptr()), C.c_void_p(self.meas_delay.data_ptr()),
-                                                     int(self.max_cmd_delay), int(self.max_meas_delay), C.c_void_p(u.data_ptr()), stream))
+        _lib.check(self._lib.kmpc_cmd_in_force_batch(self.device.index, self.B, *self._log(period), ptr(u), stream(self.device)))
         return u
 
     def predict(self, z, period, out=None):
         self._check(period)
         self._buf(z, 4, "z")
         zo = self._buf(out, 4, "out") if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_predict_ahead_batch(self.device.index, self.B, C.c_void_p(z.data_ptr()), C.c_void_p(self.cmd_hist.data_ptr()),
-                                                      self.depth, int(period), self.n_updates, C.c_void_p(self.cmd_delay.data_ptr()),
-                                                      C.c_void_p(self.meas_delay.data_ptr()), int(self.max_cmd_delay), int(self.max_meas_delay),
-                                                      self.L_a, self.L_b, C.c_void_p(zo.data_ptr()), stream))
+        _lib.check(self._lib.kmpc_predict_ahead_batch(self.device.index, self.B, ptr(z), *self._log(period), self.L_a, self.L_b, ptr(zo), stream(self.device)))
         return zo
 
     def check_observer(self, observer):
@@ -1128,12 +1020,8 @@ class LatencyCompensator:
         observer._own()
         self._buf(est, 4, "est")
         zo = self._buf(out, 4, "out") if out is not None else torch.empty((self.B, 4), dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.kmpc_predict_ahead_dist_batch(self.device.index, self.B, C.c_void_p(observer.record.data_ptr()),
-                                                           C.c_void_p(est.data_ptr()), C.c_void_p(self.cmd_hist.data_ptr()), self.depth, int(period),
-                                                           self.n_updates, C.c_void_p(self.cmd_delay.data_ptr()),
-                                                           C.c_void_p(self.meas_delay.data_ptr()), int(self.max_cmd_delay), int(self.max_meas_delay),
-                                                           self.L_a, self.L_b, observer.psi_cap, C.c_void_p(zo.data_ptr()), stream))
+        _lib.check(self._lib.kmpc_predict_ahead_dist_batch(self.device.index, self.B, ptr(observer.record), ptr(est), *self._log(period), self.L_a, self.L_b,
+                                                           observer.psi_cap, ptr(zo), stream(self.device)))
         return zo
 
     def push(self, cmd, period):
