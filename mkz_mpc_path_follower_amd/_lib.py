@@ -45,6 +45,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_road_profile_default", "kmpc_road_profile_fleet", "kmpc_speed_plan_fleet_profile",
            "kmpc_sense_faults_default", "kmpc_sense_faults_batch",
            "kmpc_wander_default", "kmpc_wander_batch"]
+# the entry points of include/kmpc_follow.h: the same library, a header of their own (EXPORTS is include/kmpc.h's list and stays that)
+EXT_EXPORTS = ["kmpc_follow_default", "kmpc_follow_stat_init", "kmpc_follow_fleet"]
 
 _lib = None
 
@@ -126,7 +128,10 @@ def load():
     L.kmpc_record_bytes.restype = C.c_int64
     L.kmpc_pack_records.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.kmpc_solve_batch_packed.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp]
-    for name in EXPORTS:
+    L.kmpc_follow_default.argtypes = [dp, i32]
+    L.kmpc_follow_stat_init.argtypes = [dp, i32]
+    L.kmpc_follow_fleet.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for name in EXPORTS + EXT_EXPORTS:
         getattr(L, name)
     _lib = L
     return L

@@ -73,6 +73,13 @@ sensor the caller's sensor rows move to `sensor.params_base` and `sensor.params`
 road the caller's rows are `sim.road_base` and the stage writes `sim.road` (in front of a road profile: base -> wander -> profile -> `sim.road`).
 Active measurement channels without sensor=, or active road channels without a simulator built with road=, are refused at construction.
 `run(history=True)` adds `wander` [steps,B,8].  Without wander= there is no launch and no tensor more.
+
+Car following: `follower=ref_traj.Follower(grt, ...)` (built on the loop's own waypoint helper, every vehicle in target-velocity mode) makes the
+vehicles exist for each other: in front of the speed plan, `follower.cap(sim.state, v_target)` gives `loop.v_follow` [B], v_target lowered where the
+vehicle ahead on the same path demands it (kmpc_follow_fleet, include/kmpc_follow.h).  With a planner that is the plan's cap (`planner.plan(st,
+v_follow)`), without one it is the period's speed for waypoints and solve.  The range sensor is perfect: the stage reads the truth, `sim.state`, for
+the arclengths and both speeds, whatever state the controller reads.  `v_target` and `des_speed` are not modified.  `run(history=True)` adds
+`v_follow` [steps,B] and `gap` [steps,B].  Without follower= there is no launch and no tensor more.
 """
 import time
 
@@ -110,7 +117,7 @@ class _ScoredLoop:
     call without arguments -> the solver's output dict, and the entries the loop adds to step()'s dict."""
 
     def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer, planner=None, track_with_time=False, blind_stop=False,
-                   wander=None):
+                   wander=None, follower=None):
         """what both loops own beside grt, sim, N, B, mpc and the target speeds: buffers, the stop latch, the library, and the stages; and the one
         check of the helper against the plant that both word alike (a loop's own refusals, worded for that loop, come before this call)"""
         dev = self.sim.device
@@ -130,6 +137,7 @@ class _ScoredLoop:
         self._init_wander(wander)
         self._init_estimator(estimator, estimator_input, compensator, observer)
         self._init_planner(planner, track_with_time)
+        self._init_follower(follower, track_with_time)
         self._init_score()
 
     def _period(self, plant_updates, time_solve):
@@ -186,12 +194,28 @@ class _ScoredLoop:
         self.planner = planner
         self.v_plan = None     # [B] the planned speed of the last period (planner given): waypoint spacing and the solver's v_target
 
+    def _init_follower(self, follower, track_with_time):
+        if follower is not None:
+            if track_with_time:
+                raise ValueError("follower= caps a speed on the arclength grid: track_with_time must stay False")
+            if getattr(follower, "fleet", None) is not self.grt:
+                raise ValueError("follower= must be a ref_traj.Follower built on this loop's own waypoint helper")
+            self._same_fleet("follower", follower)
+            if getattr(self.grt, "time_mode", None) is not None and bool(self.grt.time_mode.any().item()):
+                raise ValueError("follower= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode")
+        self.follower = follower
+        self.v_follow = None   # [B] v_target under the following law, of the last period (follower given): the plan's cap, or the period's speed
+
     def _speed(self, st):
-        """the speed this period's waypoints and solve run at: v_target, or with a planner loop.v_plan, planned on the state the controller reads
-        with v_target as the cap (v_target itself is not modified)"""
+        """the speed this period's waypoints and solve run at: v_target; with a follower loop.v_follow, v_target lowered by the following law on
+        the TRUTH (a perfect range sensor); with a planner loop.v_plan, planned on the state the controller reads with that as the cap
+        (v_target itself is not modified)"""
+        cap = self.v_target
+        if self.follower is not None:
+            cap = self.v_follow = self.follower.cap(self.sim.state, self.v_target, out=self.v_follow)
         if self.planner is None:
-            return self.v_target
-        self.v_plan = self.planner.plan(st, self.v_target, out=self.v_plan)
+            return cap
+        self.v_plan = self.planner.plan(st, cap, out=self.v_plan)
         return self.v_plan
 
     def _init_sensor(self, sensor, blind_stop=False):
@@ -308,6 +332,8 @@ class _ScoredLoop:
                 (self.observer is not None, "dist", (3,), f64, lambda: self.dist),
                 (self.compensator is not None, "est_pred", (4,), f64, lambda: self.est_pred),
                 (self.planner is not None, "v_plan", (), f64, lambda: self.v_plan),
+                (self.follower is not None, "v_follow", (), f64, lambda: self.v_follow),
+                (self.follower is not None, "gap", (), f64, lambda: self.follower.gap),
                 (self.wander is not None, "wander", (8,), f64, lambda: self.wander.x))
         return [row[1:] for row in rows if row[0]]
 
@@ -320,7 +346,8 @@ class _ScoredLoop:
         (what the controller saw then, unless a compensator follows; an observer's est_filt likewise, with dist [steps,B,3]) and, with a compensator, est_pred [steps,B,4] (what the controller saw then)
         and, with a planner, v_plan [steps,B] (the speed period j's waypoints and solve ran at) and, with a faulty sensor (SensorModel(faults=)),
         z [steps,B,4] (NaN where a source was silent: what a filter read; est is then the held state) and fault_flags [steps,B] int32 and, with
-        wander=, wander [steps,B,8] (the processes' values in period j: what was added to the biases and the road words then).
+        wander=, wander [steps,B,8] (the processes' values in period j: what was added to the biases and the road words then) and, with follower=, v_follow
+        [steps,B] (v_target under the following law in period j) and gap [steps,B] (to the leader, from state[j]; +inf without one).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -381,7 +408,7 @@ class ClosedLoop(_ScoredLoop):
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
                  mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, observer=None, planner=None,
-                 blind_stop=False, wander=None, **options):
+                 blind_stop=False, wander=None, follower=None, **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -395,7 +422,7 @@ class ClosedLoop(_ScoredLoop):
             raise ValueError("a FleetRefTrajectory owns the tracking modes (its time_mode): track_with_time must stay False")
         self.track_with_time = track_with_time
         self.des_speed, self.v_target = _target_speeds(target_vel, self.B, sim.device)  # mpc_cmd_pub.jl:58-62
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander, follower)
 
     def step(self, plant_updates=10, time_solve=False):
         """time_solve=True brackets the solve with device synchronisations and returns its wall time (`solve_s`)"""
@@ -421,7 +448,8 @@ class ClosedLoopFrenet(_ScoredLoop):
     (checked once, here).  Re-routing a stop-latched vehicle does not clear its latch: clear `command_stop[b]` yourself."""
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, estimator=None,
-                 estimator_input="actuator", compensator=None, observer=None, planner=None, blind_stop=False, wander=None, **options):
+                 estimator_input="actuator", compensator=None, observer=None, planner=None, blind_stop=False, wander=None, follower=None,
+                 **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -438,7 +466,7 @@ class ClosedLoopFrenet(_ScoredLoop):
             raise ValueError("ClosedLoopFrenet needs a float64 model=1 BatchMPC with horizon %d on %s (got %s, model=%d, N=%d, %s)"
                              % (self.N, sim.device, self.mpc.dtype, self.mpc.cfg.model, self.mpc.N, self.mpc.device))
         self.des_speed, self.v_target = des_speed, v_target
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander, follower)
 
     def step(self, plant_updates=10, time_solve=False):
         """as ClosedLoop.step; the returned dict also carries `k_poly` [B,4] and `fit_status` [B]"""

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/kmpc.h"
+#include "../../include/kmpc_follow.h"
 #include "kmpc_dispatch.h"
 
 #ifndef KMPC_HOST_ZERO_COPY_MAX
@@ -778,6 +779,46 @@ extern "C" int32_t kmpc_speed_plan_fleet_profile(kmpc_pathset *ps, int32_t B, co
 {
     return speed_plan_fleet("kmpc_speed_plan_fleet_profile", true, ps, B, kappa, profile, state, state_stride, path_id, v_cap, rows, v_plan_out,
                             info_out, closest_out, stream);
+}
+
+// ---- car following (kmpc_follow.hip; include/kmpc_follow.h) --------------------------------------------------------------
+// this project's own defaults (the reference has no such stage): the one place they exist
+extern "C" int32_t kmpc_follow_default(double *rows_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_follow_default: bad argument (B=%d)", B);
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        double *r = rows_host + KMPC_FOLLOW_WORDS * b;
+        for (int i = 0; i < KMPC_FOLLOW_WORDS; ++i) r[i] = 0.0;
+        r[KMPC_FOLLOW_D_MIN] = 5.0; r[KMPC_FOLLOW_T_HEADWAY] = 1.0; r[KMPC_FOLLOW_A_BRAKE] = 0.7; r[KMPC_FOLLOW_K_GAP] = 0.5; r[KMPC_FOLLOW_LENGTH] = 4.9;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_follow_stat_init(double *stat_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !stat_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_follow_stat_init: bad argument (B=%d)", B);
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        double *r = stat_host + KMPC_FOLLOWSTAT_WORDS * b;
+        for (int i = 0; i < KMPC_FOLLOWSTAT_WORDS; ++i) r[i] = 0.0;
+        r[KMPC_FOLLOWSTAT_MIN_GAP] = INFINITY;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_follow_fleet(int32_t device, int32_t B, const double *s_along, int32_t s_stride, const double *speed, int32_t speed_stride,
+                                     const int32_t *path_id, const uint8_t *present, const double *rows, const double *v_cap, double *v_cap_out,
+                                     double *gap_out, int32_t *leader_out, double *stat, void *stream)
+{
+    if (B < 0 || s_stride < 1 || speed_stride < 1)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_follow_fleet: bad B / s_stride / speed_stride (B=%d, s_stride=%d, speed_stride=%d; strides >= 1)", B,
+                    s_stride, speed_stride);
+    if (B > 0 && (!s_along || !speed || !rows || !v_cap || !v_cap_out))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_follow_fleet: null required buffer (s_along %s, speed %s, rows %s, v_cap %s, v_cap_out %s)",
+                    s_along ? "given" : "NULL", speed ? "given" : "NULL", rows ? "given" : "NULL", v_cap ? "given" : "NULL",
+                    v_cap_out ? "given" : "NULL");
+    if (B == 0) return KMPC_OK;
+    const FL w = {B, s_stride, speed_stride, s_along, speed, path_id, present, rows, v_cap, v_cap_out, gap_out, leader_out, stat};
+    return on_device("kmpc_follow_fleet", device, [&] { return kmpc_launch_follow_fleet(w, (hipStream_t)stream); });
 }
 
 // ---- road profile per path sample (kmpc_road_profile.hip) ----------------------------------------------------------------

@@ -235,6 +235,22 @@ struct RPF {
 };
 hipError_t kmpc_launch_road_profile_fleet(const RPF &w, hipStream_t st);
 
+// car following: a leader, a gap and a speed cap per vehicle (kmpc_follow.hip; layouts: include/kmpc_follow.h)
+struct FL {
+    int B, s_stride, speed_stride;   // vehicles; doubles between two vehicles' arclengths and between two vehicles' speeds (each >= 1)
+    const double *s_along;           // vehicle b's arclength on its path at s_along[b * s_stride]
+    const double *speed;             // vehicle b's speed at speed[b * speed_stride]
+    const int32_t *path_id;          // [B] or null: one path
+    const uint8_t *present;          // [B] or null: everybody on the road
+    const double *rows;              // [B,8] KMPC_FOLLOW_*
+    const double *v_cap;             // [B]
+    double *v_cap_out;               // [B]; may be v_cap
+    double *gap_out;                 // [B,2] gap, the leader's speed, or null
+    int32_t *leader_out;             // [B] or null: -1 = none
+    double *stat;                    // [B,8] in/out KMPC_FOLLOWSTAT_*, or null
+};
+hipError_t kmpc_launch_follow_fleet(const FL &w, hipStream_t st);
+
 // batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
 // scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)
 struct FR {

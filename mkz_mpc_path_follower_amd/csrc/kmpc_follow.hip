@@ -1,0 +1,145 @@
+// kmpc_follow.hip -- car following (kmpc_follow_fleet), gfx950 only: per vehicle the nearest usable vehicle ahead on its own path, the gap to it and
+// a speed cap from the following law of include/kmpc_follow.h.
+//
+// The hot path is the pair search: every follower sees every vehicle of the fleet, B^2 comparisons.  A workgroup of sixteen waves owns 64
+// followers, one per lane, and the SAME 64 in each of its waves.  The candidates stream through LDS in tiles of 1024 -- each thread fetches one
+// candidate (s, speed, path, present) and stores its arclength and its KEY: the path id of a usable vehicle, -1 of one that cannot lead; the next
+// tile's words are fetched before the current tile is scanned, so that their latency hides behind the scan.  Wave q scans the q-th 64 candidates
+// of the tile: the candidate's words are wave-uniform LDS reads (a broadcast, no bank conflict), the follower's own s, key and its best
+// (difference, j) so far stay in registers.  Inside a wave the candidates come in rising j, so `difference < best` alone keeps the lowest j among
+// equal differences; the waves' partial winners meet once, in LDS, and are combined by the full rule (smaller difference, then lower j).  No
+// atomics, no second launch, no workspace: the result is a function of the inputs alone.  Sixteen waves per 64 followers, not one follower per
+// thread, because a fleet of a few thousand would otherwise occupy a few CUs for a long serial scan: the scan per wave is B / 16 candidates and
+// B / 64 workgroups share the chip (at B = 4096 the call is bound by the latency of four tiles, not by the comparisons).
+// The law and the record run on wave 0's lanes with _rn intrinsics: no product and sum share a rounding.  Plain C++: vector stores, no inline
+// assembly, no scratch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/kmpc_follow.h"   // KMPC_FOLLOW_*, KMPC_FOLLOWSTAT_*: the row layouts
+#include "kmpc_dispatch.h"
+#include "kmpc_stage.h"                  // stage::finite
+
+#pragma clang fp contract(off)
+
+constexpr int FOLLOW_LANES = 64;                           // followers per workgroup
+constexpr int FOLLOW_WAVES = 16;                           // waves per workgroup: each scans its sixteenth of every tile
+constexpr int FOLLOW_TILE = FOLLOW_LANES * FOLLOW_WAVES;   // candidates per tile = threads per workgroup
+
+// vehicle j's key: its path id (0 without path ids) when it is usable, `none` when it is not
+__device__ __forceinline__ int follow_key(const FL &w, const unsigned j, const double s, const int none)
+{
+    const double v = w.speed[(size_t)j * w.speed_stride];
+    const int pid = w.path_id ? w.path_id[j] : 0;
+    const bool here = w.present ? w.present[j] != 0 : true;
+    return (stage::finite(s) && stage::finite(v) && here && pid >= 0) ? pid : none;
+}
+
+__global__ __launch_bounds__(FOLLOW_TILE) void kmpc_follow_fleet_kernel(FL w)
+{
+    __shared__ double t_s[FOLLOW_TILE];     // the tile; after the search, the waves' partial differences
+    __shared__ int t_key[FOLLOW_TILE];      //           after the search, the waves' partial leaders
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, nB = (unsigned)w.B;   // B < 2^31: no unsigned sum below wraps
+    const unsigned b = blockIdx.x * FOLLOW_LANES + lane;
+    // the follower: a key no candidate has (-2) when it is not usable or past the fleet's end, so that it finds no leader
+    double s_b = 0.0;
+    int key_b = -2;
+    if (b < nB) {
+        s_b = w.s_along[(size_t)b * w.s_stride];
+        key_b = follow_key(w, b, s_b, -2);
+    }
+    double best = INFINITY;
+    int bj = -1;
+    // this thread's candidate of the first tile; inside the loop the NEXT tile's is fetched before the scan
+    double s_j = 0.0;
+    int key_j = -1;
+    if (tid < nB) {
+        s_j = w.s_along[(size_t)tid * w.s_stride];
+        key_j = follow_key(w, tid, s_j, -1);
+    }
+    for (unsigned base = 0; base < nB; base += FOLLOW_TILE) {
+        __syncthreads();   // every wave is done with the previous tile
+        t_s[tid] = s_j;
+        t_key[tid] = key_j;
+        __syncthreads();
+        const unsigned jn = base + FOLLOW_TILE + tid;   // < 2^31 + 2^11: no wrap
+        s_j = 0.0;
+        key_j = -1;
+        if (jn < nB) {
+            s_j = w.s_along[(size_t)jn * w.s_stride];
+            key_j = follow_key(w, jn, s_j, -1);
+        }
+        const unsigned c0 = wave * FOLLOW_LANES;
+#pragma unroll 8
+        for (unsigned c = 0; c < FOLLOW_LANES; ++c) {
+            const double sc = t_s[c0 + c];
+            const int kc = t_key[c0 + c];
+            const unsigned jc = base + c0 + c;
+            const double d = __dsub_rn(sc, s_b);
+            // ahead: s_j > s_b, or the same arclength and a lower index (never b itself).  A candidate past the fleet's end has key -1
+            const bool take = kc == key_b && (sc > s_b || (sc == s_b && jc < b)) && d < best;
+            best = take ? d : best;
+            bj = take ? (int)jc : bj;
+        }
+    }
+    __syncthreads();
+    t_s[tid] = best;
+    t_key[tid] = bj;
+    __syncthreads();
+    if (wave != 0 || b >= nB) return;
+    for (unsigned q = 1; q < FOLLOW_WAVES; ++q) {   // the waves' shares interleave in j: the full rule
+        const double d = t_s[q * FOLLOW_LANES + lane];
+        const int j = t_key[q * FOLLOW_LANES + lane];
+        const bool take = j >= 0 && (bj < 0 || d < best || (d == best && j < bj));
+        best = take ? d : best;
+        bj = take ? j : bj;
+    }
+
+    const double cap = w.v_cap[b];
+    double v_out = cap, gap = INFINITY, v_j = 0.0;
+    double *st = w.stat ? w.stat + KMPC_FOLLOWSTAT_WORDS * (size_t)b : nullptr;
+    double n_leader = 0.0, n_bound = 0.0, n_contact = 0.0, min_gap = 0.0, max_closing = 0.0;
+    if (st) {
+        n_leader = st[KMPC_FOLLOWSTAT_N_LEADER]; n_bound = st[KMPC_FOLLOWSTAT_N_BOUND]; n_contact = st[KMPC_FOLLOWSTAT_N_CONTACT];
+        min_gap = st[KMPC_FOLLOWSTAT_MIN_GAP]; max_closing = st[KMPC_FOLLOWSTAT_MAX_CLOSING];
+    }
+    if (bj >= 0) {
+        const double *row = w.rows + KMPC_FOLLOW_WORDS * (size_t)b;
+        const double d_min = row[KMPC_FOLLOW_D_MIN], t_h = row[KMPC_FOLLOW_T_HEADWAY], a_b = row[KMPC_FOLLOW_A_BRAKE], k_gap = row[KMPC_FOLLOW_K_GAP];
+        const double v_b = w.speed[(size_t)b * w.speed_stride];
+        v_j = w.speed[(size_t)bj * w.speed_stride];
+        gap = __dsub_rn(best, row[KMPC_FOLLOW_LENGTH]);
+        const double g = __dsub_rn(gap, d_min), gp = g > 0.0 ? g : 0.0;
+        const double at = __dmul_rn(a_b, t_h);
+        const double rad = __dadd_rn(__dadd_rn(__dmul_rn(at, at), __dmul_rn(v_j, v_j)), __dmul_rn(__dmul_rn(2.0, a_b), gp));
+        const double v_safe = __dsub_rn(__dsqrt_rn(rad), at);
+        const double v_gap = __dadd_rn(v_j, __dmul_rn(k_gap, __dsub_rn(g, __dmul_rn(t_h, v_b))));
+        double v_f = v_gap < v_safe ? v_gap : v_safe;
+        v_f = v_f > 0.0 ? v_f : 0.0;
+        const bool bound = v_f < cap;
+        v_out = bound ? v_f : cap;
+        const double closing = __dsub_rn(v_b, v_j);
+        n_leader = __dadd_rn(n_leader, 1.0);
+        n_bound = bound ? __dadd_rn(n_bound, 1.0) : n_bound;
+        n_contact = gap < 0.0 ? __dadd_rn(n_contact, 1.0) : n_contact;
+        min_gap = gap < min_gap ? gap : min_gap;
+        max_closing = closing > max_closing ? closing : max_closing;
+    }
+    w.v_cap_out[b] = v_out;
+    if (w.gap_out) {
+        w.gap_out[2 * (size_t)b] = gap;
+        w.gap_out[2 * (size_t)b + 1] = v_j;
+    }
+    if (w.leader_out) w.leader_out[b] = bj;
+    if (st) {
+        st[KMPC_FOLLOWSTAT_N] = __dadd_rn(st[KMPC_FOLLOWSTAT_N], 1.0);
+        st[KMPC_FOLLOWSTAT_N_LEADER] = n_leader; st[KMPC_FOLLOWSTAT_N_BOUND] = n_bound; st[KMPC_FOLLOWSTAT_N_CONTACT] = n_contact;
+        st[KMPC_FOLLOWSTAT_MIN_GAP] = min_gap; st[KMPC_FOLLOWSTAT_MAX_CLOSING] = max_closing;
+    }
+}
+
+hipError_t kmpc_launch_follow_fleet(const FL &w, hipStream_t st)
+{
+    const unsigned blocks = ((unsigned)w.B + FOLLOW_LANES - 1) / FOLLOW_LANES;
+    return kmpc_launch(kmpc_follow_fleet_kernel, dim3(blocks), dim3(FOLLOW_TILE), 0, st, w);
+}

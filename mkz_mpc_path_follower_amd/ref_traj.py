@@ -346,3 +346,128 @@ class SpeedPlanner:
         else:
             _lib.check(self._lib.kmpc_speed_plan_fleet(self.fleet._h, B, ptr(self.kappa), *tail))
         return out
+
+
+FOLLOW_WORDS = 8
+FOLLOW_FIELDS = ("d_min", "t_headway", "a_brake", "k_gap", "length")   # KMPC_FOLLOW_* words 0 ... 4 of include/kmpc_follow.h, in row order (5 ... 7 are read by nobody)
+FOLLOW_STAT_FIELDS = ("n", "n_leader", "n_bound", "n_contact", "min_gap", "max_closing")   # KMPC_FOLLOWSTAT_* words 0 ... 5, in order
+
+
+def follow_default():
+    """the default following row (5.0, 1.0, 0.7, 0.5, 4.9, 0, 0, 0) as a numpy row [8], from kmpc_follow_default"""
+    return default_row("kmpc_follow_default", FOLLOW_WORDS)
+
+
+def check_follow_rows(rows):
+    """[B,8] host rows -> ValueError unless words 0 ... 4 are finite, t_headway >= 0, a_brake > 0, k_gap >= 0 and length >= 0 (d_min: any finite
+    value).  The kernel cannot refuse a row -- a bad word poisons that vehicle's own cap -- so this says so where the rows are written."""
+    rows = host_rows(rows)
+    if rows.ndim != 2 or rows.shape[1] != FOLLOW_WORDS:
+        raise ValueError("follow rows: [B,8] (%s, three unused words), got %s" % (", ".join(FOLLOW_FIELDS), rows.shape))
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(rows[:, 0:5]).all(1) & (rows[:, 1] >= 0.0) & (rows[:, 2] > 0.0) & (rows[:, 3] >= 0.0) & (rows[:, 4] >= 0.0)
+    if not ok.all():
+        raise ValueError("follow rows: every word finite, t_headway >= 0, a_brake > 0, k_gap >= 0, length >= 0 (vehicle(s) %s)" % rows_of(~ok))
+    return rows
+
+
+def follow_params(B, device=0, **overrides):
+    """[B,8] float64 following rows on `device`: the default row, with each override (`d_min=`, `t_headway=`, `a_brake=`, `k_gap=`, `length=`) a
+    scalar or one value per vehicle.  Validated on the host (check_follow_rows) before anything reaches the device."""
+    return torch.as_tensor(check_follow_rows(table_rows("follow_params", FOLLOW_FIELDS, follow_default(), B, overrides))).to(device_of(device))
+
+
+def fresh_follow_stat(B, device):
+    """[B,8] float64 on `device`: B fresh following records (kmpc_follow_stat_init: zeros, smallest gap +inf)"""
+    rec = np.empty((int(B), FOLLOW_WORDS))
+    _lib.check(_lib.load().kmpc_follow_stat_init(rec.ctypes.data_as(C.POINTER(C.c_double)), int(B)))
+    return torch.from_numpy(rec).to(device)
+
+
+class Follower:
+    """Car following on a waypoint helper's recorded paths (kmpc_follow_fleet, include/kmpc_follow.h): per vehicle the nearest vehicle ahead on
+    its own path by arclength, the gap to it, and a speed cap from the following law.  `grt`: a FleetRefTrajectory (the vehicle's path is
+    grt.path_id[b] at the time of the call) or a GPSRefTrajectory (one path; `rows` is then required, its length is the fleet's size).
+
+    rows [B,8] (follow_params): a public device tensor, read by every cap() as it is -- edit it in place between steps, like fleet.path_id.
+    After a cap(): `gap` [B] (+inf without a leader), `leader_speed` [B] (0 without), `leader` [B] int32 (-1 without); `stat` [B,8] is the
+    running record (FOLLOW_STAT_FIELDS; reset() starts it afresh, summary() downloads it)."""
+
+    def __init__(self, grt, rows=None):
+        if not isinstance(grt, (FleetRefTrajectory, GPSRefTrajectory)):
+            raise ValueError("Follower follows on a GPSRefTrajectory or a FleetRefTrajectory; a %s is neither" % type(grt).__name__)
+        self.fleet, self.device, self._lib = grt, grt.device, grt._lib
+        self._one_path = isinstance(grt, GPSRefTrajectory)
+        if self._one_path:
+            if not (isinstance(rows, torch.Tensor) and rows.dim() == 2):
+                raise ValueError("Follower on a GPSRefTrajectory: rows [B,8] (follow_params) are required, their length is the fleet's size")
+            self.B = int(rows.shape[0])
+        else:
+            self.B = int(grt.path_id.shape[0])
+        self.rows = follow_params(self.B, self.device) if rows is None else rows
+        self._check_rows()
+        dev, B = self.device, self.B
+        self.gap_leader = torch.empty((B, 2), dtype=torch.float64, device=dev)   # gap, the leader's speed: what the kernel writes
+        self.gap_leader[:, 0] = float("inf")
+        self.gap_leader[:, 1] = 0.0
+        self.leader = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self._track = None                                                       # the geometry-only score call's err, seg, closest
+        self._on_path = torch.empty((B,), dtype=torch.bool, device=dev)          # placed by the score call (and `present`, where given)
+        self.reset()
+
+    gap = property(lambda self: self.gap_leader[:, 0])
+    leader_speed = property(lambda self: self.gap_leader[:, 1])
+
+    def _check_rows(self):
+        if not is_buffer(self.rows, torch.float64, (self.B, FOLLOW_WORDS), self.device):
+            raise ValueError("rows must be a contiguous float64 tensor [%d,8] on %s (follow_params; write into it in place)" % (self.B, self.device))
+
+    def reset(self):
+        """a fresh record for every vehicle"""
+        self.stat = fresh_follow_stat(self.B, self.device)
+
+    def summary(self):
+        """the record as named numpy fields [B] (one synchronising download): FOLLOW_STAT_FIELDS, the four counts as integers"""
+        a = self.stat.cpu().numpy()
+        out = {k: a[:, i].copy() for i, k in enumerate(FOLLOW_STAT_FIELDS)}
+        for k in ("n", "n_leader", "n_bound", "n_contact"):
+            out[k] = out[k].astype(np.int64)
+        return out
+
+    def cap(self, state, v_cap, out=None, present=None):
+        """state: device tensor [B,W], X, Y, psi, v first (the plant's [B,8] as it is: no copy); v_cap [B] -> v [B] (`out`, which may be v_cap
+        itself, or a new tensor): v_cap, lowered where the vehicle ahead demands it.  present [B] (uint8 / bool) or None: 0 = not on the road.
+        One geometry-only track_score_batch call for the arclengths, then kmpc_follow_fleet; a vehicle the score call refuses (a path id
+        outside the set, a pose that is not finite) is not on the road.  Asynchronous on torch's current stream."""
+        dev, B = self.device, self.B
+        st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=dev)
+        if not (st.dtype == torch.float64 and st.device == dev and st.dim() == 2 and st.shape[1] >= 4 and (B == 0 or st.stride(1) == 1)
+                and st.stride(0) >= 4):
+            st = torch.as_tensor(st, dtype=torch.float64, device=dev).contiguous()
+        if st.dim() != 2 or st.shape[0] != B or st.shape[1] < 4:
+            raise ValueError("state: expected [%d,W] with X, Y, psi, v in the first four columns, got %s" % (B, tuple(st.shape)))
+        vc = torch.as_tensor(v_cap, dtype=torch.float64, device=dev).contiguous()
+        if tuple(vc.shape) != (B,):
+            raise ValueError("v_cap: expected [%d], got %s" % (B, tuple(vc.shape)))
+        self._check_rows()
+        pid = None if self._one_path else self.fleet.path_id
+        if pid is not None and not is_buffer(pid, torch.int32, (B,), dev):
+            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
+        if present is not None and not is_buffer(present, (torch.uint8, torch.bool), (B,), dev):
+            raise ValueError("present: expected a contiguous uint8 or bool tensor [%d] on %s" % (B, dev))
+        if not is_buffer(self.stat, torch.float64, (B, FOLLOW_WORDS), dev):
+            raise ValueError("stat must stay a contiguous float64 tensor [%d,8] on %s (reset() gives a fresh one)" % (B, dev))
+        if out is None:
+            out = torch.empty((B,), dtype=torch.float64, device=dev)
+        elif not is_buffer(out, torch.float64, (B,), dev):
+            raise ValueError("out: expected a contiguous float64 tensor [%d] on %s" % (B, dev))
+        if B == 0:
+            return out
+        self._track = self.fleet.track_score_batch(st, score=None, out=self._track)
+        torch.ge(self._track["seg"], 0, out=self._on_path)
+        if present is not None:
+            torch.logical_and(self._on_path, present, out=self._on_path)
+        _lib.check(self._lib.kmpc_follow_fleet(dev.index, B, ptr(self._track["err"][:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid),
+                                               ptr(self._on_path), ptr(self.rows), ptr(vc), ptr(out), ptr(self.gap_leader), ptr(self.leader),
+                                               ptr(self.stat), stream(dev)))
+        return out

@@ -51,7 +51,12 @@ road sweep's 48 starts at 6 m/s: a GPS error of sigma (0.1, 0.2, 0.5) m as white
 and with estimator=; a lateral gust of sigma (0.5, 1.0) m/s^2 and tau (0.5, 2, 10) s without observer=, with it at its default q_dist and at 4 x; a
 heading random walk (0, 0.003, 0.01) rad/sqrt(s) on top of GPS outages of 30 and 100 periods with estimator=.
 
+--platoon is the sweep of car following (-> profiles/robustness_sweep_platoon.txt): follower=ref_traj.Follower, platoons of eight on the three paths,
+the leader's target stepping 6 -> 3 -> 6 m/s: T_HEADWAY (0.5, 1.0, 1.5) s x command delay (0, 0.1, 0.3) s x GPS sigma (0, 0.2) m, each cell once as it
+is and once with estimator= and compensator=: smallest gap, contacts, the speed dip of the last follower over that of the first, solves not Optimal.
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
+       python tools/robustness_sweep.py --platoon [out.txt]
        python tools/robustness_sweep.py --wander [out.txt] [steps]
        python tools/robustness_sweep.py --outage [out.txt] [steps]
        python tools/robustness_sweep.py --road-profile [out.txt] [steps]
@@ -878,8 +883,80 @@ def wander_main():
             f.write("\n".join(LINES) + "\n")
 
 
+PL_T, PL_DELAY, PL_SIGMA, PL_SIZE, PL_SPACING = (0.5, 1.0, 1.5), (0, 10, 30), (0.0, 0.2), 8, 20.0
+PL_PHASES = ((6.0, 100), (3.0, 100), (6.0, 150))     # the leader's target [m/s] and for how many periods
+PL_WAYS = ("as it is", "estimator + compensator")
+
+
+def platoon_main():
+    """two loops (as it is; estimator= + compensator= assuming the true delay) of 3 x 3 x 2 cells of three platoons of eight, one per recorded path,
+    each platoon on its own copy of its path (54 paths in the set), started 20 m apart at 6 m/s, vehicle 0 of a platoon in front.  The leader's
+    target steps 6 -> 3 -> 6 m/s (loop.v_target is edited in place between run() calls); the followers' targets stay 6 m/s."""
+    from mkz_mpc_path_follower_amd.ref_traj import Follower, follow_params
+    argv = [a for a in sys.argv if a != "--platoon"]
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    cells = list(itertools.product(range(3), range(3), range(2)))
+    n_pl = 3 * len(cells)
+    B = n_pl * PL_SIZE
+    platoon = np.repeat(np.arange(n_pl), PL_SIZE)               # platoon q: cell q // 3 on a copy of path q % 3
+    rank = np.tile(np.arange(PL_SIZE), n_pl)                    # 0 = the leader, in front
+    ix = np.array(cells)[platoon // 3]                          # [B,3] grid indices: headway, delay, sigma
+    t_h, cd = np.array(PL_T)[ix[:, 0]], np.array(PL_DELAY)[ix[:, 1]]
+    sigma = np.zeros((B, 4))
+    sigma[:, 0] = sigma[:, 1] = np.array(PL_SIGMA)[ix[:, 2]]
+    steps = sum(n for _, n in PL_PHASES)
+    res = {}
+    for way in PL_WAYS:
+        fleet = FleetRefTrajectory([paths[q % 3] for q in range(n_pl)], platoon, traj_horizon=8, traj_dt=0.2)
+        pose = np.empty((B, 3))
+        for b in range(B):
+            tr = fleet.trajectories[platoon[b]]
+            i = int(np.searchsorted(tr[:, 6], 5.0 + PL_SPACING * (PL_SIZE - 1 - rank[b])))
+            pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+        sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2], cmd_delay=cd, cmd_queue_depth=5)
+        sim.state[:, 3] = PL_PHASES[0][0]
+        sensor = SensorModel(B, sigma=sigma, seed=2024)
+        kw = {}
+        if way != "as it is":
+            kw = dict(estimator=Estimator.from_sensor(sensor), compensator=LatencyCompensator(B, cmd_delay=cd, meas_delay=0), estimator_input="history")
+        follower = Follower(fleet, rows=follow_params(B, t_headway=t_h))
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=PL_PHASES[0][0], sensor=sensor, follower=follower, **kw)
+        speed = []
+        for v_lead, n in PL_PHASES:
+            loop.v_target[torch.as_tensor(rank == 0, device=sim.device)] = v_lead
+            speed.append(loop.run(n, history=True)["state"][1:, :, 3])
+        speed = torch.cat(speed, 0).cpu().numpy()               # [steps,B]
+        n0 = PL_PHASES[0][1]
+        dip = speed[n0 - 40:n0].mean(0) - speed[n0:].min(0)     # the settled speed before the step less the lowest speed after it
+        res[way] = dict(f=follower.summary(), s=loop.score_summary(), dip=dip, finite=bool(torch.isfinite(sim.state).all().item()))
+    say("%s: 2 x %d vehicles in %d platoons of %d on the three paths, %d periods of 0.1 s, nominal plant; the leader's target steps %s m/s after %s "
+        "periods; followers at 6 m/s, default following rows but T_HEADWAY; every state finite: %s; latched vehicles: %s (%s)"
+        % (torch.cuda.get_device_name(0), B, n_pl, PL_SIZE, steps, " -> ".join("%g" % v for v, _ in PL_PHASES), " / ".join(str(n) for _, n in PL_PHASES[:-1]),
+           " / ".join(str(res[w]["finite"]) for w in PL_WAYS), " / ".join(str(int((res[w]["s"]["latch_index"] >= 0).sum())) for w in PL_WAYS),
+           " / ".join(PL_WAYS)))
+    say("per cell of three platoons, %s: smallest gap [m], vehicle-periods in contact, speed dip of the last follower / of the first (median of the "
+        "three platoons; below 1: the dip shrinks down the platoon), periods not Optimal per 1000" % " | ".join(PL_WAYS))
+    for c, (t, dl, g) in enumerate(cells):
+        sel = (platoon // 3) == c
+        part = []
+        for w in PL_WAYS:
+            r = res[w]
+            ratio = [r["dip"][(platoon == q) & (rank == PL_SIZE - 1)][0] / r["dip"][(platoon == q) & (rank == 1)][0] for q in range(3 * c, 3 * c + 3)]
+            part.append("%7.3f %5d %6.3f %7.2f" % (r["f"]["min_gap"][sel].min(), r["f"]["n_contact"][sel].sum(), np.median(ratio),
+                                                    1000.0 * r["s"]["n_nonopt"][sel].sum() / max(1, r["s"]["n_live"][sel].sum())))
+        say("   T %.1f s, delay %.1f s, GPS sigma %.1f m   %s" % (PL_T[t], 0.01 * PL_DELAY[dl], PL_SIGMA[g], " | ".join(part)))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 if __name__ == "__main__":
-    if "--wander" in sys.argv[1:]:
+    if "--platoon" in sys.argv[1:]:
+        platoon_main()
+    elif "--wander" in sys.argv[1:]:
         wander_main()
     elif "--outage" in sys.argv[1:]:
         outage_main()
