@@ -213,15 +213,20 @@ int32_t kmpc_solve_batch_host(kmpc_handle *h, int32_t B, const void *z0, const v
 const char *kmpc_last_error(kmpc_handle *h);
 
 /* ---- diagnostics used by tests/ (device pointers, handle dtype) ------------------------------ */
-/* condensed Hessian H [B,2N,2N] (full symmetric, unscaled), gradient g [B,2N], cost J [B] at U [B,N,2] */
+/* condensed Hessian H [B,2N,2N] (full symmetric, unscaled), gradient g [B,2N], cost J [B] at U [B,N,2], as the generic kernel (run-time horizon)
+ * computes them.  On a model = 1 handle `ref` carries k_poly [B,4] as in kmpc_solve_batch_frenet and the kernel's own Frenet functor runs
+ * (N <= 24; a larger N is refused). */
 int32_t kmpc_debug_condense(kmpc_handle *h, int32_t B, const void *z0, const void *ref,
                             const void *v_target, const void *U, int32_t hessian, void *H, void *g,
                             void *J, void *stream);
-/* The KKT pipeline of the kernel kmpc_solve_batch runs for this handle's horizon (compile-time-horizon kernels only: N = 8, 12, ..., 28
- * one wave per problem; N = 32, 36, ..., 48 and 50 four waves): at inputs U [B,N,2], two-sided form weights w [B,5N-2] (>= 0; order: 2N input boxes,
+/* The KKT pipeline of the kernel a solve of this handle runs at this B (kmpc_select; where that is the generic kernel, the compile-time-horizon
+ * kernel of the handle's horizon instead: N = 8, 12, ..., 28 one wave per problem; N = 32, 36, ..., 48 and 50 four waves; N = 8 also four problems
+ * per wave -- the Cartesian model from B >= 1024 with the default kernel_variant, the Frenet model with kernel_variant = 3).  On a model = 1 handle
+ * `ref` carries k_poly [B,4] as in kmpc_solve_batch_frenet (four waves: fp64 only).  At inputs U [B,N,2], two-sided form weights w [B,5N-2] (>= 0; order: 2N input boxes,
  * 2(N-1) rate forms, N speed forms), objective scaling sc > 0 and shift reg >= 0 it assembles
  *     K = sc * H(U) + A^T diag(w) A + reg * I      (H: exact condensed Hessian if hessian = 1, Gauss-Newton if 0)
- * on the matrix cores, factors it (blocked Cholesky) and solves once through the block substitutions:
+ * in registers, factors it (blocked Cholesky on the matrix cores; 16 column steps in the four-per-wave kernel) and solves once through the block
+ * substitutions:
  *     K_out [B,2N,2N] full symmetric, g [B,2N] = grad J(U), x [B,2N] = K^-1 (b - sc*g), ok [B] int32 (0: K not positive definite) */
 int32_t kmpc_debug_kkt(kmpc_handle *h, int32_t B, const void *z0, const void *ref, const void *v_target, const void *u_prev,
                        const void *U, const void *w, const void *b, double sc, double reg, int32_t hessian, void *K_out, void *g,

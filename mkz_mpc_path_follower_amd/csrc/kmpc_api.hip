@@ -463,17 +463,20 @@ extern "C" int32_t kmpc_debug_condense(kmpc_handle *h, int32_t B, const void *z0
                                        const void *U, int32_t hessian, void *H, void *g, void *J, void *stream)
 {
     if (!h || B <= 0 || !z0 || !ref || !v_target || !U || !H || !g || !J) return h ? fail(h, KMPC_ERR_ARG, "kmpc_debug_condense: bad argument") : KMPC_ERR_ARG;
+    const int model = h->cfg.model;
+    if (model == 1 && h->cfg.N > KMPC_GENERIC_FRENET_MAX_N)
+        return fail(h, KMPC_ERR_ARG, "kmpc_debug_condense: the generic kernel's Frenet functor is built for N <= %d (N=%d)", KMPC_GENERIC_FRENET_MAX_N, h->cfg.N);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;  // NULL = the device's default stream, as in HIP
     const KP P = make_kp(h, B, 0, hessian);
     if (h->cfg.dtype == KMPC_F64) {
         KDbg<double> io = {(const double *)z0, (const double *)ref, (const double *)v_target, (const double *)U,
                            (double *)H, (double *)g, (double *)J};
-        HIPCHK(h, kmpc_launch_condense<double>(P, io, st));
+        HIPCHK(h, model == 1 ? kmpc_launch_condense_frenet<double>(P, io, st) : kmpc_launch_condense<double>(P, io, st));
     } else {
         KDbg<float> io = {(const float *)z0, (const float *)ref, (const float *)v_target, (const float *)U,
                           (float *)H, (float *)g, (float *)J};
-        HIPCHK(h, kmpc_launch_condense<float>(P, io, st));
+        HIPCHK(h, model == 1 ? kmpc_launch_condense_frenet<float>(P, io, st) : kmpc_launch_condense<float>(P, io, st));
     }
     return KMPC_OK;
 }
@@ -485,10 +488,19 @@ static int debug_kkt(kmpc_handle *h, int B, const void *z0, const void *ref, con
     const KP P = make_kp(h, B, 0, hessian);
     KDbgK<T> io = {(const T *)z0, (const T *)ref, (const T *)vt, (const T *)up, (const T *)U, (const T *)w, (const T *)b, sc, reg,
                    (T *)K, (T *)g, (T *)x, ok};
-    // the compile-time-horizon kernel of this N, whatever the handle's kernel_variant (= 2: neither the generic nor the four-per-wave kernel)
-    const kmpc_backend backend = kmpc_select(0, 2, P.N, sizeof(T) == 8, B).backend;
-    if (backend == KMPC_BACKEND_FAST) HIPCHK(h, kmpc_launch_fast_kkt<T>(P, io, st));
-    else if (backend == KMPC_BACKEND_WIDE) HIPCHK(h, kmpc_launch_wide_kkt<T>(P, io, st));
+    // the kernel a solve of this handle at this B would run; where that is the generic one (which has no in-register KKT pipeline), the
+    // compile-time-horizon kernel of this N (kernel_variant = 2: neither the generic nor the four-per-wave kernel)
+    const int model = h->cfg.model;
+    kmpc_backend backend = kmpc_select(model, h->cfg.kernel_variant, P.N, sizeof(T) == 8, B).backend;
+    if (backend == KMPC_BACKEND_GENERIC) backend = kmpc_select(model, 2, P.N, sizeof(T) == 8, B).backend;
+    if (backend == KMPC_BACKEND_FAST) HIPCHK(h, model == 1 ? kmpc_launch_fast_kkt_frenet<T>(P, io, st) : kmpc_launch_fast_kkt<T>(P, io, st));
+    else if (backend == KMPC_BACKEND_WIDE) {
+        if constexpr (sizeof(T) == 8) HIPCHK(h, model == 1 ? kmpc_launch_wide_kkt_frenet(P, io, st) : kmpc_launch_wide_kkt<T>(P, io, st));
+        else HIPCHK(h, kmpc_launch_wide_kkt<T>(P, io, st));   // (kmpc_select has no fp32 four-wave answer for the Frenet model)
+    }
+    else if (backend == KMPC_BACKEND_QUAD) HIPCHK(h, kmpc_launch_quad_kkt<T>(P, io, model, st));
+    else if (model == 1 && sizeof(T) != 8 && kmpc_in(kmpc_wide_horizons(), P.N))
+        return fail(h, KMPC_ERR_ARG, "kmpc_debug_kkt: the Frenet model (model = 1) at N=%d runs in fp64 only (no fp32 four-wave Frenet kernel)", P.N);
     else return fail(h, KMPC_ERR_ARG, "kmpc_debug_kkt: no compile-time-horizon kernel for N=%d in this element type", P.N);
     return KMPC_OK;
 }
@@ -499,7 +511,6 @@ extern "C" int32_t kmpc_debug_kkt(kmpc_handle *h, int32_t B, const void *z0, con
 {
     if (!h || B <= 0 || !z0 || !ref || !v_target || !u_prev || !U || !w || !b || !K_out || !g || !x || !ok || !(sc > 0) || !(reg >= 0))
         return h ? fail(h, KMPC_ERR_ARG, "kmpc_debug_kkt: bad argument") : KMPC_ERR_ARG;
-    if (h->cfg.model != 0) return fail(h, KMPC_ERR_ARG, "kmpc_debug_kkt: Cartesian model only");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     if (h->cfg.dtype == KMPC_F64) return debug_kkt<double>(h, B, z0, ref, v_target, u_prev, U, w, b, sc, reg, hessian, K_out, g, x, ok, st);

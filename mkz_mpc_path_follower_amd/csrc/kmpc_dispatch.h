@@ -86,6 +86,11 @@ template <typename T> hipError_t kmpc_launch_condense(const KP &, const KDbg<T> 
 template <typename T> hipError_t kmpc_launch_probe(const T *, const T *, T *, hipStream_t);
 template <typename T> hipError_t kmpc_launch_fast_kkt(const KP &, const KDbgK<T> &, hipStream_t);
 template <typename T> hipError_t kmpc_launch_wide_kkt(const KP &, const KDbgK<T> &, hipStream_t);
+// ... of the Frenet functor and of the four-per-wave kernel: the *.blocks.o objects (the four solver units once more with -DKMPC_KKT_BLOCKS; csrc/Makefile)
+template <typename T> hipError_t kmpc_launch_condense_frenet(const KP &, const KDbg<T> &, hipStream_t);
+template <typename T> hipError_t kmpc_launch_fast_kkt_frenet(const KP &, const KDbgK<T> &, hipStream_t);
+hipError_t kmpc_launch_wide_kkt_frenet(const KP &, const KDbgK<double> &, hipStream_t);   // fp64 only, as the solve
+template <typename T> hipError_t kmpc_launch_quad_kkt(const KP &, const KDbgK<T> &, int model, hipStream_t);
 // start order and packed records (kmpc_schedule.hip)
 template <typename T> hipError_t kmpc_launch_schedule(int B, int N, double dt, const T *z0, size_t zs, const T *ref, size_t rs, uint32_t *hist, uint32_t *hist_next,
                                                       uint32_t *tag, int32_t *perm, hipStream_t st);

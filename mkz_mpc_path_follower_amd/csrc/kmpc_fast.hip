@@ -561,10 +561,12 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? 3 : 5) void kmpc_solve_fast_de
 
 // diagnostics (tests/test_gpu_kernels.py): the KKT pipeline of THIS kernel -- roll-out, costates, condensing, in-register KKT
 // assembly, blocked Cholesky, block substitutions -- at a given point, form weights, scaling and shift
-template <typename T, int N>
-__global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : (N <= 20 ? 4 : 3)) void kmpc_fast_kkt_kernel(KP P, KDbgK<T> io)
+// (MODEL = 1: io.ref carries k_poly [B,4]; the register bounds of the Frenet solve kernel below)
+template <typename T, int N, int MODEL = 0>
+__global__ __launch_bounds__(64, MODEL == 0 ? (sizeof(T) == 8 ? 2 : (N <= 20 ? 4 : 3))
+                                            : (sizeof(T) == 8 ? (N >= 28 ? 1 : 2) : (N <= 20 ? 4 : (N >= 28 ? 2 : 3)))) void kmpc_fast_kkt_kernel(KP P, KDbgK<T> io)
 {
-    typedef FastSolver<T, N> SV;
+    typedef FastSolver<T, N, MODEL> SV;
     typedef typename SV::acc_t acc_t;
     constexpr int n = SV::n, nf = SV::nf;
     __shared__ __attribute__((aligned(16))) unsigned char smem[SV::lds_elems() * sizeof(T)];
@@ -615,6 +617,18 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? (N >= 28 ? 1 : 2) : (N <= 20 ?
 }
 
 // ---- launchers (called from kmpc_api.hip): everything else than kmpc_fast_horizons runs another kernel ----------------------------------------------
+#ifdef KMPC_KKT_BLOCKS
+// The diagnostics of the Frenet functor are an object file of their own (this file once more, with -DKMPC_KKT_BLOCKS: csrc/Makefile), so that the
+// translation unit of the solve kernels holds exactly the instantiations it held before them -- the solve kernels' code does not move.
+template <typename T> hipError_t kmpc_launch_fast_kkt_frenet(const KP &P, const KDbgK<T> &io, hipStream_t st)
+{
+    return kmpc_dispatch(kmpc_fast_horizons(), P.N, hipErrorInvalidValue, [&](auto n) {
+        return kmpc_launch(&kmpc_fast_kkt_kernel<T, decltype(n)::value, 1>, dim3(P.B), dim3(64), 0, st, P, io);
+    });
+}
+template hipError_t kmpc_launch_fast_kkt_frenet<double>(const KP &, const KDbgK<double> &, hipStream_t);
+template hipError_t kmpc_launch_fast_kkt_frenet<float>(const KP &, const KDbgK<float> &, hipStream_t);
+#else
 template <typename T> hipError_t kmpc_launch_fast_kkt(const KP &P, const KDbgK<T> &io, hipStream_t st)
 {
     return kmpc_dispatch(kmpc_fast_horizons(), P.N, hipErrorInvalidValue, [&](auto n) {
@@ -638,3 +652,4 @@ template <typename T> hipError_t kmpc_launch_solve_fast(const KP &P, const KIO<T
 }
 template hipError_t kmpc_launch_solve_fast<double>(const KP &, const KIO<double> &, int, bool, hipStream_t);
 template hipError_t kmpc_launch_solve_fast<float>(const KP &, const KIO<float> &, int, bool, hipStream_t);
+#endif

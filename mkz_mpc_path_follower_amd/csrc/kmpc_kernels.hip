@@ -1021,11 +1021,12 @@ __global__ __launch_bounds__(64) void kmpc_solve_par_kernel(KP P, KIO<T> io)
 }
 
 // diagnostics: condensed Hessian / gradient / cost at a given U (used by the parity tests)
-template <typename T, int NT>
+// (MODEL = 1: io.ref carries k_poly [B,4]; this kernel's own Frenet functor -- eval_frenet, linearize_frenet, condense_dense)
+template <typename T, int NT, int MODEL = 0>
 __global__ __launch_bounds__(64) void kmpc_condense_kernel(KP P, KDbg<T> io)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    typedef Solver<T, NT> SV;
+    typedef Solver<T, NT, MODEL> SV;
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= P.B) return;
     T scalars[16], params[32];
@@ -1089,6 +1090,18 @@ template <auto KERNEL, typename T, typename IO> static hipError_t launch_dynamic
     return kmpc_launch(KERNEL, dim3(P.B), dim3(64), lds, st, P, io);
 }
 
+#ifdef KMPC_KKT_BLOCKS
+// the condensing diagnostics of the Frenet functor: an object file of their own (this file with -DKMPC_KKT_BLOCKS; see kmpc_fast.hip)
+template <typename T> hipError_t kmpc_launch_condense_frenet(const KP &P, const KDbg<T> &io, hipStream_t st)
+{
+    return kmpc_dispatch(kmpc_generic_frenet_tiles(), (2 * P.N + 15) / 16, hipErrorInvalidValue, [&](auto t) {
+        constexpr int NT = decltype(t)::value;
+        return launch_dynamic_lds<&kmpc_condense_kernel<T, NT, 1>, T>(P, NT, io, st);
+    });
+}
+template hipError_t kmpc_launch_condense_frenet<double>(const KP &, const KDbg<double> &, hipStream_t);
+template hipError_t kmpc_launch_condense_frenet<float>(const KP &, const KDbg<float> &, hipStream_t);
+#else
 // the Frenet functor is built for horizons up to N = 24 (kmpc_generic_frenet_tiles; the reference's is N = 8)
 template <typename T> hipError_t kmpc_launch_solve(const KP &P, const KIO<T> &io, int model, hipStream_t st)
 {
@@ -1121,3 +1134,4 @@ template hipError_t kmpc_launch_condense<double>(const KP &, const KDbg<double> 
 template hipError_t kmpc_launch_condense<float>(const KP &, const KDbg<float> &, hipStream_t);
 template hipError_t kmpc_launch_probe<double>(const double *, const double *, double *, hipStream_t);
 template hipError_t kmpc_launch_probe<float>(const float *, const float *, float *, hipStream_t);
+#endif

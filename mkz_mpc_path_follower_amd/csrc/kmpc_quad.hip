@@ -210,7 +210,7 @@ template <typename T, int MODEL = 0, bool ROWPT = false> struct QuadSolver {
 
     // ---- KKT: K = sc*(H + input Hessian) + A^T W A + reg*I, one row per lane, Cholesky + the affine right-hand side in one sweep ------------
     // (needs stage_form_weights(w) done: wb = form weights, cb = suffix sums of the speed weights)
-    DEV bool kkt_factor(T sc, T reg, bool want_hmax)
+    DEV bool kkt_factor(T sc, T reg, bool want_hmax, T *Kdump = nullptr)
     {
         if constexpr (MODEL == 1) condense_frenet(sc);
         else ipm::condense_adjoint(*this, sc);   // column j (rows >= j) of sc*H into the row's packed image
@@ -231,6 +231,11 @@ template <typename T, int MODEL = 0, bool ROWPT = false> struct QuadSolver {
             v += k == i ? dgs[k] : (T)0;
             if (k < 14) v += k == i - 2 ? sbs[k] : (T)0;
             a[k] = low ? v : (T)0;
+        }
+        if (Kdump) {  // diagnostics only (kmpc_debug_kkt): the assembled matrix, full symmetric n x n
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k <= i) { Kdump[i * n + k] = a[k]; Kdump[k * n + i] = a[k]; }
         }
         T b = -sc * gb[i];
         WFENCE();   // image, dgs / sbs consumed: the exchange buffer and (later) the image may be overwritten
@@ -390,6 +395,48 @@ __global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_solve_quad_fr
     kmpc_solve_quad_par_body<T, 1>(P, io, smem);
 }
 
+// diagnostics (tests/test_kkt_blocks.py): the KKT pipeline of this kernel -- roll-out, costates, condensing, one matrix row per lane, the 16-step
+// Cholesky with the right-hand side riding along, the 4x4 block inverses and the block substitutions -- at a given point, form weights, scaling and
+// shift, four problems per wave as in the solve.  The spare rows of the last wave repeat the last problem and write nothing.
+template <typename T, int MODEL>
+__global__ __launch_bounds__(64, sizeof(T) == 8 ? 2 : 4) void kmpc_quad_kkt_kernel(KP P, KDbgK<T> io)
+{
+    typedef QuadSolver<T, MODEL> SV;
+    constexpr int n = SV::n, nf = SV::nf;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[SV::lds_elems() * sizeof(T)];
+    const int slot = 4 * (int)blockIdx.x + ((int)threadIdx.x >> 4);
+    if (4 * (int)blockIdx.x >= P.B) return;
+    const bool live = slot < P.B;
+    const int b = live ? slot : P.B - 1;
+    SV sv(P, smem);
+    StageV<T> St;
+    const T g = ipm::debug_linearize_at(sv, P, io, b, St);
+    const T sc = (T)io.sc, reg = (T)io.reg;
+    const int lane = sv.lane;
+    T w[SV::NF];
+#pragma unroll
+    for (int i = 0; i < SV::NF; ++i) { const int f = lane + 16 * i; w[i] = f < nf ? io.w[(size_t)b * nf + f] : (T)0; }
+    sv.stage_form_weights(w);
+    const bool okf = sv.kkt_factor(sc, reg, false, live ? io.K + (size_t)b * n * n : nullptr);
+    // (every row runs the substitutions, on whatever its factor holds: a row that was refused reports zero, and no row waits for another)
+    const T xs = sv.kkt_direction1(io.b[(size_t)b * n + lane]);
+    if (live) {
+        io.g[(size_t)b * n + lane] = g;
+        io.x[(size_t)b * n + lane] = okf ? xs : (T)0;
+        if (lane == 0) io.ok[b] = okf ? 1 : 0;
+    }
+}
+#ifdef KMPC_KKT_BLOCKS
+// an object file of its own (this file with -DKMPC_KKT_BLOCKS; see kmpc_fast.hip): the solve kernels' translation unit stays what it was
+template <typename T> hipError_t kmpc_launch_quad_kkt(const KP &P, const KDbgK<T> &io, int model, hipStream_t st)
+{
+    if (P.N != KMPC_QUAD_HORIZON) return hipErrorInvalidValue;
+    return kmpc_launch(model == 1 ? &kmpc_quad_kkt_kernel<T, 1> : &kmpc_quad_kkt_kernel<T, 0>, dim3((P.B + 3) / 4), dim3(64), 0, st, P, io);
+}
+template hipError_t kmpc_launch_quad_kkt<double>(const KP &, const KDbgK<double> &, int, hipStream_t);
+template hipError_t kmpc_launch_quad_kkt<float>(const KP &, const KDbgK<float> &, int, hipStream_t);
+#else
+
 // launcher (called from kmpc_api.hip): P.B problems in ceil(P.B / 4) waves
 template <typename T> hipError_t kmpc_launch_solve_quad(const KP &P, const KIO<T> &io, int model, hipStream_t st)
 {
@@ -400,3 +447,4 @@ template <typename T> hipError_t kmpc_launch_solve_quad(const KP &P, const KIO<T
 }
 template hipError_t kmpc_launch_solve_quad<double>(const KP &, const KIO<double> &, int, hipStream_t);
 template hipError_t kmpc_launch_solve_quad<float>(const KP &, const KIO<float> &, int, hipStream_t);
+#endif

@@ -568,10 +568,11 @@ __global__ __launch_bounds__(256, 2) void kmpc_solve_wide_frenet_par_kernel(KP P
 }
 
 // diagnostics (tests/test_gpu_kernels.py): the KKT pipeline of this kernel at a given point, form weights, scaling and shift
-template <typename T, int N>
+// (MODEL = 1: io.ref carries k_poly [B,4]; fp64 only, as the Frenet solve kernel)
+template <typename T, int N, int MODEL = 0>
 __global__ __launch_bounds__(256, 2) void kmpc_wide_kkt_kernel(KP P, KDbgK<T> io)
 {
-    typedef WideSolver<T, N> SV;
+    typedef WideSolver<T, N, MODEL> SV;
     constexpr int n = SV::n, nf = SV::nf;
     __shared__ __attribute__((aligned(16))) unsigned char smem[SV::lds_elems() * sizeof(T)];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -597,6 +598,15 @@ __global__ __launch_bounds__(256, 2) void kmpc_wide_kkt_kernel(KP P, KDbgK<T> io
     if (tid == 0) io.ok[b] = okf ? 1 : 0;
 }
 // ---- launchers (called from kmpc_api.hip) --------------------------------------------------------------------------------------------------------------
+#ifdef KMPC_KKT_BLOCKS
+// the diagnostics of the Frenet functor: an object file of their own (this file with -DKMPC_KKT_BLOCKS; see kmpc_fast.hip), fp64 only like the solve
+hipError_t kmpc_launch_wide_kkt_frenet(const KP &P, const KDbgK<double> &io, hipStream_t st)
+{
+    return kmpc_dispatch(kmpc_wide_horizons(), P.N, hipErrorInvalidValue, [&](auto n) {
+        return kmpc_launch(&kmpc_wide_kkt_kernel<double, decltype(n)::value, 1>, dim3(P.B), dim3(256), 0, st, P, io);
+    });
+}
+#else
 template <typename T> hipError_t kmpc_launch_wide_kkt(const KP &P, const KDbgK<T> &io, hipStream_t st)
 {
     return kmpc_dispatch(kmpc_wide_horizons(), P.N, hipErrorInvalidValue, [&](auto n) {
@@ -621,3 +631,4 @@ template <typename T> hipError_t kmpc_launch_solve_wide(const KP &P, const KIO<T
 }
 template hipError_t kmpc_launch_solve_wide<double>(const KP &, const KIO<double> &, int, hipStream_t);
 template hipError_t kmpc_launch_solve_wide<float>(const KP &, const KIO<float> &, int, hipStream_t);
+#endif

@@ -202,11 +202,16 @@ class BatchMPC:
         return o
 
     # ---- diagnostics for tests ------------------------------------------------------------------
+    def _second_shape(self):
+        """per-problem shape of the second input: the reference [N+1,3], or k_poly [4] on a model = 1 handle"""
+        return (4,) if self.cfg.model == 1 else (self.N + 1, 3)
+
     def debug_condense(self, z0, ref, v_target, U, hessian=1):
+        """kmpc_debug_condense: H, g, J of the generic kernel at U (`ref`: k_poly [B,4] on a model = 1 handle)"""
         N = self.N
         z0 = self._dev(z0, (len(z0), 4))
         B = z0.shape[0]
-        ref = self._dev(ref, (B, N + 1, 3))
+        ref = self._dev(ref, (B,) + self._second_shape())
         v_target = self._dev(v_target, (B,))
         U = self._dev(U, (B, N, 2))
         H = torch.zeros((B, 2 * N, 2 * N), dtype=self.dtype, device=self.device)
@@ -218,11 +223,12 @@ class BatchMPC:
         return H, g, J
 
     def debug_kkt(self, z0, ref, v_target, u_prev, U, w, b, sc=1.0, reg=0.0, hessian=1):
-        """kmpc_debug_kkt: K = sc*H(U) + A^T diag(w) A + reg*I as the solve kernel assembles it, gradient, K^-1 (b - sc*g), PD flag"""
+        """kmpc_debug_kkt: K = sc*H(U) + A^T diag(w) A + reg*I as the solve kernel assembles it, gradient, K^-1 (b - sc*g), PD flag
+        (`ref`: k_poly [B,4] on a model = 1 handle)"""
         N = self.N
         z0 = self._dev(z0, (len(z0), 4))
         B = z0.shape[0]
-        ref = self._dev(ref, (B, N + 1, 3))
+        ref = self._dev(ref, (B,) + self._second_shape())
         v_target = self._dev(v_target, (B,))
         u_prev = self._dev(u_prev, (B, 2))
         U = self._dev(U, (B, N, 2))

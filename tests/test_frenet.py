@@ -78,6 +78,65 @@ def test_frenet_oracle_vs_scipy(oracle):
         assert abs(res.fun - r["cost"]) <= 2e-6 * max(1.0, abs(r["cost"])), (res.fun, r["cost"])
 
 
+@pytest.mark.parametrize("N", [8, 20, 50])
+def test_frenet_gradient_and_hessian_against_finite_differences(oracle, N):
+    """tests/test_oracle.py::test_gradient_and_hessian_against_finite_differences for the Frenet functor, at the draws the block tests of
+    tests/test_kkt_blocks.py use (_cases(6, N, seed=21), accelerations within +-0.8, steering within +-0.3): O.condense(hessian=1) against central
+    differences (step 1e-6) of O.cost and O.grad, with the Cartesian test's bounds, 1e-5 on the gradient and 1e-6 on the Hessian; symmetry, g == O.grad,
+    J == O.cost, Gauss-Newton part positive semidefinite.  Worst relative errors seen: gradient 8e-11 / 2e-10 / 1.1e-7, Hessian 7e-11 / 3e-10 / 1.4e-7
+    at N = 8 / 20 / 50 -- the N = 50 figures are the noise of differencing a 100-input roll-out (rounding of a cost of ~1e4 over a 2e-6 step), not an
+    error of the oracle: they grow with the horizon, not with the step."""
+    O = oracle
+    p = O.params(N, model=1)
+    z0, kp, vt, up = _cases(6, N, seed=21)
+    rng = np.random.default_rng(5)
+    Ub = np.stack([rng.uniform(-0.8, 0.8, (6, N)), rng.uniform(-0.3, 0.3, (6, N))], axis=-1)
+    h = 1e-6
+    worst_g = worst_H = 0.0
+    for b in range(6):
+        q = O.problem_frenet(p, z0[b], kp[b], vt[b], up[b])
+        U = Ub[b]
+        g = O.grad(p, q, U)
+        H, g2, J = O.condense(p, q, U, hessian=1)
+        assert np.abs(g - g2).max() < 1e-9 * max(1, np.abs(g).max())
+        assert abs(J - O.cost(p, q, U)) < 1e-12 * max(1, J)
+        gfd = np.zeros(2 * N)
+        Hfd = np.zeros((2 * N, 2 * N))
+        for j in range(2 * N):
+            e = np.zeros(2 * N)
+            e[j] = h
+            Up, Um = (U.ravel() + e).reshape(N, 2), (U.ravel() - e).reshape(N, 2)
+            gfd[j] = (O.cost(p, q, Up) - O.cost(p, q, Um)) / (2 * h)
+            Hfd[:, j] = (O.grad(p, q, Up) - O.grad(p, q, Um)) / (2 * h)
+        eg, eH = np.abs(g - gfd).max() / max(1, np.abs(g).max()), np.abs(H - Hfd).max() / np.abs(H).max()
+        worst_g, worst_H = max(worst_g, eg), max(worst_H, eH)
+        assert eg < 1e-5, (b, eg)
+        assert eH < 1e-6, (b, eH)
+        assert np.abs(H - H.T).max() < 1e-9 * np.abs(H).max()
+        Hgn = O.condense(p, q, U, hessian=0)[0]
+        assert np.linalg.eigvalsh(Hgn).min() > -1e-8 * np.abs(Hgn).max()  # Gauss-Newton part is PSD
+    print("N=%d: worst relative error of the gradient %.1e, of the Hessian %.1e" % (N, worst_g, worst_H))
+
+
+@pytest.mark.parametrize("N", [8, 20, 50])
+def test_both_models_share_one_forms_matrix(oracle, N):
+    """The two models constrain the same linear forms of the inputs: O.ineq returns the same A for model = 0 and model = 1, and its 10N-4 one-sided
+    rows are the 5N-2 two-sided forms of tests/test_gpu_kernels.py::_forms_matrix, each once with either sign.  This is what lets the Frenet block tests
+    build A^T diag(w) A from _forms_matrix."""
+    from test_gpu_kernels import _forms_matrix
+    O = oracle
+    p0, p1 = O.params(N), O.params(N, model=1)
+    z0, kp, vt, up = _cases(2, N, seed=21)
+    ref = np.zeros((N + 1, 3))
+    for b in range(2):
+        A0, _ = O.ineq(p0, O.problem(p0, z0[b], ref, vt[b], up[b]))
+        A1, _ = O.ineq(p1, O.problem_frenet(p1, z0[b], kp[b], vt[b], up[b]))
+        assert A0.shape == (10 * N - 4, 2 * N) and np.array_equal(A0, A1)
+    F = _forms_matrix(N, dt=p1.dt)
+    want = sorted(map(tuple, np.concatenate([F, -F]) + 0.0))   # (+ 0.0: no negative zeros)
+    assert sorted(map(tuple, A1 + 0.0)) == want
+
+
 def test_curvature_polynomial_fit_recovers_a_known_curvature():
     """nav_msgs_path_frenet.py:44-86 restated: waypoints on a clothoid-like path with K(s) = 0.01 + 0.002 s are fitted back to a
     polynomial whose curvature matches over the fitted range (the double cubic fit is approximate by construction)"""
