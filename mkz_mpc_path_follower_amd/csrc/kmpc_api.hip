@@ -692,6 +692,14 @@ static int32_t queue_args(const char *fn, int32_t depth, int64_t period, const v
     return KMPC_OK;
 }
 
+// the plant calls' argument block: what every kind or every kind with rows has; the road and drive entries add their own words
+static PlantCall plant_call(int32_t B, int32_t n_updates, void *state, const void *cmd, const void *plant, const int32_t *cmd_delay, void *cmd_log,
+                            int32_t depth, int64_t period)
+{
+    return {B, n_updates, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_log, depth, (long long)period,
+            nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+
 // ---- tracking errors and the running score record (kmpc_track_score.hip) ----------------------------------------------
 extern "C" int32_t kmpc_track_score_init(double *score_host, int32_t B)
 {
@@ -864,7 +872,8 @@ extern "C" int32_t kmpc_sim_advance_batch(int32_t device, int32_t B, void *state
 {
     if (B < 0 || n_updates < 0 || (B > 0 && (!state || !cmd))) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_batch: bad argument (B=%d, n_updates=%d)", B, n_updates);
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    return on_device("kmpc_sim_advance_batch", device, [&] { return kmpc_launch_sim(B, (double *)state, (const double *)cmd, n_updates, (hipStream_t)stream); });
+    const PlantCall k = plant_call(B, n_updates, state, cmd, nullptr, nullptr, nullptr, 0, 0);
+    return on_device("kmpc_sim_advance_batch", device, [&] { return kmpc_launch_plant(KMPC_PLANT_FIXED, k, (hipStream_t)stream); });
 }
 
 // the reference's plant constants (vehicle_simulator.py:61-67, :112-113): the one place they exist for the per-vehicle plant
@@ -883,9 +892,8 @@ extern "C" int32_t kmpc_sim_advance_plant(int32_t device, int32_t B, void *state
     if (rc != KMPC_OK) return rc;
     if (B > 0 && cmd_delay && !cmd_held) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_plant: cmd_delay needs cmd_held");
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    return on_device("kmpc_sim_advance_plant", device, [&] {
-        return kmpc_launch_sim_plant(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_held, n_updates, (hipStream_t)stream);
-    });
+    const PlantCall k = plant_call(B, n_updates, state, cmd, plant, cmd_delay, cmd_held, 0, 0);
+    return on_device("kmpc_sim_advance_plant", device, [&] { return kmpc_launch_plant(KMPC_PLANT_ROWS, k, (hipStream_t)stream); });
 }
 
 extern "C" int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period, int64_t id_base,
@@ -895,7 +903,8 @@ extern "C" int32_t kmpc_sense_batch(int32_t device, int32_t B, const void *state
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_batch: bad argument (B=%d, period=%lld, id_base=%lld)", B, (long long)period, (long long)id_base);
     if (B == 0) return KMPC_OK;
     return on_device("kmpc_sense_batch", device, [&] {
-        return kmpc_launch_sense(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, (double *)est, (hipStream_t)stream);
+        return kmpc_launch_sense(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, nullptr, nullptr, 0, (double *)est,
+                                 (hipStream_t)stream);
     });
 }
 
@@ -906,10 +915,8 @@ extern "C" int32_t kmpc_sim_advance_queue(int32_t device, int32_t B, void *state
     if (rc != KMPC_OK) return rc;
     if ((rc = queue_args("kmpc_sim_advance_queue", depth, period, cmd_queue)) != KMPC_OK) return rc;
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    return on_device("kmpc_sim_advance_queue", device, [&] {
-        return kmpc_launch_sim_queue(B, (double *)state, (const double *)cmd, (const double *)plant, cmd_delay, (double *)cmd_queue, depth, (long long)period,
-                                     n_updates, (hipStream_t)stream);
-    });
+    const PlantCall k = plant_call(B, n_updates, state, cmd, plant, cmd_delay, cmd_queue, depth, period);
+    return on_device("kmpc_sim_advance_queue", device, [&] { return kmpc_launch_plant(KMPC_PLANT_QUEUE, k, (hipStream_t)stream); });
 }
 
 // the neutral road row: no grip limit, a flat and level road, no steering offset, the acceleration as commanded
@@ -929,10 +936,9 @@ extern "C" int32_t kmpc_sim_advance_road(int32_t device, int32_t B, void *state,
     if (rc != KMPC_OK) return rc;
     if ((rc = queue_args("kmpc_sim_advance_road", depth, period, cmd_queue)) != KMPC_OK) return rc;
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    return on_device("kmpc_sim_advance_road", device, [&] {
-        return kmpc_launch_sim_road(B, (double *)state, (const double *)cmd, (const double *)plant, (const double *)road, cmd_delay, (double *)cmd_queue, depth,
-                                    (long long)period, n_updates, (double *)road_stat, (hipStream_t)stream);
-    });
+    PlantCall k = plant_call(B, n_updates, state, cmd, plant, cmd_delay, cmd_queue, depth, period);
+    k.road = (const double *)road; k.road_stat = (double *)road_stat;
+    return on_device("kmpc_sim_advance_road", device, [&] { return kmpc_launch_plant(KMPC_PLANT_ROAD, k, (hipStream_t)stream); });
 }
 
 // ---- low-level controller and pedal-driven plant (kmpc_drive.hip) ----------------------------------------------------
@@ -976,11 +982,10 @@ extern "C" int32_t kmpc_sim_advance_drive(int32_t device, int32_t B, void *state
     if (B > 0 && (!drive || !llc || !llc_rec)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sim_advance_drive: null drive rows, llc rows or llc_rec");
     if ((rc = queue_args("kmpc_sim_advance_drive", depth, period, cmd_queue)) != KMPC_OK) return rc;
     if (B == 0 || n_updates == 0) return KMPC_OK;
-    return on_device("kmpc_sim_advance_drive", device, [&] {
-        return kmpc_launch_sim_drive(B, (double *)state, (const double *)cmd, (const double *)plant, (const double *)road, (const double *)drive,
-                                     (const double *)llc, (double *)llc_rec, cmd_delay, (double *)cmd_queue, depth, (long long)period, n_updates, (double *)road_stat,
-                                     (hipStream_t)stream);
-    });
+    PlantCall k = plant_call(B, n_updates, state, cmd, plant, cmd_delay, cmd_queue, depth, period);
+    k.road = (const double *)road; k.road_stat = (double *)road_stat;
+    k.drive = (const double *)drive; k.llc_rows = (const double *)llc; k.llc_rec = (double *)llc_rec;
+    return on_device("kmpc_sim_advance_drive", device, [&] { return kmpc_launch_plant(KMPC_PLANT_DRIVE, k, (hipStream_t)stream); });
 }
 
 extern "C" int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const void *state, const void *sensor, uint64_t seed, int64_t period,
@@ -992,8 +997,8 @@ extern "C" int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const voi
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_delayed_batch: bad ring (depth=%d, at least 1; meas_delay and truth_ring are required)", depth);
     if (B == 0) return KMPC_OK;
     return on_device("kmpc_sense_delayed_batch", device, [&] {
-        return kmpc_launch_sense_delayed(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, meas_delay,
-                                         (double *)truth_ring, depth, (double *)est, (hipStream_t)stream);
+        return kmpc_launch_sense(B, (const double *)state, (const double *)sensor, seed, (uint64_t)period, (uint64_t)id_base, meas_delay,
+                                 (double *)truth_ring, depth, (double *)est, (hipStream_t)stream);
     });
 }
 

@@ -95,31 +95,38 @@ template <typename T> hipError_t kmpc_launch_quad_kkt(const KP &, const KDbgK<T>
 template <typename T> hipError_t kmpc_launch_schedule(int B, int N, double dt, const T *z0, size_t zs, const T *ref, size_t rs, uint32_t *hist, uint32_t *hist_next,
                                                       uint32_t *tag, int32_t *perm, hipStream_t st);
 template <typename T> hipError_t kmpc_launch_pack(int B, int N, int stride, const T *z0, const T *ref, const T *vt, const T *up, T *rec, hipStream_t st);
-// closed-loop simulator (kmpc_sim.hip)
-hipError_t kmpc_launch_sim(int B, double *state, const double *cmd, int n_updates, hipStream_t st);
-hipError_t kmpc_launch_sim_plant(int B, double *state, const double *cmd, const double *plant, const int32_t *cmd_delay, double *cmd_held,
-                                 int n_updates, hipStream_t st);
-hipError_t kmpc_launch_sense(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base, double *est,
-                             hipStream_t st);
-hipError_t kmpc_launch_sim_queue(int B, double *state, const double *cmd, const double *plant, const int32_t *cmd_delay, double *cmd_queue, int depth,
-                                 long long period, int n_updates, hipStream_t st);
-hipError_t kmpc_launch_sense_delayed(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base,
-                                     const int32_t *meas_delay, double *truth_ring, int depth, double *est, hipStream_t st);
-hipError_t kmpc_launch_sim_road(int B, double *state, const double *cmd, const double *plant, const double *road, const int32_t *cmd_delay,
-                                double *cmd_queue, int depth, long long period, int n_updates, double *road_stat, hipStream_t st);
-// measurement stage with sensor faults (kmpc_sense_faults.hip); meas_delay and truth_ring both NULL: no ring
+// closed-loop simulator: the five plants (kmpc_sim.hip; the pedal-driven plant's kernel: kmpc_drive.hip) behind one argument block
+// FIXED reads B, state, cmd, n_updates; ROWS also plant, cmd_delay, cmd_log = cmd_held; QUEUE also depth, period, with cmd_log = cmd_queue; ROAD also
+// road, road_stat; DRIVE also drive, llc_rows, llc_rec
+enum kmpc_plant_kind { KMPC_PLANT_FIXED, KMPC_PLANT_ROWS, KMPC_PLANT_QUEUE, KMPC_PLANT_ROAD, KMPC_PLANT_DRIVE };
+struct PlantCall {
+    int B, n_updates;
+    double *state;             // [B,8] in/out
+    const double *cmd;         // [B,2]
+    const double *plant;       // [B,8] KMPC_PLANT_*
+    const int32_t *cmd_delay;  // [B] or null
+    double *cmd_log;           // the held command [B,2] (or null: no delay), or the ring [depth,B,2]
+    int depth;                 // periods in the ring
+    long long period;
+    const double *road;        // [B,8] KMPC_ROAD_*
+    double *road_stat;         // [B,4] in/out KMPC_ROAD_STAT_*, or null
+    const double *drive;       // [B,8] KMPC_DRIVE_*
+    const double *llc_rows;    // [B,8] KMPC_LLC_*
+    double *llc_rec;           // [B,16] in/out KMPC_LLCREC_*
+};
+hipError_t kmpc_launch_plant(kmpc_plant_kind kind, const PlantCall &k, hipStream_t st);
+// measurement stage (kmpc_sim.hip), and with sensor faults (kmpc_sense_faults.hip); meas_delay and truth_ring both NULL: no ring
+hipError_t kmpc_launch_sense(int B, const double *state, const double *sensor, uint64_t seed, uint64_t period, uint64_t id_base,
+                             const int32_t *meas_delay, double *truth_ring, int depth, double *est, hipStream_t st);
 hipError_t kmpc_launch_sense_faults(int B, const double *state, const double *sensor, const double *faults, uint64_t seed, uint64_t period,
                                     uint64_t id_base, const int32_t *meas_delay, double *truth_ring, int depth, double *fault_rec, double *z_out,
                                     double *held_out, int32_t *flags_out, uint8_t *blind_out, hipStream_t st);
 // Gauss-Markov stage (kmpc_wander.hip); each pair (base, out) both NULL or both given
 hipError_t kmpc_launch_wander(int B, const double *wander, double *wander_rec, uint64_t seed, uint64_t period, uint64_t id_base,
                               const double *sensor_base, double *sensor_out, const double *road_base, double *road_out, hipStream_t st);
-// low-level controller and pedal-driven plant (kmpc_drive.hip)
+// low-level controller as a stage of its own (kmpc_drive.hip)
 hipError_t kmpc_launch_llc_step(int B, const double *cmd, const double *speed, int speed_stride, const double *llc_rows, double *llc_rec,
                                 double *pedals_out, hipStream_t st);
-hipError_t kmpc_launch_sim_drive(int B, double *state, const double *cmd, const double *plant, const double *road, const double *drive,
-                                 const double *llc_rows, double *llc_rec, const int32_t *cmd_delay, double *cmd_queue, int depth, long long period,
-                                 int n_updates, double *road_stat, hipStream_t st);
 // delay compensation (kmpc_latency.hip)
 hipError_t kmpc_launch_cmd_in_force(int B, const double *hist, int depth, long long period, int n, const int32_t *cmd_delay, const int32_t *meas_delay,
                                     int max_cmd_delay, int max_meas_delay, double *u_out, hipStream_t st);

@@ -1,7 +1,7 @@
 // kmpc_drive.hip -- the low-level controller as a stage (kmpc_llc_step_batch) and the pedal-driven plant (kmpc_sim_advance_drive), gfx950 only.
 // The reference's test car never received MPC_cmd.accel_cmd as an acceleration: a 50 Hz node (src/LowLevelController.cpp) turned it into a throttle
 // fraction, a brake torque and a steering-wheel angle.  kmpc_llc.h restates that node's control law as one device function; here it runs alone, one
-// thread per controller, and inside the road plant's loop, every second 10 ms update, in front of a powertrain that turns pedals into force.
+// thread per controller, and inside the pedal-driven plant's loop, every second 10 ms update, in front of a powertrain that turns pedals into force.
 // One thread per vehicle, the state, the record and all rows in registers across the call; no lane reads another's row.  include/kmpc.h states the
 // arithmetic; contraction is off, every product and sum rounds on its own.
 #include <hip/hip_runtime.h>
@@ -39,10 +39,12 @@ hipError_t kmpc_launch_llc_step(int B, const double *cmd, const double *speed, i
     return hipGetLastError();
 }
 
-// The pedal-driven plant: kmpc_sim_road_kernel with the controller's tick in front of every even absolute update and the powertrain after every
-// sub-step.  sim_substep<true> runs as it stands, with the tick's tyre-angle target; the acceleration lag it computes is overwritten (and removed by
-// the compiler) by the net acceleration of the powertrain, which the NEXT sub-step's vx integrates exactly as it integrates `acc` today.
-// Per update: one division for the traction limit; per tick: one for the tyre-angle target; none inside the sub-step.
+// The pedal-driven plant: the road plant with the controller's tick in front of every even absolute update and the powertrain after every sub-step.
+// The tick, Fmax and the pedal lags interleave with the sub-step, so this kernel keeps a loop of its own instead of sim_plant_rows'; its prologue and
+// epilogue are the same helpers (load_plant, load_road, load_state, sim_ring_commands, store_state, fold_road_stat: kmpc_plant_step.h).
+// sim_substep<true> runs as it stands, with the tick's tyre-angle target; the acceleration lag it computes is overwritten (and removed by the
+// compiler, K_ACC's load with it) by the net acceleration of the powertrain, which the NEXT sub-step's vx integrates exactly as it integrates `acc`
+// in the other plants.  Per update: one division for the traction limit; per tick: one for the tyre-angle target; none inside the sub-step.
 __global__ __launch_bounds__(256) void kmpc_sim_drive_kernel(int B, double *__restrict__ state, const double *__restrict__ cmd,
                                                              const double *__restrict__ plant, const double *__restrict__ road,
                                                              const double *__restrict__ drive, const double *__restrict__ llc_rows,
@@ -51,15 +53,8 @@ __global__ __launch_bounds__(256) void kmpc_sim_drive_kernel(int B, double *__re
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
-    const double *pr = plant + KMPC_PLANT_WORDS * (size_t)i;
-    const double lf = pr[KMPC_PLANT_LF], lr = pr[KMPC_PLANT_LR], m = pr[KMPC_PLANT_M], Iz = pr[KMPC_PLANT_IZ];
-    const double C_alpha_f = pr[KMPC_PLANT_C_ALPHA_F], C_alpha_r = pr[KMPC_PLANT_C_ALPHA_R];
-    const double k_df = pr[KMPC_PLANT_K_DF];            // K_ACC is not read: the pedals' lags take its place
-    const double inv_m = 1.0 / m, inv_Iz = 1.0 / Iz;   // divided once, multiplied as the source does
-    const double *rr = road + KMPC_ROAD_WORDS * (size_t)i;
-    const sim_road rd{rr[KMPC_ROAD_A_LONG], rr[KMPC_ROAD_A_LAT], rr[KMPC_ROAD_DF_OFFSET], rr[KMPC_ROAD_ACC_GAIN],
-                      rr[KMPC_ROAD_MU_F] * (m * 9.81 * lr / (lf + lr)),    // mu x the static axle loads, divided once per call
-                      rr[KMPC_ROAD_MU_R] * (m * 9.81 * lf / (lf + lr))};
+    const sim_plant p = load_plant(plant + KMPC_PLANT_WORDS * (size_t)i);
+    const sim_road rd = load_road(road + KMPC_ROAD_WORDS * (size_t)i, p);
     const double *dr = drive + KMPC_DRIVE_WORDS * (size_t)i;
     const double F_peak = dr[KMPC_DRIVE_F_PEAK], P_max = dr[KMPC_DRIVE_P_MAX], k_th = dr[KMPC_DRIVE_K_TH], k_br = dr[KMPC_DRIVE_K_BR];
     const double c_roll = dr[KMPC_DRIVE_C_ROLL], c_drag = dr[KMPC_DRIVE_C_DRAG], ratio = dr[KMPC_DRIVE_STEER_RATIO];
@@ -71,16 +66,15 @@ __global__ __launch_bounds__(256) void kmpc_sim_drive_kernel(int B, double *__re
     int sat_f = 0, sat_r = 0;           // clipped sub-steps of this call
     double peak_f = 0.0, peak_r = 0.0;  // largest |C_alpha alpha| of this call [N]
     double *s = state + 8 * (size_t)i;
-    double X = s[0], Y = s[1], psi = s[2], vx = s[3], vy = s[4], wz = s[5], acc = s[6], df = s[7];
-    double acc_new, df_new, acc_old, df_old;
-    const int r = sim_ring_commands(cmd_queue, depth, B, i, period, n_updates, cmd_delay, cmd[2 * (size_t)i], cmd[2 * (size_t)i + 1], &acc_new, &df_new,
-                                    &acc_old, &df_old);
+    const sim_state z = load_state(s);
+    double X = z.X, Y = z.Y, psi = z.psi, vx = z.vx, vy = z.vy, wz = z.wz, acc = z.acc, df = z.df;   // scalars of the kernel's own: see sim_substep
+    const sim_commands c = sim_ring_commands(cmd_queue, depth, B, i, period, n_updates, cmd_delay, cmd[2 * (size_t)i], cmd[2 * (size_t)i + 1]);
     const double deltaT = 0.01 / 10.0;
     long long tau = period * (long long)n_updates;          // the absolute update
     double df_eff = ls.wheel_cmd / ratio;                    // the target held since the last tick (a fresh record: 0)
     for (int up = 0; up < n_updates; ++up, ++tau) {
         if ((tau & 1) == 0) {   // 50 Hz against the 100 Hz updates: the command in force for this update, the speed as it is now
-            llc::tick(ls, lp, vx, up < r ? acc_old : acc_new, up < r ? df_old : df_new);
+            llc::tick(ls, lp, vx, c.acc(up), c.df(up));
             df_eff = ls.wheel_cmd / ratio;                   // the PLANT's true ratio: a ratio error is a steering gain error
         }
         const double vm = vx > 1.0 ? vx : 1.0;               // compare-and-select throughout: a NaN word poisons its own vehicle
@@ -90,33 +84,17 @@ __global__ __launch_bounds__(256) void kmpc_sim_drive_kernel(int B, double *__re
         for (int it = 0; it < 10; ++it) {
             sim_state n;
             sim_grip gn;
-            sim_substep<true>(sim_state{X, Y, psi, vx, vy, wz, acc, df}, n, 0.0, df_eff, lf, lr, inv_m, inv_Iz, C_alpha_f, C_alpha_r, 0.0, k_df, rd,
-                              sim_grip{sat_f, sat_r, peak_f, peak_r}, gn);
+            sim_substep<true>(sim_state{X, Y, psi, vx, vy, wz, acc, df}, n, 0.0, df_eff, p, rd, sim_grip{sat_f, sat_r, peak_f, peak_r}, gn);
             TH = k_th * (ls.th_cmd - TH) * deltaT + TH;      // the pedal actuators lag
             BR = k_br * (ls.br_cmd - BR) * deltaT + BR;
             const double resist = n.vx > 1e-6 ? c_roll + c_drag * n.vx * n.vx : 0.0;   // rolling and air resistance, only while moving
             X = n.X; Y = n.Y; psi = n.psi; vx = n.vx; vy = n.vy; wz = n.wz; df = n.df;
-            acc = inv_m * (TH * Fmax - BR * inv_r) - resist;  // state word 6: the powertrain's net longitudinal acceleration
+            acc = p.inv_m * (TH * Fmax - BR * inv_r) - resist;  // state word 6: the powertrain's net longitudinal acceleration
             sat_f = gn.sat_f; sat_r = gn.sat_r; peak_f = gn.peak_f; peak_r = gn.peak_r;
         }
     }
-    s[0] = X; s[1] = Y; s[2] = psi; s[3] = vx; s[4] = vy; s[5] = wz; s[6] = acc; s[7] = df;
+    store_state(s, sim_state{X, Y, psi, vx, vy, wz, acc, df});
     llc::store(lrec, ls);
     lrec[KMPC_LLCREC_TH] = TH; lrec[KMPC_LLCREC_BR] = BR;
-    if (road_stat) {
-        double *rs = road_stat + KMPC_ROAD_STAT_WORDS * (size_t)i;
-        const double c_f = rs[KMPC_ROAD_STAT_SAT_F], c_r = rs[KMPC_ROAD_STAT_SAT_R], u_f = rs[KMPC_ROAD_STAT_UTIL_F], u_r = rs[KMPC_ROAD_STAT_UTIL_R];
-        const double n_f = peak_f / rd.lim_f, n_r = peak_r / rd.lim_r;   // an infinite limit: 0 by the division itself
-        rs[KMPC_ROAD_STAT_SAT_F] = c_f + (double)sat_f; rs[KMPC_ROAD_STAT_SAT_R] = c_r + (double)sat_r;
-        rs[KMPC_ROAD_STAT_UTIL_F] = n_f > u_f ? n_f : u_f; rs[KMPC_ROAD_STAT_UTIL_R] = n_r > u_r ? n_r : u_r;
-    }
-}
-
-hipError_t kmpc_launch_sim_drive(int B, double *state, const double *cmd, const double *plant, const double *road, const double *drive,
-                                 const double *llc_rows, double *llc_rec, const int32_t *cmd_delay, double *cmd_queue, int depth, long long period,
-                                 int n_updates, double *road_stat, hipStream_t st)
-{
-    hipLaunchKernelGGL(kmpc_sim_drive_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, state, cmd, plant, road, drive, llc_rows, llc_rec, cmd_delay,
-                       cmd_queue, depth, period, n_updates, road_stat);
-    return hipGetLastError();
+    if (road_stat) fold_road_stat(road_stat + KMPC_ROAD_STAT_WORDS * (size_t)i, sim_grip{sat_f, sat_r, peak_f, peak_r}, rd);
 }

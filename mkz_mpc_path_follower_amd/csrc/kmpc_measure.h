@@ -1,5 +1,5 @@
 // kmpc_measure.h -- what the measurement kernels share (kmpc_sim.hip: kmpc_sense_kernel, kmpc_sense_delayed_kernel; kmpc_sense_faults.hip): the
-// generator and the arithmetic from truth to estimate, so that a channel delivered by any of them carries the same bits.
+// generator, the ring of truths and the arithmetic from truth to estimate, so that a channel delivered by any of them carries the same bits.
 // The normals are a pure function of (seed, id_base + b, period) -- Philox4x32-10 keyed by the seed, counter = (vehicle id, period), Box-Muller
 // on the four words (include/kmpc.h has the specification) -- so a vehicle's noise does not depend on B, on the launch geometry or on the shard
 // that simulates it.  A channel with sigma == 0 skips the noise term: est = truth + bias bit for bit.
@@ -30,6 +30,23 @@ __device__ __forceinline__ void box_muller(uint32_t w0, uint32_t w1, double *n0,
     const double r = sqrt(-2.0 * log(u0)), a = 6.283185307179586 * u1;
     *n0 = r * cos(a);
     *n1 = r * sin(a);
+}
+
+// Stale fixes: this period's truth t = x, y, psi, vx goes into slot period mod depth of truth_ring [depth,B,4] (consecutive lanes write consecutive
+// 32 B) and t becomes the truth of slot (period - L) mod depth, L = clamp(meas_delay[i], 0, min(depth - 1, period)).
+__device__ __forceinline__ void sim_delayed_truth(double t[4], double *truth_ring, int depth, int B, int i, uint64_t period,
+                                                  const int32_t *__restrict__ meas_delay)
+{
+    const size_t slot_words = 4 * (size_t)B;
+    double *own = truth_ring + (size_t)(period % (uint64_t)depth) * slot_words + 4 * (size_t)i;
+    for (int c = 0; c < 4; ++c) own[c] = t[c];
+    const uint64_t lmax = period < (uint64_t)(depth - 1) ? period : (uint64_t)(depth - 1);
+    const int lraw = meas_delay[i];
+    const uint64_t L = lraw <= 0 ? 0 : ((uint64_t)lraw > lmax ? lmax : (uint64_t)lraw);
+    if (L > 0) {
+        const double *old = truth_ring + (size_t)((period - L) % (uint64_t)depth) * slot_words + 4 * (size_t)i;
+        for (int c = 0; c < 4; ++c) t[c] = old[c];
+    }
 }
 
 // what the measurement kernels do once the truth t = x, y, psi, vx is fetched and the four Philox words w are drawn: bias, noise, the plant's wrap

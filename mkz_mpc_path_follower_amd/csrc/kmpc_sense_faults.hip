@@ -1,9 +1,10 @@
 // kmpc_sense_faults.hip -- the measurement stage with sensor faults (kmpc_sense_faults_batch), gfx950 only: kmpc_sense_kernel /
 // kmpc_sense_delayed_kernel plus outages of the three sources of scripts/state_publisher.py (GPS -> x, y; IMU -> psi; steering report -> v), GPS
 // outliers and the publisher's held fixes.  One thread per vehicle, fp64; the vehicle's fault row (16 words) and fault record (16 words) are read
-// once and the record written once: about 0.5 KB moved per vehicle and call.  The truth-to-estimate arithmetic and the generator are
-// kmpc_measure.h's, so a delivered channel carries the bits the plain kernels give; everything added here is a comparison, a selection or a count
-// (include/kmpc.h states the arithmetic).  No lane reads another vehicle's words.
+// once and the record written once: about 0.5 KB moved per vehicle and call.  The generator, the ring of truths and the truth-to-estimate arithmetic
+// are kmpc_measure.h's (philox4x32_10, sim_delayed_truth, sim_measure: the code the plain kernels' one body calls), so a delivered channel carries
+// the bits they give; everything added here is a comparison, a selection or a count (include/kmpc.h states the arithmetic).  No lane reads another
+// vehicle's words.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -42,18 +43,7 @@ __global__ __launch_bounds__(256) void kmpc_sense_faults_kernel(int B, const dou
     const double *st = state + 8 * (size_t)i;
     double t[4];
     for (int c = 0; c < 4; ++c) t[c] = st[c];
-    if (meas_delay) {
-        const size_t slot_words = 4 * (size_t)B;
-        double *own = truth_ring + (size_t)(period % (uint64_t)depth) * slot_words + 4 * (size_t)i;
-        for (int c = 0; c < 4; ++c) own[c] = t[c];
-        const uint64_t lmax = period < (uint64_t)(depth - 1) ? period : (uint64_t)(depth - 1);
-        const int lraw = meas_delay[i];
-        const uint64_t L = lraw <= 0 ? 0 : ((uint64_t)lraw > lmax ? lmax : (uint64_t)lraw);
-        if (L > 0) {
-            const double *old = truth_ring + (size_t)((period - L) % (uint64_t)depth) * slot_words + 4 * (size_t)i;
-            for (int c = 0; c < 4; ++c) t[c] = old[c];
-        }
-    }
+    if (meas_delay) sim_delayed_truth(t, truth_ring, depth, B, i, period, meas_delay);
 
     const bool chain_ok = chain_w == 0.0 || chain_w == 1.0 || chain_w == 2.0 || chain_w == 3.0 || chain_w == 4.0 || chain_w == 5.0 || chain_w == 6.0 ||
                           chain_w == 7.0;

@@ -286,3 +286,166 @@ def run_loop(kind, X0, Y0, Psi0):
     out = {k: host(h[k]) for k in LOOP_KEYS}
     out["sat"] = host(sim.road_stat)
     return out
+
+
+# ================================================================ tests/golden/plant_family_parent.npz
+# The second file (tests/test_plant_family_parent.py): the pedal-driven plant and the measurement stage with faults, recorded on the build before the
+# plant kernels were given one body and the measurement kernels one truth-ring fetch.  Same conventions as above.
+
+# ---------------------------------------------------------------- the pedal-driven plant
+DRIVE_ROADS = ("neutral", "both")
+DRIVE_ROW = np.array([6000.0, 120e3, 5.0, 5.0, 0.15, 4e-4, 14.8, 0.33])            # kmpc_drive_default
+LLC_ROW = np.array([0.8, 0.4, 1.0, 1.0, 14.8, 1847.78, 0.1, 0.33])                 # kmpc_llc_default
+
+
+def drive_runs():
+    """(name, n_updates, outliers, road, with road_stat)"""
+    return [("drive_%s_%s_n%d_%s" % (rname, "stat" if stat else "nostat", n, oname), n, o, rname, stat)
+            for n in (10, 7) for oname, o in (("tail", OUTLIERS_TAIL), ("wave0", OUTLIERS_WAVE0)) for rname in DRIVE_ROADS for stat in (True, False)]
+
+
+def drive_inputs():
+    """non-default powertrain and controller rows, spread per lane, and the speeds the controllers' records start from (V_LAST)"""
+    drive = DRIVE_ROW[None, :] * (1.0 + 0.2 * np.stack([sym(61 + 2 * c, 107, c + 3) for c in range(8)], 1))
+    llc = LLC_ROW[None, :] * (1.0 + 0.2 * np.stack([sym(67 + 2 * c, 109, c + 5) for c in range(8)], 1))
+    v_last = 4.0 + 6.0 * frac(29, 97) - 0.25
+    return drive, llc, v_last
+
+
+def run_drive(n, outliers, road, stat):
+    """three consecutive periods from period 0 (with n = 7 the 50 Hz tick's parity flips between periods) -> (digest of the inputs, digest of
+    state, llc_rec (+ road_stat) after each period and of the final ring)"""
+    import torch
+    from mkz_mpc_path_follower_amd import _lib
+    from mkz_mpc_path_follower_amd.vehicle_sim import LowLevelController, VehicleSimulator, check_drive_rows, check_llc_rows
+    s0, cmd, plant, delay = plant_inputs(n, outliers)
+    drive, llc_rows, v_last = drive_inputs()
+    rows = np.tile(np.array(ROADS[road]), (B, 1))
+    hin = fresh()
+    for a in (s0, cmd.transpose(1, 0, 2), plant, delay, rows, drive, llc_rows, v_last):
+        hin = digest(hin, a)
+    llc = LowLevelController(B, v0=v_last)          # a record that is not fresh: V_LAST set
+    llc.params.copy_(dev(check_llc_rows(llc_rows)))
+    sim = VehicleSimulator(B, plant=plant, cmd_delay=delay, cmd_queue_depth=DEPTH, road=rows, drive=check_drive_rows(drive), llc=llc)
+    sim.state.copy_(dev(s0))
+    h = fresh()
+    for p in range(3):
+        sim.cmd.copy_(dev(cmd[p]))
+        if not stat:   # the class always passes its road_stat: the call without one goes to the library directly
+            L, vp = _lib.load(), C.c_void_p
+            _lib.check(L.kmpc_sim_advance_drive(0, B, vp(sim.state.data_ptr()), vp(sim.cmd.data_ptr()), vp(sim.plant.data_ptr()), vp(sim.road.data_ptr()),
+                                                vp(sim.drive.data_ptr()), vp(llc.params.data_ptr()), vp(llc.rec.data_ptr()),
+                                                vp(sim.cmd_delay.data_ptr()), vp(sim.cmd_queue.data_ptr()), DEPTH, p, n, None,
+                                                vp(torch.cuda.current_stream().cuda_stream)))
+        else:
+            sim._update_vehicle_model(n)
+        torch.cuda.synchronize()
+        h = digest(digest(h, host(sim.state)), host(llc.rec))
+        if stat:
+            h = digest(h, host(sim.road_stat))
+    h = digest(h, host(sim.cmd_queue).transpose(1, 0, 2))
+    return fold(hin), h
+
+
+# ---------------------------------------------------------------- the measurement stage with faults
+FAULT_PERIODS, FAULT_DEPTH, FAULT_SEED, FAULT_ID_BASE = 4, 3, 0x1234567890ABCDEF, (1 << 32) + 5
+FAULT_NEUTRAL = np.array([0, 0, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, np.inf, 0], dtype=np.float64)   # kmpc_sense_faults_default
+F_OUTLIER, F_BLIND, F_FRESH, F_RESET = 8, 16, 32, 64                                                 # KMPC_FAULT_FLAG_*; source s silent: 1 << s
+
+
+def fault_inputs():
+    """-> (states [5,B,8], sensor [B,8], faults [B,16], rec0 [B,16], meas_delay [B]).  The fault row of lane i belongs to group g = i % 7, its
+    source (0 GPS, 1 IMU, 2 speed) is s = (i // 7) % 3; every record but groups 2 and 6 starts fresh, so period 0 delivers every source:
+      0 neutral
+      1 source s: P_LOSE = P_REGAIN = 1 -- lost in period 1, regained in 2, lost in 3, whatever the draw
+      2 all three sources on a chain by the draw (P_LOSE = P_REGAIN = 0.5), from a record in use: 5 calls counted, chain word i % 8
+      3 a window on source s: periods 1 and 2
+      4 outliers: P_OUTLIER 1 (s = 0) or 0.5, OUTLIER_SIGMA 3 m
+      5 a window on source s over periods 1 ... 3 with MAX_AGE 1: blind from period 2
+      6 a record that resets: COUNT -1 (s = 0), COUNT NaN (1), CHAIN 8 (2), the other words in use; then GPS lost in period 1"""
+    st, sigma, bias, _ = sense_inputs()
+    i = np.arange(B)
+    g, s = i % 7, (i // 7) % 3
+    f = np.tile(FAULT_NEUTRAL, (B, 1))
+    rec = np.zeros((B, 16))
+    for b in range(B):
+        if g[b] == 1:
+            f[b, 0 + s[b]] = 1.0
+        elif g[b] == 2:
+            f[b, 0:6] = 0.5
+        elif g[b] == 3:
+            f[b, 6 + s[b]], f[b, 9 + s[b]] = 1.0, 2.0
+        elif g[b] == 4:
+            f[b, 12], f[b, 13] = (1.0 if s[b] == 0 else 0.5), 3.0
+        elif g[b] == 5:
+            f[b, 6 + s[b]], f[b, 9 + s[b]], f[b, 14] = 1.0, 3.0, 1.0
+        elif g[b] == 6:
+            f[b, 0] = 1.0
+    used = (g == 2) | (g == 6)
+    rec[used, 0:4] = st[0][used, 0:4] + 0.5
+    rec[used, 4] = 5.0
+    rec[used, 5] = (i % 8)[used]
+    rec[used, 6:9] = ((i[:, None] % 8 >> np.arange(3)[None, :]) & 1)[used] * 2.0      # a silent source's age
+    rec[used, 9:12] = 2.0; rec[used, 12:15] = 2.0; rec[used, 15] = 1.0
+    rec[(g == 6) & (s == 0), 4] = -1.0
+    rec[(g == 6) & (s == 1), 4] = np.nan
+    rec[(g == 6) & (s == 2), 5] = 8.0
+    delay = np.array([-1, 0, 1, FAULT_DEPTH - 1, FAULT_DEPTH + 3], dtype=np.int32)[i % 5]
+    return st, np.concatenate([sigma, bias], 1), f, rec, delay
+
+
+def fault_events(flags):
+    """flags [FAULT_PERIODS,B] int32 of a run over fault_inputs() -> dict event -> bool: what the rows are there to produce"""
+    i = np.arange(B)
+    g, s = i % 7, (i // 7) % 3
+    bit = (flags[:, :] >> s[None, :]) & 1           # the lane's own source silent
+    ev = {}
+    for k, name in enumerate(("gps", "imu", "spd")):
+        m = (g == 1) & (s == k)
+        ev["lost_and_regained_" + name] = bool(m.any() and (bit[0, m] == 0).all() and (bit[1, m] == 1).all() and (bit[2, m] == 0).all())
+    m = g == 3
+    ev["window"] = bool((bit[0, m] == 0).all() and (bit[1, m] == 1).all() and (bit[2, m] == 1).all() and (bit[3, m] == 0).all())
+    ev["outlier"] = bool((flags[:, g == 4] & F_OUTLIER).any())
+    ev["blind"] = bool((flags[2:, g == 5] & F_BLIND).all() and not (flags[:2] & F_BLIND).any())
+    ev["reset"] = bool((flags[0, g == 6] & F_RESET).all() and not (flags[:, g != 6] & F_RESET).any() and not (flags[1:] & F_RESET).any())
+    ev["chain_by_the_draw"] = bool((flags[:, g == 2] & 7).any() and ((flags[:, g == 2] & 7) != 7).any())
+    return ev
+
+
+def run_faults(ring):
+    """FAULT_PERIODS periods from period 0 -> (digest of the inputs, digest of z, held, flags, blind, fault_rec after each period and of the final
+    ring, the flags [FAULT_PERIODS,B] in full)"""
+    import torch
+    from mkz_mpc_path_follower_amd.vehicle_sim import SensorModel
+    st, sensor, faults, rec0, delay = fault_inputs()
+    hin = fresh()
+    for a in (st.transpose(1, 0, 2), sensor, faults, rec0, delay):
+        hin = digest(hin, a)
+    kw = dict(meas_delay=np.clip(delay, 0, FAULT_DEPTH - 1), depth=FAULT_DEPTH) if ring else {}
+    sen = SensorModel(B, sigma=sensor[:, 0:4], bias=sensor[:, 4:8], seed=FAULT_SEED, id_base=FAULT_ID_BASE, faults=faults, **kw)
+    if ring:
+        sen.meas_delay.copy_(dev(delay))       # the raw delays: the kernel clamps
+    sen.fault_record.copy_(dev(rec0))
+    h, flags = fresh(), []
+    for p in range(FAULT_PERIODS):
+        held = sen.sense(dev(st[p]), p)
+        torch.cuda.synchronize()
+        for a in (sen.z, held, sen.flags, sen.blind, sen.fault_record):
+            h = digest(h, host(a))
+        flags.append(host(sen.flags).copy())
+    if ring:
+        h = digest(h, host(sen.truth_ring).transpose(1, 0, 2))
+    return fold(hin), h, np.array(flags, dtype=np.int32)
+
+
+def fault_flags_cpu(ring):
+    """the same run on tests/sensor_fault_ref.py (numpy, no GPU) -> flags [FAULT_PERIODS,B] int32"""
+    import sensor_fault_ref as SF
+    st, sensor, faults, rec, delay = fault_inputs()
+    flags = []
+    for p in range(FAULT_PERIODS):
+        o = (SF.sense_faults_delayed(st, sensor, faults, rec, FAULT_SEED, p, delay, FAULT_DEPTH, FAULT_ID_BASE) if ring else
+             SF.sense_faults(st[p], sensor, faults, rec, FAULT_SEED, p, FAULT_ID_BASE))
+        rec = o["rec"]
+        flags.append(o["flags"])
+    return np.array(flags, dtype=np.int32)

@@ -1,10 +1,13 @@
 """Records tests/golden/stage_kernels_parent.npz (tests/test_stage_parent.py): what the closed loops' stage kernels -- the four plant kernels, the two
 measurement kernels, command-in-force and the two predict-ahead kernels, estimator, observer and command offset -- and both closed loops with every
-stage on compute on the build that is loaded, as bit patterns.  Run it from the commit whose outputs a later change has to reproduce, before that
-change (KMPC_LIB names another build of the library, as for the other tools).
+stage on compute on the build that is loaded, as bit patterns; and tests/golden/plant_family_parent.npz (tests/test_plant_family_parent.py): the
+same for the pedal-driven plant and the measurement stage with faults.  Run it from the commit whose outputs a later change has to reproduce,
+before that change (KMPC_LIB names another build of the library, as for the other tools).
 
   python tools/record_stage_golden.py record [OUT.npz]
   python tools/record_stage_golden.py check [IN.npz]     replay against the file and list the keys that differ
+  python tools/record_stage_golden.py record-family [OUT.npz]      the second file
+  python tools/record_stage_golden.py check-family [IN.npz]
 
 tests/stage_cases.py holds the cases, their inputs and what a key of the file means."""
 import os, sys
@@ -37,21 +40,35 @@ def replay(starts=None):
     return out
 
 
+def replay_family(_starts=None):
+    """the second file's cases on the loaded build"""
+    import stage_cases as SC
+    out = {}
+    runs = [SC.run_drive(n, outliers, road, stat) for _name, n, outliers, road, stat in SC.drive_runs()]
+    out["in_drive"], out["drive"] = np.concatenate([r[0] for r in runs]), np.stack([r[1] for r in runs])   # rows in drive_runs()'s order
+    for ring in (False, True):
+        k = "faults_ring" if ring else "faults"
+        out["in_" + k], out[k], out["flags_" + k] = SC.run_faults(ring)
+    return out
+
+
 def main(argv):
-    default = os.path.join(ROOT, "tests", "golden", "stage_kernels_parent.npz")
-    if len(argv) < 2 or argv[1] not in ("record", "check"):
+    if len(argv) < 2 or argv[1] not in ("record", "check", "record-family", "check-family"):
         sys.exit(__doc__)
+    family = argv[1].endswith("-family")
+    default = os.path.join(ROOT, "tests", "golden", "plant_family_parent.npz" if family else "stage_kernels_parent.npz")
+    run = replay_family if family else replay
     path = argv[2] if len(argv) > 2 else default
     if os.environ.get("KMPC_LIB"):
         from mkz_mpc_path_follower_amd import _lib
         _lib.LIB_PATH = os.path.abspath(os.environ["KMPC_LIB"])
-    if argv[1] == "record":
-        out = replay()
+    if argv[1].startswith("record"):
+        out = run()
         np.savez_compressed(path, **out)
         print("wrote %s: %d keys, %d bytes" % (path, len(out), os.path.getsize(path)))
         return 0
     gold = np.load(path)
-    out = replay(gold["loop_starts"])
+    out = run(None if family else gold["loop_starts"])
     bad = [k for k in gold.files if out[k].dtype != gold[k].dtype or out[k].tobytes() != gold[k].tobytes()]
     print("%d of %d keys differ%s" % (len(bad), len(gold.files), ": " + ", ".join(bad) if bad else ""))
     return 1 if bad else 0
