@@ -47,6 +47,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
            "kmpc_wander_default", "kmpc_wander_batch"]
 # the entry points of include/kmpc_follow.h: the same library, a header of their own (EXPORTS is include/kmpc.h's list and stays that)
 EXT_EXPORTS = ["kmpc_follow_default", "kmpc_follow_stat_init", "kmpc_follow_fleet"]
+# the entry points of include/kmpc_lanes.h, likewise a list of their own
+LANE_EXPORTS = ["kmpc_lane_default", "kmpc_lane_rec_init", "kmpc_lane_step_fleet", "kmpc_ref_offset_batch"]
 
 _lib = None
 
@@ -131,7 +133,11 @@ def load():
     L.kmpc_follow_default.argtypes = [dp, i32]
     L.kmpc_follow_stat_init.argtypes = [dp, i32]
     L.kmpc_follow_fleet.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    for name in EXPORTS + EXT_EXPORTS:
+    L.kmpc_lane_default.argtypes = [dp, i32]
+    L.kmpc_lane_rec_init.argtypes = [dp, i32]
+    L.kmpc_lane_step_fleet.argtypes = [i32, i32, i32, C.c_double, vp, i32, vp, i32, vp, i32] + [vp] * 13
+    L.kmpc_ref_offset_batch.argtypes = [i32, i32, i32, vp, vp, i32, vp]
+    for name in EXPORTS + EXT_EXPORTS + LANE_EXPORTS:
         getattr(L, name)
     _lib = L
     return L

@@ -80,6 +80,16 @@ vehicle ahead on the same path demands it (kmpc_follow_fleet, include/kmpc_follo
 v_follow)`), without one it is the period's speed for waypoints and solve.  The range sensor is perfect: the stage reads the truth, `sim.state`, for
 the arclengths and both speeds, whatever state the controller reads.  `v_target` and `des_speed` are not modified.  `run(history=True)` adds
 `v_follow` [steps,B] and `gap` [steps,B].  Without follower= there is no launch and no tensor more.
+
+Lanes: `lanes=ref_traj.Lanes(grt, ...)` takes the follower's place (the two together are refused) and gives every vehicle a lateral degree of
+freedom: in front of the speed plan, `lanes.step(sim.state, v_target, k, dt)` (kmpc_lane_step_fleet, include/kmpc_lanes.h; dt = plant_updates x
+10 ms) finds the leader among the vehicles in the vehicle's own lane(s), decides lane changes and ramps the commanded offset; `loop.v_follow` is its
+cap, used as the follower's is.  Between the waypoint call and the solve -- in the Frenet loop before the fit -- `lanes.shift(ref)` moves the
+period's waypoints by that offset to the left (kmpc_ref_offset_batch), so both models steer to the lane's line.  The stage reads the truth, as
+follower= does.  `loop.score` stays against the RECORDED line (a vehicle in lane 1 shows e_ct near one lane width); the error against the
+commanded offset lives in the stage's own record (`lanes.summary()`: sum_elane2, max_elane).  Lanes are offsets of one recorded path: the speed
+along an offset line differs by 1 - kappa * d and nothing corrects for it, and a speed plan uses the centre line's curvature.
+`run(history=True)` adds `v_follow`, `gap`, `lane` and `lane_offset` [steps,B].  Without lanes= there is no launch and no tensor more.
 """
 import time
 
@@ -117,7 +127,7 @@ class _ScoredLoop:
     call without arguments -> the solver's output dict, and the entries the loop adds to step()'s dict."""
 
     def _init_loop(self, params, sensor, estimator, estimator_input, compensator, observer, planner=None, track_with_time=False, blind_stop=False,
-                   wander=None, follower=None):
+                   wander=None, follower=None, lanes=None):
         """what both loops own beside grt, sim, N, B, mpc and the target speeds: buffers, the stop latch, the library, and the stages; and the one
         check of the helper against the plant that both word alike (a loop's own refusals, worded for that loop, come before this call)"""
         dev = self.sim.device
@@ -138,11 +148,13 @@ class _ScoredLoop:
         self._init_estimator(estimator, estimator_input, compensator, observer)
         self._init_planner(planner, track_with_time)
         self._init_follower(follower, track_with_time)
+        self._init_lanes(lanes, track_with_time)
         self._init_score()
 
     def _period(self, plant_updates, time_solve):
         """one control period -> step()'s dict: wander -> sense -> filter -> predict -> reference and solve (the loop's own) -> command stage ->
         offset -> log -> plant"""
+        self._plant_updates = plant_updates
         if self.wander is not None:   # this period's coloured errors and gusts, into the rows the sense and the plant call below read
             self.wander.step(self.k, *self._wander_rows)
         st = self.sim.state if self.sensor is None else self._sense()
@@ -206,6 +218,20 @@ class _ScoredLoop:
         self.follower = follower
         self.v_follow = None   # [B] v_target under the following law, of the last period (follower given): the plan's cap, or the period's speed
 
+    def _init_lanes(self, lanes, track_with_time):
+        if lanes is not None:
+            if self.follower is not None:
+                raise ValueError("lanes= takes the follower's place (its leaders are found by lane): give no follower=")
+            if track_with_time:
+                raise ValueError("lanes= caps a speed on the arclength grid: track_with_time must stay False")
+            if getattr(lanes, "fleet", None) is not self.grt or not hasattr(lanes, "shift"):
+                raise ValueError("lanes= must be a ref_traj.Lanes built on this loop's own waypoint helper")
+            self._same_fleet("lanes", lanes)
+            if getattr(self.grt, "time_mode", None) is not None and bool(self.grt.time_mode.any().item()):
+                raise ValueError("lanes= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode")
+        self.lanes = lanes
+        self._plant_updates = 10
+
     def _speed(self, st):
         """the speed this period's waypoints and solve run at: v_target; with a follower loop.v_follow, v_target lowered by the following law on
         the TRUTH (a perfect range sensor); with a planner loop.v_plan, planned on the state the controller reads with that as the cap
@@ -213,6 +239,8 @@ class _ScoredLoop:
         cap = self.v_target
         if self.follower is not None:
             cap = self.v_follow = self.follower.cap(self.sim.state, self.v_target, out=self.v_follow)
+        elif self.lanes is not None:   # dt: the period the plant is about to run, plant_updates x 10 ms
+            cap = self.v_follow = self.lanes.step(self.sim.state, self.v_target, self.k, 0.01 * self._plant_updates, out=self.v_follow)
         if self.planner is None:
             return cap
         self.v_plan = self.planner.plan(st, cap, out=self.v_plan)
@@ -334,6 +362,10 @@ class _ScoredLoop:
                 (self.planner is not None, "v_plan", (), f64, lambda: self.v_plan),
                 (self.follower is not None, "v_follow", (), f64, lambda: self.v_follow),
                 (self.follower is not None, "gap", (), f64, lambda: self.follower.gap),
+                (self.lanes is not None, "v_follow", (), f64, lambda: self.v_follow),
+                (self.lanes is not None, "gap", (), f64, lambda: self.lanes.gap),
+                (self.lanes is not None, "lane", (), f64, lambda: self.lanes.lane),
+                (self.lanes is not None, "lane_offset", (), f64, lambda: self.lanes.offset),
                 (self.wander is not None, "wander", (8,), f64, lambda: self.wander.x))
         return [row[1:] for row in rows if row[0]]
 
@@ -347,7 +379,9 @@ class _ScoredLoop:
         and, with a planner, v_plan [steps,B] (the speed period j's waypoints and solve ran at) and, with a faulty sensor (SensorModel(faults=)),
         z [steps,B,4] (NaN where a source was silent: what a filter read; est is then the held state) and fault_flags [steps,B] int32 and, with
         wander=, wander [steps,B,8] (the processes' values in period j: what was added to the biases and the road words then) and, with follower=, v_follow
-        [steps,B] (v_target under the following law in period j) and gap [steps,B] (to the leader, from state[j]; +inf without one).
+        [steps,B] (v_target under the following law in period j) and gap [steps,B] (to the leader, from state[j]; +inf without one) and, with lanes=,
+        v_follow and gap likewise (the leader is the one in the vehicle's own lanes), lane [steps,B] and lane_offset [steps,B] (the lane and the
+        commanded offset AFTER period j's decision and ramp step: what period j's waypoints were shifted by).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),
         the history (history=True) and the last period's step() dict as `last` (None for steps == 0)."""
         steps = int(steps)
@@ -408,7 +442,7 @@ class ClosedLoop(_ScoredLoop):
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, track_with_time=False, weights=(9.0, 9.0, 10.0, 0.0, 100.0, 1000.0, 0.0, 0.0),
                  mpc=None, params=None, sensor=None, estimator=None, estimator_input="actuator", compensator=None, observer=None, planner=None,
-                 blind_stop=False, wander=None, follower=None, **options):
+                 blind_stop=False, wander=None, follower=None, lanes=None, **options):
         if grt.traj_horizon != N:
             raise ValueError("waypoint horizon %d != MPC horizon %d (Q10: the reference passes them separately)" % (grt.traj_horizon, N))
         self.grt, self.sim, self.N = grt, sim, int(N)
@@ -422,7 +456,7 @@ class ClosedLoop(_ScoredLoop):
             raise ValueError("a FleetRefTrajectory owns the tracking modes (its time_mode): track_with_time must stay False")
         self.track_with_time = track_with_time
         self.des_speed, self.v_target = _target_speeds(target_vel, self.B, sim.device)  # mpc_cmd_pub.jl:58-62
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander, follower)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander, follower, lanes)
 
     def step(self, plant_updates=10, time_solve=False):
         """time_solve=True brackets the solve with device synchronisations and returns its wall time (`solve_s`)"""
@@ -432,6 +466,8 @@ class ClosedLoop(_ScoredLoop):
         pose = st[:, 0:3].contiguous()
         vt = self._speed(st)
         ref, stop = self.grt.get_waypoints_batch(pose, None if self.track_with_time else vt)
+        if self.lanes is not None:
+            self.lanes.shift(ref)
         z0 = st[:, 0:4].contiguous()                                                # x, y, psi, v = vx  (state_est, :43-46 of the simulator)
         return ref, stop, lambda: self.mpc.solve(z0, ref, vt, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
                                                  params=self.params), {}
@@ -449,7 +485,7 @@ class ClosedLoopFrenet(_ScoredLoop):
 
     def __init__(self, grt, sim, N=8, target_vel=0.0, weights=FRENET_WEIGHTS, mpc=None, params=None, track_with_time=False, sensor=None, estimator=None,
                  estimator_input="actuator", compensator=None, observer=None, planner=None, blind_stop=False, wander=None, follower=None,
-                 **options):
+                 lanes=None, **options):
         des_speed, v_target = _target_speeds(target_vel, sim.B, sim.device)
         if track_with_time or not all(v > 0.0 for v in (des_speed if isinstance(des_speed, tuple) else (des_speed,))):
             raise ValueError("ClosedLoopFrenet runs in target-velocity mode only: target_vel > 0 and no time tracking (got target_vel=%r, "
@@ -466,7 +502,7 @@ class ClosedLoopFrenet(_ScoredLoop):
             raise ValueError("ClosedLoopFrenet needs a float64 model=1 BatchMPC with horizon %d on %s (got %s, model=%d, N=%d, %s)"
                              % (self.N, sim.device, self.mpc.dtype, self.mpc.cfg.model, self.mpc.N, self.mpc.device))
         self.des_speed, self.v_target = des_speed, v_target
-        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander, follower)
+        self._init_loop(params, sensor, estimator, estimator_input, compensator, observer, planner, track_with_time, blind_stop, wander, follower, lanes)
 
     def step(self, plant_updates=10, time_solve=False):
         """as ClosedLoop.step; the returned dict also carries `k_poly` [B,4] and `fit_status` [B]"""
@@ -476,6 +512,8 @@ class ClosedLoopFrenet(_ScoredLoop):
         pose = st[:, 0:3].contiguous()
         vt = self._speed(st)
         ref, stop = self.grt.get_waypoints_batch(pose, vt)
+        if self.lanes is not None:
+            self.lanes.shift(ref)
         k_poly, _psi, z0, fit_status = get_reference_frenet_batch(pose, ref, st[:, 3].contiguous())
         return ref, stop, lambda: self.mpc.solve_frenet(z0, k_poly, vt, self.u_prev, warm_U=self.warm_U, warm=self.have_warm, out=self.out,
                                                         params=self.params), dict(k_poly=k_poly, fit_status=fit_status)

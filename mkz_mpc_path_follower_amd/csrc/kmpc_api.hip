@@ -13,6 +13,7 @@
 
 #include "../../include/kmpc.h"
 #include "../../include/kmpc_follow.h"
+#include "../../include/kmpc_lanes.h"
 #include "kmpc_dispatch.h"
 
 #ifndef KMPC_HOST_ZERO_COPY_MAX
@@ -838,6 +839,69 @@ extern "C" int32_t kmpc_follow_fleet(int32_t device, int32_t B, const double *s_
     if (B == 0) return KMPC_OK;
     const FL w = {B, s_stride, speed_stride, s_along, speed, path_id, present, rows, v_cap, v_cap_out, gap_out, leader_out, stat};
     return on_device("kmpc_follow_fleet", device, [&] { return kmpc_launch_follow_fleet(w, (hipStream_t)stream); });
+}
+
+// ---- lanes (kmpc_lanes.hip; include/kmpc_lanes.h) ---------------------------------------------------------------------------
+// this project's own defaults (the reference has no such stage): the one place they exist
+extern "C" int32_t kmpc_lane_default(double *rows_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_default: bad argument (B=%d)", B);
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        double *r = rows_host + KMPC_LANE_WORDS * b;
+        for (int i = 0; i < KMPC_LANE_WORDS; ++i) r[i] = 0.0;
+        r[KMPC_LANE_N_LANES] = 1.0; r[KMPC_LANE_WIDTH] = 3.5; r[KMPC_LANE_V_LAT] = 1.0; r[KMPC_LANE_GAIN] = 0.5; r[KMPC_LANE_HOLD] = 20.0;
+        r[KMPC_LANE_CLEAR_TOL] = 0.5; r[KMPC_LANE_KEEP_RIGHT] = 1.0;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_lane_rec_init(double *rec_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !rec_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_rec_init: bad argument (B=%d)", B);
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        double *r = rec_host + KMPC_LANEREC_WORDS * b;
+        for (int i = 0; i < KMPC_LANEREC_WORDS; ++i) r[i] = 0.0;
+        r[KMPC_LANEREC_MIN_GAP] = INFINITY;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_lane_step_fleet(int32_t device, int32_t B, int32_t k, double dt, const double *s_along, int32_t s_stride, const double *e_ct,
+                                        int32_t e_stride, const double *speed, int32_t speed_stride, const int32_t *path_id,
+                                        const uint8_t *present, const double *follow_rows, const double *lane_rows, const double *v_cap,
+                                        double *v_cap_out, const uint32_t *occ_in, uint32_t *occ_out, double *rec, double *gap_out,
+                                        int32_t *leader_out, double *nbr_out, void *stream)
+{
+    if (B < 0 || k < 0 || s_stride < 1 || e_stride < 1 || speed_stride < 1)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_step_fleet: bad B / k / stride (B=%d, k=%d, s_stride=%d, e_stride=%d, speed_stride=%d; strides >= 1)",
+                    B, k, s_stride, e_stride, speed_stride);
+    if (!pos(dt)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_step_fleet: dt must be finite and > 0");
+    if (B > 0 && (!s_along || !e_ct || !speed || !follow_rows || !lane_rows || !v_cap || !v_cap_out || !occ_in || !occ_out || !rec))
+        return fail(nullptr, KMPC_ERR_ARG,
+                    "kmpc_lane_step_fleet: null required buffer (s_along %s, e_ct %s, speed %s, follow_rows %s, lane_rows %s, v_cap %s, v_cap_out %s, "
+                    "occ_in %s, occ_out %s, rec %s)",
+                    s_along ? "given" : "NULL", e_ct ? "given" : "NULL", speed ? "given" : "NULL", follow_rows ? "given" : "NULL",
+                    lane_rows ? "given" : "NULL", v_cap ? "given" : "NULL", v_cap_out ? "given" : "NULL", occ_in ? "given" : "NULL",
+                    occ_out ? "given" : "NULL", rec ? "given" : "NULL");
+    if (B > 0 && occ_in == occ_out)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_step_fleet: occ_in == occ_out (the occupancy every vehicle reads is a snapshot nobody writes)");
+    if (B == 0) return KMPC_OK;
+    const LN w = {B, k, s_stride, e_stride, speed_stride, dt, s_along, e_ct, speed, path_id, present, follow_rows, lane_rows, v_cap, v_cap_out,
+                  occ_in, occ_out, rec, gap_out, leader_out, nbr_out};
+    return on_device("kmpc_lane_step_fleet", device, [&] { return kmpc_launch_lane_step(w, (hipStream_t)stream); });
+}
+
+extern "C" int32_t kmpc_ref_offset_batch(int32_t device, int32_t B, int32_t H1, double *ref, const double *offset, int32_t offset_stride, void *stream)
+{
+    if (B < 0 || H1 < 1 || offset_stride < 1 || (long long)B * H1 > 2147483647LL)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_ref_offset_batch: bad B / H1 / offset_stride (B=%d, H1=%d, >= 1, B * H1 < 2^31; offset_stride=%d, >= 1)",
+                    B, H1, offset_stride);
+    if (B > 0 && (!ref || !offset))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_ref_offset_batch: null required buffer (ref %s, offset %s)", ref ? "given" : "NULL",
+                    offset ? "given" : "NULL");
+    if (B == 0) return KMPC_OK;
+    const RO w = {B, H1, offset_stride, ref, offset};
+    return on_device("kmpc_ref_offset_batch", device, [&] { return kmpc_launch_ref_offset(w, (hipStream_t)stream); });
 }
 
 // ---- road profile per path sample (kmpc_road_profile.hip) ----------------------------------------------------------------

@@ -263,6 +263,33 @@ struct FL {
 };
 hipError_t kmpc_launch_follow_fleet(const FL &w, hipStream_t st);
 
+// lanes: a lane and a lateral offset per vehicle, leaders by lane, lane changes (kmpc_lanes.hip; layouts: include/kmpc_lanes.h)
+struct LN {
+    int B, k, s_stride, e_stride, speed_stride;   // vehicles, the period's index; doubles between two vehicles' words (each >= 1)
+    double dt;                       // the period [s]
+    const double *s_along, *e_ct, *speed;
+    const int32_t *path_id;          // [B] or null: one path
+    const uint8_t *present;          // [B] or null: everybody on the road
+    const double *follow_rows;       // [B,8] KMPC_FOLLOW_*
+    const double *lane_rows;         // [B,8] KMPC_LANE_*
+    const double *v_cap;             // [B]
+    double *v_cap_out;               // [B]; may be v_cap
+    const uint32_t *occ_in;          // [B] the snapshot every vehicle reads
+    uint32_t *occ_out;               // [B] never occ_in
+    double *rec;                     // [B,16] in/out KMPC_LANEREC_*
+    double *gap_out;                 // [B,2] or null
+    int32_t *leader_out;             // [B] or null
+    double *nbr_out;                 // [B,4,2] or null
+};
+hipError_t kmpc_launch_lane_step(const LN &w, hipStream_t st);
+// the lateral shift of a waypoint table (kmpc_lanes.hip)
+struct RO {
+    int B, H1, offset_stride;
+    double *ref;                     // [B,H1,3] X, Y, psi, shifted in place
+    const double *offset;            // vehicle b's offset at offset[b * offset_stride]
+};
+hipError_t kmpc_launch_ref_offset(const RO &w, hipStream_t st);
+
 // batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
 // scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)
 struct FR {

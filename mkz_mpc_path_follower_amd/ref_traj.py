@@ -471,3 +471,183 @@ class Follower:
                                                ptr(self._on_path), ptr(self.rows), ptr(vc), ptr(out), ptr(self.gap_leader), ptr(self.leader),
                                                ptr(self.stat), stream(dev)))
         return out
+
+
+LANE_WORDS, LANE_REC_WORDS = 8, 16
+LANE_FIELDS = ("n_lanes", "width", "v_lat", "gain", "hold", "clear_tol", "keep_right")   # KMPC_LANE_* words 0 ... 6 of include/kmpc_lanes.h, in row order (7 is read by nobody)
+LANE_REC_FIELDS = ("lane", "lane_from", "offset", "hold_left", "n", "n_leader", "n_bound", "n_contact", "min_gap", "max_closing", "n_changes",
+                   "sum_elane2", "max_elane")   # KMPC_LANEREC_* words 0 ... 12, in order
+
+
+def lane_default():
+    """the default lane row (1, 3.5, 1.0, 0.5, 20, 0.5, 1, 0) as a numpy row [8], from kmpc_lane_default"""
+    return default_row("kmpc_lane_default", LANE_WORDS)
+
+
+def check_lane_rows(rows):
+    """[B,8] host rows -> ValueError unless words 0 ... 6 are finite, n_lanes is an integer in 1 ... 32, width > 0, v_lat > 0, gain >= 0, hold an
+    integer >= 0, clear_tol >= 0 and keep_right 0 or 1.  The kernel cannot refuse a row -- a bad word poisons that vehicle's own lane -- so this
+    says so where the rows are written."""
+    rows = host_rows(rows)
+    if rows.ndim != 2 or rows.shape[1] != LANE_WORDS:
+        raise ValueError("lane rows: [B,8] (%s, one unused word), got %s" % (", ".join(LANE_FIELDS), rows.shape))
+    with np.errstate(invalid="ignore"):
+        ok = (np.isfinite(rows[:, 0:7]).all(1) & (rows[:, 0] >= 1.0) & (rows[:, 0] <= 32.0) & (rows[:, 0] == np.floor(rows[:, 0]))
+              & (rows[:, 1] > 0.0) & (rows[:, 2] > 0.0) & (rows[:, 3] >= 0.0) & (rows[:, 4] >= 0.0) & (rows[:, 4] == np.floor(rows[:, 4]))
+              & (rows[:, 5] >= 0.0) & ((rows[:, 6] == 0.0) | (rows[:, 6] == 1.0)))
+    if not ok.all():
+        raise ValueError("lane rows: every word finite, n_lanes an integer in 1 ... 32, width > 0, v_lat > 0, gain >= 0, hold an integer >= 0, "
+                         "clear_tol >= 0, keep_right 0 or 1 (vehicle(s) %s)" % rows_of(~ok))
+    return rows
+
+
+def lane_params(B, device=0, **overrides):
+    """[B,8] float64 lane rows on `device`: the default row, with each override (`n_lanes=`, `width=`, `v_lat=`, `gain=`, `hold=`, `clear_tol=`,
+    `keep_right=`) a scalar or one value per vehicle.  Validated on the host (check_lane_rows) before anything reaches the device."""
+    return torch.as_tensor(check_lane_rows(table_rows("lane_params", LANE_FIELDS, lane_default(), B, overrides))).to(device_of(device))
+
+
+def fresh_lane_rec(B, device):
+    """[B,16] float64 on `device`: B fresh lane records (kmpc_lane_rec_init: lane 0, not changing, offset 0, counters 0, smallest gap +inf)"""
+    rec = np.empty((int(B), LANE_REC_WORDS))
+    _lib.check(_lib.load().kmpc_lane_rec_init(rec.ctypes.data_as(C.POINTER(C.c_double)), int(B)))
+    return torch.from_numpy(rec).to(device)
+
+
+class Lanes:
+    """Lanes on a waypoint helper's recorded paths (kmpc_lane_step_fleet, kmpc_ref_offset_batch; include/kmpc_lanes.h): per vehicle a lane and a
+    commanded lateral offset (lane L's centre runs L * width to the LEFT of the recorded line), the leader among the vehicles in its own lane(s)
+    with the following law's cap, the neighbours in the adjacent lanes, the lane-change decision and the offset ramp.  `grt`: a FleetRefTrajectory
+    or a GPSRefTrajectory (one path; `follow_rows` or `lane_rows` is then required, its length is the fleet's size), as for Follower.
+    `lane0` [B]: the starting lanes (integers inside each vehicle's n_lanes); a vehicle started in lane L has offset L * width.
+
+    rows [B,8] (lane_params), follow_rows [B,8] (follow_params), rec [B,16] (LANE_REC_FIELDS): public device tensors, read by every step() as
+    they are -- edit them in place between steps.  Views after a step(): `lane` [B], `offset` [B] (columns of rec), `gap` [B] (+inf without a
+    leader), `leader_speed` [B], `leader` [B] int32 (-1 without), `neighbours` [B,4,2] (gap and speed of left-ahead, left-behind, right-ahead,
+    right-behind; (+inf, 0) where there is none).  Limits: lanes are offsets of ONE recorded path; the speed along an offset line differs by
+    1 - kappa * d and nothing corrects for it; the range sensor is perfect."""
+
+    def __init__(self, grt, follow_rows=None, lane_rows=None, lane0=None):
+        if not isinstance(grt, (FleetRefTrajectory, GPSRefTrajectory)):
+            raise ValueError("Lanes run on a GPSRefTrajectory or a FleetRefTrajectory; a %s is neither" % type(grt).__name__)
+        self.fleet, self.device, self._lib = grt, grt.device, grt._lib
+        self._one_path = isinstance(grt, GPSRefTrajectory)
+        if self._one_path:
+            given = [r for r in (follow_rows, lane_rows) if isinstance(r, torch.Tensor) and r.dim() == 2]
+            if not given:
+                raise ValueError("Lanes on a GPSRefTrajectory: rows [B,8] (follow_params or lane_params) are required, their length is the fleet's size")
+            self.B = int(given[0].shape[0])
+        else:
+            self.B = int(grt.path_id.shape[0])
+        dev, B = self.device, self.B
+        self.follow_rows = follow_params(B, dev) if follow_rows is None else follow_rows
+        self.rows = lane_params(B, dev) if lane_rows is None else lane_rows
+        self._check_rows()
+        if lane0 is None:
+            self._lane0 = np.zeros(B)
+        else:
+            self._lane0 = np.asarray(lane0.detach().cpu().numpy() if isinstance(lane0, torch.Tensor) else lane0, dtype=np.float64)
+            n_lanes = self.rows[:, 0].cpu().numpy()
+            if self._lane0.shape != (B,) or not ((self._lane0 == np.floor(self._lane0)) & (self._lane0 >= 0.0) & (self._lane0 < n_lanes)).all():
+                raise ValueError("lane0: one integer lane per vehicle [%d], each inside 0 ... n_lanes - 1 of its lane row" % B)
+        self.gap_leader = torch.empty((B, 2), dtype=torch.float64, device=dev)   # gap, the leader's speed: what the kernel writes
+        self.leader = torch.empty((B,), dtype=torch.int32, device=dev)
+        self.neighbours = torch.empty((B, 4, 2), dtype=torch.float64, device=dev)
+        self._occ = [torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(2)]   # the occupancy words (uint32 bit patterns), ping-ponged
+        self._track = None                                                       # the geometry-only score call's err, seg, closest
+        self._on_path = torch.empty((B,), dtype=torch.bool, device=dev)
+        self.reset()
+
+    lane = property(lambda self: self.rec[:, 0])
+    offset = property(lambda self: self.rec[:, 2])
+    gap = property(lambda self: self.gap_leader[:, 0])
+    leader_speed = property(lambda self: self.gap_leader[:, 1])
+    occupancy = property(lambda self: self._occ[self._cur])
+
+    def _check_rows(self):
+        if not is_buffer(self.rows, torch.float64, (self.B, LANE_WORDS), self.device):
+            raise ValueError("rows must be a contiguous float64 tensor [%d,8] on %s (lane_params; write into it in place)" % (self.B, self.device))
+        if not is_buffer(self.follow_rows, torch.float64, (self.B, FOLLOW_WORDS), self.device):
+            raise ValueError("follow_rows must be a contiguous float64 tensor [%d,8] on %s (follow_params; write into it in place)"
+                             % (self.B, self.device))
+
+    def reset(self):
+        """a fresh record for every vehicle, in its starting lane at that lane's offset; nobody changing, no leader seen yet"""
+        rec = fresh_lane_rec(self.B, "cpu").numpy()
+        rec[:, 0] = rec[:, 1] = self._lane0
+        rec[:, 2] = self._lane0 * self.rows[:, 1].cpu().numpy()
+        self.rec = torch.from_numpy(rec).to(self.device)
+        self._occ[0].copy_(torch.from_numpy((1 << self._lane0.astype(np.int64)).astype(np.uint32).view(np.int32)))
+        self._cur = 0
+        self.gap_leader[:, 0] = float("inf")
+        self.gap_leader[:, 1] = 0.0
+        self.leader.fill_(-1)
+        self.neighbours[:, :, 0] = float("inf")
+        self.neighbours[:, :, 1] = 0.0
+
+    def summary(self):
+        """the record as named numpy fields [B] (one synchronising download): LANE_REC_FIELDS, the lanes and the counts as integers, plus
+        rms_elane (already divided by the number of calls; 0 where none was)"""
+        a = self.rec.cpu().numpy()
+        out = {k: a[:, i].copy() for i, k in enumerate(LANE_REC_FIELDS)}
+        for k in ("lane", "lane_from", "hold_left", "n", "n_leader", "n_bound", "n_contact", "n_changes"):
+            out[k] = out[k].astype(np.int64)
+        out["rms_elane"] = np.sqrt(out["sum_elane2"] / np.maximum(out["n"], 1))
+        return out
+
+    def step(self, state, v_cap, k, dt, out=None, present=None):
+        """one control period of the stage.  state: device tensor [B,W], X, Y, psi, v first (the plant's [B,8] as it is: no copy); v_cap [B] -> v [B]
+        (`out`, which may be v_cap itself, or a new tensor): v_cap, lowered where the leader in the vehicle's own lane(s) demands it.  k: the
+        period's index (left moves are decided in even, right moves in odd periods); dt: the period [s].  present [B] (uint8 / bool) or None.
+        One geometry-only track_score_batch call for s_along and e_ct, then kmpc_lane_step_fleet; a vehicle the score call refuses is not on
+        the road.  Asynchronous on torch's current stream."""
+        dev, B = self.device, self.B
+        st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=dev)
+        if not (st.dtype == torch.float64 and st.device == dev and st.dim() == 2 and st.shape[1] >= 4 and (B == 0 or st.stride(1) == 1)
+                and st.stride(0) >= 4):
+            st = torch.as_tensor(st, dtype=torch.float64, device=dev).contiguous()
+        if st.dim() != 2 or st.shape[0] != B or st.shape[1] < 4:
+            raise ValueError("state: expected [%d,W] with X, Y, psi, v in the first four columns, got %s" % (B, tuple(st.shape)))
+        vc = torch.as_tensor(v_cap, dtype=torch.float64, device=dev).contiguous()
+        if tuple(vc.shape) != (B,):
+            raise ValueError("v_cap: expected [%d], got %s" % (B, tuple(vc.shape)))
+        self._check_rows()
+        pid = None if self._one_path else self.fleet.path_id
+        if pid is not None and not is_buffer(pid, torch.int32, (B,), dev):
+            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
+        if present is not None and not is_buffer(present, (torch.uint8, torch.bool), (B,), dev):
+            raise ValueError("present: expected a contiguous uint8 or bool tensor [%d] on %s" % (B, dev))
+        if not is_buffer(self.rec, torch.float64, (B, LANE_REC_WORDS), dev):
+            raise ValueError("rec must stay a contiguous float64 tensor [%d,16] on %s (reset() gives a fresh one)" % (B, dev))
+        if out is None:
+            out = torch.empty((B,), dtype=torch.float64, device=dev)
+        elif not is_buffer(out, torch.float64, (B,), dev):
+            raise ValueError("out: expected a contiguous float64 tensor [%d] on %s" % (B, dev))
+        if B == 0:
+            return out
+        self._track = self.fleet.track_score_batch(st, score=None, out=self._track)
+        torch.ge(self._track["seg"], 0, out=self._on_path)
+        if present is not None:
+            torch.logical_and(self._on_path, present, out=self._on_path)
+        err = self._track["err"]
+        occ_in, occ_out = self._occ[self._cur], self._occ[1 - self._cur]
+        _lib.check(self._lib.kmpc_lane_step_fleet(dev.index, B, int(k), float(dt), ptr(err[:, 3]), 4, ptr(err[:, 0]), 4, ptr(st[:, 3]),
+                                                  int(st.stride(0)), ptr(pid), ptr(self._on_path), ptr(self.follow_rows), ptr(self.rows), ptr(vc),
+                                                  ptr(out), ptr(occ_in), ptr(occ_out), ptr(self.rec), ptr(self.gap_leader), ptr(self.leader),
+                                                  ptr(self.neighbours), stream(dev)))
+        self._cur = 1 - self._cur
+        return out
+
+    def shift(self, ref):
+        """ref [B,H+1,3] (X, Y, psi: a waypoint call's table) -> the same tensor, every point moved by the vehicle's commanded offset to the left
+        of its heading (kmpc_ref_offset_batch on rec's offset column by stride: no copy); psi untouched.  One offset holds for the whole horizon."""
+        B = self.B
+        if not (isinstance(ref, torch.Tensor) and ref.dim() == 3 and is_buffer(ref, torch.float64, (B, ref.shape[1], 3), self.device)):
+            raise ValueError("ref: expected a contiguous float64 tensor [%d,H+1,3] on %s" % (B, self.device))
+        if not is_buffer(self.rec, torch.float64, (B, LANE_REC_WORDS), self.device):
+            raise ValueError("rec must stay a contiguous float64 tensor [%d,16] on %s (reset() gives a fresh one)" % (B, self.device))
+        if B == 0 or ref.shape[1] == 0:
+            return ref
+        _lib.check(self._lib.kmpc_ref_offset_batch(self.device.index, B, int(ref.shape[1]), ptr(ref), ptr(self.rec[:, 2]), LANE_REC_WORDS,
+                                                   stream(self.device)))
+        return ref

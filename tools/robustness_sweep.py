@@ -55,8 +55,13 @@ heading random walk (0, 0.003, 0.01) rad/sqrt(s) on top of GPS outages of 30 and
 the leader's target stepping 6 -> 3 -> 6 m/s: T_HEADWAY (0.5, 1.0, 1.5) s x command delay (0, 0.1, 0.3) s x GPS sigma (0, 0.2) m, each cell once as it
 is and once with estimator= and compensator=: smallest gap, contacts, the speed dip of the last follower over that of the first, solves not Optimal.
 
+--overtake is the sweep of the lane stage (-> profiles/robustness_sweep_overtake.txt): lanes=ref_traj.Lanes on two lanes, platoons of six on the three
+paths, a slow vehicle (3 m/s) in front and five at 6 m/s behind it, under --platoon's cells and both of its ways: contacts, smallest own-lane gap, lane
+changes, how many of the fast vehicles end ahead of the slow one and back in lane 0, their mean speed, solves not Optimal.
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
        python tools/robustness_sweep.py --platoon [out.txt]
+       python tools/robustness_sweep.py --overtake [out.txt]
        python tools/robustness_sweep.py --wander [out.txt] [steps]
        python tools/robustness_sweep.py --outage [out.txt] [steps]
        python tools/robustness_sweep.py --road-profile [out.txt] [steps]
@@ -953,8 +958,75 @@ def platoon_main():
             f.write("\n".join(LINES) + "\n")
 
 
+OV_SIZE, OV_STEPS, OV_SLOW, OV_FAST = 6, 350, 3.0, 6.0
+
+
+def overtake_main():
+    """--platoon's cells (T_HEADWAY x command delay x GPS sigma) and ways, three platoons of six per cell, one per recorded path on its own copy of it,
+    started 20 m apart in lane 0 of two lanes: vehicle 0 of a platoon in front with a 3 m/s target, five behind it at 6 m/s.  default lane rows but
+    N_LANES = 2.  The stage reads the truth (a perfect range sensor); delay and noise reach it through how well the vehicles hold their lines."""
+    from mkz_mpc_path_follower_amd.ref_traj import Lanes, follow_params, lane_params
+    argv = [a for a in sys.argv if a != "--overtake"]
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    cells = list(itertools.product(range(3), range(3), range(2)))
+    n_pl = 3 * len(cells)
+    B = n_pl * OV_SIZE
+    platoon = np.repeat(np.arange(n_pl), OV_SIZE)
+    rank = np.tile(np.arange(OV_SIZE), n_pl)                    # 0 = the slow vehicle, in front
+    ix = np.array(cells)[platoon // 3]
+    t_h, cd = np.array(PL_T)[ix[:, 0]], np.array(PL_DELAY)[ix[:, 1]]
+    sigma = np.zeros((B, 4))
+    sigma[:, 0] = sigma[:, 1] = np.array(PL_SIGMA)[ix[:, 2]]
+    targets = np.where(rank == 0, OV_SLOW, OV_FAST)
+    res = {}
+    for way in PL_WAYS:
+        fleet = FleetRefTrajectory([paths[q % 3] for q in range(n_pl)], platoon, traj_horizon=8, traj_dt=0.2)
+        pose = np.empty((B, 3))
+        for b in range(B):
+            tr = fleet.trajectories[platoon[b]]
+            i = int(np.searchsorted(tr[:, 6], 5.0 + PL_SPACING * (OV_SIZE - 1 - rank[b])))
+            pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+        sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2], cmd_delay=cd, cmd_queue_depth=5)
+        sim.state[:, 3] = torch.as_tensor(targets, device=sim.device)
+        sensor = SensorModel(B, sigma=sigma, seed=2024)
+        kw = {}
+        if way != "as it is":
+            kw = dict(estimator=Estimator.from_sensor(sensor), compensator=LatencyCompensator(B, cmd_delay=cd, meas_delay=0), estimator_input="history")
+        lanes = Lanes(fleet, follow_rows=follow_params(B, t_headway=t_h), lane_rows=lane_params(B, n_lanes=2))
+        loop = ClosedLoop(fleet, sim, N=8, target_vel=targets, sensor=sensor, lanes=lanes, **kw)
+        speed = loop.run(OV_STEPS, history=True)["state"][1:, :, 3].mean(0).cpu().numpy()
+        res[way] = dict(f=lanes.summary(), s=loop.score_summary(), speed=speed, finite=bool(torch.isfinite(sim.state).all().item()))
+    say("%s: 2 x %d vehicles in %d platoons of %d on the three paths, two lanes, %d periods of 0.1 s, nominal plant; vehicle 0 of a platoon in front at "
+        "%g m/s, the others behind it at %g m/s, %g m apart; default rows but T_HEADWAY and N_LANES = 2; every state finite: %s; latched vehicles: %s (%s)"
+        % (torch.cuda.get_device_name(0), B, n_pl, OV_SIZE, OV_STEPS, OV_SLOW, OV_FAST, PL_SPACING, " / ".join(str(res[w]["finite"]) for w in PL_WAYS),
+           " / ".join(str(int((res[w]["s"]["latch_index"] >= 0).sum())) for w in PL_WAYS), " / ".join(PL_WAYS)))
+    say("per cell of three platoons (15 fast vehicles), %s: smallest own-lane gap [m], vehicle-periods in contact, lane changes, fast vehicles that end "
+        "ahead of their slow one and back in lane 0, mean speed of the fast vehicles [m/s], largest |e_lane| [m], periods not Optimal per 1000"
+        % " | ".join(PL_WAYS))
+    for c, (t, dl, g) in enumerate(cells):
+        sel = (platoon // 3) == c
+        fast = sel & (rank > 0)
+        part = []
+        for w in PL_WAYS:
+            r = res[w]
+            s_slow = r["s"]["s_along"][sel & (rank == 0)][platoon[fast] - 3 * c]
+            done = (r["s"]["s_along"][fast] > s_slow) & (r["f"]["lane"][fast] == 0) & (r["f"]["lane_from"][fast] == 0)
+            part.append("%7.3f %4d %4d %3d %6.3f %6.3f %7.2f" % (r["f"]["min_gap"][sel].min(), r["f"]["n_contact"][sel].sum(), r["f"]["n_changes"][sel].sum(),
+                                                               done.sum(), r["speed"][fast].mean(), r["f"]["max_elane"][sel].max(),
+                                                               1000.0 * r["s"]["n_nonopt"][sel].sum() / max(1, r["s"]["n_live"][sel].sum())))
+        say("   T %.1f s, delay %.1f s, GPS sigma %.1f m   %s" % (PL_T[t], 0.01 * PL_DELAY[dl], PL_SIGMA[g], " | ".join(part)))
+    if len(argv) > 1:
+        with open(argv[1], "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 if __name__ == "__main__":
-    if "--platoon" in sys.argv[1:]:
+    if "--overtake" in sys.argv[1:]:
+        overtake_main()
+    elif "--platoon" in sys.argv[1:]:
         platoon_main()
     elif "--wander" in sys.argv[1:]:
         wander_main()
