@@ -49,6 +49,8 @@ EXPORTS = ["kmpc_abi_version", "kmpc_config_default", "kmpc_create", "kmpc_destr
 EXT_EXPORTS = ["kmpc_follow_default", "kmpc_follow_stat_init", "kmpc_follow_fleet"]
 # the entry points of include/kmpc_lanes.h, likewise a list of their own
 LANE_EXPORTS = ["kmpc_lane_default", "kmpc_lane_rec_init", "kmpc_lane_step_fleet", "kmpc_ref_offset_batch"]
+# the entry points of include/kmpc_range.h, likewise
+RANGE_EXPORTS = ["kmpc_range_default", "kmpc_range_rec_init", "kmpc_range_follow_batch"]
 
 _lib = None
 
@@ -137,7 +139,10 @@ def load():
     L.kmpc_lane_rec_init.argtypes = [dp, i32]
     L.kmpc_lane_step_fleet.argtypes = [i32, i32, i32, C.c_double, vp, i32, vp, i32, vp, i32] + [vp] * 13
     L.kmpc_ref_offset_batch.argtypes = [i32, i32, i32, vp, vp, i32, vp]
-    for name in EXPORTS + EXT_EXPORTS + LANE_EXPORTS:
+    L.kmpc_range_default.argtypes = [dp, i32]
+    L.kmpc_range_rec_init.argtypes = [dp, i32]
+    L.kmpc_range_follow_batch.argtypes = [i32, i32, C.c_double, vp, vp, vp, i32, vp, i32, vp, vp, C.c_uint64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
+    for name in EXPORTS + EXT_EXPORTS + LANE_EXPORTS + RANGE_EXPORTS:
         getattr(L, name)
     _lib = L
     return L

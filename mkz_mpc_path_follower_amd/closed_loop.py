@@ -80,6 +80,13 @@ vehicle ahead on the same path demands it (kmpc_follow_fleet, include/kmpc_follo
 v_follow)`), without one it is the period's speed for waypoints and solve.  The range sensor is perfect: the stage reads the truth, `sim.state`, for
 the arclengths and both speeds, whatever state the controller reads.  `v_target` and `des_speed` are not modified.  `run(history=True)` adds
 `v_follow` [steps,B] and `gap` [steps,B].  Without follower= there is no launch and no tensor more.
+A follower with a range sensor, `Follower(grt, rows, radar=ref_traj.RangeSensor(B, ...))`, no longer reads the truth: behind the search,
+kmpc_range_follow_batch (include/kmpc_range.h) measures the gap and the leader's speed (range limit, bias, seeded noise, dropouts), tracks them, and
+applies the law to what the track believes, with the follower's own speed from the state the CONTROLLER reads (sensed, filtered or predicted,
+whichever the loop has) -- `follower.cap(sim.state, v_target, known=st, k=loop.k, dt=plant_updates x 10 ms)`.  `follower.stat` and `gap` stay the
+truth's; `follower.v_ideal` is what a perfect sensor would have said.  `run(history=True)` adds `gap_seen` and `v_lead_seen` [steps,B] (+inf and
+0 without a track).  A follower without a radar, and lanes=, launch and allocate nothing more (lanes= has no radar: its decision is fused with
+its search).
 
 Lanes: `lanes=ref_traj.Lanes(grt, ...)` takes the follower's place (the two together are refused) and gives every vehicle a lateral degree of
 freedom: in front of the speed plan, `lanes.step(sim.state, v_target, k, dt)` (kmpc_lane_step_fleet, include/kmpc_lanes.h; dt = plant_updates x
@@ -234,11 +241,15 @@ class _ScoredLoop:
 
     def _speed(self, st):
         """the speed this period's waypoints and solve run at: v_target; with a follower loop.v_follow, v_target lowered by the following law on
-        the TRUTH (a perfect range sensor); with a planner loop.v_plan, planned on the state the controller reads with that as the cap
-        (v_target itself is not modified)"""
+        the TRUTH (a perfect range sensor) or, when the follower has a radar, on its track of a measured gap; with a planner loop.v_plan, planned
+        on the state the controller reads with that as the cap (v_target itself is not modified)"""
         cap = self.v_target
         if self.follower is not None:
-            cap = self.v_follow = self.follower.cap(self.sim.state, self.v_target, out=self.v_follow)
+            if getattr(self.follower, "radar", None) is None:
+                cap = self.v_follow = self.follower.cap(self.sim.state, self.v_target, out=self.v_follow)
+            else:   # a measured gap, and the follower's own speed from the state the controller reads; dt as for the lanes
+                cap = self.v_follow = self.follower.cap(self.sim.state, self.v_target, out=self.v_follow, known=st, k=self.k,
+                                                        dt=0.01 * self._plant_updates)
         elif self.lanes is not None:   # dt: the period the plant is about to run, plant_updates x 10 ms
             cap = self.v_follow = self.lanes.step(self.sim.state, self.v_target, self.k, 0.01 * self._plant_updates, out=self.v_follow)
         if self.planner is None:
@@ -353,6 +364,7 @@ class _ScoredLoop:
         """what run(history=True) records beside state, cmd, status and latch, for the stages this loop has: (key, trailing shape, dtype, source), in
         the order the keys appear in run()'s dict; source() is the tensor a period leaves behind"""
         f64 = torch.float64
+        radar = self.follower is not None and getattr(self.follower, "radar", None) is not None
         rows = ((self.sensor is not None, "est", (4,), f64, lambda: self.est),
                 (self.faulty, "z", (4,), f64, lambda: self.sensor.z),
                 (self.faulty, "fault_flags", (), torch.int32, lambda: self.sensor.flags),
@@ -362,6 +374,8 @@ class _ScoredLoop:
                 (self.planner is not None, "v_plan", (), f64, lambda: self.v_plan),
                 (self.follower is not None, "v_follow", (), f64, lambda: self.v_follow),
                 (self.follower is not None, "gap", (), f64, lambda: self.follower.gap),
+                (radar, "gap_seen", (), f64, lambda: self.follower.gap_seen),
+                (radar, "v_lead_seen", (), f64, lambda: self.follower.v_lead_seen),
                 (self.lanes is not None, "v_follow", (), f64, lambda: self.v_follow),
                 (self.lanes is not None, "gap", (), f64, lambda: self.lanes.gap),
                 (self.lanes is not None, "lane", (), f64, lambda: self.lanes.lane),
@@ -379,7 +393,8 @@ class _ScoredLoop:
         and, with a planner, v_plan [steps,B] (the speed period j's waypoints and solve ran at) and, with a faulty sensor (SensorModel(faults=)),
         z [steps,B,4] (NaN where a source was silent: what a filter read; est is then the held state) and fault_flags [steps,B] int32 and, with
         wander=, wander [steps,B,8] (the processes' values in period j: what was added to the biases and the road words then) and, with follower=, v_follow
-        [steps,B] (v_target under the following law in period j) and gap [steps,B] (to the leader, from state[j]; +inf without one) and, with lanes=,
+        [steps,B] (v_target under the following law in period j) and gap [steps,B] (to the leader, from state[j]; +inf without one) and, when the
+        follower has a radar, gap_seen and v_lead_seen [steps,B] (the track after period j's call; +inf and 0 without a track) and, with lanes=,
         v_follow and gap likewise (the leader is the one in the vehicle's own lanes), lane [steps,B] and lane_offset [steps,B] (the lane and the
         commanded offset AFTER period j's decision and ramp step: what period j's waypoints were shifted by).
         -> dict of device tensors: score [B,16] (the loop's own, not a copy), err / seg / closest of the last scored state (score=True),

@@ -14,6 +14,7 @@
 #include "../../include/kmpc.h"
 #include "../../include/kmpc_follow.h"
 #include "../../include/kmpc_lanes.h"
+#include "../../include/kmpc_range.h"
 #include "kmpc_dispatch.h"
 
 #ifndef KMPC_HOST_ZERO_COPY_MAX
@@ -902,6 +903,55 @@ extern "C" int32_t kmpc_ref_offset_batch(int32_t device, int32_t B, int32_t H1, 
     if (B == 0) return KMPC_OK;
     const RO w = {B, H1, offset_stride, ref, offset};
     return on_device("kmpc_ref_offset_batch", device, [&] { return kmpc_launch_ref_offset(w, (hipStream_t)stream); });
+}
+
+// ---- range sensor and leader tracker (kmpc_range.hip; include/kmpc_range.h) -------------------------------------------------
+// this project's own defaults (the reference has no such stage): the one place they exist
+extern "C" int32_t kmpc_range_default(double *rows_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_default: bad argument (B=%d)", B);
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        double *r = rows_host + KMPC_RANGE_WORDS * b;
+        for (int i = 0; i < KMPC_RANGE_WORDS; ++i) r[i] = 0.0;
+        r[KMPC_RANGE_RANGE_MAX] = 120.0; r[KMPC_RANGE_SIGMA_R] = 0.25; r[KMPC_RANGE_SIGMA_V] = 0.12; r[KMPC_RANGE_FILTER] = 1.0;
+        r[KMPC_RANGE_COAST_MAX] = 5.0; r[KMPC_RANGE_Q_GAP] = 0.01; r[KMPC_RANGE_Q_V] = 0.25; r[KMPC_RANGE_R_GAP] = 0.0625; r[KMPC_RANGE_R_V] = 0.0144;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_range_rec_init(double *rec_host, int32_t B)
+{
+    if (B < 0 || (B > 0 && !rec_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_rec_init: bad argument (B=%d)", B);
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        double *r = rec_host + KMPC_RANGEREC_WORDS * b;
+        for (int i = 0; i < KMPC_RANGEREC_WORDS; ++i) r[i] = 0.0;
+        r[KMPC_RANGEREC_TRACK_ID] = -1.0;
+    }
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_range_follow_batch(int32_t device, int32_t B, double dt, const double *truth, const int32_t *leader, const double *speed_true,
+                                           int32_t speed_true_stride, const double *speed_known, int32_t speed_known_stride,
+                                           const double *follow_rows, const double *range_rows, uint64_t seed, int64_t period, int64_t id_base,
+                                           const double *v_cap, double *v_cap_out, double *rec, double *meas_out, void *stream)
+{
+    if (B < 0 || speed_true_stride < 1 || speed_known_stride < 1)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_follow_batch: bad B / stride (B=%d, speed_true_stride=%d, speed_known_stride=%d; strides >= 1)", B,
+                    speed_true_stride, speed_known_stride);
+    if (!pos(dt)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_follow_batch: dt must be finite and > 0");
+    if (period < 0 || period >= ((int64_t)1 << 61))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_follow_batch: bad period (%lld; 0 <= period < 2^61)", (long long)period);
+    if (B > 0 && (!truth || !leader || !speed_true || !speed_known || !follow_rows || !range_rows || !v_cap || !v_cap_out || !rec))
+        return fail(nullptr, KMPC_ERR_ARG,
+                    "kmpc_range_follow_batch: null required buffer (truth %s, leader %s, speed_true %s, speed_known %s, follow_rows %s, range_rows %s, "
+                    "v_cap %s, v_cap_out %s, rec %s)",
+                    truth ? "given" : "NULL", leader ? "given" : "NULL", speed_true ? "given" : "NULL", speed_known ? "given" : "NULL",
+                    follow_rows ? "given" : "NULL", range_rows ? "given" : "NULL", v_cap ? "given" : "NULL", v_cap_out ? "given" : "NULL",
+                    rec ? "given" : "NULL");
+    if (B == 0) return KMPC_OK;
+    const RG w = {B, speed_true_stride, speed_known_stride, dt, seed, (uint64_t)period, (uint64_t)id_base, truth, leader, speed_true, speed_known,
+                  follow_rows, range_rows, v_cap, v_cap_out, rec, meas_out};
+    return on_device("kmpc_range_follow_batch", device, [&] { return kmpc_launch_range_follow(w, (hipStream_t)stream); });
 }
 
 // ---- road profile per path sample (kmpc_road_profile.hip) ----------------------------------------------------------------

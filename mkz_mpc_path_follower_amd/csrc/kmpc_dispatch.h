@@ -290,6 +290,24 @@ struct RO {
 };
 hipError_t kmpc_launch_ref_offset(const RO &w, hipStream_t st);
 
+// range sensor and leader tracker behind kmpc_follow_fleet (kmpc_range.hip; layouts: include/kmpc_range.h)
+struct RG {
+    int B, true_stride, known_stride;   // vehicles; doubles between two vehicles' speeds (each >= 1)
+    double dt;                       // the period [s]
+    uint64_t seed, period, id_base;  // the draws' key and counter
+    const double *truth;             // [B,2] the true gap, the leader's true speed (kmpc_follow_fleet's gap_out)
+    const int32_t *leader;           // [B] -1 = none (kmpc_follow_fleet's leader_out)
+    const double *speed_true;        // follower b's speed at speed_true[b * true_stride]
+    const double *speed_known;       // ... as its controller knows it, at speed_known[b * known_stride]; may be speed_true
+    const double *follow_rows;       // [B,8] KMPC_FOLLOW_*
+    const double *range_rows;        // [B,16] KMPC_RANGE_*
+    const double *v_cap;             // [B]
+    double *v_cap_out;               // [B]; may be v_cap
+    double *rec;                     // [B,16] in/out KMPC_RANGEREC_*
+    double *meas_out;                // [B,4] z_r, z_v, detected, COAST, or null
+};
+hipError_t kmpc_launch_range_follow(const RG &w, hipStream_t st);
+
 // batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
 // scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)
 struct FR {

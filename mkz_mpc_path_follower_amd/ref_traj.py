@@ -384,6 +384,92 @@ def fresh_follow_stat(B, device):
     return torch.from_numpy(rec).to(device)
 
 
+RANGE_WORDS = 16
+RANGE_FIELDS = ("range_max", "sigma_r", "sigma_v", "bias_r", "p_drop", "filter", "coast_max", "q_gap", "q_v", "r_gap", "r_v")   # KMPC_RANGE_* words 0 ... 10 of include/kmpc_range.h, in row order (11 ... 15 are read by nobody)
+RANGE_REC_FIELDS = ("gap_hat", "v_hat", "p00", "p01", "p11", "track_id", "coast", "n", "n_detect", "n_drop", "n_out", "n_new", "n_lost", "n_bound",
+                    "sum_egap2", "max_egap")   # KMPC_RANGEREC_* words 0 ... 15, in order
+
+
+def range_default():
+    """the default sensor row, a plain automotive radar (120, 0.25, 0.12, 0, 0, 1, 5, 0.01, 0.25, 0.0625, 0.0144, 0 ...), as a numpy row [16], from
+    kmpc_range_default"""
+    return default_row("kmpc_range_default", RANGE_WORDS)
+
+
+def range_neutral():
+    """the neutral sensor row [16]: no range limit, no noise, no bias, no dropouts, no filter, no coasting -- behind kmpc_follow_fleet the stage
+    then gives that kernel's own cap bit for bit.  The words the neutral stage does not read (Q_*, R_*) keep their defaults."""
+    row = range_default()
+    row[0:7] = (np.inf, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+    return row
+
+
+def check_range_rows(rows):
+    """[B,16] host rows -> ValueError unless words 0 ... 10 are finite (range_max may be +inf), range_max > 0, both sigmas >= 0, 0 <= p_drop <= 1,
+    filter is 0 or 1, coast_max is a whole number in 0 ... 1000, q_gap and q_v >= 0, r_gap and r_v > 0.  The kernel cannot refuse a row -- a bad
+    word poisons that vehicle's own cap -- so this says so where the rows are written."""
+    rows = host_rows(rows)
+    if rows.ndim != 2 or rows.shape[1] != RANGE_WORDS:
+        raise ValueError("range rows: [B,16] (%s, five unused words), got %s" % (", ".join(RANGE_FIELDS), rows.shape))
+    with np.errstate(invalid="ignore"):
+        ok = (np.isfinite(rows[:, 1:11]).all(1) & (rows[:, 0] > 0.0) & (rows[:, 1] >= 0.0) & (rows[:, 2] >= 0.0) & (rows[:, 4] >= 0.0)
+              & (rows[:, 4] <= 1.0) & ((rows[:, 5] == 0.0) | (rows[:, 5] == 1.0)) & (rows[:, 6] == np.floor(rows[:, 6])) & (rows[:, 6] >= 0.0)
+              & (rows[:, 6] <= 1000.0) & (rows[:, 7] >= 0.0) & (rows[:, 8] >= 0.0) & (rows[:, 9] > 0.0) & (rows[:, 10] > 0.0))
+    if not ok.all():
+        raise ValueError("range rows: every word finite (range_max may be +inf), range_max > 0, sigma_r and sigma_v >= 0, 0 <= p_drop <= 1, filter 0 "
+                         "or 1, coast_max a whole number in 0 ... 1000, q_gap and q_v >= 0, r_gap and r_v > 0 (vehicle(s) %s)" % rows_of(~ok))
+    return rows
+
+
+def range_params(B, device=0, **overrides):
+    """[B,16] float64 sensor rows on `device`: the default row, with each override (RANGE_FIELDS) a scalar or one value per vehicle.  Validated on
+    the host (check_range_rows) before anything reaches the device."""
+    return torch.as_tensor(check_range_rows(table_rows("range_params", RANGE_FIELDS, range_default(), B, overrides))).to(device_of(device))
+
+
+def fresh_range_rec(B, device):
+    """[B,16] float64 on `device`: B fresh track records (kmpc_range_rec_init: no track, zeros)"""
+    rec = np.empty((int(B), RANGE_WORDS))
+    _lib.check(_lib.load().kmpc_range_rec_init(rec.ctypes.data_as(C.POINTER(C.c_double)), int(B)))
+    return torch.from_numpy(rec).to(device_of(device))
+
+
+class RangeSensor:
+    """A range sensor and a leader tracker per vehicle (kmpc_range_follow_batch, include/kmpc_range.h), for Follower(radar=): range limit, bias,
+    seeded noise on range and on the leader's speed, dropouts, and a two-state Kalman track on (gap, leader speed) that coasts through dropouts.
+    `seed`: the draws' key; vehicle b draws as vehicle id_base + b of period k, whatever B or the shard.
+
+    rows [B,16] (range_params), rec [B,16] (RANGE_REC_FIELDS), meas [B,4] (z_r, z_v -- NaN when nothing was detected --, detected, coast of the
+    last call): public device tensors, the first two read by every call as they are -- edit them in place between steps.  reset() starts the
+    record afresh, summary() downloads it."""
+
+    def __init__(self, B, device=0, rows=None, seed=0, id_base=0):
+        self.B, self.device = int(B), device_of(device)
+        self.seed, self.id_base = int(seed), int(id_base)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed: an integer in 0 ... 2^64 - 1")
+        self.rows = range_params(self.B, self.device) if rows is None else rows
+        self._check()
+        self.meas = torch.zeros((self.B, 4), dtype=torch.float64, device=self.device)
+        self.reset()
+
+    def _check(self):
+        if not is_buffer(self.rows, torch.float64, (self.B, RANGE_WORDS), self.device):
+            raise ValueError("rows must be a contiguous float64 tensor [%d,16] on %s (range_params; write into it in place)" % (self.B, self.device))
+
+    def reset(self):
+        """a fresh record for every vehicle: no track"""
+        self.rec = fresh_range_rec(self.B, self.device)
+
+    def summary(self):
+        """the record as named numpy fields [B] (one synchronising download): RANGE_REC_FIELDS, the track id, coast and the counts as integers"""
+        a = self.rec.cpu().numpy()
+        out = {k: a[:, i].copy() for i, k in enumerate(RANGE_REC_FIELDS)}
+        for k in ("track_id", "coast", "n", "n_detect", "n_drop", "n_out", "n_new", "n_lost", "n_bound"):
+            out[k] = out[k].astype(np.int64)
+        return out
+
+
 class Follower:
     """Car following on a waypoint helper's recorded paths (kmpc_follow_fleet, include/kmpc_follow.h): per vehicle the nearest vehicle ahead on
     its own path by arclength, the gap to it, and a speed cap from the following law.  `grt`: a FleetRefTrajectory (the vehicle's path is
@@ -391,9 +477,15 @@ class Follower:
 
     rows [B,8] (follow_params): a public device tensor, read by every cap() as it is -- edit it in place between steps, like fleet.path_id.
     After a cap(): `gap` [B] (+inf without a leader), `leader_speed` [B] (0 without), `leader` [B] int32 (-1 without); `stat` [B,8] is the
-    running record (FOLLOW_STAT_FIELDS; reset() starts it afresh, summary() downloads it)."""
+    running record (FOLLOW_STAT_FIELDS; reset() starts it afresh, summary() downloads it).
 
-    def __init__(self, grt, rows=None):
+    radar=RangeSensor(B, ...): the law no longer reads the truth.  cap() runs the search as before -- `stat`, `gap`, `leader_speed` and `leader` stay
+    the record of the TRUTH: contacts and the smallest gap are physical facts -- and keeps that call's cap as `v_ideal` [B], what a perfect sensor
+    would have said; then kmpc_range_follow_batch (include/kmpc_range.h) measures, tracks and applies the law to what the track believes, with the
+    follower's own speed from `known`: that is the cap returned.  `gap_seen`, `v_lead_seen` [B]: the track's gap and leader speed (+inf and 0
+    without a track).  Without radar= the class makes exactly the library calls it made without the argument."""
+
+    def __init__(self, grt, rows=None, radar=None):
         if not isinstance(grt, (FleetRefTrajectory, GPSRefTrajectory)):
             raise ValueError("Follower follows on a GPSRefTrajectory or a FleetRefTrajectory; a %s is neither" % type(grt).__name__)
         self.fleet, self.device, self._lib = grt, grt.device, grt._lib
@@ -413,18 +505,33 @@ class Follower:
         self.leader = torch.full((B,), -1, dtype=torch.int32, device=dev)
         self._track = None                                                       # the geometry-only score call's err, seg, closest
         self._on_path = torch.empty((B,), dtype=torch.bool, device=dev)          # placed by the score call (and `present`, where given)
+        if radar is not None and not (isinstance(radar, RangeSensor) and radar.B == B and radar.device == dev):
+            raise ValueError("radar= must be a ref_traj.RangeSensor for %d vehicles on %s" % (B, dev))
+        self.radar = radar
+        self.v_ideal = torch.empty((B,), dtype=torch.float64, device=dev) if radar is not None else None
         self.reset()
 
     gap = property(lambda self: self.gap_leader[:, 0])
     leader_speed = property(lambda self: self.gap_leader[:, 1])
+
+    def _seen(self, word, none):
+        if self.radar is None:
+            raise ValueError("gap_seen and v_lead_seen are a radar's: this Follower has none (radar=RangeSensor(...))")
+        rec = self.radar.rec
+        return torch.where(rec[:, 5] >= 0.0, rec[:, word], torch.full_like(rec[:, word], none))
+
+    gap_seen = property(lambda self: self._seen(0, float("inf")))
+    v_lead_seen = property(lambda self: self._seen(1, 0.0))
 
     def _check_rows(self):
         if not is_buffer(self.rows, torch.float64, (self.B, FOLLOW_WORDS), self.device):
             raise ValueError("rows must be a contiguous float64 tensor [%d,8] on %s (follow_params; write into it in place)" % (self.B, self.device))
 
     def reset(self):
-        """a fresh record for every vehicle"""
+        """a fresh record for every vehicle (and, with a radar, no track)"""
         self.stat = fresh_follow_stat(self.B, self.device)
+        if self.radar is not None:
+            self.radar.reset()
 
     def summary(self):
         """the record as named numpy fields [B] (one synchronising download): FOLLOW_STAT_FIELDS, the four counts as integers"""
@@ -434,12 +541,33 @@ class Follower:
             out[k] = out[k].astype(np.int64)
         return out
 
-    def cap(self, state, v_cap, out=None, present=None):
+    def cap(self, state, v_cap, out=None, present=None, known=None, k=None, dt=None):
         """state: device tensor [B,W], X, Y, psi, v first (the plant's [B,8] as it is: no copy); v_cap [B] -> v [B] (`out`, which may be v_cap
         itself, or a new tensor): v_cap, lowered where the vehicle ahead demands it.  present [B] (uint8 / bool) or None: 0 = not on the road.
         One geometry-only track_score_batch call for the arclengths, then kmpc_follow_fleet; a vehicle the score call refuses (a path id
-        outside the set, a pose that is not finite) is not on the road.  Asynchronous on torch's current stream."""
+        outside the set, a pose that is not finite) is not on the road.  With a radar: known [B,W] (v in column 3: the state the controllers
+        read; None: `state`), k (the period's index: the draws' counter) and dt (the period [s]) -- k and dt are then required.
+        Asynchronous on torch's current stream."""
         dev, B = self.device, self.B
+        radar = self.radar
+        if radar is None:
+            if known is not None or k is not None or dt is not None:
+                raise ValueError("known=, k= and dt= are read by a radar: this Follower has none (radar=RangeSensor(...))")
+        else:
+            if k is None or dt is None:
+                raise ValueError("a Follower with a radar needs the period's index k= (the draws' counter) and its length dt= [s] in every cap()")
+            k, dt = int(k), float(dt)
+            if not (k >= 0 and 0.0 < dt < float("inf")):
+                raise ValueError("k >= 0 and a finite dt > 0, got k=%d, dt=%r" % (k, dt))
+            kn = state if known is None else known
+            if not (type(kn) is torch.Tensor and kn.dtype == torch.float64 and kn.device == dev and kn.dim() == 2 and kn.shape[0] == B
+                    and kn.shape[1] >= 4 and (B == 0 or kn.stride(1) == 1) and kn.stride(0) >= 4):
+                kn = torch.as_tensor(kn, dtype=torch.float64, device=dev).contiguous()
+                if kn.dim() != 2 or kn.shape[0] != B or kn.shape[1] < 4:
+                    raise ValueError("known: expected [%d,W] with v in column 3, got %s" % (B, tuple(kn.shape)))
+            radar._check()
+            if not is_buffer(radar.rec, torch.float64, (B, RANGE_WORDS), dev):
+                raise ValueError("radar.rec must stay a contiguous float64 tensor [%d,16] on %s (reset() gives a fresh one)" % (B, dev))
         st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=dev)
         if not (st.dtype == torch.float64 and st.device == dev and st.dim() == 2 and st.shape[1] >= 4 and (B == 0 or st.stride(1) == 1)
                 and st.stride(0) >= 4):
@@ -468,8 +596,12 @@ class Follower:
         if present is not None:
             torch.logical_and(self._on_path, present, out=self._on_path)
         _lib.check(self._lib.kmpc_follow_fleet(dev.index, B, ptr(self._track["err"][:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid),
-                                               ptr(self._on_path), ptr(self.rows), ptr(vc), ptr(out), ptr(self.gap_leader), ptr(self.leader),
-                                               ptr(self.stat), stream(dev)))
+                                               ptr(self._on_path), ptr(self.rows), ptr(vc), ptr(out if radar is None else self.v_ideal),
+                                               ptr(self.gap_leader), ptr(self.leader), ptr(self.stat), stream(dev)))
+        if radar is not None:
+            _lib.check(self._lib.kmpc_range_follow_batch(dev.index, B, dt, ptr(self.gap_leader), ptr(self.leader), ptr(st[:, 3]), int(st.stride(0)),
+                                                         ptr(kn[:, 3]), int(kn.stride(0)), ptr(self.rows), ptr(radar.rows), radar.seed, k,
+                                                         radar.id_base, ptr(vc), ptr(out), ptr(radar.rec), ptr(radar.meas), stream(dev)))
         return out
 
 

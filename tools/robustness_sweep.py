@@ -59,7 +59,14 @@ is and once with estimator= and compensator=: smallest gap, contacts, the speed 
 paths, a slow vehicle (3 m/s) in front and five at 6 m/s behind it, under --platoon's cells and both of its ways: contacts, smallest own-lane gap, lane
 changes, how many of the fast vehicles end ahead of the slow one and back in lane 0, their mean speed, solves not Optimal.
 
+--radar is the sweep of the range sensor (-> profiles/robustness_sweep_radar.txt): follower=ref_traj.Follower(radar=ref_traj.RangeSensor), --platoon's
+platoons of eight at T_HEADWAY 1 s without command delay, GPS sigma 0.2 m and speed sigma 0.1 m/s (the law's own speed is the sensed one): SIGMA_R
+(0, 0.25, 0.5, 1) m x P_DROP (0, 0.1, 0.3) x RANGE_MAX (+inf, 30, 15) m x FILTER (0, 1): smallest true gap, contacts, the dip ratio, the rms change
+of v_follow from period to period (noise passed to the command), the rms of GAP_HAT - gap, the share of Optimal solves; and a standing leader 100 m
+ahead of a 6 m/s follower per RANGE_MAX: where it stops.
+
 usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
+       python tools/robustness_sweep.py --radar [out.txt]
        python tools/robustness_sweep.py --platoon [out.txt]
        python tools/robustness_sweep.py --overtake [out.txt]
        python tools/robustness_sweep.py --wander [out.txt] [steps]
@@ -958,6 +965,106 @@ def platoon_main():
             f.write("\n".join(LINES) + "\n")
 
 
+RD_SIGMA, RD_DROP, RD_RANGE, RD_FILTER = (0.0, 0.25, 0.5, 1.0), (0.0, 0.1, 0.3), (float("inf"), 30.0, 15.0), (0, 1)
+RD_STAND_GAP, RD_STAND_STEPS = 100.0, 400
+
+
+def _paths():
+    paths = []
+    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
+        d = np.load(os.path.join(ROOT, "tests", "golden", name))
+        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    return paths
+
+
+def radar_main():
+    """one loop of 4 x 3 x 3 x 2 cells of three platoons of eight (--platoon's, T_HEADWAY 1 s, no command delay), every follower with a range sensor
+    of its cell's row (the other words default); then one loop of three pairs on path1, a standing leader RD_STAND_GAP m ahead of a 6 m/s follower,
+    one pair per RANGE_MAX with a noise-free sensor."""
+    from mkz_mpc_path_follower_amd.ref_traj import Follower, RangeSensor, follow_params, range_params
+    argv = [a for a in sys.argv if a != "--radar"]
+    paths = _paths()
+    cells = list(itertools.product(range(4), range(3), range(3), range(2)))
+    n_pl = 3 * len(cells)
+    B = n_pl * PL_SIZE
+    platoon = np.repeat(np.arange(n_pl), PL_SIZE)
+    rank = np.tile(np.arange(PL_SIZE), n_pl)
+    ix = np.array(cells)[platoon // 3]                          # [B,4] grid indices: sigma_r, p_drop, range_max, filter
+    steps = sum(n for _, n in PL_PHASES)
+    fleet = FleetRefTrajectory([paths[q % 3] for q in range(n_pl)], platoon, traj_horizon=8, traj_dt=0.2)
+    pose = np.empty((B, 3))
+    for b in range(B):
+        tr = fleet.trajectories[platoon[b]]
+        i = int(np.searchsorted(tr[:, 6], 5.0 + PL_SPACING * (PL_SIZE - 1 - rank[b])))
+        pose[b] = tr[i, 4], tr[i, 5], tr[i, 3]
+    sim = VehicleSimulator(B, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2])
+    sim.state[:, 3] = PL_PHASES[0][0]
+    radar = RangeSensor(B, rows=range_params(B, sigma_r=np.array(RD_SIGMA)[ix[:, 0]], p_drop=np.array(RD_DROP)[ix[:, 1]],
+                                             range_max=np.array(RD_RANGE)[ix[:, 2]], filter=np.array(RD_FILTER)[ix[:, 3]]), seed=77)
+    follower = Follower(fleet, rows=follow_params(B), radar=radar)
+    loop = ClosedLoop(fleet, sim, N=8, target_vel=PL_PHASES[0][0], sensor=SensorModel(B, sigma=(0.2, 0.2, 0.0, 0.1), seed=2024), follower=follower)
+    hist = {k: [] for k in ("state", "v_follow", "gap", "gap_seen", "status")}
+    for v_lead, n in PL_PHASES:
+        loop.v_target[torch.as_tensor(rank == 0, device=sim.device)] = v_lead
+        o = loop.run(n, history=True)
+        for k in hist:
+            hist[k].append(o[k][1:] if k == "state" else o[k])
+    h = {k: torch.cat(v, 0).cpu().numpy() for k, v in hist.items()}
+    speed = h["state"][:, :, 3]
+    n0 = PL_PHASES[0][1]
+    dip = speed[n0 - 40:n0].mean(0) - speed[n0:].min(0)
+    f, rs = follower.summary(), radar.summary()
+    say("%s: %d vehicles in %d platoons of %d on the three paths, %d periods of 0.1 s, nominal plant, default following rows; the leader's target steps "
+        "%s m/s after %s periods; GPS sigma 0.2 m, speed sigma 0.1 m/s, no filter on the ego state; every state finite: %s; latched vehicles: %d"
+        % (torch.cuda.get_device_name(0), B, n_pl, PL_SIZE, steps, " -> ".join("%g" % v for v, _ in PL_PHASES),
+           " / ".join(str(n) for _, n in PL_PHASES[:-1]), bool(torch.isfinite(sim.state).all().item()), int(loop.command_stop.sum().item())))
+    say("per cell of three platoons (21 followers): smallest true gap [m], vehicle-periods in contact, speed dip of the last follower / of the first "
+        "(median of the three platoons), rms change of v_follow per period [m/s], rms of GAP_HAT - gap [m] over the tracked periods, share of the "
+        "followers' periods with a track, share of Optimal solves")
+    fol = rank > 0
+    for c, (a, d, r, fl) in enumerate(cells):
+        sel = (platoon // 3) == c
+        fs = sel & fol
+        ratio = [dip[(platoon == q) & (rank == PL_SIZE - 1)][0] / dip[(platoon == q) & (rank == 1)][0] for q in range(3 * c, 3 * c + 3)]
+        dv = np.diff(h["v_follow"][:, fs], axis=0)
+        tracked = np.isfinite(h["gap_seen"][:, fs]) & np.isfinite(h["gap"][:, fs])
+        eg = (h["gap_seen"][:, fs] - h["gap"][:, fs])[tracked]
+        say("   SIGMA_R %.2f m, P_DROP %.1f, RANGE_MAX %4s m, FILTER %d   %7.3f %5d %6.3f %7.4f %7.4f %6.3f %7.4f"
+            % (RD_SIGMA[a], RD_DROP[d], "inf" if np.isinf(RD_RANGE[r]) else "%g" % RD_RANGE[r], RD_FILTER[fl], f["min_gap"][sel].min(),
+               f["n_contact"][sel].sum(), np.median(ratio), np.sqrt((dv * dv).mean()), np.sqrt((eg * eg).mean()) if eg.size else float("nan"),
+               tracked.mean(), (h["status"][:, sel] == 0).mean()))
+    say("tracks started %d, given up %d; detections %d, dropped %d, out of range %d of %d follower-periods"
+        % (rs["n_new"].sum(), rs["n_lost"].sum(), rs["n_detect"].sum(), rs["n_drop"].sum(), rs["n_out"].sum(), int(fol.sum()) * steps))
+    # a standing leader: stopping distance against range
+    n = len(RD_RANGE)
+    tr = FleetRefTrajectory([paths[0]] * n, np.repeat(np.arange(n), 2), traj_horizon=8, traj_dt=0.2)
+    pose = np.empty((2 * n, 3))
+    for b in range(2 * n):
+        t = tr.trajectories[b // 2]
+        i = int(np.searchsorted(t[:, 6], 5.0 + (RD_STAND_GAP + 4.9 if b % 2 == 0 else 0.0)))      # even: the standing leader, in front
+        pose[b] = t[i, 4], t[i, 5], t[i, 3]
+    targets = np.tile([0.0, VT], n)
+    sim = VehicleSimulator(2 * n, X0=pose[:, 0], Y0=pose[:, 1], Psi0=pose[:, 2])
+    sim.state[:, 3] = torch.as_tensor(targets, device=sim.device)
+    radar = RangeSensor(2 * n, rows=range_params(2 * n, sigma_r=0.0, sigma_v=0.0, range_max=np.repeat(RD_RANGE, 2)), seed=78)
+    follower = Follower(tr, rows=follow_params(2 * n), radar=radar)
+    loop = ClosedLoop(tr, sim, N=8, target_vel=list(targets), follower=follower)
+    o = loop.run(RD_STAND_STEPS, history=True)
+    gap, v = o["gap"].cpu().numpy(), o["state"][1:, :, 3].cpu().numpy()
+    f = follower.summary()
+    say("a standing leader %g m ahead of a follower at %g m/s on path1, noise-free sensor, default following row (D_MIN 5 m, A_BRAKE 0.7 m/s^2, "
+        "T_HEADWAY 1 s), %d periods; every state finite: %s" % (RD_STAND_GAP, VT, RD_STAND_STEPS, bool(torch.isfinite(sim.state).all().item())))
+    for q in range(n):
+        b = 2 * q + 1
+        first = int(np.argmax(np.isfinite(o["gap_seen"][:, b].cpu().numpy())))
+        say("   RANGE_MAX %4s m: first seen at a gap of %7.3f m, smallest gap %7.3f m, last gap %7.3f m, last speed %6.3f m/s, periods in contact %d; the "
+            "leader moved %.3f m" % ("inf" if np.isinf(RD_RANGE[q]) else "%g" % RD_RANGE[q], gap[first, b], f["min_gap"][b], gap[-1, b], v[-1, b],
+                                     f["n_contact"][b], float(np.hypot(*(o["state"][-1, 2 * q, 0:2] - o["state"][0, 2 * q, 0:2]).cpu().numpy()))))
+    if len(argv) > 1:
+        with open(argv[1], "w") as fh:
+            fh.write("\n".join(LINES) + "\n")
+
+
 OV_SIZE, OV_STEPS, OV_SLOW, OV_FAST = 6, 350, 3.0, 6.0
 
 
@@ -1024,7 +1131,9 @@ def overtake_main():
 
 
 if __name__ == "__main__":
-    if "--overtake" in sys.argv[1:]:
+    if "--radar" in sys.argv[1:]:
+        radar_main()
+    elif "--overtake" in sys.argv[1:]:
         overtake_main()
     elif "--platoon" in sys.argv[1:]:
         platoon_main()
