@@ -51,6 +51,8 @@ EXT_EXPORTS = ["kmpc_follow_default", "kmpc_follow_stat_init", "kmpc_follow_flee
 LANE_EXPORTS = ["kmpc_lane_default", "kmpc_lane_rec_init", "kmpc_lane_step_fleet", "kmpc_ref_offset_batch"]
 # the entry points of include/kmpc_range.h, likewise
 RANGE_EXPORTS = ["kmpc_range_default", "kmpc_range_rec_init", "kmpc_range_follow_batch"]
+# the entry points of include/kmpc_order.h, likewise
+ORDER_EXPORTS = ["kmpc_order_bytes", "kmpc_order_fleet", "kmpc_order_follow_fleet", "kmpc_order_lane_step_fleet"]
 
 _lib = None
 
@@ -142,7 +144,11 @@ def load():
     L.kmpc_range_default.argtypes = [dp, i32]
     L.kmpc_range_rec_init.argtypes = [dp, i32]
     L.kmpc_range_follow_batch.argtypes = [i32, i32, C.c_double, vp, vp, vp, i32, vp, i32, vp, vp, C.c_uint64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
-    for name in EXPORTS + EXT_EXPORTS + LANE_EXPORTS + RANGE_EXPORTS:
+    L.kmpc_order_bytes.argtypes = [i32, i32, C.POINTER(C.c_int64)]
+    L.kmpc_order_fleet.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp]
+    L.kmpc_order_follow_fleet.argtypes = L.kmpc_follow_fleet.argtypes[:-1] + [vp, vp]                              # ..., order, stream
+    L.kmpc_order_lane_step_fleet.argtypes = L.kmpc_lane_step_fleet.argtypes[:-1] + [vp, i32, vp, C.c_int64, vp]    # ..., order, lanes_max, workspace, bytes, stream
+    for name in EXPORTS + EXT_EXPORTS + LANE_EXPORTS + RANGE_EXPORTS + ORDER_EXPORTS:
         getattr(L, name)
     _lib = L
     return L

@@ -15,6 +15,7 @@
 #include "../../include/kmpc_follow.h"
 #include "../../include/kmpc_lanes.h"
 #include "../../include/kmpc_range.h"
+#include "../../include/kmpc_order.h"
 #include "kmpc_dispatch.h"
 
 #ifndef KMPC_HOST_ZERO_COPY_MAX
@@ -952,6 +953,90 @@ extern "C" int32_t kmpc_range_follow_batch(int32_t device, int32_t B, double dt,
     const RG w = {B, speed_true_stride, speed_known_stride, dt, seed, (uint64_t)period, (uint64_t)id_base, truth, leader, speed_true, speed_known,
                   follow_rows, range_rows, v_cap, v_cap_out, rec, meas_out};
     return on_device("kmpc_range_follow_batch", device, [&] { return kmpc_launch_range_follow(w, (hipStream_t)stream); });
+}
+
+// ---- the order of a fleet and the searches along it (kmpc_order.hip; include/kmpc_order.h) ----------------------------------
+extern "C" int32_t kmpc_order_bytes(int32_t B, int32_t lanes_max, int64_t *bytes_out)
+{
+    if (B < 0 || lanes_max < 0 || lanes_max > 32 || !bytes_out)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_bytes: bad argument (B=%d, lanes_max=%d (0 ... 32), bytes_out %s)", B, lanes_max,
+                    bytes_out ? "given" : "NULL");
+    *bytes_out = (int64_t)kmpc_order_layout(B, lanes_max).bytes;
+    return KMPC_OK;
+}
+
+extern "C" int32_t kmpc_order_fleet(int32_t device, int32_t B, const double *s_along, int32_t s_stride, const double *speed, int32_t speed_stride,
+                                    const int32_t *path_id, const uint8_t *present, int32_t *order_out, int32_t *count_out, void *workspace,
+                                    int64_t workspace_bytes, void *stream)
+{
+    if (B < 0 || s_stride < 1 || speed_stride < 1)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_fleet: bad B / s_stride / speed_stride (B=%d, s_stride=%d, speed_stride=%d; strides >= 1)", B,
+                    s_stride, speed_stride);
+    const OrderLayout o = kmpc_order_layout(B, 0);
+    if (workspace_bytes < (int64_t)o.bytes)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_fleet: workspace_bytes %lld < kmpc_order_bytes(%d, 0) = %lld", (long long)workspace_bytes, B,
+                    (long long)o.bytes);
+    if (B > 0 && (!s_along || !speed || !order_out || !workspace))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_fleet: null required buffer (s_along %s, speed %s, order_out %s, workspace %s)",
+                    s_along ? "given" : "NULL", speed ? "given" : "NULL", order_out ? "given" : "NULL", workspace ? "given" : "NULL");
+    if (B == 0) return KMPC_OK;
+    char *ws = (char *)workspace;
+    const OS w = {B, s_stride, speed_stride, s_along, speed, path_id, present, order_out, count_out, (uint64_t *)(ws + o.key_lo),
+                  (uint32_t *)(ws + o.key_hi), (int32_t *)(ws + o.idx), (uint32_t *)(ws + o.hist), (uint64_t *)(ws + o.blk),
+                  (uint32_t *)(ws + o.flags), o.key_blocks, o.sort_blocks, o.chunk};
+    return on_device("kmpc_order_fleet", device, [&] { return kmpc_launch_order(w, (hipStream_t)stream); });
+}
+
+extern "C" int32_t kmpc_order_follow_fleet(int32_t device, int32_t B, const double *s_along, int32_t s_stride, const double *speed,
+                                           int32_t speed_stride, const int32_t *path_id, const uint8_t *present, const double *rows,
+                                           const double *v_cap, double *v_cap_out, double *gap_out, int32_t *leader_out, double *stat,
+                                           const int32_t *order, void *stream)
+{
+    if (B < 0 || s_stride < 1 || speed_stride < 1)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_follow_fleet: bad B / s_stride / speed_stride (B=%d, s_stride=%d, speed_stride=%d; strides >= 1)",
+                    B, s_stride, speed_stride);
+    if (B > 0 && (!s_along || !speed || !rows || !v_cap || !v_cap_out || !order))
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_follow_fleet: null required buffer (s_along %s, speed %s, rows %s, v_cap %s, v_cap_out %s, order %s)",
+                    s_along ? "given" : "NULL", speed ? "given" : "NULL", rows ? "given" : "NULL", v_cap ? "given" : "NULL",
+                    v_cap_out ? "given" : "NULL", order ? "given" : "NULL");
+    if (B == 0) return KMPC_OK;
+    const OF w = {{B, s_stride, speed_stride, s_along, speed, path_id, present, rows, v_cap, v_cap_out, gap_out, leader_out, stat}, order};
+    return on_device("kmpc_order_follow_fleet", device, [&] { return kmpc_launch_order_follow(w, (hipStream_t)stream); });
+}
+
+extern "C" int32_t kmpc_order_lane_step_fleet(int32_t device, int32_t B, int32_t k, double dt, const double *s_along, int32_t s_stride,
+                                              const double *e_ct, int32_t e_stride, const double *speed, int32_t speed_stride,
+                                              const int32_t *path_id, const uint8_t *present, const double *follow_rows, const double *lane_rows,
+                                              const double *v_cap, double *v_cap_out, const uint32_t *occ_in, uint32_t *occ_out, double *rec,
+                                              double *gap_out, int32_t *leader_out, double *nbr_out, const int32_t *order, int32_t lanes_max,
+                                              void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (B < 0 || k < 0 || s_stride < 1 || e_stride < 1 || speed_stride < 1)
+        return fail(nullptr, KMPC_ERR_ARG,
+                    "kmpc_order_lane_step_fleet: bad B / k / stride (B=%d, k=%d, s_stride=%d, e_stride=%d, speed_stride=%d; strides >= 1)", B, k,
+                    s_stride, e_stride, speed_stride);
+    if (!pos(dt)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_lane_step_fleet: dt must be finite and > 0");
+    if (lanes_max < 0 || lanes_max > 32) return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_lane_step_fleet: lanes_max %d outside 0 ... 32", lanes_max);
+    const OrderLayout o = kmpc_order_layout(B, lanes_max);
+    if (workspace_bytes < (int64_t)o.bytes)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_lane_step_fleet: workspace_bytes %lld < kmpc_order_bytes(%d, %d) = %lld",
+                    (long long)workspace_bytes, B, lanes_max, (long long)o.bytes);
+    if (B > 0 && (!s_along || !e_ct || !speed || !follow_rows || !lane_rows || !v_cap || !v_cap_out || !occ_in || !occ_out || !rec || !order || !workspace))
+        return fail(nullptr, KMPC_ERR_ARG,
+                    "kmpc_order_lane_step_fleet: null required buffer (s_along %s, e_ct %s, speed %s, follow_rows %s, lane_rows %s, v_cap %s, "
+                    "v_cap_out %s, occ_in %s, occ_out %s, rec %s, order %s, workspace %s)",
+                    s_along ? "given" : "NULL", e_ct ? "given" : "NULL", speed ? "given" : "NULL", follow_rows ? "given" : "NULL",
+                    lane_rows ? "given" : "NULL", v_cap ? "given" : "NULL", v_cap_out ? "given" : "NULL", occ_in ? "given" : "NULL",
+                    occ_out ? "given" : "NULL", rec ? "given" : "NULL", order ? "given" : "NULL", workspace ? "given" : "NULL");
+    if (B > 0 && occ_in == occ_out)
+        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_lane_step_fleet: occ_in == occ_out (the occupancy every vehicle reads is a snapshot nobody writes)");
+    if (B == 0) return KMPC_OK;
+    char *ws = (char *)workspace;
+    const OL w = {{B, k, s_stride, e_stride, speed_stride, dt, s_along, e_ct, speed, path_id, present, follow_rows, lane_rows, v_cap, v_cap_out,
+                   occ_in, occ_out, rec, gap_out, leader_out, nbr_out},
+                  order, lanes_max, o.lane_blocks, (int32_t *)(ws + o.nxt), (int32_t *)(ws + o.prv), (int32_t *)(ws + o.first),
+                  (int32_t *)(ws + o.last), (int32_t *)(ws + o.carry_next), (int32_t *)(ws + o.carry_prev)};
+    return on_device("kmpc_order_lane_step_fleet", device, [&] { return kmpc_launch_order_lane_step(w, (hipStream_t)stream); });
 }
 
 // ---- road profile per path sample (kmpc_road_profile.hip) ----------------------------------------------------------------

@@ -308,6 +308,66 @@ struct RG {
 };
 hipError_t kmpc_launch_range_follow(const RG &w, hipStream_t st);
 
+// the order of a fleet by (path, arclength) and the searches along it (kmpc_order.hip; include/kmpc_order.h).  The workspace, laid out once for
+// kmpc_order_bytes, kmpc_order_fleet and kmpc_order_lane_step_fleet: byte offsets of its regions (each a multiple of 256) and the launch geometry
+// that sizes them.  Monotone in B and in lanes_max; B == 0 needs nothing.
+struct OrderLayout {
+    size_t key_lo, key_hi, idx, hist, blk, flags;           // the sort: keys by vehicle, the second index buffer, digit counts, block reductions, flags
+    size_t nxt, prv, first, last, carry_next, carry_prev;   // the lanes: tables [lanes_max,B], block marks and carries [lanes_max,lane_blocks]
+    size_t bytes;
+    int key_blocks, sort_blocks, chunk, lane_blocks;
+};
+inline OrderLayout kmpc_order_layout(int B, int lanes_max)
+{
+    OrderLayout o = {};
+    if (B <= 0) return o;
+    const size_t n = (size_t)B, lm = (size_t)lanes_max;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t kb = (n + 255) / 256, big = (size_t)1 << 21;
+    o.key_blocks = (int)(kb < 1024 ? kb : 1024);
+    o.chunk = n <= big ? 2048 : (int)up((n + 1023) / 1024);     // positions per workgroup of a sort pass: at most 1024 workgroups
+    o.sort_blocks = (int)((n + (size_t)o.chunk - 1) / (size_t)o.chunk);
+    o.lane_blocks = (int)kb;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += up(bytes); return at; };
+    o.key_lo = take(8 * n); o.key_hi = take(4 * n); o.idx = take(4 * n);
+    o.hist = take(4 * 256 * (n <= big ? (n + 2047) / 2048 : (size_t)1024));
+    o.blk = take(32 * (size_t)o.key_blocks); o.flags = take(256);
+    o.nxt = take(4 * n * lm); o.prv = take(4 * n * lm);
+    o.first = take(4 * kb * lm); o.last = take(4 * kb * lm); o.carry_next = take(4 * kb * lm); o.carry_prev = take(4 * kb * lm);
+    o.bytes = off;
+    return o;
+}
+struct OS {                          // kmpc_order_fleet
+    int B, s_stride, speed_stride;
+    const double *s_along, *speed;
+    const int32_t *path_id;          // [B] or null
+    const uint8_t *present;          // [B] or null
+    int32_t *order_out;              // [B]: also the first of the two index buffers of the sort
+    int32_t *count_out;              // [1] or null
+    uint64_t *key_lo;                // [B] by vehicle: the low 64 bits of its key
+    uint32_t *key_hi;                // [B] by vehicle: the high 32 bits
+    int32_t *idx;                    // [B] the second index buffer
+    uint32_t *hist;                  // [256,sort_blocks] a pass's digit counts, scanned in place
+    uint64_t *blk;                   // [key_blocks,4] OR and AND of the keys, the usable count, per workgroup of the key kernel
+    uint32_t *flags;                 // [0] bit p: digit p is the same for the whole fleet; [1] the usable count
+    int key_blocks, sort_blocks, chunk;
+};
+hipError_t kmpc_launch_order(const OS &w, hipStream_t st);
+struct OF {                          // kmpc_order_follow_fleet
+    FL f;
+    const int32_t *order;            // [B]
+};
+hipError_t kmpc_launch_order_follow(const OF &k, hipStream_t st);
+struct OL {                          // kmpc_order_lane_step_fleet
+    LN l;
+    const int32_t *order;            // [B]
+    int lanes_max, lane_blocks;
+    int32_t *nxt, *prv;              // [lanes_max,B] next / previous position whose vehicle is usable and occupies the lane, -1 = none
+    int32_t *first, *last, *carry_next, *carry_prev;   // [lanes_max,lane_blocks]
+};
+hipError_t kmpc_launch_order_lane_step(const OL &k, hipStream_t st);
+
 // batched Frenet reference: vehicle-frame path, curvature-polynomial fit, initial condition (kmpc_frenet_ref.hip;
 // scripts/nodes_gazebo_sim/gazebo_sim_mpc_cmd_pub_frenet.jl:54-85, scripts/sim_path_utils/nav_msgs_path_frenet.py:44-86)
 struct FR {

@@ -470,6 +470,24 @@ class RangeSensor:
         return out
 
 
+SEARCHES = ("pairs", "sorted")
+
+
+def check_search(search):
+    """search= of Follower and Lanes: "pairs" (the exact pair search) or "sorted" (the search along the order, include/kmpc_order.h)"""
+    if search not in SEARCHES:
+        raise ValueError("search= must be one of %s, got %r" % (" / ".join(repr(s) for s in SEARCHES), search))
+    return search
+
+
+def order_buffers(lib, B, lanes_max, device):
+    """what a sorted search owns, allocated once: order [B] int32, the usable count [1] int32, a workspace of kmpc_order_bytes(B, lanes_max)"""
+    n = C.c_int64()
+    _lib.check(lib.kmpc_order_bytes(int(B), int(lanes_max), C.byref(n)))
+    return (torch.empty((B,), dtype=torch.int32, device=device), torch.zeros((1,), dtype=torch.int32, device=device),
+            torch.empty((max(int(n.value), 1),), dtype=torch.uint8, device=device))
+
+
 class Follower:
     """Car following on a waypoint helper's recorded paths (kmpc_follow_fleet, include/kmpc_follow.h): per vehicle the nearest vehicle ahead on
     its own path by arclength, the gap to it, and a speed cap from the following law.  `grt`: a FleetRefTrajectory (the vehicle's path is
@@ -483,9 +501,14 @@ class Follower:
     the record of the TRUTH: contacts and the smallest gap are physical facts -- and keeps that call's cap as `v_ideal` [B], what a perfect sensor
     would have said; then kmpc_range_follow_batch (include/kmpc_range.h) measures, tracks and applies the law to what the track believes, with the
     follower's own speed from `known`: that is the cap returned.  `gap_seen`, `v_lead_seen` [B]: the track's gap and leader speed (+inf and 0
-    without a track).  Without radar= the class makes exactly the library calls it made without the argument."""
+    without a track).  Without radar= the class makes exactly the library calls it made without the argument.
 
-    def __init__(self, grt, rows=None, radar=None):
+    search="pairs": kmpc_follow_fleet's exact pair search, O(B^2) -- the default, and the faster one for a few thousand vehicles.  search="sorted":
+    every cap() orders the fleet by (path, arclength) (kmpc_order_fleet) and searches along that order (kmpc_order_follow_fleet;
+    include/kmpc_order.h), O(B log B) with the same results bit for bit; `order` [B] int32, the count word and the workspace are allocated once,
+    here.  The radar works unchanged behind either: it reads `gap_leader` and `leader`."""
+
+    def __init__(self, grt, rows=None, radar=None, search="pairs"):
         if not isinstance(grt, (FleetRefTrajectory, GPSRefTrajectory)):
             raise ValueError("Follower follows on a GPSRefTrajectory or a FleetRefTrajectory; a %s is neither" % type(grt).__name__)
         self.fleet, self.device, self._lib = grt, grt.device, grt._lib
@@ -509,6 +532,9 @@ class Follower:
             raise ValueError("radar= must be a ref_traj.RangeSensor for %d vehicles on %s" % (B, dev))
         self.radar = radar
         self.v_ideal = torch.empty((B,), dtype=torch.float64, device=dev) if radar is not None else None
+        self.search = check_search(search)
+        if search == "sorted":
+            self.order, self._count, self._ws = order_buffers(self._lib, B, 0, dev)
         self.reset()
 
     gap = property(lambda self: self.gap_leader[:, 0])
@@ -595,9 +621,13 @@ class Follower:
         torch.ge(self._track["seg"], 0, out=self._on_path)
         if present is not None:
             torch.logical_and(self._on_path, present, out=self._on_path)
-        _lib.check(self._lib.kmpc_follow_fleet(dev.index, B, ptr(self._track["err"][:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid),
-                                               ptr(self._on_path), ptr(self.rows), ptr(vc), ptr(out if radar is None else self.v_ideal),
-                                               ptr(self.gap_leader), ptr(self.leader), ptr(self.stat), stream(dev)))
+        args = (dev.index, B, ptr(self._track["err"][:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid), ptr(self._on_path))
+        outs = (ptr(self.rows), ptr(vc), ptr(out if radar is None else self.v_ideal), ptr(self.gap_leader), ptr(self.leader), ptr(self.stat))
+        if self.search == "pairs":
+            _lib.check(self._lib.kmpc_follow_fleet(*args, *outs, stream(dev)))
+        else:
+            _lib.check(self._lib.kmpc_order_fleet(*args, ptr(self.order), ptr(self._count), ptr(self._ws), self._ws.numel(), stream(dev)))
+            _lib.check(self._lib.kmpc_order_follow_fleet(*args, *outs, ptr(self.order), stream(dev)))
         if radar is not None:
             _lib.check(self._lib.kmpc_range_follow_batch(dev.index, B, dt, ptr(self.gap_leader), ptr(self.leader), ptr(st[:, 3]), int(st.stride(0)),
                                                          ptr(kn[:, 3]), int(kn.stride(0)), ptr(self.rows), ptr(radar.rows), radar.seed, k,
@@ -657,9 +687,15 @@ class Lanes:
     they are -- edit them in place between steps.  Views after a step(): `lane` [B], `offset` [B] (columns of rec), `gap` [B] (+inf without a
     leader), `leader_speed` [B], `leader` [B] int32 (-1 without), `neighbours` [B,4,2] (gap and speed of left-ahead, left-behind, right-ahead,
     right-behind; (+inf, 0) where there is none).  Limits: lanes are offsets of ONE recorded path; the speed along an offset line differs by
-    1 - kappa * d and nothing corrects for it; the range sensor is perfect."""
+    1 - kappa * d and nothing corrects for it; the range sensor is perfect.
 
-    def __init__(self, grt, follow_rows=None, lane_rows=None, lane0=None):
+    search="pairs": kmpc_lane_step_fleet's exact pair search, O(B^2), the default.  search="sorted": every step() orders the fleet
+    (kmpc_order_fleet) and runs kmpc_order_lane_step_fleet (include/kmpc_order.h), O(B log B) with the same results bit for bit.  lanes_max: the
+    lanes its per-lane tables cover, 0 ... 32; None sizes them from the largest n_lanes in `lane_rows` here, at construction (one download; none
+    later).  A vehicle whose lanes reach beyond lanes_max is still searched exactly, by a walk.  `order`, the count word and the workspace are
+    allocated once, here."""
+
+    def __init__(self, grt, follow_rows=None, lane_rows=None, lane0=None, search="pairs", lanes_max=None):
         if not isinstance(grt, (FleetRefTrajectory, GPSRefTrajectory)):
             raise ValueError("Lanes run on a GPSRefTrajectory or a FleetRefTrajectory; a %s is neither" % type(grt).__name__)
         self.fleet, self.device, self._lib = grt, grt.device, grt._lib
@@ -688,6 +724,17 @@ class Lanes:
         self._occ = [torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(2)]   # the occupancy words (uint32 bit patterns), ping-ponged
         self._track = None                                                       # the geometry-only score call's err, seg, closest
         self._on_path = torch.empty((B,), dtype=torch.bool, device=dev)
+        self.search = check_search(search)
+        if search == "sorted":
+            if lanes_max is None:
+                n_max = float(self.rows[:, 0].max().item()) if B > 0 else 1.0
+                lanes_max = int(min(max(n_max, 1.0), 32.0)) if n_max == n_max else 32
+            if not (isinstance(lanes_max, int) and 0 <= lanes_max <= 32):
+                raise ValueError("lanes_max: an integer in 0 ... 32 or None, got %r" % (lanes_max,))
+            self.lanes_max = lanes_max
+            self.order, self._count, self._ws = order_buffers(self._lib, B, lanes_max, dev)
+        elif lanes_max is not None:
+            raise ValueError("lanes_max= sizes the tables of search=\"sorted\"; the pair search has none")
         self.reset()
 
     lane = property(lambda self: self.rec[:, 0])
@@ -763,10 +810,15 @@ class Lanes:
             torch.logical_and(self._on_path, present, out=self._on_path)
         err = self._track["err"]
         occ_in, occ_out = self._occ[self._cur], self._occ[1 - self._cur]
-        _lib.check(self._lib.kmpc_lane_step_fleet(dev.index, B, int(k), float(dt), ptr(err[:, 3]), 4, ptr(err[:, 0]), 4, ptr(st[:, 3]),
-                                                  int(st.stride(0)), ptr(pid), ptr(self._on_path), ptr(self.follow_rows), ptr(self.rows), ptr(vc),
-                                                  ptr(out), ptr(occ_in), ptr(occ_out), ptr(self.rec), ptr(self.gap_leader), ptr(self.leader),
-                                                  ptr(self.neighbours), stream(dev)))
+        args = (dev.index, B, int(k), float(dt), ptr(err[:, 3]), 4, ptr(err[:, 0]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid),
+                ptr(self._on_path), ptr(self.follow_rows), ptr(self.rows), ptr(vc), ptr(out), ptr(occ_in), ptr(occ_out), ptr(self.rec),
+                ptr(self.gap_leader), ptr(self.leader), ptr(self.neighbours))
+        if self.search == "pairs":
+            _lib.check(self._lib.kmpc_lane_step_fleet(*args, stream(dev)))
+        else:
+            _lib.check(self._lib.kmpc_order_fleet(dev.index, B, ptr(err[:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid), ptr(self._on_path),
+                                                  ptr(self.order), ptr(self._count), ptr(self._ws), self._ws.numel(), stream(dev)))
+            _lib.check(self._lib.kmpc_order_lane_step_fleet(*args, ptr(self.order), self.lanes_max, ptr(self._ws), self._ws.numel(), stream(dev)))
         self._cur = 1 - self._cur
         return out
 
