@@ -108,7 +108,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._stage import is_buffer, ptr, stream
+from ._stage import is_buffer, ptr, record_fields, stream
 from .kinematic_mpc_frenet import get_reference_frenet_batch
 from .ref_traj import SCORE_FIELDS, FleetRefTrajectory, fresh_score
 from .solver import BatchMPC
@@ -205,27 +205,29 @@ class _ScoredLoop:
         if stage.B != self.B or stage.device != self.sim.device:
             raise ValueError("%s for %d vehicles on %s, plant with %d on %s" % (name, stage.B, stage.device, self.B, self.sim.device))
 
+    def _init_path_stage(self, name, stage, track_with_time, does, built, must_have=None):
+        """what a stage on the helper's arclength grid (planner=, follower=, lanes=) must be, checked in this order: no time grid; built on this
+        loop's own helper (and, `must_have` given, with that method: lanes= is told from a follower by its shift()); for the plant's fleet; every
+        vehicle in target-velocity mode.  `does` and `built`: the stage's own words for the first two refusals."""
+        if track_with_time:
+            raise ValueError("%s= %s: track_with_time must stay False" % (name, does))
+        if getattr(stage, "fleet", None) is not self.grt or (must_have is not None and not hasattr(stage, must_have)):
+            raise ValueError("%s= must be a ref_traj.%s" % (name, built))
+        self._same_fleet(name, stage)
+        if getattr(self.grt, "time_mode", None) is not None and bool(self.grt.time_mode.any().item()):
+            raise ValueError("%s= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode" % name)
+
     def _init_planner(self, planner, track_with_time):
         if planner is not None:
-            if track_with_time:
-                raise ValueError("planner= plans a speed along the arclength grid: track_with_time must stay False")
-            if getattr(planner, "fleet", None) is not self.grt:
-                raise ValueError("planner= must be a ref_traj.SpeedPlanner built on this loop's own waypoint helper (a FleetRefTrajectory)")
-            self._same_fleet("planner", planner)
-            if self.grt.time_mode is not None and bool(self.grt.time_mode.any().item()):
-                raise ValueError("planner= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode")
+            self._init_path_stage("planner", planner, track_with_time, "plans a speed along the arclength grid",
+                                  "SpeedPlanner built on this loop's own waypoint helper (a FleetRefTrajectory)")
         self.planner = planner
         self.v_plan = None     # [B] the planned speed of the last period (planner given): waypoint spacing and the solver's v_target
 
     def _init_follower(self, follower, track_with_time):
         if follower is not None:
-            if track_with_time:
-                raise ValueError("follower= caps a speed on the arclength grid: track_with_time must stay False")
-            if getattr(follower, "fleet", None) is not self.grt:
-                raise ValueError("follower= must be a ref_traj.Follower built on this loop's own waypoint helper")
-            self._same_fleet("follower", follower)
-            if getattr(self.grt, "time_mode", None) is not None and bool(self.grt.time_mode.any().item()):
-                raise ValueError("follower= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode")
+            self._init_path_stage("follower", follower, track_with_time, "caps a speed on the arclength grid",
+                                  "Follower built on this loop's own waypoint helper")
         self.follower = follower
         self.v_follow = None   # [B] v_target under the following law, of the last period (follower given): the plan's cap, or the period's speed
 
@@ -233,13 +235,8 @@ class _ScoredLoop:
         if lanes is not None:
             if self.follower is not None:
                 raise ValueError("lanes= takes the follower's place (its leaders are found by lane): give no follower=")
-            if track_with_time:
-                raise ValueError("lanes= caps a speed on the arclength grid: track_with_time must stay False")
-            if getattr(lanes, "fleet", None) is not self.grt or not hasattr(lanes, "shift"):
-                raise ValueError("lanes= must be a ref_traj.Lanes built on this loop's own waypoint helper")
-            self._same_fleet("lanes", lanes)
-            if getattr(self.grt, "time_mode", None) is not None and bool(self.grt.time_mode.any().item()):
-                raise ValueError("lanes= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode")
+            self._init_path_stage("lanes", lanes, track_with_time, "caps a speed on the arclength grid",
+                                  "Lanes built on this loop's own waypoint helper", must_have="shift")
         self.lanes = lanes
         self._plant_updates = 10
 
@@ -442,15 +439,12 @@ class _ScoredLoop:
         scored state (nan before the first)."""
         B = self.B
         tail = self.track["err"][:, 3:4] if self.track is not None else torch.full((B, 1), float("nan"), dtype=torch.float64, device=self.score.device)
-        a = torch.cat([self.score, tail], 1).cpu().numpy()
-        out = {k: a[:, i].copy() for i, k in enumerate(SCORE_FIELDS)}
-        for k in ("n", "settle_index", "n_refused", "n_live", "n_nonopt", "sum_iters", "latch_index"):
-            out[k] = out[k].astype(np.int64)
+        out = record_fields(torch.cat([self.score, tail], 1), SCORE_FIELDS + ("s_along",),
+                            ("n", "settle_index", "n_refused", "n_live", "n_nonopt", "sum_iters", "latch_index"))
         n = np.maximum(out["n"], 1)
         out["rms_ect"], out["rms_epsi"] = np.sqrt(out["sum_ect2"] / n), np.sqrt(out["sum_epsi2"] / n)
         out["t_settle"] = out["settle_index"] * dt
         out["mean_iters"] = out["sum_iters"] / np.maximum(out["n_live"], 1)
-        out["s_along"] = a[:, len(SCORE_FIELDS)].copy()
         return out
 
 

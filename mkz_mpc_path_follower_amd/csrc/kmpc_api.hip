@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <chrono>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -675,6 +676,39 @@ static int32_t on_device(const char *fn, int device, Launch launch)
 static bool pos(double a) { return a > 0.0 && a <= 1.7976931348623157e308; }       // finite and > 0
 static bool nonneg(double a) { return a >= 0.0 && a <= 1.7976931348623157e308; }   // finite and >= 0
 
+// how a refusal words a pointer argument
+static const char *given(const void *p) { return p ? "given" : "NULL"; }
+
+// "fn: null required buffer (a given, b NULL, ...)" unless every one of the first `n` of `bufs` is given (an entry point that shares its list with
+// a neighbour of more buffers names only its own); KMPC_OK when they all are.  The text is put together only on the way out.
+struct Buf { const char *name; const void *p; };
+static int32_t need_buffers(const char *fn, std::initializer_list<Buf> bufs, size_t n = (size_t)-1)
+{
+    const Buf *end = bufs.begin() + (n < bufs.size() ? n : bufs.size());
+    bool all = true;
+    for (const Buf *b = bufs.begin(); b != end; ++b) all = all && b->p;
+    if (all) return KMPC_OK;
+    std::string list;
+    for (const Buf *b = bufs.begin(); b != end; ++b) list += std::string(b == bufs.begin() ? "" : ", ") + b->name + " " + given(b->p);
+    return fail(nullptr, KMPC_ERR_ARG, "%s: null required buffer (%s)", fn, list.c_str());
+}
+
+// a table of `n` host rows of `words` doubles: zeros, then the {index, value} words of `set` in every row (the row fillers: kmpc_*_default,
+// kmpc_*_init).  `refusal` is the caller's own sentence for n < 0 or a NULL table with n > 0: a format that is handed fn, n and the word for `rows`
+// and takes as many of them as it says.
+struct Word { int index; double value; };
+static int32_t fill_rows(const char *fn, double *rows, int32_t n, int words, std::initializer_list<Word> set,
+                         const char *refusal = "%s: bad argument (B=%d)")
+{
+    if (n < 0 || (n > 0 && !rows)) return fail(nullptr, KMPC_ERR_ARG, refusal, fn, n, given(rows));
+    for (size_t b = 0; b < (size_t)n; ++b) {
+        double *r = rows + (size_t)words * b;
+        for (int i = 0; i < words; ++i) r[i] = 0.0;
+        for (const Word &w : set) r[w.index] = w.value;
+    }
+    return KMPC_OK;
+}
+
 // the plant calls' common arguments, in the order their refusals are documented: B / n_updates / state / cmd, then the plant rows, then the road rows
 // (where the entry point has them).  The drive rows and the queue follow in the callers, and only then "B == 0 or n_updates == 0: nothing to do".
 static int32_t sim_args(const char *fn, int32_t B, int32_t n_updates, const void *state, const void *cmd, const void *plant, const void *road,
@@ -691,7 +725,7 @@ static int32_t queue_args(const char *fn, int32_t depth, int64_t period, const v
 {
     if (depth < 2 || period < 0 || !cmd_queue)
         return fail(nullptr, KMPC_ERR_ARG, "%s: bad queue (depth=%d, at least 2; period=%lld, at least 0; cmd_queue %s)", fn, depth, (long long)period,
-                    cmd_queue ? "given" : "NULL");
+                    given(cmd_queue));
     return KMPC_OK;
 }
 
@@ -706,9 +740,7 @@ static PlantCall plant_call(int32_t B, int32_t n_updates, void *state, const voi
 // ---- tracking errors and the running score record (kmpc_track_score.hip) ----------------------------------------------
 extern "C" int32_t kmpc_track_score_init(double *score_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !score_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_track_score_init: bad argument (B=%d)", B);
-    for (size_t i = 0; i < (size_t)B * KMPC_SCORE_WORDS; ++i) score_host[i] = i % KMPC_SCORE_WORDS == KMPC_SCORE_LATCH_INDEX ? -1.0 : 0.0;
-    return KMPC_OK;
+    return fill_rows("kmpc_track_score_init", score_host, B, KMPC_SCORE_WORDS, {{KMPC_SCORE_LATCH_INDEX, -1.0}});
 }
 
 // the checks both entry points share, before the handle is touched; 1 = nothing to do (B = 0)
@@ -762,13 +794,8 @@ extern "C" int32_t kmpc_pathset_curvature(kmpc_pathset *ps, double window, doubl
 // this project's own defaults (the reference has no such stage): the one place they exist
 extern "C" int32_t kmpc_speed_plan_default(double *rows_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_speed_plan_default: bad argument (B=%d)", B);
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        double *r = rows_host + KMPC_PLAN_WORDS * b;
-        for (int i = 0; i < KMPC_PLAN_WORDS; ++i) r[i] = 0.0;
-        r[KMPC_PLAN_A_LAT] = 2.0; r[KMPC_PLAN_A_BRAKE] = 0.7; r[KMPC_PLAN_V_FLOOR] = 1.0; r[KMPC_PLAN_END_STOP] = 0.0;
-    }
-    return KMPC_OK;
+    return fill_rows("kmpc_speed_plan_default", rows_host, B, KMPC_PLAN_WORDS,
+                     {{KMPC_PLAN_A_LAT, 2.0}, {KMPC_PLAN_A_BRAKE, 0.7}, {KMPC_PLAN_V_FLOOR, 1.0}, {KMPC_PLAN_END_STOP, 0.0}});
 }
 
 // both plan entry points: `profile` is the map of kmpc_speed_plan_fleet_profile (required there), null for kmpc_speed_plan_fleet
@@ -807,39 +834,35 @@ extern "C" int32_t kmpc_speed_plan_fleet_profile(kmpc_pathset *ps, int32_t B, co
 // this project's own defaults (the reference has no such stage): the one place they exist
 extern "C" int32_t kmpc_follow_default(double *rows_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_follow_default: bad argument (B=%d)", B);
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        double *r = rows_host + KMPC_FOLLOW_WORDS * b;
-        for (int i = 0; i < KMPC_FOLLOW_WORDS; ++i) r[i] = 0.0;
-        r[KMPC_FOLLOW_D_MIN] = 5.0; r[KMPC_FOLLOW_T_HEADWAY] = 1.0; r[KMPC_FOLLOW_A_BRAKE] = 0.7; r[KMPC_FOLLOW_K_GAP] = 0.5; r[KMPC_FOLLOW_LENGTH] = 4.9;
-    }
-    return KMPC_OK;
+    return fill_rows("kmpc_follow_default", rows_host, B, KMPC_FOLLOW_WORDS,
+                     {{KMPC_FOLLOW_D_MIN, 5.0}, {KMPC_FOLLOW_T_HEADWAY, 1.0}, {KMPC_FOLLOW_A_BRAKE, 0.7}, {KMPC_FOLLOW_K_GAP, 0.5}, {KMPC_FOLLOW_LENGTH, 4.9}});
 }
 
 extern "C" int32_t kmpc_follow_stat_init(double *stat_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !stat_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_follow_stat_init: bad argument (B=%d)", B);
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        double *r = stat_host + KMPC_FOLLOWSTAT_WORDS * b;
-        for (int i = 0; i < KMPC_FOLLOWSTAT_WORDS; ++i) r[i] = 0.0;
-        r[KMPC_FOLLOWSTAT_MIN_GAP] = INFINITY;
-    }
-    return KMPC_OK;
+    return fill_rows("kmpc_follow_stat_init", stat_host, B, KMPC_FOLLOWSTAT_WORDS, {{KMPC_FOLLOWSTAT_MIN_GAP, INFINITY}});
+}
+
+// the argument block of both follow entry points, checked in the documented order.  `order` is kmpc_order_follow_fleet's one more required buffer
+// (`ordered`); kmpc_follow_fleet has none and does not name it.  1 = nothing to do (B = 0)
+static int follow_args(const char *fn, const FL &w, const int32_t *order, bool ordered)
+{
+    if (w.B < 0 || w.s_stride < 1 || w.speed_stride < 1)
+        return fail(nullptr, KMPC_ERR_ARG, "%s: bad B / s_stride / speed_stride (B=%d, s_stride=%d, speed_stride=%d; strides >= 1)", fn, w.B, w.s_stride,
+                    w.speed_stride);
+    if (w.B > 0 && need_buffers(fn, {{"s_along", w.s_along}, {"speed", w.speed}, {"rows", w.rows}, {"v_cap", w.v_cap}, {"v_cap_out", w.v_cap_out},
+                                     {"order", order}}, ordered ? 6 : 5) != KMPC_OK)
+        return KMPC_ERR_ARG;
+    return w.B == 0 ? 1 : KMPC_OK;
 }
 
 extern "C" int32_t kmpc_follow_fleet(int32_t device, int32_t B, const double *s_along, int32_t s_stride, const double *speed, int32_t speed_stride,
                                      const int32_t *path_id, const uint8_t *present, const double *rows, const double *v_cap, double *v_cap_out,
                                      double *gap_out, int32_t *leader_out, double *stat, void *stream)
 {
-    if (B < 0 || s_stride < 1 || speed_stride < 1)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_follow_fleet: bad B / s_stride / speed_stride (B=%d, s_stride=%d, speed_stride=%d; strides >= 1)", B,
-                    s_stride, speed_stride);
-    if (B > 0 && (!s_along || !speed || !rows || !v_cap || !v_cap_out))
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_follow_fleet: null required buffer (s_along %s, speed %s, rows %s, v_cap %s, v_cap_out %s)",
-                    s_along ? "given" : "NULL", speed ? "given" : "NULL", rows ? "given" : "NULL", v_cap ? "given" : "NULL",
-                    v_cap_out ? "given" : "NULL");
-    if (B == 0) return KMPC_OK;
     const FL w = {B, s_stride, speed_stride, s_along, speed, path_id, present, rows, v_cap, v_cap_out, gap_out, leader_out, stat};
+    const int rc = follow_args("kmpc_follow_fleet", w, nullptr, false);
+    if (rc != KMPC_OK) return rc < 0 ? rc : KMPC_OK;
     return on_device("kmpc_follow_fleet", device, [&] { return kmpc_launch_follow_fleet(w, (hipStream_t)stream); });
 }
 
@@ -847,25 +870,38 @@ extern "C" int32_t kmpc_follow_fleet(int32_t device, int32_t B, const double *s_
 // this project's own defaults (the reference has no such stage): the one place they exist
 extern "C" int32_t kmpc_lane_default(double *rows_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_default: bad argument (B=%d)", B);
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        double *r = rows_host + KMPC_LANE_WORDS * b;
-        for (int i = 0; i < KMPC_LANE_WORDS; ++i) r[i] = 0.0;
-        r[KMPC_LANE_N_LANES] = 1.0; r[KMPC_LANE_WIDTH] = 3.5; r[KMPC_LANE_V_LAT] = 1.0; r[KMPC_LANE_GAIN] = 0.5; r[KMPC_LANE_HOLD] = 20.0;
-        r[KMPC_LANE_CLEAR_TOL] = 0.5; r[KMPC_LANE_KEEP_RIGHT] = 1.0;
-    }
-    return KMPC_OK;
+    return fill_rows("kmpc_lane_default", rows_host, B, KMPC_LANE_WORDS,
+                     {{KMPC_LANE_N_LANES, 1.0}, {KMPC_LANE_WIDTH, 3.5}, {KMPC_LANE_V_LAT, 1.0}, {KMPC_LANE_GAIN, 0.5}, {KMPC_LANE_HOLD, 20.0},
+                      {KMPC_LANE_CLEAR_TOL, 0.5}, {KMPC_LANE_KEEP_RIGHT, 1.0}});
 }
 
 extern "C" int32_t kmpc_lane_rec_init(double *rec_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !rec_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_rec_init: bad argument (B=%d)", B);
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        double *r = rec_host + KMPC_LANEREC_WORDS * b;
-        for (int i = 0; i < KMPC_LANEREC_WORDS; ++i) r[i] = 0.0;
-        r[KMPC_LANEREC_MIN_GAP] = INFINITY;
-    }
+    return fill_rows("kmpc_lane_rec_init", rec_host, B, KMPC_LANEREC_WORDS, {{KMPC_LANEREC_MIN_GAP, INFINITY}});
+}
+
+// the argument block of both lane entry points, checked in the documented order, in two halves: between them kmpc_order_lane_step_fleet checks
+// its own lanes_max and workspace size.  First B, k, the strides and dt ...
+static int lane_scalars(const char *fn, const LN &w)
+{
+    if (w.B < 0 || w.k < 0 || w.s_stride < 1 || w.e_stride < 1 || w.speed_stride < 1)
+        return fail(nullptr, KMPC_ERR_ARG, "%s: bad B / k / stride (B=%d, k=%d, s_stride=%d, e_stride=%d, speed_stride=%d; strides >= 1)", fn, w.B, w.k,
+                    w.s_stride, w.e_stride, w.speed_stride);
+    if (!pos(w.dt)) return fail(nullptr, KMPC_ERR_ARG, "%s: dt must be finite and > 0", fn);
     return KMPC_OK;
+}
+
+// ... then the buffers: `order` and `workspace` are the ordered entry point's two more required ones (`ordered`); kmpc_lane_step_fleet has
+// neither and does not name them.  1 = nothing to do (B = 0)
+static int lane_buffers(const char *fn, const LN &w, const int32_t *order, const void *workspace, bool ordered)
+{
+    if (w.B > 0 && need_buffers(fn, {{"s_along", w.s_along}, {"e_ct", w.e_ct}, {"speed", w.speed}, {"follow_rows", w.follow_rows},
+                                     {"lane_rows", w.lane_rows}, {"v_cap", w.v_cap}, {"v_cap_out", w.v_cap_out}, {"occ_in", w.occ_in},
+                                     {"occ_out", w.occ_out}, {"rec", w.rec}, {"order", order}, {"workspace", workspace}}, ordered ? 12 : 10) != KMPC_OK)
+        return KMPC_ERR_ARG;
+    if (w.B > 0 && w.occ_in == w.occ_out)
+        return fail(nullptr, KMPC_ERR_ARG, "%s: occ_in == occ_out (the occupancy every vehicle reads is a snapshot nobody writes)", fn);
+    return w.B == 0 ? 1 : KMPC_OK;
 }
 
 extern "C" int32_t kmpc_lane_step_fleet(int32_t device, int32_t B, int32_t k, double dt, const double *s_along, int32_t s_stride, const double *e_ct,
@@ -874,22 +910,11 @@ extern "C" int32_t kmpc_lane_step_fleet(int32_t device, int32_t B, int32_t k, do
                                         double *v_cap_out, const uint32_t *occ_in, uint32_t *occ_out, double *rec, double *gap_out,
                                         int32_t *leader_out, double *nbr_out, void *stream)
 {
-    if (B < 0 || k < 0 || s_stride < 1 || e_stride < 1 || speed_stride < 1)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_step_fleet: bad B / k / stride (B=%d, k=%d, s_stride=%d, e_stride=%d, speed_stride=%d; strides >= 1)",
-                    B, k, s_stride, e_stride, speed_stride);
-    if (!pos(dt)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_step_fleet: dt must be finite and > 0");
-    if (B > 0 && (!s_along || !e_ct || !speed || !follow_rows || !lane_rows || !v_cap || !v_cap_out || !occ_in || !occ_out || !rec))
-        return fail(nullptr, KMPC_ERR_ARG,
-                    "kmpc_lane_step_fleet: null required buffer (s_along %s, e_ct %s, speed %s, follow_rows %s, lane_rows %s, v_cap %s, v_cap_out %s, "
-                    "occ_in %s, occ_out %s, rec %s)",
-                    s_along ? "given" : "NULL", e_ct ? "given" : "NULL", speed ? "given" : "NULL", follow_rows ? "given" : "NULL",
-                    lane_rows ? "given" : "NULL", v_cap ? "given" : "NULL", v_cap_out ? "given" : "NULL", occ_in ? "given" : "NULL",
-                    occ_out ? "given" : "NULL", rec ? "given" : "NULL");
-    if (B > 0 && occ_in == occ_out)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_lane_step_fleet: occ_in == occ_out (the occupancy every vehicle reads is a snapshot nobody writes)");
-    if (B == 0) return KMPC_OK;
     const LN w = {B, k, s_stride, e_stride, speed_stride, dt, s_along, e_ct, speed, path_id, present, follow_rows, lane_rows, v_cap, v_cap_out,
                   occ_in, occ_out, rec, gap_out, leader_out, nbr_out};
+    int rc = lane_scalars("kmpc_lane_step_fleet", w);
+    if (rc == KMPC_OK) rc = lane_buffers("kmpc_lane_step_fleet", w, nullptr, nullptr, false);
+    if (rc != KMPC_OK) return rc < 0 ? rc : KMPC_OK;
     return on_device("kmpc_lane_step_fleet", device, [&] { return kmpc_launch_lane_step(w, (hipStream_t)stream); });
 }
 
@@ -898,9 +923,7 @@ extern "C" int32_t kmpc_ref_offset_batch(int32_t device, int32_t B, int32_t H1, 
     if (B < 0 || H1 < 1 || offset_stride < 1 || (long long)B * H1 > 2147483647LL)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_ref_offset_batch: bad B / H1 / offset_stride (B=%d, H1=%d, >= 1, B * H1 < 2^31; offset_stride=%d, >= 1)",
                     B, H1, offset_stride);
-    if (B > 0 && (!ref || !offset))
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_ref_offset_batch: null required buffer (ref %s, offset %s)", ref ? "given" : "NULL",
-                    offset ? "given" : "NULL");
+    if (B > 0 && need_buffers("kmpc_ref_offset_batch", {{"ref", ref}, {"offset", offset}}) != KMPC_OK) return KMPC_ERR_ARG;
     if (B == 0) return KMPC_OK;
     const RO w = {B, H1, offset_stride, ref, offset};
     return on_device("kmpc_ref_offset_batch", device, [&] { return kmpc_launch_ref_offset(w, (hipStream_t)stream); });
@@ -910,25 +933,14 @@ extern "C" int32_t kmpc_ref_offset_batch(int32_t device, int32_t B, int32_t H1, 
 // this project's own defaults (the reference has no such stage): the one place they exist
 extern "C" int32_t kmpc_range_default(double *rows_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_default: bad argument (B=%d)", B);
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        double *r = rows_host + KMPC_RANGE_WORDS * b;
-        for (int i = 0; i < KMPC_RANGE_WORDS; ++i) r[i] = 0.0;
-        r[KMPC_RANGE_RANGE_MAX] = 120.0; r[KMPC_RANGE_SIGMA_R] = 0.25; r[KMPC_RANGE_SIGMA_V] = 0.12; r[KMPC_RANGE_FILTER] = 1.0;
-        r[KMPC_RANGE_COAST_MAX] = 5.0; r[KMPC_RANGE_Q_GAP] = 0.01; r[KMPC_RANGE_Q_V] = 0.25; r[KMPC_RANGE_R_GAP] = 0.0625; r[KMPC_RANGE_R_V] = 0.0144;
-    }
-    return KMPC_OK;
+    return fill_rows("kmpc_range_default", rows_host, B, KMPC_RANGE_WORDS,
+                     {{KMPC_RANGE_RANGE_MAX, 120.0}, {KMPC_RANGE_SIGMA_R, 0.25}, {KMPC_RANGE_SIGMA_V, 0.12}, {KMPC_RANGE_FILTER, 1.0},
+                      {KMPC_RANGE_COAST_MAX, 5.0}, {KMPC_RANGE_Q_GAP, 0.01}, {KMPC_RANGE_Q_V, 0.25}, {KMPC_RANGE_R_GAP, 0.0625}, {KMPC_RANGE_R_V, 0.0144}});
 }
 
 extern "C" int32_t kmpc_range_rec_init(double *rec_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !rec_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_rec_init: bad argument (B=%d)", B);
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        double *r = rec_host + KMPC_RANGEREC_WORDS * b;
-        for (int i = 0; i < KMPC_RANGEREC_WORDS; ++i) r[i] = 0.0;
-        r[KMPC_RANGEREC_TRACK_ID] = -1.0;
-    }
-    return KMPC_OK;
+    return fill_rows("kmpc_range_rec_init", rec_host, B, KMPC_RANGEREC_WORDS, {{KMPC_RANGEREC_TRACK_ID, -1.0}});
 }
 
 extern "C" int32_t kmpc_range_follow_batch(int32_t device, int32_t B, double dt, const double *truth, const int32_t *leader, const double *speed_true,
@@ -942,13 +954,10 @@ extern "C" int32_t kmpc_range_follow_batch(int32_t device, int32_t B, double dt,
     if (!pos(dt)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_follow_batch: dt must be finite and > 0");
     if (period < 0 || period >= ((int64_t)1 << 61))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_range_follow_batch: bad period (%lld; 0 <= period < 2^61)", (long long)period);
-    if (B > 0 && (!truth || !leader || !speed_true || !speed_known || !follow_rows || !range_rows || !v_cap || !v_cap_out || !rec))
-        return fail(nullptr, KMPC_ERR_ARG,
-                    "kmpc_range_follow_batch: null required buffer (truth %s, leader %s, speed_true %s, speed_known %s, follow_rows %s, range_rows %s, "
-                    "v_cap %s, v_cap_out %s, rec %s)",
-                    truth ? "given" : "NULL", leader ? "given" : "NULL", speed_true ? "given" : "NULL", speed_known ? "given" : "NULL",
-                    follow_rows ? "given" : "NULL", range_rows ? "given" : "NULL", v_cap ? "given" : "NULL", v_cap_out ? "given" : "NULL",
-                    rec ? "given" : "NULL");
+    if (B > 0 && need_buffers("kmpc_range_follow_batch", {{"truth", truth}, {"leader", leader}, {"speed_true", speed_true}, {"speed_known", speed_known},
+                                                          {"follow_rows", follow_rows}, {"range_rows", range_rows}, {"v_cap", v_cap},
+                                                          {"v_cap_out", v_cap_out}, {"rec", rec}}) != KMPC_OK)
+        return KMPC_ERR_ARG;
     if (B == 0) return KMPC_OK;
     const RG w = {B, speed_true_stride, speed_known_stride, dt, seed, (uint64_t)period, (uint64_t)id_base, truth, leader, speed_true, speed_known,
                   follow_rows, range_rows, v_cap, v_cap_out, rec, meas_out};
@@ -960,7 +969,7 @@ extern "C" int32_t kmpc_order_bytes(int32_t B, int32_t lanes_max, int64_t *bytes
 {
     if (B < 0 || lanes_max < 0 || lanes_max > 32 || !bytes_out)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_bytes: bad argument (B=%d, lanes_max=%d (0 ... 32), bytes_out %s)", B, lanes_max,
-                    bytes_out ? "given" : "NULL");
+                    given(bytes_out));
     *bytes_out = (int64_t)kmpc_order_layout(B, lanes_max).bytes;
     return KMPC_OK;
 }
@@ -976,9 +985,8 @@ extern "C" int32_t kmpc_order_fleet(int32_t device, int32_t B, const double *s_a
     if (workspace_bytes < (int64_t)o.bytes)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_fleet: workspace_bytes %lld < kmpc_order_bytes(%d, 0) = %lld", (long long)workspace_bytes, B,
                     (long long)o.bytes);
-    if (B > 0 && (!s_along || !speed || !order_out || !workspace))
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_fleet: null required buffer (s_along %s, speed %s, order_out %s, workspace %s)",
-                    s_along ? "given" : "NULL", speed ? "given" : "NULL", order_out ? "given" : "NULL", workspace ? "given" : "NULL");
+    if (B > 0 && need_buffers("kmpc_order_fleet", {{"s_along", s_along}, {"speed", speed}, {"order_out", order_out}, {"workspace", workspace}}) != KMPC_OK)
+        return KMPC_ERR_ARG;
     if (B == 0) return KMPC_OK;
     char *ws = (char *)workspace;
     const OS w = {B, s_stride, speed_stride, s_along, speed, path_id, present, order_out, count_out, (uint64_t *)(ws + o.key_lo),
@@ -992,15 +1000,9 @@ extern "C" int32_t kmpc_order_follow_fleet(int32_t device, int32_t B, const doub
                                            const double *v_cap, double *v_cap_out, double *gap_out, int32_t *leader_out, double *stat,
                                            const int32_t *order, void *stream)
 {
-    if (B < 0 || s_stride < 1 || speed_stride < 1)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_follow_fleet: bad B / s_stride / speed_stride (B=%d, s_stride=%d, speed_stride=%d; strides >= 1)",
-                    B, s_stride, speed_stride);
-    if (B > 0 && (!s_along || !speed || !rows || !v_cap || !v_cap_out || !order))
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_follow_fleet: null required buffer (s_along %s, speed %s, rows %s, v_cap %s, v_cap_out %s, order %s)",
-                    s_along ? "given" : "NULL", speed ? "given" : "NULL", rows ? "given" : "NULL", v_cap ? "given" : "NULL",
-                    v_cap_out ? "given" : "NULL", order ? "given" : "NULL");
-    if (B == 0) return KMPC_OK;
     const OF w = {{B, s_stride, speed_stride, s_along, speed, path_id, present, rows, v_cap, v_cap_out, gap_out, leader_out, stat}, order};
+    const int rc = follow_args("kmpc_order_follow_fleet", w.f, order, true);
+    if (rc != KMPC_OK) return rc < 0 ? rc : KMPC_OK;
     return on_device("kmpc_order_follow_fleet", device, [&] { return kmpc_launch_order_follow(w, (hipStream_t)stream); });
 }
 
@@ -1011,30 +1013,19 @@ extern "C" int32_t kmpc_order_lane_step_fleet(int32_t device, int32_t B, int32_t
                                               double *gap_out, int32_t *leader_out, double *nbr_out, const int32_t *order, int32_t lanes_max,
                                               void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (B < 0 || k < 0 || s_stride < 1 || e_stride < 1 || speed_stride < 1)
-        return fail(nullptr, KMPC_ERR_ARG,
-                    "kmpc_order_lane_step_fleet: bad B / k / stride (B=%d, k=%d, s_stride=%d, e_stride=%d, speed_stride=%d; strides >= 1)", B, k,
-                    s_stride, e_stride, speed_stride);
-    if (!pos(dt)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_lane_step_fleet: dt must be finite and > 0");
+    const LN l = {B, k, s_stride, e_stride, speed_stride, dt, s_along, e_ct, speed, path_id, present, follow_rows, lane_rows, v_cap, v_cap_out,
+                  occ_in, occ_out, rec, gap_out, leader_out, nbr_out};
+    int rc = lane_scalars("kmpc_order_lane_step_fleet", l);
+    if (rc != KMPC_OK) return rc;
     if (lanes_max < 0 || lanes_max > 32) return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_lane_step_fleet: lanes_max %d outside 0 ... 32", lanes_max);
     const OrderLayout o = kmpc_order_layout(B, lanes_max);
     if (workspace_bytes < (int64_t)o.bytes)
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_lane_step_fleet: workspace_bytes %lld < kmpc_order_bytes(%d, %d) = %lld",
                     (long long)workspace_bytes, B, lanes_max, (long long)o.bytes);
-    if (B > 0 && (!s_along || !e_ct || !speed || !follow_rows || !lane_rows || !v_cap || !v_cap_out || !occ_in || !occ_out || !rec || !order || !workspace))
-        return fail(nullptr, KMPC_ERR_ARG,
-                    "kmpc_order_lane_step_fleet: null required buffer (s_along %s, e_ct %s, speed %s, follow_rows %s, lane_rows %s, v_cap %s, "
-                    "v_cap_out %s, occ_in %s, occ_out %s, rec %s, order %s, workspace %s)",
-                    s_along ? "given" : "NULL", e_ct ? "given" : "NULL", speed ? "given" : "NULL", follow_rows ? "given" : "NULL",
-                    lane_rows ? "given" : "NULL", v_cap ? "given" : "NULL", v_cap_out ? "given" : "NULL", occ_in ? "given" : "NULL",
-                    occ_out ? "given" : "NULL", rec ? "given" : "NULL", order ? "given" : "NULL", workspace ? "given" : "NULL");
-    if (B > 0 && occ_in == occ_out)
-        return fail(nullptr, KMPC_ERR_ARG, "kmpc_order_lane_step_fleet: occ_in == occ_out (the occupancy every vehicle reads is a snapshot nobody writes)");
-    if (B == 0) return KMPC_OK;
+    rc = lane_buffers("kmpc_order_lane_step_fleet", l, order, workspace, true);
+    if (rc != KMPC_OK) return rc < 0 ? rc : KMPC_OK;
     char *ws = (char *)workspace;
-    const OL w = {{B, k, s_stride, e_stride, speed_stride, dt, s_along, e_ct, speed, path_id, present, follow_rows, lane_rows, v_cap, v_cap_out,
-                   occ_in, occ_out, rec, gap_out, leader_out, nbr_out},
-                  order, lanes_max, o.lane_blocks, (int32_t *)(ws + o.nxt), (int32_t *)(ws + o.prv), (int32_t *)(ws + o.first),
+    const OL w = {l, order, lanes_max, o.lane_blocks, (int32_t *)(ws + o.nxt), (int32_t *)(ws + o.prv), (int32_t *)(ws + o.first),
                   (int32_t *)(ws + o.last), (int32_t *)(ws + o.carry_next), (int32_t *)(ws + o.carry_prev)};
     return on_device("kmpc_order_lane_step_fleet", device, [&] { return kmpc_launch_order_lane_step(w, (hipStream_t)stream); });
 }
@@ -1042,13 +1033,8 @@ extern "C" int32_t kmpc_order_lane_step_fleet(int32_t device, int32_t B, int32_t
 // ---- road profile per path sample (kmpc_road_profile.hip) ----------------------------------------------------------------
 extern "C" int32_t kmpc_road_profile_default(double *rows_host, int32_t n)
 {
-    if (n < 0 || (n > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_road_profile_default: bad argument (n=%d)", n);
-    for (size_t g = 0; g < (size_t)n; ++g) {
-        double *r = rows_host + KMPC_PROFILE_WORDS * g;
-        for (int i = 0; i < KMPC_PROFILE_WORDS; ++i) r[i] = 0.0;
-        r[KMPC_PROFILE_MU_SCALE] = 1.0; r[KMPC_PROFILE_V_LIMIT] = INFINITY;
-    }
-    return KMPC_OK;
+    return fill_rows("kmpc_road_profile_default", rows_host, n, KMPC_PROFILE_WORDS, {{KMPC_PROFILE_MU_SCALE, 1.0}, {KMPC_PROFILE_V_LIMIT, INFINITY}},
+                     "%s: bad argument (n=%d)");
 }
 
 extern "C" int32_t kmpc_road_profile_fleet(kmpc_pathset *ps, int32_t B, const double *profile, const double *state, int32_t state_stride,
@@ -1205,14 +1191,9 @@ extern "C" int32_t kmpc_sense_delayed_batch(int32_t device, int32_t B, const voi
 // the neutral fault row: no source is ever lost, a lost one returns at once, no window, no outlier, never blind
 extern "C" int32_t kmpc_sense_faults_default(double *rows_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_faults_default: bad argument (B=%d, rows %s)", B, rows_host ? "given" : "NULL");
-    for (int32_t b = 0; b < B; ++b) {
-        double *r = rows_host + KMPC_FAULT_WORDS * (size_t)b;
-        for (int w = 0; w < KMPC_FAULT_WORDS; ++w) r[w] = 0.0;
-        r[KMPC_FAULT_P_REGAIN_GPS] = 1.0; r[KMPC_FAULT_P_REGAIN_IMU] = 1.0; r[KMPC_FAULT_P_REGAIN_SPD] = 1.0;
-        r[KMPC_FAULT_MAX_AGE] = INFINITY;
-    }
-    return KMPC_OK;
+    return fill_rows("kmpc_sense_faults_default", rows_host, B, KMPC_FAULT_WORDS,
+                     {{KMPC_FAULT_P_REGAIN_GPS, 1.0}, {KMPC_FAULT_P_REGAIN_IMU, 1.0}, {KMPC_FAULT_P_REGAIN_SPD, 1.0}, {KMPC_FAULT_MAX_AGE, INFINITY}},
+                     "%s: bad argument (B=%d, rows %s)");
 }
 
 extern "C" int32_t kmpc_sense_faults_batch(int32_t device, int32_t B, const void *state, const void *sensor, const void *faults, uint64_t seed,
@@ -1224,7 +1205,7 @@ extern "C" int32_t kmpc_sense_faults_batch(int32_t device, int32_t B, const void
                     "z_out and held_out are required)", B, (long long)period, (long long)id_base);
     if ((meas_delay != nullptr) != (truth_ring != nullptr))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_faults_batch: meas_delay and truth_ring go together (meas_delay %s, truth_ring %s)",
-                    meas_delay ? "given" : "NULL", truth_ring ? "given" : "NULL");
+                    given(meas_delay), given(truth_ring));
     if (meas_delay && depth < 1) return fail(nullptr, KMPC_ERR_ARG, "kmpc_sense_faults_batch: bad ring (depth=%d, at least 1)", depth);
     if (B == 0) return KMPC_OK;
     return on_device("kmpc_sense_faults_batch", device, [&] {
@@ -1238,9 +1219,7 @@ extern "C" int32_t kmpc_sense_faults_batch(int32_t device, int32_t B, const void
 // the neutral row: 24 zeros, every channel off
 extern "C" int32_t kmpc_wander_default(double *rows_host, int32_t B)
 {
-    if (B < 0 || (B > 0 && !rows_host)) return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_default: bad argument (B=%d, rows %s)", B, rows_host ? "given" : "NULL");
-    for (size_t w = 0; w < KMPC_WANDER_WORDS * (size_t)B; ++w) rows_host[w] = 0.0;
-    return KMPC_OK;
+    return fill_rows("kmpc_wander_default", rows_host, B, KMPC_WANDER_WORDS, {}, "%s: bad argument (B=%d, rows %s)");
 }
 
 extern "C" int32_t kmpc_wander_batch(int32_t device, int32_t B, const void *wander, void *wander_rec, uint64_t seed, int64_t period, int64_t id_base,
@@ -1248,10 +1227,10 @@ extern "C" int32_t kmpc_wander_batch(int32_t device, int32_t B, const void *wand
 {
     if (B < 0 || period < 0 || id_base < 0 || period >= ((int64_t)1 << 62) || (B > 0 && (!wander || !wander_rec)))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_batch: bad argument (B=%d, period=%lld, below 2^62; id_base=%lld; wander %s, wander_rec %s)", B,
-                    (long long)period, (long long)id_base, wander ? "given" : "NULL", wander_rec ? "given" : "NULL");
+                    (long long)period, (long long)id_base, given(wander), given(wander_rec));
     if ((sensor_base != nullptr) != (sensor_out != nullptr) || (road_base != nullptr) != (road_out != nullptr))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_batch: a base and its out go together (sensor_base %s, sensor_out %s, road_base %s, road_out %s)",
-                    sensor_base ? "given" : "NULL", sensor_out ? "given" : "NULL", road_base ? "given" : "NULL", road_out ? "given" : "NULL");
+                    given(sensor_base), given(sensor_out), given(road_base), given(road_out));
     if ((sensor_out && sensor_out == sensor_base) || (road_out && road_out == road_base))
         return fail(nullptr, KMPC_ERR_ARG, "kmpc_wander_batch: an out must not be its base (the sum would compound call after call)");
     if (B == 0) return KMPC_OK;

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._stage import default_row, device_of, host_rows, is_buffer, ptr, rows_of, stream, table_rows
+from ._stage import (cap_in, cap_out, check_present, default_row, device_of, fresh_record, host_rows, is_buffer, own_path_id, ptr, record_fields,
+                     rows_of, state_view, stream, table_rows)
 
 LAT0, LON0, YAW0 = 37.917929, -122.331798, 0.0  # launch/path_follow.launch:19-21
 
@@ -50,19 +51,12 @@ SCORE_FIELDS = ("n", "sum_ect2", "max_ect", "sum_epsi2", "max_epsi", "max_enear"
 
 def fresh_score(B, device):
     """[B,16] float64 on `device`: B fresh score records (kmpc_track_score_init: zeros, latch index -1)"""
-    rec = np.empty((int(B), SCORE_WORDS))
-    _lib.check(_lib.load().kmpc_track_score_init(rec.ctypes.data_as(C.POINTER(C.c_double)), int(B)))
-    return torch.from_numpy(rec).to(device)
+    return fresh_record("kmpc_track_score_init", B, SCORE_WORDS, device)
 
 
 def _track_score(lib, entry, handle, device, B_fixed, path_id, state, score, status, iters, cmd, stop_latch, settle_tol, out):
     """argument marshalling shared by GPSRefTrajectory.track_score_batch and FleetRefTrajectory.track_score_batch"""
-    st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=device)
-    if not (st.dtype == torch.float64 and st.device == device and st.dim() == 2 and st.shape[1] >= 3 and (st.shape[0] == 0 or st.stride(1) == 1)
-            and st.stride(0) >= 3):
-        st = torch.as_tensor(st, dtype=torch.float64, device=device).contiguous()
-        if st.dim() != 2 or st.shape[1] < 3:
-            raise ValueError("state: expected [B,W] with X, Y, psi in the first three columns, got %s" % (tuple(st.shape),))
+    st = state_view(state, 3, device, None, "state: expected [B,W] with X, Y, psi in the first three columns, got %s")
     B = st.shape[0]
     if B_fixed is not None and B != B_fixed:
         raise ValueError("state: expected %d rows, got %d" % (B_fixed, B))
@@ -227,6 +221,8 @@ class FleetRefTrajectory:
                 raise ValueError("a fleet with per-vehicle modes needs v_target (it is not read for the vehicles in time mode)")
             if not is_buffer(tm, torch.uint8, (B,), self.device):
                 raise ValueError("time_mode must stay a contiguous uint8 tensor [%d] on %s (write into it in place)" % (B, self.device))
+        # own_path_id's check, written out: every loop makes this call every period, and through the helper it measured 19.5 us against the
+        # parent's 19.4 us per call at B = 4096 in both of two alternating runs (profiles/fleet_front_ab.txt)
         pid = self.path_id   # a plain attribute: what reaches the kernel is a raw pointer
         if not is_buffer(pid, torch.int32, (B,), self.device):
             raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, self.device))
@@ -242,10 +238,8 @@ class FleetRefTrajectory:
     def track_score_batch(self, state, score=None, status=None, iters=None, cmd=None, stop_latch=None, settle_tol=0.5, out=None):
         """GPSRefTrajectory.track_score_batch for the fleet: vehicle b against paths[path_id[b]] (kmpc_track_score_fleet).  A vehicle whose
         path_id is outside the set, or whose X, Y or psi is not finite, is refused: err row 0, seg = closest = -1, only its refused count moves."""
-        pid = self.path_id
-        B = pid.shape[0]
-        if not is_buffer(pid, torch.int32, (B,), self.device):
-            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, self.device))
+        B = self.path_id.shape[0]
+        pid = own_path_id(self.path_id, B, self.device)
         return _track_score(self._lib, self._lib.kmpc_track_score_fleet, self._h, self.device, B, pid, state, score, status, iters, cmd,
                             stop_latch, settle_tol, out)
 
@@ -318,23 +312,11 @@ class SpeedPlanner:
         """state: device tensor [B,W], X and Y first (the plant's [B,8], an estimate [B,4], a pose [B,3]: no copy); v_cap [B] -> v_plan [B] (`out`
         or a new tensor).  want_info=True also fills self.info [B,4] and self.closest [B].  Asynchronous on torch's current stream."""
         dev, B = self.device, self.B
-        st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=dev)
-        if not (st.dtype == torch.float64 and st.device == dev and st.dim() == 2 and st.shape[1] >= 2 and (B == 0 or st.stride(1) == 1)
-                and st.stride(0) >= 2):
-            st = torch.as_tensor(st, dtype=torch.float64, device=dev).contiguous()
-        if st.dim() != 2 or st.shape[0] != B or st.shape[1] < 2:
-            raise ValueError("state: expected [%d,W] with X, Y in the first two columns, got %s" % (B, tuple(st.shape)))
-        vc = torch.as_tensor(v_cap, dtype=torch.float64, device=dev).contiguous()
-        if tuple(vc.shape) != (B,):
-            raise ValueError("v_cap: expected [%d], got %s" % (B, tuple(vc.shape)))
+        st = state_view(state, 2, dev, B, "state: expected [%d,W] with X, Y in the first two columns, got %s")
+        vc = cap_in(v_cap, B, dev)
         self._check_rows()
-        pid = self.fleet.path_id
-        if not is_buffer(pid, torch.int32, (B,), dev):
-            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
-        if out is None:
-            out = torch.empty((B,), dtype=torch.float64, device=dev)
-        elif not is_buffer(out, torch.float64, (B,), dev):
-            raise ValueError("out: expected a contiguous float64 tensor [%d] on %s" % (B, dev))
+        pid = own_path_id(self.fleet.path_id, B, dev)
+        out = cap_out(out, B, dev)
         if want_info and self.info is None:
             self.info = torch.empty((B, 4), dtype=torch.float64, device=dev)
             self.closest = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -348,7 +330,7 @@ class SpeedPlanner:
         return out
 
 
-FOLLOW_WORDS = 8
+FOLLOW_WORDS, FOLLOW_STAT_WORDS = 8, 8
 FOLLOW_FIELDS = ("d_min", "t_headway", "a_brake", "k_gap", "length")   # KMPC_FOLLOW_* words 0 ... 4 of include/kmpc_follow.h, in row order (5 ... 7 are read by nobody)
 FOLLOW_STAT_FIELDS = ("n", "n_leader", "n_bound", "n_contact", "min_gap", "max_closing")   # KMPC_FOLLOWSTAT_* words 0 ... 5, in order
 
@@ -379,12 +361,10 @@ def follow_params(B, device=0, **overrides):
 
 def fresh_follow_stat(B, device):
     """[B,8] float64 on `device`: B fresh following records (kmpc_follow_stat_init: zeros, smallest gap +inf)"""
-    rec = np.empty((int(B), FOLLOW_WORDS))
-    _lib.check(_lib.load().kmpc_follow_stat_init(rec.ctypes.data_as(C.POINTER(C.c_double)), int(B)))
-    return torch.from_numpy(rec).to(device)
+    return fresh_record("kmpc_follow_stat_init", B, FOLLOW_STAT_WORDS, device)
 
 
-RANGE_WORDS = 16
+RANGE_WORDS, RANGE_REC_WORDS = 16, 16
 RANGE_FIELDS = ("range_max", "sigma_r", "sigma_v", "bias_r", "p_drop", "filter", "coast_max", "q_gap", "q_v", "r_gap", "r_v")   # KMPC_RANGE_* words 0 ... 10 of include/kmpc_range.h, in row order (11 ... 15 are read by nobody)
 RANGE_REC_FIELDS = ("gap_hat", "v_hat", "p00", "p01", "p11", "track_id", "coast", "n", "n_detect", "n_drop", "n_out", "n_new", "n_lost", "n_bound",
                     "sum_egap2", "max_egap")   # KMPC_RANGEREC_* words 0 ... 15, in order
@@ -429,9 +409,7 @@ def range_params(B, device=0, **overrides):
 
 def fresh_range_rec(B, device):
     """[B,16] float64 on `device`: B fresh track records (kmpc_range_rec_init: no track, zeros)"""
-    rec = np.empty((int(B), RANGE_WORDS))
-    _lib.check(_lib.load().kmpc_range_rec_init(rec.ctypes.data_as(C.POINTER(C.c_double)), int(B)))
-    return torch.from_numpy(rec).to(device_of(device))
+    return fresh_record("kmpc_range_rec_init", B, RANGE_REC_WORDS, device)
 
 
 class RangeSensor:
@@ -463,11 +441,7 @@ class RangeSensor:
 
     def summary(self):
         """the record as named numpy fields [B] (one synchronising download): RANGE_REC_FIELDS, the track id, coast and the counts as integers"""
-        a = self.rec.cpu().numpy()
-        out = {k: a[:, i].copy() for i, k in enumerate(RANGE_REC_FIELDS)}
-        for k in ("track_id", "coast", "n", "n_detect", "n_drop", "n_out", "n_new", "n_lost", "n_bound"):
-            out[k] = out[k].astype(np.int64)
-        return out
+        return record_fields(self.rec, RANGE_REC_FIELDS, ("track_id", "coast", "n", "n_detect", "n_drop", "n_out", "n_new", "n_lost", "n_bound"))
 
 
 SEARCHES = ("pairs", "sorted")
@@ -488,7 +462,58 @@ def order_buffers(lib, B, lanes_max, device):
             torch.empty((max(int(n.value), 1),), dtype=torch.uint8, device=device))
 
 
-class Follower:
+class _FleetSearch:
+    """What Follower and Lanes share: the waypoint helper they stand on and the fleet's size, search= with the buffers of the sorted one, the
+    geometry-only score call that places the vehicles, the kmpc_order_fleet call, and the `gap` / `leader_speed` views.  The two stages differ in
+    the words of their refusals, which they pass in, and in their kernels: cap() and step() stay their own."""
+
+    gap = property(lambda self: self.gap_leader[:, 0])
+    leader_speed = property(lambda self: self.gap_leader[:, 1])
+
+    def _init_helper(self, grt, name, verb, rows, makers):
+        """grt: the helper; `name` and `verb`: "Follower", "follows" / "Lanes", "run", for the refusals.  On a GPSRefTrajectory (one path, no
+        path_id) the first of `rows` that is a [B,W] tensor gives the fleet's size; `makers` names what builds such rows."""
+        if not isinstance(grt, (FleetRefTrajectory, GPSRefTrajectory)):
+            raise ValueError("%s %s on a GPSRefTrajectory or a FleetRefTrajectory; a %s is neither" % (name, verb, type(grt).__name__))
+        self.fleet, self.device, self._lib = grt, grt.device, grt._lib
+        self._one_path = isinstance(grt, GPSRefTrajectory)
+        if self._one_path:
+            given = [r for r in rows if isinstance(r, torch.Tensor) and r.dim() == 2]
+            if not given:
+                raise ValueError("%s on a GPSRefTrajectory: rows [B,8] (%s) are required, their length is the fleet's size" % (name, makers))
+            self.B = int(given[0].shape[0])
+        else:
+            self.B = int(grt.path_id.shape[0])
+        self._track = None                                                                  # the geometry-only score call's err, seg, closest
+        self._on_path = torch.empty((self.B,), dtype=torch.bool, device=self.device)        # placed by the score call (and `present`, where given)
+
+    def _init_search(self, search, lanes_max=0):
+        """search=; `order` [B] int32, the count word and the workspace of the sorted one are allocated once, here"""
+        self.search = check_search(search)
+        if search == "sorted":
+            self.order, self._count, self._ws = order_buffers(self._lib, self.B, lanes_max, self.device)
+
+    def _path_id(self):
+        """the helper's path_id as the kernels read it; None on a one-path helper"""
+        return None if self._one_path else own_path_id(self.fleet.path_id, self.B, self.device)
+
+    def _place(self, st, present):
+        """one geometry-only track_score_batch call -> err [B,4] (e_ct, e_near, e_psi, s_along); a vehicle it refuses, or that `present` marks 0, is
+        not on the road (self._on_path)"""
+        self._track = self.fleet.track_score_batch(st, score=None, out=self._track)
+        torch.ge(self._track["seg"], 0, out=self._on_path)
+        if present is not None:
+            torch.logical_and(self._on_path, present, out=self._on_path)
+        return self._track["err"]
+
+    def _sort(self, err, st, pid):
+        """kmpc_order_fleet: the fleet's order by (path, arclength), into self.order, for the search along it"""
+        dev = self.device
+        _lib.check(self._lib.kmpc_order_fleet(dev.index, self.B, ptr(err[:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid), ptr(self._on_path),
+                                              ptr(self.order), ptr(self._count), ptr(self._ws), self._ws.numel(), stream(dev)))
+
+
+class Follower(_FleetSearch):
     """Car following on a waypoint helper's recorded paths (kmpc_follow_fleet, include/kmpc_follow.h): per vehicle the nearest vehicle ahead on
     its own path by arclength, the gap to it, and a speed cap from the following law.  `grt`: a FleetRefTrajectory (the vehicle's path is
     grt.path_id[b] at the time of the call) or a GPSRefTrajectory (one path; `rows` is then required, its length is the fleet's size).
@@ -509,16 +534,7 @@ class Follower:
     here.  The radar works unchanged behind either: it reads `gap_leader` and `leader`."""
 
     def __init__(self, grt, rows=None, radar=None, search="pairs"):
-        if not isinstance(grt, (FleetRefTrajectory, GPSRefTrajectory)):
-            raise ValueError("Follower follows on a GPSRefTrajectory or a FleetRefTrajectory; a %s is neither" % type(grt).__name__)
-        self.fleet, self.device, self._lib = grt, grt.device, grt._lib
-        self._one_path = isinstance(grt, GPSRefTrajectory)
-        if self._one_path:
-            if not (isinstance(rows, torch.Tensor) and rows.dim() == 2):
-                raise ValueError("Follower on a GPSRefTrajectory: rows [B,8] (follow_params) are required, their length is the fleet's size")
-            self.B = int(rows.shape[0])
-        else:
-            self.B = int(grt.path_id.shape[0])
+        self._init_helper(grt, "Follower", "follows", (rows,), "follow_params")
         self.rows = follow_params(self.B, self.device) if rows is None else rows
         self._check_rows()
         dev, B = self.device, self.B
@@ -526,28 +542,22 @@ class Follower:
         self.gap_leader[:, 0] = float("inf")
         self.gap_leader[:, 1] = 0.0
         self.leader = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        self._track = None                                                       # the geometry-only score call's err, seg, closest
-        self._on_path = torch.empty((B,), dtype=torch.bool, device=dev)          # placed by the score call (and `present`, where given)
         if radar is not None and not (isinstance(radar, RangeSensor) and radar.B == B and radar.device == dev):
             raise ValueError("radar= must be a ref_traj.RangeSensor for %d vehicles on %s" % (B, dev))
         self.radar = radar
         self.v_ideal = torch.empty((B,), dtype=torch.float64, device=dev) if radar is not None else None
-        self.search = check_search(search)
-        if search == "sorted":
-            self.order, self._count, self._ws = order_buffers(self._lib, B, 0, dev)
+        self._init_search(search)
         self.reset()
 
-    gap = property(lambda self: self.gap_leader[:, 0])
-    leader_speed = property(lambda self: self.gap_leader[:, 1])
-
-    def _seen(self, word, none):
+    def _seen(self, field, none):
         if self.radar is None:
             raise ValueError("gap_seen and v_lead_seen are a radar's: this Follower has none (radar=RangeSensor(...))")
         rec = self.radar.rec
-        return torch.where(rec[:, 5] >= 0.0, rec[:, word], torch.full_like(rec[:, word], none))
+        word = rec[:, RANGE_REC_FIELDS.index(field)]
+        return torch.where(rec[:, RANGE_REC_FIELDS.index("track_id")] >= 0.0, word, torch.full_like(word, none))
 
-    gap_seen = property(lambda self: self._seen(0, float("inf")))
-    v_lead_seen = property(lambda self: self._seen(1, 0.0))
+    gap_seen = property(lambda self: self._seen("gap_hat", float("inf")))
+    v_lead_seen = property(lambda self: self._seen("v_hat", 0.0))
 
     def _check_rows(self):
         if not is_buffer(self.rows, torch.float64, (self.B, FOLLOW_WORDS), self.device):
@@ -561,11 +571,7 @@ class Follower:
 
     def summary(self):
         """the record as named numpy fields [B] (one synchronising download): FOLLOW_STAT_FIELDS, the four counts as integers"""
-        a = self.stat.cpu().numpy()
-        out = {k: a[:, i].copy() for i, k in enumerate(FOLLOW_STAT_FIELDS)}
-        for k in ("n", "n_leader", "n_bound", "n_contact"):
-            out[k] = out[k].astype(np.int64)
-        return out
+        return record_fields(self.stat, FOLLOW_STAT_FIELDS, ("n", "n_leader", "n_bound", "n_contact"))
 
     def cap(self, state, v_cap, out=None, present=None, known=None, k=None, dt=None):
         """state: device tensor [B,W], X, Y, psi, v first (the plant's [B,8] as it is: no copy); v_cap [B] -> v [B] (`out`, which may be v_cap
@@ -585,48 +591,27 @@ class Follower:
             k, dt = int(k), float(dt)
             if not (k >= 0 and 0.0 < dt < float("inf")):
                 raise ValueError("k >= 0 and a finite dt > 0, got k=%d, dt=%r" % (k, dt))
-            kn = state if known is None else known
-            if not (type(kn) is torch.Tensor and kn.dtype == torch.float64 and kn.device == dev and kn.dim() == 2 and kn.shape[0] == B
-                    and kn.shape[1] >= 4 and (B == 0 or kn.stride(1) == 1) and kn.stride(0) >= 4):
-                kn = torch.as_tensor(kn, dtype=torch.float64, device=dev).contiguous()
-                if kn.dim() != 2 or kn.shape[0] != B or kn.shape[1] < 4:
-                    raise ValueError("known: expected [%d,W] with v in column 3, got %s" % (B, tuple(kn.shape)))
+            kn = state_view(state if known is None else known, 4, dev, B, "known: expected [%d,W] with v in column 3, got %s")
             radar._check()
-            if not is_buffer(radar.rec, torch.float64, (B, RANGE_WORDS), dev):
+            if not is_buffer(radar.rec, torch.float64, (B, RANGE_REC_WORDS), dev):
                 raise ValueError("radar.rec must stay a contiguous float64 tensor [%d,16] on %s (reset() gives a fresh one)" % (B, dev))
-        st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=dev)
-        if not (st.dtype == torch.float64 and st.device == dev and st.dim() == 2 and st.shape[1] >= 4 and (B == 0 or st.stride(1) == 1)
-                and st.stride(0) >= 4):
-            st = torch.as_tensor(st, dtype=torch.float64, device=dev).contiguous()
-        if st.dim() != 2 or st.shape[0] != B or st.shape[1] < 4:
-            raise ValueError("state: expected [%d,W] with X, Y, psi, v in the first four columns, got %s" % (B, tuple(st.shape)))
-        vc = torch.as_tensor(v_cap, dtype=torch.float64, device=dev).contiguous()
-        if tuple(vc.shape) != (B,):
-            raise ValueError("v_cap: expected [%d], got %s" % (B, tuple(vc.shape)))
+        st = state_view(state, 4, dev, B, "state: expected [%d,W] with X, Y, psi, v in the first four columns, got %s")
+        vc = cap_in(v_cap, B, dev)
         self._check_rows()
-        pid = None if self._one_path else self.fleet.path_id
-        if pid is not None and not is_buffer(pid, torch.int32, (B,), dev):
-            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
-        if present is not None and not is_buffer(present, (torch.uint8, torch.bool), (B,), dev):
-            raise ValueError("present: expected a contiguous uint8 or bool tensor [%d] on %s" % (B, dev))
-        if not is_buffer(self.stat, torch.float64, (B, FOLLOW_WORDS), dev):
+        pid = self._path_id()
+        check_present(present, B, dev)
+        if not is_buffer(self.stat, torch.float64, (B, FOLLOW_STAT_WORDS), dev):
             raise ValueError("stat must stay a contiguous float64 tensor [%d,8] on %s (reset() gives a fresh one)" % (B, dev))
-        if out is None:
-            out = torch.empty((B,), dtype=torch.float64, device=dev)
-        elif not is_buffer(out, torch.float64, (B,), dev):
-            raise ValueError("out: expected a contiguous float64 tensor [%d] on %s" % (B, dev))
+        out = cap_out(out, B, dev)
         if B == 0:
             return out
-        self._track = self.fleet.track_score_batch(st, score=None, out=self._track)
-        torch.ge(self._track["seg"], 0, out=self._on_path)
-        if present is not None:
-            torch.logical_and(self._on_path, present, out=self._on_path)
-        args = (dev.index, B, ptr(self._track["err"][:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid), ptr(self._on_path))
+        err = self._place(st, present)
+        args = (dev.index, B, ptr(err[:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid), ptr(self._on_path))
         outs = (ptr(self.rows), ptr(vc), ptr(out if radar is None else self.v_ideal), ptr(self.gap_leader), ptr(self.leader), ptr(self.stat))
         if self.search == "pairs":
             _lib.check(self._lib.kmpc_follow_fleet(*args, *outs, stream(dev)))
         else:
-            _lib.check(self._lib.kmpc_order_fleet(*args, ptr(self.order), ptr(self._count), ptr(self._ws), self._ws.numel(), stream(dev)))
+            self._sort(err, st, pid)
             _lib.check(self._lib.kmpc_order_follow_fleet(*args, *outs, ptr(self.order), stream(dev)))
         if radar is not None:
             _lib.check(self._lib.kmpc_range_follow_batch(dev.index, B, dt, ptr(self.gap_leader), ptr(self.leader), ptr(st[:, 3]), int(st.stride(0)),
@@ -671,12 +656,10 @@ def lane_params(B, device=0, **overrides):
 
 def fresh_lane_rec(B, device):
     """[B,16] float64 on `device`: B fresh lane records (kmpc_lane_rec_init: lane 0, not changing, offset 0, counters 0, smallest gap +inf)"""
-    rec = np.empty((int(B), LANE_REC_WORDS))
-    _lib.check(_lib.load().kmpc_lane_rec_init(rec.ctypes.data_as(C.POINTER(C.c_double)), int(B)))
-    return torch.from_numpy(rec).to(device)
+    return fresh_record("kmpc_lane_rec_init", B, LANE_REC_WORDS, device)
 
 
-class Lanes:
+class Lanes(_FleetSearch):
     """Lanes on a waypoint helper's recorded paths (kmpc_lane_step_fleet, kmpc_ref_offset_batch; include/kmpc_lanes.h): per vehicle a lane and a
     commanded lateral offset (lane L's centre runs L * width to the LEFT of the recorded line), the leader among the vehicles in its own lane(s)
     with the following law's cap, the neighbours in the adjacent lanes, the lane-change decision and the offset ramp.  `grt`: a FleetRefTrajectory
@@ -696,17 +679,7 @@ class Lanes:
     allocated once, here."""
 
     def __init__(self, grt, follow_rows=None, lane_rows=None, lane0=None, search="pairs", lanes_max=None):
-        if not isinstance(grt, (FleetRefTrajectory, GPSRefTrajectory)):
-            raise ValueError("Lanes run on a GPSRefTrajectory or a FleetRefTrajectory; a %s is neither" % type(grt).__name__)
-        self.fleet, self.device, self._lib = grt, grt.device, grt._lib
-        self._one_path = isinstance(grt, GPSRefTrajectory)
-        if self._one_path:
-            given = [r for r in (follow_rows, lane_rows) if isinstance(r, torch.Tensor) and r.dim() == 2]
-            if not given:
-                raise ValueError("Lanes on a GPSRefTrajectory: rows [B,8] (follow_params or lane_params) are required, their length is the fleet's size")
-            self.B = int(given[0].shape[0])
-        else:
-            self.B = int(grt.path_id.shape[0])
+        self._init_helper(grt, "Lanes", "run", (follow_rows, lane_rows), "follow_params or lane_params")
         dev, B = self.device, self.B
         self.follow_rows = follow_params(B, dev) if follow_rows is None else follow_rows
         self.rows = lane_params(B, dev) if lane_rows is None else lane_rows
@@ -722,25 +695,20 @@ class Lanes:
         self.leader = torch.empty((B,), dtype=torch.int32, device=dev)
         self.neighbours = torch.empty((B, 4, 2), dtype=torch.float64, device=dev)
         self._occ = [torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(2)]   # the occupancy words (uint32 bit patterns), ping-ponged
-        self._track = None                                                       # the geometry-only score call's err, seg, closest
-        self._on_path = torch.empty((B,), dtype=torch.bool, device=dev)
-        self.search = check_search(search)
-        if search == "sorted":
+        if check_search(search) == "sorted":
             if lanes_max is None:
                 n_max = float(self.rows[:, 0].max().item()) if B > 0 else 1.0
                 lanes_max = int(min(max(n_max, 1.0), 32.0)) if n_max == n_max else 32
             if not (isinstance(lanes_max, int) and 0 <= lanes_max <= 32):
                 raise ValueError("lanes_max: an integer in 0 ... 32 or None, got %r" % (lanes_max,))
             self.lanes_max = lanes_max
-            self.order, self._count, self._ws = order_buffers(self._lib, B, lanes_max, dev)
         elif lanes_max is not None:
             raise ValueError("lanes_max= sizes the tables of search=\"sorted\"; the pair search has none")
+        self._init_search(search, lanes_max or 0)
         self.reset()
 
     lane = property(lambda self: self.rec[:, 0])
     offset = property(lambda self: self.rec[:, 2])
-    gap = property(lambda self: self.gap_leader[:, 0])
-    leader_speed = property(lambda self: self.gap_leader[:, 1])
     occupancy = property(lambda self: self._occ[self._cur])
 
     def _check_rows(self):
@@ -767,10 +735,7 @@ class Lanes:
     def summary(self):
         """the record as named numpy fields [B] (one synchronising download): LANE_REC_FIELDS, the lanes and the counts as integers, plus
         rms_elane (already divided by the number of calls; 0 where none was)"""
-        a = self.rec.cpu().numpy()
-        out = {k: a[:, i].copy() for i, k in enumerate(LANE_REC_FIELDS)}
-        for k in ("lane", "lane_from", "hold_left", "n", "n_leader", "n_bound", "n_contact", "n_changes"):
-            out[k] = out[k].astype(np.int64)
+        out = record_fields(self.rec, LANE_REC_FIELDS, ("lane", "lane_from", "hold_left", "n", "n_leader", "n_bound", "n_contact", "n_changes"))
         out["rms_elane"] = np.sqrt(out["sum_elane2"] / np.maximum(out["n"], 1))
         return out
 
@@ -781,34 +746,17 @@ class Lanes:
         One geometry-only track_score_batch call for s_along and e_ct, then kmpc_lane_step_fleet; a vehicle the score call refuses is not on
         the road.  Asynchronous on torch's current stream."""
         dev, B = self.device, self.B
-        st = state if type(state) is torch.Tensor else torch.as_tensor(state, dtype=torch.float64, device=dev)
-        if not (st.dtype == torch.float64 and st.device == dev and st.dim() == 2 and st.shape[1] >= 4 and (B == 0 or st.stride(1) == 1)
-                and st.stride(0) >= 4):
-            st = torch.as_tensor(st, dtype=torch.float64, device=dev).contiguous()
-        if st.dim() != 2 or st.shape[0] != B or st.shape[1] < 4:
-            raise ValueError("state: expected [%d,W] with X, Y, psi, v in the first four columns, got %s" % (B, tuple(st.shape)))
-        vc = torch.as_tensor(v_cap, dtype=torch.float64, device=dev).contiguous()
-        if tuple(vc.shape) != (B,):
-            raise ValueError("v_cap: expected [%d], got %s" % (B, tuple(vc.shape)))
+        st = state_view(state, 4, dev, B, "state: expected [%d,W] with X, Y, psi, v in the first four columns, got %s")
+        vc = cap_in(v_cap, B, dev)
         self._check_rows()
-        pid = None if self._one_path else self.fleet.path_id
-        if pid is not None and not is_buffer(pid, torch.int32, (B,), dev):
-            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
-        if present is not None and not is_buffer(present, (torch.uint8, torch.bool), (B,), dev):
-            raise ValueError("present: expected a contiguous uint8 or bool tensor [%d] on %s" % (B, dev))
+        pid = self._path_id()
+        check_present(present, B, dev)
         if not is_buffer(self.rec, torch.float64, (B, LANE_REC_WORDS), dev):
             raise ValueError("rec must stay a contiguous float64 tensor [%d,16] on %s (reset() gives a fresh one)" % (B, dev))
-        if out is None:
-            out = torch.empty((B,), dtype=torch.float64, device=dev)
-        elif not is_buffer(out, torch.float64, (B,), dev):
-            raise ValueError("out: expected a contiguous float64 tensor [%d] on %s" % (B, dev))
+        out = cap_out(out, B, dev)
         if B == 0:
             return out
-        self._track = self.fleet.track_score_batch(st, score=None, out=self._track)
-        torch.ge(self._track["seg"], 0, out=self._on_path)
-        if present is not None:
-            torch.logical_and(self._on_path, present, out=self._on_path)
-        err = self._track["err"]
+        err = self._place(st, present)
         occ_in, occ_out = self._occ[self._cur], self._occ[1 - self._cur]
         args = (dev.index, B, int(k), float(dt), ptr(err[:, 3]), 4, ptr(err[:, 0]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid),
                 ptr(self._on_path), ptr(self.follow_rows), ptr(self.rows), ptr(vc), ptr(out), ptr(occ_in), ptr(occ_out), ptr(self.rec),
@@ -816,8 +764,7 @@ class Lanes:
         if self.search == "pairs":
             _lib.check(self._lib.kmpc_lane_step_fleet(*args, stream(dev)))
         else:
-            _lib.check(self._lib.kmpc_order_fleet(dev.index, B, ptr(err[:, 3]), 4, ptr(st[:, 3]), int(st.stride(0)), ptr(pid), ptr(self._on_path),
-                                                  ptr(self.order), ptr(self._count), ptr(self._ws), self._ws.numel(), stream(dev)))
+            self._sort(err, st, pid)
             _lib.check(self._lib.kmpc_order_lane_step_fleet(*args, ptr(self.order), self.lanes_max, ptr(self._ws), self._ws.numel(), stream(dev)))
         self._cur = 1 - self._cur
         return out

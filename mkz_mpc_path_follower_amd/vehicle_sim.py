@@ -38,7 +38,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._stage import default_row, device_of, fill_blocks, host_rows, is_buffer, ptr, rows_of, stream, table_rows
+from ._stage import (default_row, device_of, fill_blocks, host_rows, is_buffer, is_state_view, own_path_id, ptr, record_fields, rows_of, stream,
+                     table_rows)
 from .messages import StateEst
 
 X0, Y0, PSI0 = -300.0, -450.0, 1.0  # vehicle_simulator.py:28-30 (rosparam defaults)
@@ -280,10 +281,8 @@ class Wander:
     def summary(self):
         """the records so far, one download -> dict of numpy arrays: x [B,8] (the current values), count [B] int64 and one [B] array per channel
         named by WANDER_RECORD_FIELDS"""
-        rec = self.rec.detach().cpu().numpy()
-        out = {k: rec[:, i].copy() for i, k in enumerate(WANDER_RECORD_FIELDS)}
-        out["count"] = out["count"].astype(np.int64)
-        out["x"] = rec[:, 0:WANDER_CHANNELS].copy()
+        out = record_fields(self.rec, WANDER_RECORD_FIELDS, ("count",))
+        out["x"] = np.column_stack([out[k] for k in WANDER_RECORD_FIELDS[:WANDER_CHANNELS]])
         return out
 
 
@@ -372,15 +371,12 @@ class RoadProfile:
         rows the plant reads this period.  want_closest=True also fills self.closest [B].  Asynchronous on torch's current stream."""
         dev, B = self.device, self.B
         self._own()
-        if not (isinstance(state, torch.Tensor) and state.dtype == torch.float64 and state.device == dev and state.dim() == 2 and state.shape[0] == B
-                and state.shape[1] >= 2 and (B == 0 or state.stride(1) == 1) and state.stride(0) >= 2):
+        if not (isinstance(state, torch.Tensor) and is_state_view(state, 2, dev, B)):   # refused, where the other stages copy
             raise ValueError("state: a float64 tensor [%d,W] on %s with X, Y in the first two columns" % (B, dev))
         for t, name in ((road_base, "road_base"), (out, "out")):
             if not is_buffer(t, torch.float64, (B, 8), dev):
                 raise ValueError("%s: a contiguous float64 tensor [%d,8] on %s" % (name, B, dev))
-        pid = self.fleet.path_id
-        if not is_buffer(pid, torch.int32, (B,), dev):
-            raise ValueError("path_id must stay a contiguous int32 tensor [%d] on %s (write into it in place)" % (B, dev))
+        pid = own_path_id(self.fleet.path_id, B, dev)
         if want_closest and self.closest is None:
             self.closest = torch.empty((B,), dtype=torch.int32, device=dev)
         _lib.check(self._lib.kmpc_road_profile_fleet(self.fleet._h, B, ptr(self.table), ptr(state), int(state.stride(0)) if B else 2, ptr(pid),
@@ -494,10 +490,7 @@ class LowLevelController:
     def summary(self):
         """the record so far, one download -> dict of numpy arrays [B]: every LLC_RECORD_FIELDS word (the counters as int64) and rms_err, the root
         mean square of ac - LPF over the ticks"""
-        r = self.rec.detach().cpu().numpy()
-        out = {k: r[:, i].copy() for i, k in enumerate(LLC_RECORD_FIELDS)}
-        for k in ("ticks", "n_th_sat", "n_deadband", "n_brake"):
-            out[k] = out[k].astype(np.int64)
+        out = record_fields(self.rec, LLC_RECORD_FIELDS, ("ticks", "n_th_sat", "n_deadband", "n_brake"))
         with np.errstate(all="ignore"):
             out["rms_err"] = np.sqrt(out["sum_err2"] / np.maximum(out["ticks"], 1))
         return out
@@ -746,11 +739,7 @@ class SensorModel:
         faults="""
         if self.faults is None:
             return None
-        rec = self.fault_record.detach().cpu().numpy()
-        out = {k: rec[:, i].copy() for i, k in enumerate(FAULT_RECORD_FIELDS)}
-        for k in FAULT_RECORD_FIELDS[4:]:
-            out[k] = out[k].astype(np.int64)
-        return out
+        return record_fields(self.fault_record, FAULT_RECORD_FIELDS, FAULT_RECORD_FIELDS[4:])
 
     def _sense_faults(self, state, period, est):
         own = ((self.faults, (self.B, FAULT_WORDS), torch.float64), (self.fault_record, (self.B, FAULT_WORDS), torch.float64),

@@ -7,6 +7,10 @@ CPU part needs no device and the `gpu` part launches nothing.
 
 The CPU part builds the stages with device="cpu" (as tests/test_predict_dist_ref.py does) for B = 3 vehicles; the `gpu` part covers what needs a
 device to construct, on a two-path fleet of the fixture paths.
+
+The fleet stages (RangeSensor, Follower, Lanes, SpeedPlanner.plan's state and v_cap, check_search, the loops' planner= / follower= / lanes=
+checks) were written down the same way, from the code as it stood before they were given one state-view rule, one v_cap / out pair and one base
+class; where two things are wrong at once the case names the text that must win.
 """
 import types
 
@@ -308,6 +312,102 @@ def test_loop_refusals_of_a_stage_for_another_fleet():
     assert loop.sensor is sensor and loop.estimator.B == B and loop.compensator is None and loop.observer is None
 
 
+def test_range_sensor_and_search_contracts():
+    """RangeSensor.__init__ / _check and check_search: the radar's rows are a public tensor, checked where it is built and again by every cap()"""
+    import torch
+    from mkz_mpc_path_follower_amd.ref_traj import RangeSensor, check_search, range_params
+    rows = "rows must be a contiguous float64 tensor [3,16] on cpu (range_params; write into it in place)"
+    seed = "seed: an integer in 0 ... 2^64 - 1"
+    radar = RangeSensor(B, device="cpu")
+    refused([
+        ("radar seed < 0", lambda: RangeSensor(B, device="cpu", seed=-1), seed),
+        ("radar seed 2^64", lambda: RangeSensor(B, device="cpu", seed=2 ** 64), seed),
+        ("radar seed before rows", lambda: RangeSensor(B, device="cpu", seed=-1, rows=f64(B, 8)), seed),
+        ("radar rows float32", lambda: RangeSensor(B, device="cpu", rows=f64(B, 16).float()), rows),
+        ("radar rows for another fleet", lambda: RangeSensor(B, device="cpu", rows=range_params(4, "cpu")), rows),
+        ("radar rows follow-sized", lambda: RangeSensor(B, device="cpu", rows=f64(B, 8)), rows),
+        ("radar rows strided", lambda: RangeSensor(B, device="cpu", rows=strided(16)), rows),
+        ("radar rows numpy", lambda: RangeSensor(B, device="cpu", rows=np.zeros((B, 16))), rows),
+        ("radar rows replaced float32", swapped(radar, "rows", radar.rows.float(), radar._check), rows),
+        ("radar rows replaced strided", swapped(radar, "rows", strided(16), radar._check), rows),
+        ("radar rows replaced numpy", swapped(radar, "rows", radar.rows.numpy(), radar._check), rows),
+        ("search unknown", lambda: check_search("fast"), "search= must be one of 'pairs' / 'sorted', got 'fast'"),
+        ("search None", lambda: check_search(None), "search= must be one of 'pairs' / 'sorted', got None"),
+    ])
+    radar._check()
+    assert check_search("pairs") == "pairs" and check_search("sorted") == "sorted"
+    assert radar.rows.dtype == torch.float64 and radar.rec.shape == (B, 16) and radar.meas.shape == (B, 4)
+    assert sorted(radar.summary()) == sorted(("gap_hat", "v_hat", "p00", "p01", "p11", "track_id", "coast", "n", "n_detect", "n_drop", "n_out", "n_new",
+                                              "n_lost", "n_bound", "sum_egap2", "max_egap"))
+    assert radar.summary()["track_id"].tolist() == [-1, -1, -1] and radar.summary()["track_id"].dtype == np.int64
+
+
+def test_loop_refusals_of_a_path_stage():
+    """_init_planner, _init_follower and _init_lanes: the grid, the stage's own helper, its fleet, the time mode -- in that order, each stage in
+    its own sentences (lanes= refuses a follower first)"""
+    import torch
+    from mkz_mpc_path_follower_amd.closed_loop import _ScoredLoop
+    cpu = torch.device("cpu")
+    grt = types.SimpleNamespace(time_mode=None)
+    timed = types.SimpleNamespace(time_mode=torch.tensor([0, 1, 0], dtype=torch.uint8))
+    single = types.SimpleNamespace()   # a one-path helper has no time_mode at all
+
+    def loop(helper, follower=None):
+        lp = _ScoredLoop()
+        lp.B, lp.grt, lp.follower = B, helper, follower
+        lp.sim = types.SimpleNamespace(B=B, device=cpu, road=None)
+        return lp
+    stage = lambda helper, n=B, **kw: types.SimpleNamespace(fleet=helper, device=cpu, B=n, **kw)
+    lanes = lambda helper, n=B: stage(helper, n, shift=None)
+    fleet = "%s for %d vehicles on cpu, plant with 3 on cpu"
+    mode = "%s= needs every vehicle in target-velocity mode: the fleet helper has vehicles in time mode"
+    p_own = "planner= must be a ref_traj.SpeedPlanner built on this loop's own waypoint helper (a FleetRefTrajectory)"
+    f_own = "follower= must be a ref_traj.Follower built on this loop's own waypoint helper"
+    l_own = "lanes= must be a ref_traj.Lanes built on this loop's own waypoint helper"
+    p_grid = "planner= plans a speed along the arclength grid: track_with_time must stay False"
+    f_grid = "follower= caps a speed on the arclength grid: track_with_time must stay False"
+    l_grid = "lanes= caps a speed on the arclength grid: track_with_time must stay False"
+    l_both = "lanes= takes the follower's place (its leaders are found by lane): give no follower="
+    refused([
+        ("planner grid", lambda: loop(grt)._init_planner(stage(grt), True), p_grid),
+        ("planner helper", lambda: loop(grt)._init_planner(stage(timed), False), p_own),
+        ("planner no stage at all", lambda: loop(grt)._init_planner(object(), False), p_own),
+        ("planner fleet", lambda: loop(grt)._init_planner(stage(grt, 4), False), fleet % ("planner", 4)),
+        ("planner mode", lambda: loop(timed)._init_planner(stage(timed), False), mode % "planner"),
+        ("planner: the grid before the helper", lambda: loop(grt)._init_planner(stage(timed, 4), True), p_grid),
+        ("planner: the helper before the fleet", lambda: loop(grt)._init_planner(stage(timed, 4), False), p_own),
+        ("planner: the fleet before the mode", lambda: loop(timed)._init_planner(stage(timed, 4), False), fleet % ("planner", 4)),
+        ("follower grid", lambda: loop(grt)._init_follower(stage(grt), True), f_grid),
+        ("follower helper", lambda: loop(grt)._init_follower(stage(timed), False), f_own),
+        ("follower no stage at all", lambda: loop(grt)._init_follower(object(), False), f_own),
+        ("follower fleet", lambda: loop(grt)._init_follower(stage(grt, 5), False), fleet % ("follower", 5)),
+        ("follower mode", lambda: loop(timed)._init_follower(stage(timed), False), mode % "follower"),
+        ("follower: the grid before the helper", lambda: loop(grt)._init_follower(stage(timed, 4), True), f_grid),
+        ("follower: the helper before the fleet", lambda: loop(grt)._init_follower(stage(timed, 4), False), f_own),
+        ("follower: the fleet before the mode", lambda: loop(timed)._init_follower(stage(timed, 4), False), fleet % ("follower", 4)),
+        ("lanes with a follower", lambda: loop(grt, stage(grt))._init_lanes(lanes(grt), False), l_both),
+        ("lanes grid", lambda: loop(grt)._init_lanes(lanes(grt), True), l_grid),
+        ("lanes helper", lambda: loop(grt)._init_lanes(lanes(timed), False), l_own),
+        ("lanes a follower in their place", lambda: loop(grt)._init_lanes(stage(grt), False), l_own),
+        ("lanes fleet", lambda: loop(grt)._init_lanes(lanes(grt, 2), False), fleet % ("lanes", 2)),
+        ("lanes mode", lambda: loop(timed)._init_lanes(lanes(timed), False), mode % "lanes"),
+        ("lanes: the follower before the grid", lambda: loop(grt, stage(grt))._init_lanes(lanes(timed, 4), True), l_both),
+        ("lanes: the grid before the helper", lambda: loop(grt)._init_lanes(lanes(timed, 4), True), l_grid),
+        ("lanes: the helper before the fleet", lambda: loop(grt)._init_lanes(lanes(timed, 4), False), l_own),
+        ("lanes: the fleet before the mode", lambda: loop(timed)._init_lanes(lanes(timed, 4), False), fleet % ("lanes", 4)),
+    ])
+    lp = loop(single)   # a one-path helper (no time_mode) passes the follower's and the lanes' mode check; nothing given is nothing checked
+    fol, ln = stage(single), lanes(single)
+    lp._init_follower(fol, False)
+    assert lp.follower is fol and lp.v_follow is None
+    lp.follower = None
+    lp._init_lanes(ln, False)
+    assert lp.lanes is ln
+    lp = loop(grt)
+    lp._init_planner(None, True), lp._init_follower(None, True), lp._init_lanes(None, True)
+    assert lp.planner is None and lp.v_plan is None and lp.follower is None and lp.lanes is None
+
+
 # ---- what needs a device to construct -------------------------------------------------------------------------------------
 def _fleet():
     import fleet_scenario as F
@@ -418,3 +518,232 @@ def test_fleet_profile_and_planner_contracts():
         ("score out err strided", lambda: grt.track_score_batch(state, out=dict(err=d64(4, B).t())), buf % ("err", "torch.float64", "(3, 4)")),
     ])
     assert grt.path_id.dtype == torch.int32 and grt.time_mode.dtype == torch.uint8 and pl.rows.dtype == torch.float64
+
+
+def _single():
+    import fleet_scenario as F
+    from mkz_mpc_path_follower_amd.ref_traj import GPSRefTrajectory
+    d = F.path_dict(0)
+    return GPSRefTrajectory(arrays=d, traj_horizon=8, traj_dt=0.2, lat0=d["lat0"], lon0=d["lon0"])
+
+
+@pytest.mark.gpu
+def test_planner_state_contracts():
+    """SpeedPlanner.plan's state: the plant's state or a view of it passes as it is, anything else is copied first and then refused by shape"""
+    import torch
+    from mkz_mpc_path_follower_amd.ref_traj import SpeedPlanner
+    grt = _fleet()
+    dev = grt.device
+    pl = SpeedPlanner(grt)
+    d64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+    st = "state: expected [3,W] with X, Y in the first two columns, got %s"
+    refused([
+        ("plan state one column", lambda: pl.plan(d64(B, 1), d64(B)), st % "(3, 1)"),
+        ("plan state rows", lambda: pl.plan(d64(B + 1, 8), d64(B)), st % "(4, 8)"),
+        ("plan state 1-D", lambda: pl.plan(d64(B), d64(B)), st % "(3,)"),
+        ("plan state numpy rows", lambda: pl.plan(np.zeros((2, 8)), d64(B)), st % "(2, 8)"),
+        ("plan state float32 one column", lambda: pl.plan(d64(B, 1).float(), d64(B)), st % "(3, 1)"),
+        ("plan v_cap shape", lambda: pl.plan(d64(B, 8), d64(B, 1)), "v_cap: expected [3], got (3, 1)"),
+        ("plan v_cap numpy length", lambda: pl.plan(d64(B, 8), np.zeros(2)), "v_cap: expected [3], got (2,)"),
+        ("plan: the state before v_cap", lambda: pl.plan(d64(B, 1), d64(B + 1)), st % "(3, 1)"),
+        ("plan: v_cap before the rows", swapped(pl, "rows", pl.rows.float(), lambda: pl.plan(d64(B, 8), d64(B + 1))), "v_cap: expected [3], got (4,)"),
+        ("plan: the rows before path_id", swapped(grt, "path_id", grt.path_id.long(), swapped(pl, "rows", pl.rows.float(), lambda: pl.plan(d64(B, 8), d64(B)))),
+         "rows must be a contiguous float64 tensor [3,8] on cuda:0 (speed_plan_params; write into it in place)"),
+        ("plan: path_id before out", swapped(grt, "path_id", grt.path_id.long(), lambda: pl.plan(d64(B, 8), d64(B), out=d64(B + 1))),
+         "path_id must stay a contiguous int32 tensor [3] on cuda:0 (write into it in place)"),
+    ])
+
+
+@pytest.mark.gpu
+def test_follower_contracts():
+    """Follower.__init__ / cap / gap_seen, without and with a radar: every refusal, and the order of cap()'s checks"""
+    import torch
+    from mkz_mpc_path_follower_amd.ref_traj import Follower, RangeSensor, follow_params
+    grt = _fleet()
+    dev = grt.device
+    d64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+    u8 = lambda n: torch.ones(n, dtype=torch.uint8, device=dev)
+    fol = Follower(grt)
+    rad = Follower(grt, radar=RangeSensor(B, dev))
+    state, vcap = d64(B, 8), d64(B)
+    rows = "rows must be a contiguous float64 tensor [3,8] on cuda:0 (follow_params; write into it in place)"
+    radar = "radar= must be a ref_traj.RangeSensor for 3 vehicles on cuda:0"
+    none = "known=, k= and dt= are read by a radar: this Follower has none (radar=RangeSensor(...))"
+    need = "a Follower with a radar needs the period's index k= (the draws' counter) and its length dt= [s] in every cap()"
+    st = "state: expected [3,W] with X, Y, psi, v in the first four columns, got %s"
+    kn = "known: expected [3,W] with v in column 3, got %s"
+    pid = "path_id must stay a contiguous int32 tensor [3] on cuda:0 (write into it in place)"
+    pres = "present: expected a contiguous uint8 or bool tensor [3] on cuda:0"
+    stat = "stat must stay a contiguous float64 tensor [3,8] on cuda:0 (reset() gives a fresh one)"
+    out = "out: expected a contiguous float64 tensor [3] on cuda:0"
+    rrows = "rows must be a contiguous float64 tensor [3,16] on cuda:0 (range_params; write into it in place)"
+    rrec = "radar.rec must stay a contiguous float64 tensor [3,16] on cuda:0 (reset() gives a fresh one)"
+    seen = "gap_seen and v_lead_seen are a radar's: this Follower has none (radar=RangeSensor(...))"
+    cap = lambda **kw: rad.cap(state, vcap, **dict(dict(k=0, dt=0.1), **kw))
+    refused([
+        ("follower helper", lambda: Follower(object()), "Follower follows on a GPSRefTrajectory or a FleetRefTrajectory; a object is neither"),
+        ("follower one path without rows", lambda: Follower(_single()),
+         "Follower on a GPSRefTrajectory: rows [B,8] (follow_params) are required, their length is the fleet's size"),
+        ("follower one path numpy rows", lambda: Follower(_single(), rows=np.zeros((B, 8))),
+         "Follower on a GPSRefTrajectory: rows [B,8] (follow_params) are required, their length is the fleet's size"),
+        ("follower rows float32", lambda: Follower(grt, rows=d64(B, 8).float()), rows),
+        ("follower rows for another fleet", lambda: Follower(grt, rows=follow_params(4, dev)), rows),
+        ("follower rows strided", lambda: Follower(grt, rows=d64(8, B).t()), rows),
+        ("follower rows numpy", lambda: Follower(grt, rows=np.zeros((B, 8))), rows),
+        ("follower rows on the host", lambda: Follower(grt, rows=follow_params(B, "cpu")), rows),
+        ("follower radar for another fleet", lambda: Follower(grt, radar=RangeSensor(4, dev)), radar),
+        ("follower radar on the host", lambda: Follower(grt, radar=RangeSensor(B, "cpu")), radar),
+        ("follower radar no sensor", lambda: Follower(grt, radar=object()), radar),
+        ("follower search", lambda: Follower(grt, search="tree"), "search= must be one of 'pairs' / 'sorted', got 'tree'"),
+        ("follower: the rows before the radar", lambda: Follower(grt, rows=d64(B, 8).float(), radar=object()), rows),
+        ("follower: the radar before the search", lambda: Follower(grt, radar=object(), search="tree"), radar),
+        ("gap_seen without a radar", lambda: fol.gap_seen, seen),
+        ("v_lead_seen without a radar", lambda: fol.v_lead_seen, seen),
+        ("cap known without a radar", lambda: fol.cap(state, vcap, known=state), none),
+        ("cap k without a radar", lambda: fol.cap(state, vcap, k=0), none),
+        ("cap dt without a radar", lambda: fol.cap(state, vcap, dt=0.1), none),
+        ("cap state three columns", lambda: fol.cap(d64(B, 3), vcap), st % "(3, 3)"),
+        ("cap state rows", lambda: fol.cap(d64(B + 1, 8), vcap), st % "(4, 8)"),
+        ("cap state numpy rows", lambda: fol.cap(np.zeros((2, 8)), vcap), st % "(2, 8)"),
+        ("cap state float32 three columns", lambda: fol.cap(d64(B, 3).float(), vcap), st % "(3, 3)"),
+        ("cap state 1-D", lambda: fol.cap(d64(B), vcap), st % "(3,)"),
+        ("cap v_cap shape", lambda: fol.cap(state, d64(B + 1)), "v_cap: expected [3], got (4,)"),
+        ("cap v_cap column", lambda: fol.cap(state, d64(B, 1)), "v_cap: expected [3], got (3, 1)"),
+        ("cap rows float32", swapped(fol, "rows", fol.rows.float(), lambda: fol.cap(state, vcap)), rows),
+        ("cap rows strided", swapped(fol, "rows", d64(8, B).t(), lambda: fol.cap(state, vcap)), rows),
+        ("cap rows numpy", swapped(fol, "rows", np.zeros((B, 8)), lambda: fol.cap(state, vcap)), rows),
+        ("cap path_id int64", swapped(grt, "path_id", grt.path_id.long(), lambda: fol.cap(state, vcap)), pid),
+        ("cap path_id strided", swapped(grt, "path_id", torch.zeros(2 * B, dtype=torch.int32, device=dev)[::2], lambda: fol.cap(state, vcap)), pid),
+        ("cap path_id numpy", swapped(grt, "path_id", np.zeros(B, dtype=np.int32), lambda: fol.cap(state, vcap)), pid),
+        ("cap present int32", lambda: fol.cap(state, vcap, present=torch.ones(B, dtype=torch.int32, device=dev)), pres),
+        ("cap present length", lambda: fol.cap(state, vcap, present=u8(B + 1)), pres),
+        ("cap present strided", lambda: fol.cap(state, vcap, present=u8(2 * B)[::2]), pres),
+        ("cap present numpy", lambda: fol.cap(state, vcap, present=np.ones(B, dtype=np.uint8)), pres),
+        ("cap stat float32", swapped(fol, "stat", fol.stat.float(), lambda: fol.cap(state, vcap)), stat),
+        ("cap stat strided", swapped(fol, "stat", d64(8, B).t(), lambda: fol.cap(state, vcap)), stat),
+        ("cap stat numpy", swapped(fol, "stat", np.zeros((B, 8)), lambda: fol.cap(state, vcap)), stat),
+        ("cap out float32", lambda: fol.cap(state, vcap, out=vcap.float()), out),
+        ("cap out shape", lambda: fol.cap(state, vcap, out=d64(B, 1)), out),
+        ("cap out strided", lambda: fol.cap(state, vcap, out=d64(2 * B)[::2]), out),
+        ("cap out numpy", lambda: fol.cap(state, vcap, out=np.zeros(B)), out),
+        ("cap: the state before v_cap", lambda: fol.cap(d64(B, 3), d64(B + 1)), st % "(3, 3)"),
+        ("cap: v_cap before the rows", swapped(fol, "rows", fol.rows.float(), lambda: fol.cap(state, d64(B + 1))), "v_cap: expected [3], got (4,)"),
+        ("cap: the rows before path_id", swapped(grt, "path_id", grt.path_id.long(), swapped(fol, "rows", fol.rows.float(), lambda: fol.cap(state, vcap))), rows),
+        ("cap: path_id before present", swapped(grt, "path_id", grt.path_id.long(), lambda: fol.cap(state, vcap, present=u8(B + 1))), pid),
+        ("cap: present before stat", swapped(fol, "stat", fol.stat.float(), lambda: fol.cap(state, vcap, present=u8(B + 1))), pres),
+        ("cap: stat before out", swapped(fol, "stat", fol.stat.float(), lambda: fol.cap(state, vcap, out=d64(B + 1))), stat),
+        ("radar cap without k", lambda: rad.cap(state, vcap, dt=0.1), need),
+        ("radar cap without dt", lambda: rad.cap(state, vcap, k=0), need),
+        ("radar cap k < 0", lambda: cap(k=-1), "k >= 0 and a finite dt > 0, got k=-1, dt=0.1"),
+        ("radar cap dt 0", lambda: cap(dt=0), "k >= 0 and a finite dt > 0, got k=0, dt=0.0"),
+        ("radar cap dt inf", lambda: cap(k=2, dt=float("inf")), "k >= 0 and a finite dt > 0, got k=2, dt=inf"),
+        ("radar cap known three columns", lambda: cap(known=d64(B, 3)), kn % "(3, 3)"),
+        ("radar cap known rows", lambda: cap(known=d64(B + 1, 4)), kn % "(4, 4)"),
+        ("radar cap known numpy rows", lambda: cap(known=np.zeros((2, 4))), kn % "(2, 4)"),
+        ("radar cap known float32 three columns", lambda: cap(known=d64(B, 3).float()), kn % "(3, 3)"),
+        ("radar cap state as known", lambda: rad.cap(d64(B, 3), vcap, k=0, dt=0.1), kn % "(3, 3)"),
+        ("radar rows float32", swapped(rad.radar, "rows", rad.radar.rows.float(), cap), rrows),
+        ("radar rows strided", swapped(rad.radar, "rows", d64(16, B).t(), cap), rrows),
+        ("radar rows numpy", swapped(rad.radar, "rows", np.zeros((B, 16)), cap), rrows),
+        ("radar rec float32", swapped(rad.radar, "rec", rad.radar.rec.float(), cap), rrec),
+        ("radar rec strided", swapped(rad.radar, "rec", d64(16, B).t(), cap), rrec),
+        ("radar rec numpy", swapped(rad.radar, "rec", np.zeros((B, 16)), cap), rrec),
+        ("radar: k and dt before known", lambda: cap(k=-1, known=d64(B, 3)), "k >= 0 and a finite dt > 0, got k=-1, dt=0.1"),
+        ("radar: known before the radar's rows", swapped(rad.radar, "rows", rad.radar.rows.float(), lambda: cap(known=d64(B, 3))), kn % "(3, 3)"),
+        ("radar: the radar's rows before its rec", swapped(rad.radar, "rec", rad.radar.rec.float(), swapped(rad.radar, "rows", rad.radar.rows.float(), cap)), rrows),
+        ("radar: the radar's rec before the state", swapped(rad.radar, "rec", rad.radar.rec.float(), lambda: rad.cap(d64(B, 3), vcap, known=state, k=0, dt=0.1)), rrec),
+        ("radar: the state before v_cap", lambda: rad.cap(d64(B, 3), d64(B + 1), known=state, k=0, dt=0.1), st % "(3, 3)"),
+    ])
+    assert grt.path_id.dtype == torch.int32 and fol.rows.dtype == torch.float64 and fol.stat.dtype == torch.float64
+    assert rad.radar.rows.dtype == torch.float64 and rad.radar.rec.dtype == torch.float64
+    assert rad.gap_seen.tolist() == [float("inf")] * B and rad.v_lead_seen.tolist() == [0.0] * B   # no track yet
+    assert fol.gap.tolist() == [float("inf")] * B and fol.leader_speed.tolist() == [0.0] * B and fol.leader.tolist() == [-1] * B
+
+
+@pytest.mark.gpu
+def test_lanes_contracts():
+    """Lanes.__init__ / step / shift: every refusal, and the order of step()'s checks"""
+    import torch
+    from mkz_mpc_path_follower_amd.ref_traj import Lanes, follow_params, lane_params
+    grt = _fleet()
+    dev = grt.device
+    d64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+    u8 = lambda n: torch.ones(n, dtype=torch.uint8, device=dev)
+    ln = Lanes(grt, lane_rows=lane_params(B, dev, n_lanes=2))
+    state, vcap, ref = d64(B, 8), d64(B), d64(B, 9, 3)
+    rows = "rows must be a contiguous float64 tensor [3,8] on cuda:0 (lane_params; write into it in place)"
+    frows = "follow_rows must be a contiguous float64 tensor [3,8] on cuda:0 (follow_params; write into it in place)"
+    one = "Lanes on a GPSRefTrajectory: rows [B,8] (follow_params or lane_params) are required, their length is the fleet's size"
+    lane0 = "lane0: one integer lane per vehicle [3], each inside 0 ... n_lanes - 1 of its lane row"
+    st = "state: expected [3,W] with X, Y, psi, v in the first four columns, got %s"
+    pid = "path_id must stay a contiguous int32 tensor [3] on cuda:0 (write into it in place)"
+    pres = "present: expected a contiguous uint8 or bool tensor [3] on cuda:0"
+    rec = "rec must stay a contiguous float64 tensor [3,16] on cuda:0 (reset() gives a fresh one)"
+    out = "out: expected a contiguous float64 tensor [3] on cuda:0"
+    rtext = "ref: expected a contiguous float64 tensor [3,H+1,3] on cuda:0"
+    step = lambda s=state, v=vcap, **kw: ln.step(s, v, 0, 0.1, **kw)
+    refused([
+        ("lanes helper", lambda: Lanes(object()), "Lanes run on a GPSRefTrajectory or a FleetRefTrajectory; a object is neither"),
+        ("lanes one path without rows", lambda: Lanes(_single()), one),
+        ("lanes one path numpy rows", lambda: Lanes(_single(), follow_rows=np.zeros((B, 8)), lane_rows=np.zeros((B, 8))), one),
+        ("lanes rows float32", lambda: Lanes(grt, lane_rows=d64(B, 8).float()), rows),
+        ("lanes rows for another fleet", lambda: Lanes(grt, lane_rows=lane_params(4, dev)), rows),
+        ("lanes rows strided", lambda: Lanes(grt, lane_rows=d64(8, B).t()), rows),
+        ("lanes rows numpy", lambda: Lanes(grt, lane_rows=np.zeros((B, 8))), rows),
+        ("lanes follow_rows float32", lambda: Lanes(grt, follow_rows=d64(B, 8).float()), frows),
+        ("lanes follow_rows for another fleet", lambda: Lanes(grt, follow_rows=follow_params(4, dev)), frows),
+        ("lanes follow_rows numpy", lambda: Lanes(grt, follow_rows=np.zeros((B, 8))), frows),
+        ("lanes: the lane rows before the follow rows", lambda: Lanes(grt, follow_rows=d64(B, 8).float(), lane_rows=d64(B, 8).float()), rows),
+        ("lanes lane0 length", lambda: Lanes(grt, lane0=[0, 0]), lane0),
+        ("lanes lane0 outside", lambda: Lanes(grt, lane0=[0, 1, 0]), lane0),
+        ("lanes lane0 fraction", lambda: Lanes(grt, lane_rows=lane_params(B, dev, n_lanes=2), lane0=[0, 0.5, 1]), lane0),
+        ("lanes lane0 negative", lambda: Lanes(grt, lane0=torch.tensor([0, -1, 0])), lane0),
+        ("lanes search", lambda: Lanes(grt, search="tree"), "search= must be one of 'pairs' / 'sorted', got 'tree'"),
+        ("lanes lanes_max 33", lambda: Lanes(grt, search="sorted", lanes_max=33), "lanes_max: an integer in 0 ... 32 or None, got 33"),
+        ("lanes lanes_max < 0", lambda: Lanes(grt, search="sorted", lanes_max=-1), "lanes_max: an integer in 0 ... 32 or None, got -1"),
+        ("lanes lanes_max float", lambda: Lanes(grt, search="sorted", lanes_max=2.0), "lanes_max: an integer in 0 ... 32 or None, got 2.0"),
+        ("lanes lanes_max with pairs", lambda: Lanes(grt, lanes_max=2), "lanes_max= sizes the tables of search=\"sorted\"; the pair search has none"),
+        ("lanes: lane0 before the search", lambda: Lanes(grt, lane0=[0, 0], search="tree"), lane0),
+        ("step state three columns", lambda: step(d64(B, 3)), st % "(3, 3)"),
+        ("step state rows", lambda: step(d64(B + 1, 8)), st % "(4, 8)"),
+        ("step state numpy rows", lambda: step(np.zeros((2, 8))), st % "(2, 8)"),
+        ("step state float32 three columns", lambda: step(d64(B, 3).float()), st % "(3, 3)"),
+        ("step v_cap shape", lambda: step(v=d64(B + 1)), "v_cap: expected [3], got (4,)"),
+        ("step rows float32", swapped(ln, "rows", ln.rows.float(), step), rows),
+        ("step rows strided", swapped(ln, "rows", d64(8, B).t(), step), rows),
+        ("step rows numpy", swapped(ln, "rows", np.zeros((B, 8)), step), rows),
+        ("step follow_rows float32", swapped(ln, "follow_rows", ln.follow_rows.float(), step), frows),
+        ("step follow_rows strided", swapped(ln, "follow_rows", d64(8, B).t(), step), frows),
+        ("step follow_rows numpy", swapped(ln, "follow_rows", np.zeros((B, 8)), step), frows),
+        ("step path_id int64", swapped(grt, "path_id", grt.path_id.long(), step), pid),
+        ("step path_id strided", swapped(grt, "path_id", torch.zeros(2 * B, dtype=torch.int32, device=dev)[::2], step), pid),
+        ("step path_id numpy", swapped(grt, "path_id", np.zeros(B, dtype=np.int32), step), pid),
+        ("step present int32", lambda: step(present=torch.ones(B, dtype=torch.int32, device=dev)), pres),
+        ("step present length", lambda: step(present=u8(B + 1)), pres),
+        ("step present numpy", lambda: step(present=np.ones(B, dtype=np.uint8)), pres),
+        ("step rec float32", swapped(ln, "rec", ln.rec.float(), step), rec),
+        ("step rec strided", swapped(ln, "rec", d64(16, B).t(), step), rec),
+        ("step rec numpy", swapped(ln, "rec", np.zeros((B, 16)), step), rec),
+        ("step out float32", lambda: step(out=vcap.float()), out),
+        ("step out shape", lambda: step(out=d64(B, 1)), out),
+        ("step out strided", lambda: step(out=d64(2 * B)[::2]), out),
+        ("step out numpy", lambda: step(out=np.zeros(B)), out),
+        ("step: the state before v_cap", lambda: step(d64(B, 3), d64(B + 1)), st % "(3, 3)"),
+        ("step: v_cap before the rows", swapped(ln, "rows", ln.rows.float(), lambda: step(v=d64(B + 1))), "v_cap: expected [3], got (4,)"),
+        ("step: the rows before path_id", swapped(grt, "path_id", grt.path_id.long(), swapped(ln, "follow_rows", ln.follow_rows.float(), step)), frows),
+        ("step: path_id before present", swapped(grt, "path_id", grt.path_id.long(), lambda: step(present=u8(B + 1))), pid),
+        ("step: present before rec", swapped(ln, "rec", ln.rec.float(), lambda: step(present=u8(B + 1))), pres),
+        ("step: rec before out", swapped(ln, "rec", ln.rec.float(), lambda: step(out=d64(B + 1))), rec),
+        ("shift ref float32", lambda: ln.shift(ref.float()), rtext),
+        ("shift ref rows", lambda: ln.shift(d64(B + 1, 9, 3)), rtext),
+        ("shift ref two words", lambda: ln.shift(d64(B, 9, 2)), rtext),
+        ("shift ref 2-D", lambda: ln.shift(d64(B, 3)), rtext),
+        ("shift ref strided", lambda: ln.shift(d64(9, B, 3).transpose(0, 1)), rtext),
+        ("shift ref numpy", lambda: ln.shift(np.zeros((B, 9, 3))), rtext),
+        ("shift rec float32", swapped(ln, "rec", ln.rec.float(), lambda: ln.shift(ref)), rec),
+        ("shift rec numpy", swapped(ln, "rec", np.zeros((B, 16)), lambda: ln.shift(ref)), rec),
+        ("shift: the ref before rec", swapped(ln, "rec", ln.rec.float(), lambda: ln.shift(ref.float())), rtext),
+    ])
+    assert grt.path_id.dtype == torch.int32 and ln.rows.dtype == torch.float64 and ln.follow_rows.dtype == torch.float64 and ln.rec.dtype == torch.float64
+    assert ln.lane.tolist() == [0.0] * B and ln.offset.tolist() == [0.0] * B and ln.gap.tolist() == [float("inf")] * B
+    assert ln.leader_speed.tolist() == [0.0] * B and ln.leader.tolist() == [-1] * B and ln.shift(d64(B, 0, 3)).shape == (B, 0, 3)
