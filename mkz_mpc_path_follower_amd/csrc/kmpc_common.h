@@ -69,7 +69,8 @@ template <typename T> DEV T scan_suffix(T x, int lane) {  // inclusive, lane 63 
 #elif defined(KMPC_STAMPS)
 #define STAMP_MEMBERS unsigned long long st_t0_, st_acc_[16];
 #define STAMP_DECL_AT(o) do { (o).st_t0_ = __builtin_readcyclecounter(); for (int i_ = 0; i_ < 16; ++i_) (o).st_acc_[i_] = 0; } while (0);
-#define STAMP_AT(o, i) do { unsigned long long t_ = __builtin_readcyclecounter(); (o).st_acc_[i] += t_ - (o).st_t0_; (o).st_t0_ = t_; } while (0)
+// (bits 0 .. 47 of a slot: cycles; bits 48 .. 63: how often the stamp was passed -- stamp 3 once per factorisation attempt; tools/phase_profile.py splits them)
+#define STAMP_AT(o, i) do { unsigned long long t_ = __builtin_readcyclecounter(); (o).st_acc_[i] += (t_ - (o).st_t0_) + (1ull << 48); (o).st_t0_ = t_; } while (0)
 #define STAMP_OUT_AT(o, ptr, b) do { if ((ptr) && threadIdx.x == 0) for (int i_ = 0; i_ < 16; ++i_) (ptr)[(size_t)(b) * 16 + i_] = (o).st_acc_[i_]; } while (0)
 #else
 #define STAMP_MEMBERS

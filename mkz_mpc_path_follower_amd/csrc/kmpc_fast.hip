@@ -52,6 +52,9 @@ template <typename T, int N, int MODEL = 0> struct FastSolver {
     typedef typename Real<T>::acc_t acc_t;
     typedef T real;
     static constexpr int N_ = N, NTH = 64, GS = 64, MODEL_ID = MODEL;   // what kmpc_ipm.h reads: horizon, threads per problem, stride of the G_N table, functor
+    // the constraint forms request their LDS words ahead, behind one wait per exchange (kmpc_ipm.h, forms_apply): fp64, Cartesian model, three tile rows
+    // (N = 16, 20) -- the instantiations whose tile assembly does the same (build_tiles, AHEAD); every other one keeps its code
+    static constexpr bool FORMS_AHEAD = MODEL == 0 && sizeof(T) == 8 && (n + 1 + 15) / 16 == 3;
     // Split adjoint recursion (kmpc_ipm.h, condense_adjoint): lanes n .. n + 2M - 1 run the stages below M for the columns < 2M while lanes
     // 0 .. n - 1 run the stages from M up -- M = N / 2 where 3N lanes exist (N <= 20: both halves N / 2 trips), else what the spare lanes allow
     static constexpr int MSPLIT = MODEL == 1 ? 0 : ((64 - n) / 2 < N / 2 ? (64 - n) / 2 : N / 2), LOW0 = n, GMS = 2 * MSPLIT;

@@ -13,7 +13,8 @@
 // What a back-end SV supplies (all wave-/workgroup-uniform decisions are taken here on values that are identical in every thread):
 //   types / constants  real, N_, n, R, nf, NTH (threads per problem), NF (forms per thread), SROWS, GS (stride of the G_N table), LSTR, MODEL_ID,
 //                      MSPLIT (stage at which the adjoint condensing recursion is split, 0 = not split); with MSPLIT > 0 also LOW0 (first thread of
-//                      the lower half), GMS (stride of the G_M table) and the LDS buffers gmb [3][GMS], pm(c) [2 MSPLIT] (c = 0..3), hm [2 MSPLIT]
+//                      the lower half), GMS (stride of the G_M table) and the LDS buffers gmb [3][GMS], pm(c) [2 MSPLIT] (c = 0..3), hm [2 MSPLIT];
+//                      FORMS_AHEAD (forms_apply / forms_applyT request every LDS word of an exchange behind one wait: one wave per problem only)
 //   ids                lane (stage index), vid (index of the input / form slot this thread holds), refresh_ids()
 //   LDS pointers       xb, wb, cb, lin, gnb, gb, Lc, cs, pt, cwt, kc
 //   problem data       psi0, v0, vt, rx, ry, rp, up(j); x0, y0, kp0..3 for the Frenet functor
@@ -135,6 +136,42 @@ template <class SV> DEV void forms_apply(SV &s, typename SV::real x, typename SV
 {
     typedef typename SV::real T;
     constexpr int N = SV::N_, n = SV::n, R = SV::R, nf = SV::nf;
+    if constexpr (SV::FORMS_AHEAD) {
+        // One wave per problem, fp64, three tile rows (SV::FORMS_AHEAD): a lone wave sits out every LDS wait in full, and the arms below are one wait each.
+        // Here the box forms are the lane's own x (slot 0 of lane j < n is form j), the xb words of the rate forms are requested with the scan's
+        // operand, behind one wait, and the speed forms take a second one behind the scan: clamped addresses and selects, no exec-masked arm.
+        static_assert(SV::NTH == 64 && n <= 64, "slot 0 of lane j < n is form j");
+        __builtin_assume(s.vid >= 0 && s.vid < 64);   // (refresh_ids makes the index opaque: the slot a form can fall into folds at compile time again)
+        if (s.vid < n) s.xb[s.vid] = x;
+        xsync<SV::NTH>();
+        T a = s.xb[s.lane < N ? 2 * s.lane : 0];
+        T xa[SV::NF], xc[SV::NF];
+#pragma unroll
+        for (int i = 0; i < SV::NF; ++i) {
+            const int f = s.vid + 64 * i, r = (f >= n && f < n + R) ? f - n : 0;   // r + 2 <= R + 1 < n
+            xa[i] = s.xb[r]; xc[i] = s.xb[r + 2];
+        }
+        const T dt = s.pt[PT_DT];
+        a = s.lane < N ? a : (T)0;
+        a = dpp_scan_prefix<SV::SROWS>(a);
+        if (s.lane < N) s.cb[s.lane] = a;
+        WFENCE();
+        T ck[SV::NF];
+#pragma unroll
+        for (int i = 0; i < SV::NF; ++i) {
+            const int f = s.vid + 64 * i;
+            ck[i] = s.cb[(64 * (i + 1) > n + R && f >= n + R && f < nf) ? f - n - R : 0];
+        }
+#pragma unroll
+        for (int i = 0; i < SV::NF; ++i) {
+            const int f = s.vid + 64 * i, r = f - n;
+            T v = (64 * (i + 1) > n + R && f >= n + R && f < nf) ? dt * ck[i] : (T)0;
+            v = (f >= n && f < n + R) ? (r < 2 ? xa[i] : xc[i] - xa[i]) : v;
+            y[i] = (64 * i < n && f < n) ? x : v;
+        }
+        xsync<SV::NTH>();
+        return;
+    }
     if (s.vid < n) s.xb[s.vid] = x;
     xsync<SV::NTH>();
     T a = s.lane < N ? s.xb[2 * s.lane] : (T)0;
@@ -168,6 +205,36 @@ template <class SV> DEV typename SV::real forms_applyT(SV &s, const typename SV:
 {
     typedef typename SV::real T;
     constexpr int n = SV::n, R = SV::R;
+    if constexpr (SV::FORMS_AHEAD) {
+        // (see forms_apply) Lane j's box term wb[j] is the w[0] it stores itself; the rate words wb[n + j], wb[n + j - 2] do not depend on the suffix scan and
+        // are requested with its operand, behind one wait, so the only read behind the scan is cb[j >> 1].  Terms a lane does not have are selected to the
+        // neutral element of their operation (x + -0.0 == x and x - +0.0 == x for every x, signed zeros included): value and order of the sum are the arms'.
+        constexpr int N = SV::N_, nf = SV::nf;
+        static_assert(SV::NTH == 64 && n <= 64, "slot 0 of lane j < n is form j");
+        __builtin_assume(s.vid >= 0 && s.vid < 64);   // (refresh_ids makes the index opaque: the slot a form can fall into folds at compile time again)
+        const int j = s.vid;
+#pragma unroll
+        for (int i = 0; i < SV::NF; ++i) { const int f = s.vid + SV::NTH * i; if (f < nf) s.wb[f] = w[i]; }
+        xsync<SV::NTH>();
+        T t = s.wb[n + R + (s.lane < N ? s.lane : 0)];
+        const T w1 = s.wb[n + (j < R ? j : 0)], w2 = s.wb[n + ((j >= 4 && j < n) ? j - 2 : 0)];
+        const T dt = s.pt[PT_DT];
+        t = s.lane < N ? t : (T)0;
+        t = dpp_scan_suffix<SV::SROWS>(t, s.lane);
+        if (s.lane < N) s.cb[s.lane] = t;
+        WFENCE();
+        const T ck = s.cb[j < n ? j >> 1 : 0];
+        T o = w[0];
+        o += j < 2 ? w1 : -(T)0;
+        o += j >= 4 ? w2 : -(T)0;
+        o -= (j >= 2 && j < R) ? w1 : (T)0;
+        T oe = o;
+        oe += dt * ck;
+        o = (j & 1) ? o : oe;
+        o = j < n ? o : (T)0;
+        xsync<SV::NTH>();
+        return o;
+    }
     stage_form_weights(s, w);
     T o = (T)0;
     const int j = s.vid;
@@ -800,6 +867,21 @@ template <class SV> DEV void kkt_diag_staging(SV &s, typename SV::real sc, typen
         // this toolchain's allocator twice put spill code ahead of the mask restore, at the point of highest register pressure
         const int j = s.vid < n ? s.vid : n - 1, jj = j & 1, k = j >> 1;
         const T Cu2 = s.cwt[jj ? 7 : 6], Cdl2 = s.cwt[jj ? 5 : 4];
+        if constexpr (SV::FORMS_AHEAD) {
+            // (see forms_apply) the box, rate and second-order words behind one wait; a term the column does not have is selected out of the sum, not branched around
+            const T wj = s.wb[j], w1 = s.wb[n + (j < R ? j : 0)], w2 = s.wb[n + (j >= 4 ? j - 2 : 0)], mdd = s.lin[SV::LSTR * k + 12];
+            T dg = wj + sc * (Cu2 + Cdl2 * (T)((k > 0) + (k < N - 1))) + reg;
+            T ds = dg;
+            ds += sc * mdd;
+            dg = (second_order && jj) ? ds : dg;
+            dg += j < 2 ? w1 : -(T)0;
+            dg += j >= 4 ? w2 : -(T)0;
+            const T wr = (j >= 2 && j < R) ? w1 : (T)0;
+            dgs[j] = dg + wr;
+            sbs[j] = -wr - sc * Cdl2;
+            xsync<SV::NTH>();
+            return;
+        }
         T dg = s.wb[j] + sc * (Cu2 + Cdl2 * (T)((k > 0) + (k < N - 1))) + reg;
         if (second_order && jj) dg += sc * s.lin[SV::LSTR * k + 12];  // m_dd of stage k: the second-order (d_f, d_f) entry
         if (j < 2) dg += s.wb[n + j];

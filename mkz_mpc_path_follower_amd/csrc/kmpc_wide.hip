@@ -39,6 +39,7 @@ template <typename T, int N, int MODEL = 0> struct WideSolver {
     typedef T real;
     // what kmpc_ipm.h reads: horizon, threads per problem, forms per thread (one), stride of the G_N table, record stride, functor
     static constexpr int N_ = N, NTH = 256, NF = 1, GS = 128, LSTR = MODEL == 1 ? KMPC_STG : WLIN, MODEL_ID = MODEL;
+    static constexpr bool FORMS_AHEAD = false;
     // split adjoint recursion (kmpc_ipm.h, condense_adjoint): threads 128 + j (waves 2 and 3, idle in the unsplit recursion) run the stages below
     // M = N / 2 for the columns j < 2M while threads j < n run the stages from M up: N / 2 trips instead of N
     // (Frenet: no split, no G_N / G_M tables -- their LDS goes to the wider stage records)
