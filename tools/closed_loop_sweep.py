@@ -9,19 +9,13 @@ usage: python tools/closed_loop_sweep.py [--settings 256] [--poses 16] [--steps 
                                          [--settle-tol 0.5] [--seed 0] [--top 10]
 """
 import argparse
-import os
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
+import _timing as T
 from mkz_mpc_path_follower_amd import ClosedLoop  # noqa: E402
-from mkz_mpc_path_follower_amd.ref_traj import GPSRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import VehicleSimulator  # noqa: E402
 import scenario as S  # noqa: E402
 
@@ -41,9 +35,7 @@ def main():
     ap.add_argument("--top", type=int, default=10)
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
-    arr, lat0, lon0 = S.path_arrays(a.path)
-    grt = GPSRefTrajectory(arrays=arr, traj_horizon=N, traj_dt=0.2, lat0=lat0, lon0=lon0)
-    tr = grt.get_global_trajectory_reference()
+    grt, tr = T.single_path(N, a.path)
     nS, nV = a.settings, a.poses
     settings = np.array(S.WEIGHTS)[None, :].repeat(nS, 0)
     settings[1:, [1, 2, 5]] *= np.exp(rng.uniform(-a.spread, a.spread, (nS - 1, 3)))   # setting 0 stays the launch file's

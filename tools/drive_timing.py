@@ -7,50 +7,23 @@ controller rows, with road_stat) of
   - kmpc_sim_advance_road of this build;
   - kmpc_sim_advance_drive;
   - kmpc_llc_step_batch alone, five ticks (what the node costs as a stage of its own)
-at B = 4096 and B = 262 144.  Device events around REPS launches after a warm-up, the kernels in rotation inside one process, five repeats each,
-median and range; every variant restarts from the same states in every repeat.  No target is set: the tick is a few dozen operations per 20
-sub-steps, and the sub-step gains two lags and one multiply-add chain.
+at B = 4096 and B = 262 144; every variant restarts from the same states in every repeat.  Method: tools/_timing.py.
+No target is set: the tick is a few dozen operations per 20 sub-steps, and the sub-step gains two lags and one multiply-add chain.
 
 usage: python tools/drive_timing.py [--parent-lib PATH/libkmpc_hip.so] [out.txt]
 """
 import ctypes as C
-import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
+import _timing as T
+from _timing import med, say
 from mkz_mpc_path_follower_amd import _lib  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import drive_params, llc_params, plant_params, road_params  # noqa: E402
 
-REPEATS, REPS = 5, 100
-LINES = []
-
-
-def say(s):
-    print(s, flush=True)
-    LINES.append(s)
-
-
-def med(xs):
-    xs = sorted(xs)
-    return xs[len(xs) // 2], xs[0], xs[-1]
-
-
-def event_time(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps   # us per call
+REPS = 100
 
 
 def main():
@@ -67,9 +40,9 @@ def main():
         LP.kmpc_sim_advance_road.argtypes = L.kmpc_sim_advance_road.argtypes
         assert not hasattr(LP, "kmpc_sim_advance_drive"), "the parent build has no pedal-driven plant"
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    say("%s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    say(T.header())
     say("us per control period, median [min, max] of %d repeats of %d back-to-back launches; parent build: %s"
-        % (REPEATS, REPS, "a separate library built from the parent commit" if parent else "NOT GIVEN, this build's kmpc_sim_advance_road stands in"))
+        % (T.REPEATS, REPS, "a separate library built from the parent commit" if parent else "NOT GIVEN, this build's kmpc_sim_advance_road stands in"))
     for B in (4096, 262144):
         rng = np.random.default_rng(B)
         s0 = np.zeros((B, 8))
@@ -109,12 +82,10 @@ def main():
         run = {names[0]: road_call(names[0], LP), names[1]: road_call(names[1], L), names[2]: drive_call, names[3]: stage_call}
         for k, fn in run.items():
             assert fn() == 0, k
-        res = {k: [] for k in run}
-        for _ in range(REPEATS):
+        def restart():
             for k in names:
                 st[k].copy_(s0); stat[k].zero_(); rec[k].copy_(rec0)
-            for k, fn in run.items():   # in rotation
-                res[k].append(event_time(fn, REPS))
+        res = T.rotate({k: (fn, REPS) for k, fn in run.items()}, before=restart)
         torch.cuda.synchronize()
         assert all(torch.isfinite(t).all().item() for t in st.values()) and torch.isfinite(rec[names[2]]).all().item()
         assert torch.equal(st[names[0]], st[names[1]])
@@ -122,9 +93,7 @@ def main():
             say("   B = %-7d %-40s %8.1f [%8.1f, %8.1f]" % ((B, k) + med(res[k])))
         say("   B = %-7d this build's road plant = the parent build's states bit for bit after %d periods; drive / parent road = %.3f"
             % (B, REPS + 3, med(res[names[2]])[0] / med(res[names[0]])[0]))
-    if args:
-        with open(args[0], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(sys.argv[:1] + args)
 
 
 if __name__ == "__main__":

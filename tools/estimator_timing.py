@@ -1,60 +1,32 @@
 """Timing of the state estimator and of the closed loop with it on one MI355X (-> profiles/estimator_timing.txt).
 
   1. one call of kmpc_estimate_batch (records in mid-run; with and without innov / flags outputs) next to kmpc_sense_batch on the same states at
-     B = 4096 and B = 262 144: device events around REPS launches after a warm-up, the kernels in rotation inside one process, five repeats each,
-     median and range.
+     B = 4096 and B = 262 144.
   2. ClosedLoop vehicle-steps per second at B = 4096, N = 8 on path1 with a sensor, with and without the estimator stage, from the same run.
+Method: tools/_timing.py.
 
 usage: python tools/estimator_timing.py [out.txt]
 """
 import ctypes as C
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
+import _timing as T
+from _timing import med, say
 from mkz_mpc_path_follower_amd import _lib  # noqa: E402
 from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
-from mkz_mpc_path_follower_amd.ref_traj import GPSRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import Estimator, SensorModel, VehicleSimulator  # noqa: E402
 
-REPEATS, REPS = 5, 100
+REPS = 100
 SIGMA = (0.2, 0.2, 0.01, 0.1)
-LINES = []
-
-
-def say(s):
-    print(s, flush=True)
-    LINES.append(s)
-
-
-def med(xs):
-    xs = sorted(xs)
-    return xs[len(xs) // 2], xs[0], xs[-1]
-
-
-def event_time(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps   # us per call
 
 
 def kernels():
     L = _lib.load()
     p = lambda t: C.c_void_p(t.data_ptr())
-    say("1. us per call, median [min, max] of %d repeats of %d back-to-back launches" % (REPEATS, REPS))
+    say("1. us per call, median [min, max] of %d repeats of %d back-to-back launches" % (T.REPEATS, REPS))
     for B in (4096, 262144):
         rng = np.random.default_rng(B)
         s0 = np.zeros((B, 8))
@@ -72,10 +44,7 @@ def kernels():
         run = {"kmpc_sense_batch": lambda: L.kmpc_sense_batch(0, B, p(s0), p(sensor), 1, 0, 0, p(z), None),
                "kmpc_estimate_batch": lambda: L.kmpc_estimate_batch(*args, None, None, None),
                "kmpc_estimate_batch + innov, flags": lambda: L.kmpc_estimate_batch(*args, p(est.innov), p(est.flags), None)}
-        res = {k: [] for k in run}
-        for _ in range(REPEATS):
-            for k, fn in run.items():   # in rotation
-                res[k].append(event_time(fn, REPS))
+        res = T.rotate({k: (fn, REPS) for k, fn in run.items()})
         assert torch.isfinite(est.record).all().item() and not (est.flags & 32).any().item()
         for k in run:
             say("   B = %-7d %-36s %8.1f [%8.1f, %8.1f]" % ((B, k) + med(res[k])))
@@ -83,41 +52,26 @@ def kernels():
 
 def loops(B=4096, N=8, vt=8.0, steps=100):
     say("2. ClosedLoop, B = %d, N = %d, path1 at %.0f m/s, sensor sigma %s, %d periods per repeat after 20 warm-up periods: M vehicle-steps/s "
-        "(median [min, max] of %d)" % (B, N, vt, SIGMA, steps, REPEATS))
-    d = np.load(os.path.join(ROOT, "tests", "golden", "path1_decimated.npz"))
-    grt = GPSRefTrajectory(arrays=dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"]), traj_horizon=N, traj_dt=0.2)
-    tr = grt.get_global_trajectory_reference()
-    rng = np.random.default_rng(2)
-    idx = rng.integers(0, int(0.5 * len(tr)), B)
-    X0, Y0, P0 = tr[idx, 4] + rng.uniform(-0.5, 0.5, B), tr[idx, 5] + rng.uniform(-0.5, 0.5, B), tr[idx, 3] + rng.uniform(-0.05, 0.05, B)
+        "(median [min, max] of %d)" % (B, N, vt, SIGMA, steps, T.REPEATS))
+    grt, tr = T.single_path(N)
+    start = T.scatter(tr, B, np.random.default_rng(2))
 
     def make(kind):
-        sim = VehicleSimulator(B, X0=X0, Y0=Y0, Psi0=P0)
+        sim = VehicleSimulator(B, X0=start[:, 0], Y0=start[:, 1], Psi0=start[:, 2])
         sim.state[:, 3] = vt
         sensor = SensorModel(B, sigma=SIGMA, seed=1)
         return ClosedLoop(grt, sim, N=N, target_vel=vt, sensor=sensor, estimator=Estimator.from_sensor(sensor) if kind == "sensor + estimator" else None)
     kinds = ("sensor", "sensor + estimator")
-    res = {k: [] for k in kinds}
-    for _ in range(REPEATS):
-        for k in kinds:
-            loop = make(k)
-            loop.run(20, score=False)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            loop.run(steps, score=False)
-            torch.cuda.synchronize()
-            res[k].append(B * steps / (time.perf_counter() - t0) / 1e6)
+    res, _ = T.loop_rates(kinds, make, B, steps)
     for k in kinds:
         say("   %-32s %6.2f [%6.2f, %6.2f]" % ((k,) + med(res[k])))
 
 
 def main():
-    say("%s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    say(T.header())
     kernels()
     loops()
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(sys.argv)
 
 
 if __name__ == "__main__":

@@ -2,60 +2,32 @@
 
   1. kmpc_sim_advance_queue (one control period, depth 4, delays 0 ... 30) next to kmpc_sim_advance_plant with a delay, kmpc_sense_delayed_batch
      (depth 3) next to kmpc_sense_batch, kmpc_cmd_in_force_batch, and kmpc_predict_ahead_batch at 35, 50 and 80 serial Euler steps per vehicle,
-     at B = 4096 and B = 262 144: device events around REPS launches after a warm-up, the kernels in rotation inside one process, five repeats
-     each, median and range.
+     at B = 4096 and B = 262 144; the plant states restart from the same values in every repeat.
   2. ClosedLoop vehicle-steps per second at B = 4096, N = 8 on path1: sensor + estimator, and the same with a command queue (delay 25 updates), a fix
-     one period old and the compensator (35 steps of prediction per vehicle and period), alternating, median of five.
+     one period old and the compensator (35 steps of prediction per vehicle and period).
+Method: tools/_timing.py.
 
 usage: python tools/latency_timing.py [out.txt]
 """
 import ctypes as C
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
+import _timing as T
+from _timing import med, say
 from mkz_mpc_path_follower_amd import _lib  # noqa: E402
 from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
-from mkz_mpc_path_follower_amd.ref_traj import GPSRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import Estimator, LatencyCompensator, SensorModel, VehicleSimulator, plant_params  # noqa: E402
 
-REPEATS, REPS = 5, 100
-LINES = []
-
-
-def say(s):
-    print(s, flush=True)
-    LINES.append(s)
-
-
-def med(xs):
-    xs = sorted(xs)
-    return xs[len(xs) // 2], xs[0], xs[-1]
-
-
-def event_time(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps   # us per call
+REPS = 100
 
 
 def kernels():
     L = _lib.load()
     p = lambda t: C.c_void_p(t.data_ptr())
-    say("1. us per call, median [min, max] of %d repeats of %d back-to-back launches" % (REPEATS, REPS))
+    say("1. us per call, median [min, max] of %d repeats of %d back-to-back launches" % (T.REPEATS, REPS))
     for B in (4096, 262144):
         rng = np.random.default_rng(B)
         s0 = np.zeros((B, 8))
@@ -92,12 +64,7 @@ def kernels():
                "kmpc_predict_ahead_batch, 80 steps": lambda: L.kmpc_predict_ahead_batch(0, B, p(z), p(hist), 9, 100, 10, p(d30), p(l5), 30, 5, 1.108, 1.742, p(zo), None)}
         for k, fn in run.items():
             assert fn() == 0, k
-        res = {k: [] for k in run}
-        for _ in range(REPEATS):
-            for t in st.values():
-                t.copy_(s0)
-            for k, fn in run.items():   # in rotation
-                res[k].append(event_time(fn, REPS))
+        res = T.rotate({k: (fn, REPS) for k, fn in run.items()}, before=lambda: [t.copy_(s0) for t in st.values()])
         assert all(torch.isfinite(t).all().item() for t in (st["plant"], st["queue"], est, zo, uo))
         for k in run:
             say("   B = %-7d %-36s %8.1f [%8.1f, %8.1f]" % ((B, k) + med(res[k])))
@@ -105,47 +72,32 @@ def kernels():
 
 def loops(B=4096, N=8, vt=8.0, steps=100):
     say("2. ClosedLoop, B = %d, N = %d, path1 at %.0f m/s, %d periods per repeat after 20 warm-up periods, alternating: M vehicle-steps/s "
-        "(median [min, max] of %d)" % (B, N, vt, steps, REPEATS))
-    d = np.load(os.path.join(ROOT, "tests", "golden", "path1_decimated.npz"))
-    grt = GPSRefTrajectory(arrays=dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"]), traj_horizon=N, traj_dt=0.2)
-    tr = grt.get_global_trajectory_reference()
-    rng = np.random.default_rng(2)
-    idx = rng.integers(0, int(0.5 * len(tr)), B)
-    X0, Y0, P0 = tr[idx, 4] + rng.uniform(-0.5, 0.5, B), tr[idx, 5] + rng.uniform(-0.5, 0.5, B), tr[idx, 3] + rng.uniform(-0.05, 0.05, B)
+        "(median [min, max] of %d)" % (B, N, vt, steps, T.REPEATS))
+    grt, tr = T.single_path(N)
+    start = T.scatter(tr, B, np.random.default_rng(2))
 
     def make(kind):
         if kind == "sensor + estimator":
-            sim = VehicleSimulator(B, X0=X0, Y0=Y0, Psi0=P0, cmd_delay=0)
+            sim = VehicleSimulator(B, X0=start[:, 0], Y0=start[:, 1], Psi0=start[:, 2], cmd_delay=0)
             sim.state[:, 3] = vt
             sensor = SensorModel(B, sigma=(0.1, 0.1, 0.005, 0.05), seed=1)
             return ClosedLoop(grt, sim, N=N, target_vel=vt, sensor=sensor, estimator=Estimator.from_sensor(sensor))
-        sim = VehicleSimulator(B, X0=X0, Y0=Y0, Psi0=P0, cmd_delay=25, cmd_queue_depth=4)
+        sim = VehicleSimulator(B, X0=start[:, 0], Y0=start[:, 1], Psi0=start[:, 2], cmd_delay=25, cmd_queue_depth=4)
         sim.state[:, 3] = vt
         sensor = SensorModel(B, sigma=(0.1, 0.1, 0.005, 0.05), seed=1, meas_delay=1)
         return ClosedLoop(grt, sim, N=N, target_vel=vt, sensor=sensor, estimator=Estimator.from_sensor(sensor), estimator_input="history",
                           compensator=LatencyCompensator(B, cmd_delay=25, meas_delay=1))
     kinds = ("sensor + estimator", "+ queue, stale fix, compensator")
-    res = {k: [] for k in kinds}
-    for _ in range(REPEATS):
-        for k in kinds:
-            loop = make(k)
-            loop.run(20, score=False)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            loop.run(steps, score=False)
-            torch.cuda.synchronize()
-            res[k].append(B * steps / (time.perf_counter() - t0) / 1e6)
+    res, _ = T.loop_rates(kinds, make, B, steps)
     for k in kinds:
         say("   %-36s %6.2f [%6.2f, %6.2f]" % ((k,) + med(res[k])))
 
 
 def main():
-    say("%s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    say(T.header())
     kernels()
     loops()
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(sys.argv)
 
 
 if __name__ == "__main__":

@@ -1,37 +1,29 @@
 """Timing of the ordered leader search (include/kmpc_order.h) against the pair searches on one MI355X (-> profiles/order_timing.txt).
 
-  1. Per call at B = 4096, 32768 and 262144 on tools/lanes_timing.py's dense fleet (the three fixture paths, ids interleaved, random poses; the
+  1. Per call at B = 4096, 32768 and 262144 on the dense fleet of tools/_timing.py (the three fixture paths, ids interleaved, random poses; the
      arclengths and cross-track errors are the track score's): kmpc_order_fleet alone; the ordered follower (kmpc_order_fleet +
      kmpc_order_follow_fleet) against kmpc_follow_fleet; the ordered lane step (kmpc_order_fleet + kmpc_order_lane_step_fleet: tables and
      searches, lanes_max = 2) against kmpc_lane_step_fleet on two lanes in three populations -- everyone in lane 0, one vehicle in 64 in lane 1,
      half and half.  The records' HOLD_LEFT is set far ahead, so that nobody decides a change and a population stays what it is over the
-     repeats; every search still runs.  Device events around REPS back-to-back calls through the Python host, so launch overhead is in -- the
-     ordered path is a few dozen launches.  Before the timing the two searches' outputs are compared once, word for word.
-  2. Vehicle-steps per second of ONE ClosedLoop of 32768 vehicles (tools/follow_timing.py's platoons of eight) with lanes= on two lanes under
+     repeats; every search still runs.  The calls go through the Python host, so launch overhead is in -- the ordered path is a few dozen
+     launches.  Before the timing the two searches' outputs are compared once, word for word.
+  2. Vehicle-steps per second of ONE ClosedLoop of 32768 vehicles (the platoons of eight of tools/_timing.py) with lanes= on two lanes under
      search="pairs" and search="sorted".
-Method of tools/follow_timing.py: both searches come from the same build and alternate inside one process, five repeats
-each, median and range.  The pair-search kernels are the parent's code.
+Method: tools/_timing.py; both searches come from the same build.  The pair-search kernels are the parent's code.
 
 usage: python tools/order_timing.py [out.txt]
 """
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-
-import follow_timing as FT  # noqa: E402  (puts the tree and tests/ on the path)
-from mkz_mpc_path_follower_amd import ClosedLoop, FleetRefTrajectory  # noqa: E402
+import _timing as T
+from _timing import med, say
 from mkz_mpc_path_follower_amd._stage import ptr, stream  # noqa: E402
 from mkz_mpc_path_follower_amd.ref_traj import Follower, Lanes, lane_params  # noqa: E402
-from mkz_mpc_path_follower_amd.vehicle_sim import VehicleSimulator  # noqa: E402
 
-REPEATS, N = FT.REPEATS, FT.N
-say, med, event_time = FT.say, FT.med, FT.event_time
+N, PLATOON = T.N, T.PLATOON
 WINS = {}      # stage -> the sizes at which the ordered search took less time
 
 
@@ -41,15 +33,7 @@ def bits(t):
 
 def kernels(B, reps):
     rng = np.random.default_rng(1)
-    paths = [FT.path_dict(f) for f in FT.FILES]
-    pid = np.arange(B) % 3
-    fleet = FleetRefTrajectory(paths, pid, traj_horizon=N)
-    state = np.zeros((B, 8))
-    for p, tr in enumerate(fleet.trajectories):
-        sel = np.where(pid == p)[0]
-        idx = rng.integers(0, int(0.6 * len(tr)), len(sel))
-        state[sel, 0], state[sel, 1], state[sel, 2] = tr[idx, 4] + rng.uniform(-1, 1, len(sel)), tr[idx, 5] + rng.uniform(-1, 1, len(sel)), tr[idx, 3]
-    state[:, 3] = rng.uniform(2.0, 8.0, B)
+    fleet, state = T.dense_fleet(B, rng)
     st = torch.as_tensor(state, device="cuda")
     vt = torch.full((B,), 6.0, dtype=torch.float64, device="cuda")
     dev = torch.device("cuda", 0)
@@ -109,29 +93,26 @@ def kernels(B, reps):
         a = snapshot(lane_step(la, False), outs)
         b = snapshot(lane_step(la, True), outs)
         same.append(all(torch.equal(x, y) for x, y in zip(a, b)))
-    t_o, t_fp, t_fo = [], [], []
-    t_lp, t_lo = [[] for _ in stages], [[] for _ in stages]
-    for _ in range(REPEATS):   # alternating
-        t_o.append(event_time(lambda: order_alone(fo), reps))
-        t_fp.append(event_time(follow(False), reps))
-        t_fo.append(event_time(follow(True), reps))
-        for i, (_, la) in enumerate(stages):
-            t_lp[i].append(event_time(lane_step(la, False), reps))
-            t_lo[i].append(event_time(lane_step(la, True), reps))
+    cases = {"order": (lambda: order_alone(fo), reps), "follow, pairs": (follow(False), reps), "follow, sorted": (follow(True), reps)}
+    for name, la in stages:
+        cases[name, "pairs"], cases[name, "sorted"] = (lane_step(la, False), reps), (lane_step(la, True), reps)
+    t = {k: med(v) for k, v in T.rotate(cases).items()}
+    t_fp, t_fo = t["follow, pairs"], t["follow, sorted"]
     say("   B = %d (%d vehicles with a leader; the two searches' outputs equal word for word: %s), %d calls per repeat:"
         % (B, int((fo.leader >= 0).sum().item()), all(same), reps))
-    say("     kmpc_order_fleet alone:                                              %10.1f [%10.1f, %10.1f]" % med(t_o))
-    say("     kmpc_follow_fleet (pair search):                                     %10.1f [%10.1f, %10.1f]" % med(t_fp))
+    say("     kmpc_order_fleet alone:                                              %10.1f [%10.1f, %10.1f]" % t["order"])
+    say("     kmpc_follow_fleet (pair search):                                     %10.1f [%10.1f, %10.1f]" % t_fp)
     say("     kmpc_order_fleet + kmpc_order_follow_fleet:                          %10.1f [%10.1f, %10.1f]   %.3f x the pair search"
-        % (med(t_fo) + (med(t_fo)[0] / med(t_fp)[0],)))
-    if med(t_fo)[0] < med(t_fp)[0]:
+        % (t_fo + (t_fo[0] / t_fp[0],)))
+    if t_fo[0] < t_fp[0]:
         WINS.setdefault("follower", []).append(B)
-    for i, (name, _) in enumerate(stages):
+    for name, _ in stages:
+        t_lp, t_lo = t[name, "pairs"], t[name, "sorted"]
         say("     two lanes, %s:" % name)
-        say("       kmpc_lane_step_fleet (pair search):                                %10.1f [%10.1f, %10.1f]" % med(t_lp[i]))
+        say("       kmpc_lane_step_fleet (pair search):                                %10.1f [%10.1f, %10.1f]" % t_lp)
         say("       kmpc_order_fleet + kmpc_order_lane_step_fleet (tables, searches):  %10.1f [%10.1f, %10.1f]   %.3f x the pair search"
-            % (med(t_lo[i]) + (med(t_lo[i])[0] / med(t_lp[i])[0],)))
-        if med(t_lo[i])[0] < med(t_lp[i])[0]:
+            % (t_lo + (t_lo[0] / t_lp[0],)))
+        if t_lo[0] < t_lp[0]:
             WINS.setdefault("lane step, " + name, []).append(B)
         else:
             WINS.setdefault("lane step, " + name, [])
@@ -141,41 +122,29 @@ def kernels(B, reps):
 _SETUP = {}
 
 
-def loop_rate(B, search, steps):
+def make_loop(B, search):
     if B not in _SETUP:                # one waypoint helper for every loop: setting up thousands of paths takes longer than the loops run
-        _SETUP[B] = FT.setup(B, B // FT.PLATOON)
+        _SETUP[B] = T.platoons(B, B // PLATOON)
     fleet, state = _SETUP[B]
-    sim = VehicleSimulator(B, X0=state[:, 0], Y0=state[:, 1], Psi0=state[:, 2])
-    sim.state[:, 3] = 6.0
-    loop = ClosedLoop(fleet, sim, N=N, target_vel=6.0, lanes=Lanes(fleet, lane_rows=lane_params(B, n_lanes=2), search=search))
-    for _w in range(20):
-        loop.step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _s in range(steps):
-        o = loop.step()
-    torch.cuda.synchronize()
-    rate = B * steps / (time.perf_counter() - t0) / 1e6
-    return rate, int(o["status"].max().item()), int(loop.lanes.summary()["n_changes"].sum())
+    return T.platoon_loop(fleet, state, lanes=Lanes(fleet, lane_rows=lane_params(B, n_lanes=2), search=search))
+
+
+def last_step(loop, o):
+    return int(o["status"].max().item()), int(loop.lanes.summary()["n_changes"].sum())
 
 
 def loops(B=32768, steps=50):
-    res, last = {"pairs": [], "sorted": []}, {}
-    for _ in range(REPEATS):
-        for search in res:
-            r = loop_rate(B, search, steps)
-            res[search].append(r[0])
-            last[search] = r[1:]
+    res, last = T.loop_rates(["pairs", "sorted"], lambda search: make_loop(B, search), B, steps, advance=T.step_periods, after=last_step)
     say("2. ClosedLoop of %d vehicles in %d platoons of %d with lanes= (two lanes), N = %d, %d steps per repeat after 20 warm-up steps: M vehicle-steps/s "
-        "(median [min, max] of %d, the two searches alternating)" % (B, B // FT.PLATOON, FT.PLATOON, N, steps, REPEATS))
+        "(median [min, max] of %d, the two searches alternating)" % (B, B // PLATOON, PLATOON, N, steps, T.REPEATS))
     for search in res:
-        say("   search=%-10r %6.2f [%6.2f, %6.2f]   (worst status of the last step: %d; lane changes: %d)" % ((search,) + med(res[search]) + last[search]))
+        say("   search=%-10r %6.2f [%6.2f, %6.2f]   (worst status of the last step: %d; lane changes: %d)" % ((search,) + med(res[search]) + last[search][-1]))
     say("   ratio of the medians, sorted / pairs: %.3f" % (med(res["sorted"])[0] / med(res["pairs"])[0]))
 
 
 def main():
-    say("%s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
-    say("1. per call, us (median [min, max] of %d repeats; device events around back-to-back calls through the Python host)" % REPEATS)
+    say(T.header())
+    say("1. per call, us (median [min, max] of %d repeats; device events around back-to-back calls through the Python host)" % T.REPEATS)
     kernels(4096, 100)
     kernels(32768, 30)
     kernels(262144, 5)
@@ -183,9 +152,7 @@ def main():
     for stage, sizes in WINS.items():
         say("     %-50s %s" % (stage + ":", min(sizes) if sizes else "none of them"))
     loops()
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
-            f.write("\n".join(FT.LINES) + "\n")
+    T.finish(sys.argv)
 
 
 if __name__ == "__main__":

@@ -8,70 +8,24 @@
      own path set made from the same arrays), on the default rows at 8 m/s and with a_brake 0.05 (the pass runs to the path's end).  Without
      KMPC_PARENT_LIB the parent's columns are left out and said to be.
   3. vehicle-steps per second of ONE ClosedLoop of 4096 vehicles on the three paths (VehicleSimulator(road=)) without and with road_profile=.
-Method of tools/speed_plan_timing.py: device events around back-to-back calls through the Python host (launch overhead is
-in), the configurations of a group alternate inside one process, five repeats each after a warm-up call, median and range.
+Method: tools/_timing.py; the calls go through the Python host, so launch overhead is in.
 
 usage: [KMPC_PARENT_LIB=parent/libkmpc_hip.so] python tools/road_profile_timing.py [out.txt]
 """
 import ctypes as C
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
+import _timing as T
+from _timing import med, say
 from mkz_mpc_path_follower_amd import ClosedLoop, FleetRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.ref_traj import SpeedPlanner, speed_plan_params  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import RoadProfile, VehicleSimulator, road_params  # noqa: E402
-import scenario as S  # noqa: E402
 
-REPEATS, N = 5, 8
-FILES = ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz")
-LINES = []
-
-
-def say(s):
-    print(s, flush=True)
-    LINES.append(s)
-
-
-def med(xs):
-    xs = sorted(xs)
-    return xs[len(xs) // 2], xs[0], xs[-1]
-
-
-def path_dict(name):
-    arr, lat0, lon0 = S.path_arrays(name)
-    return dict(arr, lat0=lat0, lon0=lon0)
-
-
-def event_time(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps   # us per call
-
-
-def setup(paths, B, rng, frac=0.6):
-    """B vehicles, ids interleaved, poses within 1 m of a sample of the first 60 % of the vehicle's path -> fleet, pose [B,3] (host)"""
-    pid = np.arange(B) % len(paths)
-    fleet = FleetRefTrajectory(paths, pid, traj_horizon=N)
-    pose = np.empty((B, 3))
-    for p, tr in enumerate(fleet.trajectories):
-        sel = np.where(pid == p)[0]
-        idx = rng.integers(0, int(frac * len(tr)), len(sel))
-        pose[sel] = np.stack([tr[idx, 4] + rng.uniform(-1, 1, len(sel)), tr[idx, 5] + rng.uniform(-1, 1, len(sel)), tr[idx, 3] + rng.uniform(-0.2, 0.2, len(sel))], 1)
-    return fleet, pose
+N = T.N
 
 
 class ParentPlan:
@@ -100,46 +54,41 @@ class ParentPlan:
 
 
 def kernels(paths, B, reps, parent_lib):
-    rng = np.random.default_rng(1)
-    fleet, pose = setup(paths, B, rng)
+    fleet, pose = T.interleaved_fleet(paths, B, np.random.default_rng(1))
     pose_d = torch.as_tensor(pose, device="cuda")
     vt = torch.full((B,), 8.0, dtype=torch.float64, device="cuda")
     prof = RoadProfile(fleet)
     base, road = road_params(B, mu=1.0), torch.empty((B, 8), dtype=torch.float64, device="cuda")
     out = torch.empty((B,), dtype=torch.float64, device="cuda")
     say("   B = %d:" % B)
-    tw, tr = [], []
-    for _ in range(REPEATS):   # alternating
-        tw.append(event_time(lambda: fleet.get_waypoints_batch(pose_d, vt), reps))
-        tr.append(event_time(lambda: prof.apply(pose_d, base, road), reps))
-    say("     kmpc_waypoints_fleet, target-velocity mode:                    %8.1f [%8.1f, %8.1f]" % med(tw))
-    say("     kmpc_road_profile_fleet:                                       %8.1f [%8.1f, %8.1f]   %.3f x the waypoint call" % (med(tr) + (med(tr)[0] / med(tw)[0],)))
+    t = T.rotate({"waypoints": (lambda: fleet.get_waypoints_batch(pose_d, vt), reps), "profile": (lambda: prof.apply(pose_d, base, road), reps)})
+    tw, tr = med(t["waypoints"]), med(t["profile"])
+    say("     kmpc_waypoints_fleet, target-velocity mode:                    %8.1f [%8.1f, %8.1f]" % tw)
+    say("     kmpc_road_profile_fleet:                                       %8.1f [%8.1f, %8.1f]   %.3f x the waypoint call" % (tr + (tr[0] / tw[0],)))
     parent = ParentPlan(parent_lib, fleet) if parent_lib else None
     for label, kw in (("default rows (early exit after the first chunks)", {}), ("a_brake 0.05 (the pass runs to the path's end)", dict(a_brake=0.05))):
         rows = speed_plan_params(B, **kw)
         plain, mapped = SpeedPlanner(fleet, rows=rows), SpeedPlanner(fleet, rows=rows, profile=prof)
-        t0, t1, tp = [], [], []
-        for _ in range(REPEATS):
-            if parent:
-                tp.append(event_time(lambda: parent.plan(pose_d, vt, rows, out), reps))
-            t0.append(event_time(lambda: plain.plan(pose_d, vt, out=out), reps))
-            t1.append(event_time(lambda: mapped.plan(pose_d, vt, out=out), reps))
+        cases = {"parent": (lambda: parent.plan(pose_d, vt, rows, out), reps)} if parent else {}
+        cases.update(plain=(lambda: plain.plan(pose_d, vt, out=out), reps), mapped=(lambda: mapped.plan(pose_d, vt, out=out), reps))
+        t = {k: med(v) for k, v in T.rotate(cases).items()}
+        t0, t1 = t["plain"], t["mapped"]
         same = torch.equal(plain.plan(pose_d, vt), mapped.plan(pose_d, vt))
         if parent:
             same = same and torch.equal(plain.plan(pose_d, vt), parent.plan(pose_d, vt, rows, torch.empty_like(out)))
         say("     %s; outputs of all builds and both entries identical: %s" % (label, same))
         if parent:
-            say("       kmpc_speed_plan_fleet, parent build:                         %8.1f [%8.1f, %8.1f]" % med(tp))
-        ref = med(tp)[0] if parent else med(t0)[0]
+            say("       kmpc_speed_plan_fleet, parent build:                         %8.1f [%8.1f, %8.1f]" % t["parent"])
+        ref = t["parent"][0] if parent else t0[0]
         say("       kmpc_speed_plan_fleet, this build:                           %8.1f [%8.1f, %8.1f]   %.3f x %s"
-            % (med(t0) + (med(t0)[0] / ref, "the parent's" if parent else "itself (no parent build given: not measured)")))
+            % (t0 + (t0[0] / ref, "the parent's" if parent else "itself (no parent build given: not measured)")))
         say("       kmpc_speed_plan_fleet_profile, neutral map:                  %8.1f [%8.1f, %8.1f]   %.3f x %s"
-            % (med(t1) + (med(t1)[0] / ref, "the parent's kmpc_speed_plan_fleet" if parent else "this build's kmpc_speed_plan_fleet")))
+            % (t1 + (t1[0] / ref, "the parent's kmpc_speed_plan_fleet" if parent else "this build's kmpc_speed_plan_fleet")))
 
 
 def loops(paths, B=4096, steps=100):
     rng = np.random.default_rng(2)
-    _, pose = setup(paths, B, rng)
+    _, pose = T.interleaved_fleet(paths, B, rng)
     pid = np.arange(B) % len(paths)
     vt = rng.uniform(3.0, 9.0, B)
 
@@ -149,40 +98,26 @@ def loops(paths, B=4096, steps=100):
                                road_profile=RoadProfile(fleet) if profiled else None)
         sim.state[:, 3] = torch.as_tensor(vt, device=sim.device)
         return ClosedLoop(fleet, sim, N=N, target_vel=vt)
-    kinds = [("road= alone", False), ("road= and road_profile= (neutral table)", True)]
-    res = {k: [] for k, _ in kinds}
-    worst = {k: 0 for k, _ in kinds}
-    for _ in range(REPEATS):
-        for name, profiled in kinds:
-            loop = make(profiled)
-            for _w in range(20):
-                loop.step()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _s in range(steps):
-                o = loop.step()
-            torch.cuda.synchronize()
-            res[name].append(B * steps / (time.perf_counter() - t0) / 1e6)
-            worst[name] = max(worst[name], int(o["status"].max().item()))
+    kinds = {"road= alone": False, "road= and road_profile= (neutral table)": True}
+    res, worst = T.loop_rates(list(kinds), lambda k: make(kinds[k]), B, steps, advance=T.step_periods, after=lambda loop, o: int(o["status"].max().item()))
     say("3. ClosedLoop of %d vehicles on the three paths, N = %d, road mu = 1.0, target speeds 3 ... 9 m/s, %d steps per repeat after 20 warm-up steps: "
-        "M vehicle-steps/s (median [min, max] of %d)" % (B, N, steps, REPEATS))
-    for name, _ in kinds:
-        say("   %-42s %6.2f [%6.2f, %6.2f]   (worst status of the last step: %d)" % ((name,) + med(res[name]) + (worst[name],)))
-    say("   ratio of the medians with / without: %.3f" % (med(res[kinds[1][0]])[0] / med(res[kinds[0][0]])[0]))
+        "M vehicle-steps/s (median [min, max] of %d)" % (B, N, steps, T.REPEATS))
+    for name in kinds:
+        say("   %-42s %6.2f [%6.2f, %6.2f]   (worst status of the last step: %d)" % ((name,) + med(res[name]) + (max(worst[name]),)))
+    without, with_ = kinds
+    say("   ratio of the medians with / without: %.3f" % (med(res[with_])[0] / med(res[without])[0]))
 
 
 def main():
-    paths = [path_dict(f) for f in FILES]
+    paths = [T.path_dict(f) for f in T.FILES]
     parent_lib = os.environ.get("KMPC_PARENT_LIB")
-    say("%s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    say(T.header())
     say("1., 2. per call, N = %d, us (median [min, max] of %d repeats; device events around back-to-back calls through the Python host: 200 at B = 4096, "
-        "20 at B = 262144); parent build: %s" % (N, REPEATS, "given" if parent_lib else "not given, its columns are not measured"))
+        "20 at B = 262144); parent build: %s" % (N, T.REPEATS, "given" if parent_lib else "not given, its columns are not measured"))
     kernels(paths, 4096, 200, parent_lib)
     kernels(paths, 262144, 20, parent_lib)
     loops(paths)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(sys.argv)
 
 
 if __name__ == "__main__":

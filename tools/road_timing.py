@@ -5,62 +5,34 @@
      of kmpc_sim_advance_road with two saturating rows -- mu_f = 0.2 alone (the front axle runs out of grip, the vehicle understeers and its slip
      angles stay inside the plant kernels' polynomial range: what the clip itself costs) and mu = 0.2 on both axles with a bank of 0.5 m/s^2 and an
      offset of 0.03 rad (the rear lets go as well, vehicles slide and the wave takes the library's atan2) -- and of the neutral row without
-     road_stat, at B = 4096 and B = 262 144; the share of clipped sub-steps and the largest slip tangent at the end are printed.  Device events
-     around REPS launches after a warm-up, the kernels in rotation inside one process, five repeats each, median and range.  Every variant restarts from the same states in every repeat.
-  2. ClosedLoop vehicle-steps per second at B = 4096, N = 8 on path1 with VehicleSimulator(cmd_queue_depth=2) and with road=road_params(B, mu=0.5),
-     alternating, median of five.
+     road_stat, at B = 4096 and B = 262 144; the share of clipped sub-steps and the largest slip tangent at the end are printed.  Every variant
+     restarts from the same states in every repeat.
+  2. ClosedLoop vehicle-steps per second at B = 4096, N = 8 on path1 with VehicleSimulator(cmd_queue_depth=2) and with road=road_params(B, mu=0.5).
+Method: tools/_timing.py.
 
 No target is set: the figure to compare against is the queue kernel of the same build in the same process.
 
 usage: python tools/road_timing.py [out.txt]
 """
 import ctypes as C
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
+import _timing as T
+from _timing import med, say
 from mkz_mpc_path_follower_amd import _lib  # noqa: E402
 from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
-from mkz_mpc_path_follower_amd.ref_traj import GPSRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import VehicleSimulator, plant_params, road_params  # noqa: E402
 
-REPEATS, REPS = 5, 100
-LINES = []
-
-
-def say(s):
-    print(s, flush=True)
-    LINES.append(s)
-
-
-def med(xs):
-    xs = sorted(xs)
-    return xs[len(xs) // 2], xs[0], xs[-1]
-
-
-def event_time(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps   # us per call
+REPS = 100
 
 
 def kernels():
     L = _lib.load()
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    say("1. us per control period, median [min, max] of %d repeats of %d back-to-back launches" % (REPEATS, REPS))
+    say("1. us per control period, median [min, max] of %d repeats of %d back-to-back launches" % (T.REPEATS, REPS))
     for B in (4096, 262144):
         rng = np.random.default_rng(B)
         s0 = np.zeros((B, 8))
@@ -92,12 +64,10 @@ def kernels():
                names[3]: road_call(names[3], front), names[4]: road_call(names[4], slippery)}
         for k, fn in run.items():
             assert fn() == 0, k
-        res = {k: [] for k in run}
-        for _ in range(REPEATS):
+        def restart():
             for k in names:
                 st[k].copy_(s0); stat[k].zero_()
-            for k, fn in run.items():   # in rotation
-                res[k].append(event_time(fn, REPS))
+        res = T.rotate({k: (fn, REPS) for k, fn in run.items()}, before=restart)
         torch.cuda.synchronize()
         assert all(torch.isfinite(t).all().item() for t in st.values())
         assert torch.equal(st[names[0]], st[names[1]]) and torch.equal(st[names[0]], st[names[2]]) and not stat[names[1]].any().item()
@@ -113,43 +83,28 @@ def kernels():
 
 def loops(B=4096, N=8, vt=6.0, steps=100):
     say("2. ClosedLoop, B = %d, N = %d, path1 at %.0f m/s, %d periods per repeat after 20 warm-up periods, alternating: M vehicle-steps/s "
-        "(median [min, max] of %d)" % (B, N, vt, steps, REPEATS))
-    d = np.load(os.path.join(ROOT, "tests", "golden", "path1_decimated.npz"))
-    grt = GPSRefTrajectory(arrays=dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"]), traj_horizon=N, traj_dt=0.2)
-    tr = grt.get_global_trajectory_reference()
-    rng = np.random.default_rng(2)
-    idx = rng.integers(0, int(0.5 * len(tr)), B)
-    X0, Y0, P0 = tr[idx, 4] + rng.uniform(-0.5, 0.5, B), tr[idx, 5] + rng.uniform(-0.5, 0.5, B), tr[idx, 3] + rng.uniform(-0.05, 0.05, B)
+        "(median [min, max] of %d)" % (B, N, vt, steps, T.REPEATS))
+    grt, tr = T.single_path(N)
+    start = T.scatter(tr, B, np.random.default_rng(2))
 
     def make(kind):
         if kind == "cmd_queue_depth=2":
-            sim = VehicleSimulator(B, X0=X0, Y0=Y0, Psi0=P0, cmd_queue_depth=2)
+            sim = VehicleSimulator(B, X0=start[:, 0], Y0=start[:, 1], Psi0=start[:, 2], cmd_queue_depth=2)
         else:
-            sim = VehicleSimulator(B, X0=X0, Y0=Y0, Psi0=P0, road=road_params(B, mu=0.5))
+            sim = VehicleSimulator(B, X0=start[:, 0], Y0=start[:, 1], Psi0=start[:, 2], road=road_params(B, mu=0.5))
         sim.state[:, 3] = vt
         return ClosedLoop(grt, sim, N=N, target_vel=vt)
     kinds = ("cmd_queue_depth=2", "road=road_params(B, mu=0.5)")
-    res = {k: [] for k in kinds}
-    for _ in range(REPEATS):
-        for k in kinds:
-            loop = make(k)
-            loop.run(20, score=False)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            loop.run(steps, score=False)
-            torch.cuda.synchronize()
-            res[k].append(B * steps / (time.perf_counter() - t0) / 1e6)
+    res, _ = T.loop_rates(kinds, make, B, steps)
     for k in kinds:
         say("   %-36s %6.2f [%6.2f, %6.2f]" % ((k,) + med(res[k])))
 
 
 def main():
-    say("%s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    say(T.header())
     kernels()
     loops()
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(sys.argv)
 
 
 if __name__ == "__main__":

@@ -80,15 +80,13 @@ usage: python tools/robustness_sweep.py [--estimator] [out.txt] [steps]
        python tools/robustness_sweep.py --road [out.txt] [steps]
 """
 import itertools
-import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
+import _timing as T
+from _timing import say
 from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
 from mkz_mpc_path_follower_amd.ref_traj import FleetRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import Estimator, LatencyCompensator, SensorModel, VehicleSimulator, plant_default, plant_params  # noqa: E402
@@ -97,22 +95,13 @@ from mkz_mpc_path_follower_amd.vehicle_sim import DisturbanceObserver  # noqa: E
 
 MASS, STIFF, SIGMA, DELAY = (0.85, 1.0, 1.15, 1.3), (0.6, 0.8, 1.0, 1.2), (0.0, 0.1, 0.2, 0.5), (0, 2, 4, 8)
 PER_CELL, VT = 16, 6.0
-LINES = []
-
-
-def say(s):
-    print(s, flush=True)
-    LINES.append(s)
 
 
 def main():
     use_estimator = "--estimator" in sys.argv[1:]
     argv = [a for a in sys.argv if a != "--estimator"]
     steps = int(argv[2]) if len(argv) > 2 else 150
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(4), repeat=4))
     B = len(cells) * PER_CELL
     cell = np.repeat(np.arange(len(cells)), PER_CELL)
@@ -169,9 +158,7 @@ def main():
         for lv in range(4):
             sel = ix[:, 2] == lv
             say("   GPS sigma [m] %.1f              %7.3f -> %7.3f" % (SIGMA[lv], np.median(e_raw[sel]), np.median(e_filt[sel])))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 LAT_CMD, LAT_FIX, LAT_PER_CELL = (0, 10, 20, 30), (0, 1, 2), 48
@@ -182,10 +169,7 @@ def latency_main():
     estimate bit for bit and its filter input is the previous period's command (estimator_input="command" without a compensator)."""
     argv = [a for a in sys.argv if a != "--latency"]
     steps = int(argv[2]) if len(argv) > 2 else 150
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(4), range(3), range(2)))
     B = len(cells) * LAT_PER_CELL
     cell = np.repeat(np.arange(len(cells)), LAT_PER_CELL)
@@ -223,9 +207,7 @@ def latency_main():
             base = (ix[:, 0] == c) & (ix[:, 1] == f)
             say("   command delay %2d updates, fix %d periods old   %7.3f %7.3f %8.3f %8.2f   ->  %7.3f %7.3f %8.3f %8.2f"
                 % ((LAT_CMD[c], LAT_FIX[f]) + fig(base & (ix[:, 2] == 0)) + fig(base & (ix[:, 2] == 1))))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 ROAD_MU, ROAD_VT, ROAD_LAT, ROAD_OFFSET, ROAD_PER_CELL = (float("inf"), 1.0, 0.7, 0.5, 0.35, 0.25), (6.0, 8.0), (0.0, 0.75, 1.5), (0.0, 0.015, 0.03), 48
@@ -235,10 +217,7 @@ def road_main():
     """one loop of 6 x 2 x 3 x 3 cells of 48 vehicles, each cell the same 48 starts: on the path, heading along it, already at the cell's speed"""
     argv = [a for a in sys.argv if a != "--road"]
     steps = int(argv[2]) if len(argv) > 2 else 150
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(6), range(2), range(3), range(3)))
     B = len(cells) * ROAD_PER_CELL
     cell = np.repeat(np.arange(len(cells)), ROAD_PER_CELL)
@@ -286,9 +265,7 @@ def road_main():
         sel = [(ix[:, 0] == m) & (ix[:, 1] == v) & (ix[:, 2] == 0) & (ix[:, 3] == 0) for v in range(2)]
         say("   mu %.2f   %6.2f / %-6.2f   %6.2f / %-6.2f" % (ROAD_MU[m], np.median(grip["util_f"][sel[0]]), np.median(grip["util_r"][sel[0]]),
                                                            np.median(grip["util_f"][sel[1]]), np.median(grip["util_r"][sel[1]])))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 def speed_plan_main():
@@ -297,10 +274,7 @@ def speed_plan_main():
     from mkz_mpc_path_follower_amd.ref_traj import SpeedPlanner, speed_plan_params
     argv = [a for a in sys.argv if a != "--speed-plan"]
     steps = int(argv[2]) if len(argv) > 2 else 150
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(6), range(2)))
     B = len(cells) * ROAD_PER_CELL
     ix = np.array(cells)[np.repeat(np.arange(len(cells)), ROAD_PER_CELL)]      # [B,2] grid indices: mu, speed
@@ -350,9 +324,7 @@ def speed_plan_main():
             sel = (ix[:, 0] == m) & (ix[:, 1] == v) & ~res[1]["late"]
             say("   %-20s %8.3f | %8.3f   %2d" % ("mu %.2f at %.0f m/s" % (ROAD_MU[m], ROAD_VT[v]), res[0]["s"]["max_ect"][sel].max(),
                                                  res[1]["s"]["max_ect"][sel].max(), int(sel.sum())))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 RP_SCALE, RP_KAPPA, RP_REACH, RP_BANK, RP_STRETCH = (0.7, 0.5, 0.35, 0.25), 0.03, 10.0, 1.5, 100.0
@@ -366,10 +338,7 @@ def road_profile_main():
     from mkz_mpc_path_follower_amd.vehicle_sim import RoadProfile, road_profile_patch, road_profile_table
     argv = [a for a in sys.argv if a != "--road-profile"]
     steps = int(argv[2]) if len(argv) > 2 else 150
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(len(RP_SCALE)), range(2)))
     B = len(cells) * ROAD_PER_CELL
     ix = np.array(cells)[np.repeat(np.arange(len(cells)), ROAD_PER_CELL)]      # [B,2] grid indices: MU_SCALE, speed
@@ -473,9 +442,7 @@ def road_profile_main():
     for w in (False, True):
         a, c = obs[(True, w)], obs[(False, w)]
         say("   %-28s %6.3f %6.3f %6.2f %s  | %6.3f %6.3f %6.2f %s" % (("with DisturbanceObserver" if w else "without an observer",) + a + c))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 OBS_LONG = (0.0, -0.5)
@@ -486,10 +453,7 @@ def observer_main():
     scored in two halves: the whole run carries the start and the corners, the second half is what stays."""
     argv = [a for a in sys.argv if a != "--observer"]
     steps = int(argv[2]) if len(argv) > 2 else 200
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(3), range(3), range(2)))
     B = len(cells) * ROAD_PER_CELL
     ix = np.array(cells)[np.repeat(np.arange(len(cells)), ROAD_PER_CELL)]     # [B,3] grid indices: lateral force, steering offset, longitudinal force
@@ -533,9 +497,7 @@ def observer_main():
                                                           1000.0 * r["nonopt"][sel].sum() / max(1, r["live"][sel].sum()), np.median(r["v"][sel])))
         d = np.median(res[True]["dist"][sel], 0)
         say("   %.2f m/s^2, %.3f rad, %+.1f m/s^2   %s | %s   %+.4f %+.4f %+.4f" % (ROAD_LAT[a], ROAD_OFFSET[o], OBS_LONG[g], part[0], part[1], d[0], d[1], d[2]))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 OL_DEAD = ((10, 0), (10, 1), (25, 1))     # command delay [updates], age of the fix [periods]: 0.1, 0.2, 0.35 s
@@ -549,10 +511,7 @@ def observer_latency_main():
     limit): the plant's queue and the sensor's stale fix per vehicle, the controller assuming the true delays.  Scored in two halves as --observer."""
     argv = [a for a in sys.argv if a != "--observer-latency"]
     steps = int(argv[2]) if len(argv) > 2 else 200
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(3), range(3), range(2), range(3), range(3)))
     B = len(cells) * OL_PER_CELL
     ix = np.array(cells)[np.repeat(np.arange(len(cells)), OL_PER_CELL)]     # [B,5]: lateral force, steering offset, longitudinal force, dead time, q_dist scale
@@ -617,9 +576,7 @@ def observer_latency_main():
     for a, o, g in itertools.product(range(3), range(3), range(2)):
         row("%.2f m/s^2, %.3f rad, %+.1f m/s^2" % (ROAD_LAT[a], ROAD_OFFSET[o], OBS_LONG[g]),
             (ix[:, 0] == a) & (ix[:, 1] == o) & (ix[:, 2] == g) & (ix[:, 3] == 0) & (ix[:, 4] == 0))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 ACT_DEADBAND, ACT_MASS, ACT_FPEAK, ACT_RATIO, ACT_PER_CELL = (0.0, 0.1, 0.2), (0.85, 1.0, 1.3), (2500.0, 6000.0), (0.0, 0.05, -0.05), 12
@@ -631,10 +588,7 @@ def actuation_main():
     from mkz_mpc_path_follower_amd.vehicle_sim import LowLevelController, drive_params
     argv = [a for a in sys.argv if a != "--actuation"]
     steps = int(argv[2]) if len(argv) > 2 else 200
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(3), range(3), range(2), range(3)))
     B = len(cells) * ACT_PER_CELL
     ix = np.array(cells)[np.repeat(np.arange(len(cells)), ACT_PER_CELL)]     # [B,4] grid indices: deadband, mass, F_PEAK, ratio error
@@ -693,9 +647,7 @@ def actuation_main():
     for dbi, mi, fi in itertools.product(range(3), range(3), range(2)):
         row("%.1f m/s^2, mass x %.2f, %4.0f N" % (ACT_DEADBAND[dbi], ACT_MASS[mi], ACT_FPEAK[fi]),
             (ix[:, 0] == dbi) & (ix[:, 1] == mi) & (ix[:, 2] == fi) & (ix[:, 3] == 0))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 OUT_LEN, OUT_BIAS, OUT_PER_CELL = (0, 10, 30, 100), (0.0, 0.02), 48
@@ -709,10 +661,7 @@ def outage_main():
     from mkz_mpc_path_follower_amd.vehicle_sim import fault_params
     argv = [a for a in sys.argv if a != "--outage"]
     steps = int(argv[2]) if len(argv) > 2 else 200
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     rng = np.random.default_rng(0)
     frac48 = rng.uniform(0.02, 0.45, ROAD_PER_CELL)          # the road sweep's starts
     from48 = rng.integers(10, 40, OUT_PER_CELL).astype(float)
@@ -780,9 +729,7 @@ def outage_main():
         li = li[li >= 0]
         say(("   window %3d periods                       " + fmt + "   %s") % ((w,) + cols(blind[0], blind[1], sel)
                                                                                 + (("%d ... %d" % (li.min(), li.max())) if len(li) else "-",)))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 WAN_SIGMA, WAN_TAU = (0.1, 0.2, 0.5), (0.0, 2.0, 10.0, 30.0)             # GPS error [m]; its correlation time [s], 0 = white (the sensor's own noise)
@@ -799,10 +746,7 @@ def wander_main():
     from mkz_mpc_path_follower_amd.vehicle_sim import Wander, fault_params, wander_params
     argv = [a for a in sys.argv if a != "--wander"]
     steps = int(argv[2]) if len(argv) > 2 else 300
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     rng = np.random.default_rng(0)
     frac48 = rng.uniform(0.02, 0.45, ROAD_PER_CELL)          # the road sweep's starts
     from48 = rng.integers(10, 40, ROAD_PER_CELL).astype(float)
@@ -890,9 +834,7 @@ def wander_main():
         sel = (ix[:, 0] == w) & (ix[:, 1] == k)
         say("   window %3d periods, walk %.3f rad/sqrt(s)   %7.3f %8.3f %7.3f" %
             (WAN_WINDOW[w], WAN_WALK[k], np.median(out["max_ect"][sel]), out["max_ect"][sel].max(), np.median(out["rms_ect"][sel])))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 PL_T, PL_DELAY, PL_SIGMA, PL_SIZE, PL_SPACING = (0.5, 1.0, 1.5), (0, 10, 30), (0.0, 0.2), 8, 20.0
@@ -906,10 +848,7 @@ def platoon_main():
     target steps 6 -> 3 -> 6 m/s (loop.v_target is edited in place between run() calls); the followers' targets stay 6 m/s."""
     from mkz_mpc_path_follower_amd.ref_traj import Follower, follow_params
     argv = [a for a in sys.argv if a != "--platoon"]
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(3), range(3), range(2)))
     n_pl = 3 * len(cells)
     B = n_pl * PL_SIZE
@@ -960,9 +899,7 @@ def platoon_main():
             part.append("%7.3f %5d %6.3f %7.2f" % (r["f"]["min_gap"][sel].min(), r["f"]["n_contact"][sel].sum(), np.median(ratio),
                                                     1000.0 * r["s"]["n_nonopt"][sel].sum() / max(1, r["s"]["n_live"][sel].sum())))
         say("   T %.1f s, delay %.1f s, GPS sigma %.1f m   %s" % (PL_T[t], 0.01 * PL_DELAY[dl], PL_SIGMA[g], " | ".join(part)))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 RD_SIGMA, RD_DROP, RD_RANGE, RD_FILTER = (0.0, 0.25, 0.5, 1.0), (0.0, 0.1, 0.3), (float("inf"), 30.0, 15.0), (0, 1)
@@ -970,10 +907,7 @@ RD_STAND_GAP, RD_STAND_STEPS = 100.0, 400
 
 
 def _paths():
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     return paths
 
 
@@ -1060,9 +994,7 @@ def radar_main():
         say("   RANGE_MAX %4s m: first seen at a gap of %7.3f m, smallest gap %7.3f m, last gap %7.3f m, last speed %6.3f m/s, periods in contact %d; the "
             "leader moved %.3f m" % ("inf" if np.isinf(RD_RANGE[q]) else "%g" % RD_RANGE[q], gap[first, b], f["min_gap"][b], gap[-1, b], v[-1, b],
                                      f["n_contact"][b], float(np.hypot(*(o["state"][-1, 2 * q, 0:2] - o["state"][0, 2 * q, 0:2]).cpu().numpy()))))
-    if len(argv) > 1:
-        with open(argv[1], "w") as fh:
-            fh.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 OV_SIZE, OV_STEPS, OV_SLOW, OV_FAST = 6, 350, 3.0, 6.0
@@ -1074,10 +1006,7 @@ def overtake_main():
     N_LANES = 2.  The stage reads the truth (a perfect range sensor); delay and noise reach it through how well the vehicles hold their lines."""
     from mkz_mpc_path_follower_amd.ref_traj import Lanes, follow_params, lane_params
     argv = [a for a in sys.argv if a != "--overtake"]
-    paths = []
-    for name in ("path1_decimated.npz", "path2_decimated.npz", "path3_decimated.npz"):
-        d = np.load(os.path.join(ROOT, "tests", "golden", name))
-        paths.append(dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"], lat0=float(d["lat0"]), lon0=float(d["lon0"])))
+    paths = [T.path_dict(f) for f in T.FILES]
     cells = list(itertools.product(range(3), range(3), range(2)))
     n_pl = 3 * len(cells)
     B = n_pl * OV_SIZE
@@ -1125,9 +1054,7 @@ def overtake_main():
                                                                done.sum(), r["speed"][fast].mean(), r["f"]["max_elane"][sel].max(),
                                                                1000.0 * r["s"]["n_nonopt"][sel].sum() / max(1, r["s"]["n_live"][sel].sum())))
         say("   T %.1f s, delay %.1f s, GPS sigma %.1f m   %s" % (PL_T[t], 0.01 * PL_DELAY[dl], PL_SIGMA[g], " | ".join(part)))
-    if len(argv) > 1:
-        with open(argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(argv)
 
 
 if __name__ == "__main__":

@@ -1,61 +1,32 @@
 """Timing of the measurement stage with sensor faults and of the closed loop with it on one MI355X (-> profiles/sensor_fault_timing.txt).
 
   1. kmpc_sense_faults_batch (neutral rows; rows with chains, windows and outliers; with a ring of depth 3) next to kmpc_sense_batch and
-     kmpc_sense_delayed_batch on the same states at B = 4096 and B = 262 144: device events around REPS launches after a warm-up, the cases in
-     rotation inside one process, five repeats each, median and range; then the ratios of the medians.
-  2. ClosedLoop vehicle-steps per second at B = 4096, N = 8 on path1: the plain sensor + estimator, and the same with a neutral faulty sensor,
-     alternating, median of five; then the ratio.
-No threshold is set: the stage moves about 0.5 KB per vehicle and is about 1 % of a period.
+     kmpc_sense_delayed_batch on the same states at B = 4096 and B = 262 144; then the ratios of the medians.
+  2. ClosedLoop vehicle-steps per second at B = 4096, N = 8 on path1: the plain sensor + estimator, and the same with a neutral faulty sensor;
+     then the ratio.
+Method: tools/_timing.py.  No threshold is set: the stage moves about 0.5 KB per vehicle and is about 1 % of a period.
 
 usage: python tools/sensor_fault_timing.py [out.txt]
 """
 import ctypes as C
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
+import _timing as T
+from _timing import med, say
 from mkz_mpc_path_follower_amd import _lib  # noqa: E402
 from mkz_mpc_path_follower_amd.closed_loop import ClosedLoop  # noqa: E402
-from mkz_mpc_path_follower_amd.ref_traj import GPSRefTrajectory  # noqa: E402
 from mkz_mpc_path_follower_amd.vehicle_sim import Estimator, SensorModel, VehicleSimulator, fault_params  # noqa: E402
 
-REPEATS, REPS = 5, 100
-LINES = []
-
-
-def say(s):
-    print(s, flush=True)
-    LINES.append(s)
-
-
-def med(xs):
-    xs = sorted(xs)
-    return xs[len(xs) // 2], xs[0], xs[-1]
-
-
-def event_time(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps   # us per call
+REPS = 100
 
 
 def kernels():
     L = _lib.load()
     p = lambda t: C.c_void_p(t.data_ptr())
-    say("1. us per call, median [min, max] of %d repeats of %d back-to-back launches" % (REPEATS, REPS))
+    say("1. us per call, median [min, max] of %d repeats of %d back-to-back launches" % (T.REPEATS, REPS))
     for B in (4096, 262144):
         rng = np.random.default_rng(B)
         s0 = np.zeros((B, 8))
@@ -86,10 +57,7 @@ def kernels():
                "kmpc_sense_faults_batch, neutral, ring": faulty(neutral, rec["ring"], True)}
         for k, fn in run.items():
             assert fn() == 0, k
-        res = {k: [] for k in run}
-        for _ in range(REPEATS):
-            for k, fn in run.items():   # in rotation
-                res[k].append(event_time(fn, REPS))
+        res = T.rotate({k: (fn, REPS) for k, fn in run.items()})
         assert torch.isfinite(est).all().item() and torch.isfinite(held).all().item() and int(rec["busy"][:, 9].sum().item()) > 0
         for k in run:
             say("   B = %-7d %-40s %8.1f [%8.1f, %8.1f]" % ((B, k) + med(res[k])))
@@ -101,42 +69,27 @@ def kernels():
 
 def loops(B=4096, N=8, vt=8.0, steps=100):
     say("2. ClosedLoop, B = %d, N = %d, path1 at %.0f m/s, sensor + estimator, %d periods per repeat after 20 warm-up periods, alternating: M vehicle-steps/s "
-        "(median [min, max] of %d)" % (B, N, vt, steps, REPEATS))
-    d = np.load(os.path.join(ROOT, "tests", "golden", "path1_decimated.npz"))
-    grt = GPSRefTrajectory(arrays=dict(t=d["t"], lat=d["lat"], lon=d["lon"], psi=d["psi"]), traj_horizon=N, traj_dt=0.2)
-    tr = grt.get_global_trajectory_reference()
-    rng = np.random.default_rng(2)
-    idx = rng.integers(0, int(0.5 * len(tr)), B)
-    X0, Y0, P0 = tr[idx, 4] + rng.uniform(-0.5, 0.5, B), tr[idx, 5] + rng.uniform(-0.5, 0.5, B), tr[idx, 3] + rng.uniform(-0.05, 0.05, B)
+        "(median [min, max] of %d)" % (B, N, vt, steps, T.REPEATS))
+    grt, tr = T.single_path(N)
+    start = T.scatter(tr, B, np.random.default_rng(2))
 
     def make(kind):
-        sim = VehicleSimulator(B, X0=X0, Y0=Y0, Psi0=P0, cmd_delay=0)
+        sim = VehicleSimulator(B, X0=start[:, 0], Y0=start[:, 1], Psi0=start[:, 2], cmd_delay=0)
         sim.state[:, 3] = vt
         sensor = SensorModel(B, sigma=(0.1, 0.1, 0.005, 0.05), seed=1, faults=fault_params(B) if kind == "neutral faulty sensor" else None)
         return ClosedLoop(grt, sim, N=N, target_vel=vt, sensor=sensor, estimator=Estimator.from_sensor(sensor))
     kinds = ("plain sensor", "neutral faulty sensor")
-    res = {k: [] for k in kinds}
-    for _ in range(REPEATS):
-        for k in kinds:
-            loop = make(k)
-            loop.run(20, score=False)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            loop.run(steps, score=False)
-            torch.cuda.synchronize()
-            res[k].append(B * steps / (time.perf_counter() - t0) / 1e6)
+    res, _ = T.loop_rates(kinds, make, B, steps)
     for k in kinds:
         say("   %-36s %6.2f [%6.2f, %6.2f]" % ((k,) + med(res[k])))
     say("   ratio of the medians, neutral faulty sensor / plain sensor: %.3f" % (med(res[kinds[1]])[0] / med(res[kinds[0]])[0]))
 
 
 def main():
-    say("%s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    say(T.header())
     kernels()
     loops()
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    T.finish(sys.argv)
 
 
 if __name__ == "__main__":
